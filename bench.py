@@ -17,12 +17,17 @@ loop being partitioned) is split into N spatially contiguous shards, the target 
 all-reduces ONE accumulator of 96 doubles per linearization (21 H, 6 b, e, inliers + the 63 moments of the quadratic error model)
 with RCCL on its own stream (csrc/comm.hip); the trial errors of the LM steps are evaluated on every rank's host from the reduced
 moments — no collective per error pass; every rank runs the same host LM on the reduced numbers.  value = iterations/s of that one
-job.  Rank 0 also runs the unsharded registration and the bench asserts that the N-rank pose equals it (1e-9 in fp64 per-pair
+job.  With --full, rank 0 also runs the unsharded registration and the bench asserts that the N-rank pose equals it (1e-9 in fp64 per-pair
 arithmetic, 1e-5 in the timed fp32 arithmetic).  If the native communicator cannot be created the torch.distributed callback path (30 doubles per
 linearization + 1 per error pass, still one rank per GPU, the all-reduce through torch's RCCL) is measured instead, the JSON says
 "fallback": true with "fallback_reason", and stderr says so; --require-native makes that case fail instead.  --scaling weak: every rank owns an independent 1M-point source (value = N x the job's iteration rate).
 
-Extra objects on the JSON line: "roofline" (K1 = search + factor kernel of one linearize pass, algorithmic bytes / HIP-event time vs
+A plain run sets up, warms up, times exactly --steps steps in one region and prints the JSON line (metric, value, unit, ms_per_step,
+dtype, ...); --dump-outputs DIR also writes the result of the last timed registration (the fields of RegistrationResult, float64) as
+DIR/<name>.npy.  Everything else is measured and checked only with --full.
+
+With --full, a request for fewer than 100 steps is timed 9 times and the median region is reported ("timed_regions"), and the extra
+objects below join the JSON line: "roofline" (K1 = search + factor kernel of one linearize pass, algorithmic bytes / HIP-event time vs
 8 TB/s; traffic = FETCH_SIZE / WRITE_SIZE of one registration re-run under rocprofv3 when it is on the box), "cpu_baseline" (the
 unmodified reference code, oracle/_ref, timed on this box's host cores on the same clouds; rank 0, N = 1 only), "parity_vs_reference"
 (the same 10 LM iterations on the GPU against that reference run, with the number of differing correspondences), "to_convergence"
@@ -75,6 +80,9 @@ def parse():
     ap.add_argument("--sustain-s", type=float, default=3.0, help="extra (reported separately) sustained run of the same steps for this many seconds; 0 = skip")
     ap.add_argument("--force-dist", action="store_true", help="use the torch.distributed/RCCL path even at world size 1 (validation)")
     ap.add_argument("--oversubscribe", action="store_true", help="testing only: place ranks on device rank %% visible devices")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline (roofline, CPU baseline, parity, other precisions, sizes and "
+                                                        "configurations, odometry); a plain run only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the result of the last timed registration as DIR/<field>.npy (float64)")
     return ap.parse_args()
 
 
@@ -193,7 +201,7 @@ def main():
     # (fp64 per-pair arithmetic: the sharded sums then equal the unsharded ones to rounding of the fp64 row sums, 1e-9 m; in the
     # default fp32 arithmetic the partial sums GROUP by shard — 64 / 256 points per fp32 sum — and the poses agree to ~1e-6 m)
     ref_pose = {}
-    if strong and world > 1 and rank == 0:
+    if args.full and strong and world > 1 and rank == 0:
         for m in ("fp64", "fp32"):
             ref_pose[m] = sga.Problem(tree, src_full, np.eye(4)).align(setting_for(ITERS_PER_ALIGN, m)).T_target_source
 
@@ -290,29 +298,33 @@ def main():
         return done, last, el
 
     run_steps(args.warmup)
-    # The timed region (it carries no event records at all).  A request for fewer than 100 steps is a region of a few milliseconds (the
-    # driver's --steps 20: two registrations, 2.5 ms) whose rate scatters by several per cent from run to run; such a region is therefore
-    # timed REPEATS = 9 times back to back — each one exactly `steps` steps between the barriers — and `value` / `ms_per_step` are those of
-    # the MEDIAN region; every region is listed ("median of >= 5 runs after 1 warm-up").
-    REPEATS = 9 if args.steps < 100 else 1
+    # The timed region (it carries no event records at all): exactly `steps` steps between the barriers.  With --full, a request for
+    # fewer than 100 steps is a region of a few milliseconds (the driver's --steps 20: two registrations, 2.5 ms) whose rate scatters by
+    # several per cent from run to run; such a region is therefore timed REPEATS = 9 times back to back and `value` / `ms_per_step` are
+    # those of the MEDIAN region; every region is listed ("median of >= 5 runs after 1 warm-up").
+    REPEATS = 9 if args.full and args.steps < 100 else 1
     regions = [timed(args.steps) for _ in range(REPEATS)]
     order = sorted(range(REPEATS), key=lambda i: regions[i][2] / regions[i][0])
     steps_done, last, elapsed = regions[order[REPEATS // 2]]
     timed_regions = [{"steps": d, "seconds": e, "iterations_per_s": d / e * (1 if strong else world)} for d, _, e in regions]
-    # the kernel times of the roofline come from PROFILE_ALIGNS further, untimed registrations with HIP events around EVERY pass
-    # (>= 10 cold and >= 20 warm launches instead of the three a sampled timed region gave)
-    ctx.set_profiling(1)
-    for _ in range(PROFILE_ALIGNS):
-        run_align(ITERS_PER_ALIGN)
-    kms = ctx.kernel_ms()
-    stats = problem.pass_stats()
-    ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, regions[-1][1])
+    kms = stats = None
+    if args.full:
+        # the kernel times of the roofline come from PROFILE_ALIGNS further, untimed registrations with HIP events around EVERY pass
+        # (>= 10 cold and >= 20 warm launches instead of the three a sampled timed region gave)
+        ctx.set_profiling(1)
+        for _ in range(PROFILE_ALIGNS):
+            run_align(ITERS_PER_ALIGN)
+        kms = ctx.kernel_ms()
+        stats = problem.pass_stats()
+        ctx.set_profiling(False)
 
     # sanity: the pose the timed registrations converge to
     pose_err_t, pose_err_r = pose_error(last.T_target_source, T_gt)
 
     shard_check = None
-    if strong and world > 1:
+    if args.full and strong and world > 1:
         shard_check = {}
         for m, tol in (("fp64", 1e-9), ("fp32", 1e-5)):
             full = run_align(ITERS_PER_ALIGN, m)  # a complete registration of the sharded job
@@ -324,13 +336,13 @@ def main():
             shard_check["note"] = "fp64 per-pair arithmetic: equal to the rounding of the fp64 row sums; fp32 (the timed mode): the fp32 partial sums group by shard"
 
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         k = max(args.steps, int(args.sustain_s * steps_done / max(elapsed, 1e-6)))
         d2, _, e2 = timed(k)
         sustained = {"steps": d2, "seconds": e2, "iterations_per_s": d2 / e2 * (1 if strong else world)}
 
     fp64 = None
-    if not args.no_fp64 and args.math == "fp32":
+    if args.full and not args.no_fp64 and args.math == "fp32":
         run_steps(ITERS_PER_ALIGN, "fp64")
         d3, l3, e3 = timed(max(40, min(args.steps, 200)), "fp64")
         t3, r3 = pose_error(l3.T_target_source, T_gt)
@@ -338,7 +350,7 @@ def main():
                 "note": "the same steps with fp64 per-pair arithmetic (SGA_MATH_FP64); data in HBM stays fp32"}
 
     per_rank = None
-    if use_dist:  # so that the first real multi-GPU run explains itself: every rank's pass time and its time inside the collective
+    if args.full and use_dist:  # so that the first real multi-GPU run explains itself: every rank's pass time and its time inside the collective
         mine = {"rank": rank, "source_points": src.size(), "k1_avg_us": kms["linearize_ms"] * 1e3, "cold_pass_avg_us": kms["cold_ms"] * 1e3, "warm_pass_avg_us": kms["warm_ms"] * 1e3,
                 "collective_avg_us": kms["comm_ms"] * 1e3, "collective_launches_timed": kms["comm_calls"], "passes_timed": kms["linearize_calls"]}
         per_rank = [None] * world
@@ -347,26 +359,7 @@ def main():
     if rank == 0:
         job_rate = steps_done / elapsed
         value = job_rate * (1 if strong else world)
-        lin_us = kms["linearize_ms"] * 1e3
-        err_us = kms["error_ms"] * 1e3
-        # the search + factor kernel of the cold passes alone: (all passes' - the warm passes') kernel time / cold launches
-        cold_search_us = (kms["search_ms"] * kms["search_calls"] - kms["warm_search_ms"] * kms["warm_calls"]) / max(kms["cold_calls"], 1) * 1e3
         n_rank = src.size()
-        achieved = (ALG_BYTES_PER_POINT["linearize_gicp"] * n_rank) / (lin_us * 1e-6) / 1e9 if lin_us > 0 else None
-        traffic, traffic_source, traffic_measured = None, None, False
-        if world == 1 and not use_dist:
-            traffic, traffic_source = measure_traffic(args)
-            traffic_measured = traffic is not None
-        if traffic is None:
-            why = traffic_source
-            tpath = os.path.join(ROOT, "profiles", "k1_traffic.json")
-            if os.path.exists(tpath):
-                try:
-                    tj = json.load(open(tpath))
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_source = "NOT measured in this run (%s): profiles/k1_traffic.json, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of scripts/profile_gpu.sh at commit %s" % (why, tj.get("commit", "?"))
-                except Exception:  # noqa: BLE001
-                    traffic = None
         out = {
             "metric": "GICP iterations/sec (1M<->1M pts)",
             "value": value,
@@ -393,6 +386,30 @@ def main():
                 "source_points_per_gpu": n_rank,
             },
             "iters_per_sec_job": job_rate,
+            "preprocess_s": prep_s,
+            "final_pose_error": {"trans_m": pose_err_t, "rot_rad": pose_err_r},
+        }
+    if rank == 0 and args.full:
+        lin_us = kms["linearize_ms"] * 1e3
+        err_us = kms["error_ms"] * 1e3
+        # the search + factor kernel of the cold passes alone: (all passes' - the warm passes') kernel time / cold launches
+        cold_search_us = (kms["search_ms"] * kms["search_calls"] - kms["warm_search_ms"] * kms["warm_calls"]) / max(kms["cold_calls"], 1) * 1e3
+        achieved = (ALG_BYTES_PER_POINT["linearize_gicp"] * n_rank) / (lin_us * 1e-6) / 1e9 if lin_us > 0 else None
+        traffic, traffic_source, traffic_measured = None, None, False
+        if world == 1 and not use_dist:
+            traffic, traffic_source = measure_traffic(args)
+            traffic_measured = traffic is not None
+        if traffic is None:
+            why = traffic_source
+            tpath = os.path.join(ROOT, "profiles", "k1_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_source = "NOT measured in this run (%s): profiles/k1_traffic.json, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of scripts/profile_gpu.sh at commit %s" % (why, tj.get("commit", "?"))
+                except Exception:  # noqa: BLE001
+                    traffic = None
+        out.update({
             "timed_regions": {"repeats": REPEATS, "reported": "median" if REPEATS > 1 else "the one region", "regions": timed_regions,
                               "note": "fewer than 100 steps requested: the region of exactly `steps` steps is timed %d times back to back and value / ms_per_step are the median region's" % REPEATS if REPEATS > 1 else "one timed region of `steps` steps"},
             "roofline": {
@@ -422,9 +439,7 @@ def main():
                 "error_kernel_avg_us": err_us if err_us > 0 else None,  # None: no error pass ran (the error model answered)
                 "error_kernel_achieved_GBs": (ALG_BYTES_PER_POINT["error_gicp"] * n_rank) / (err_us * 1e-6) / 1e9 if err_us > 0 else None,
             },
-            "preprocess_s": prep_s,
-            "final_pose_error": {"trans_m": pose_err_t, "rot_rad": pose_err_r},
-        }
+        })
         if MEASURED_VALU:
             # What actually binds K1: the walks are VALU work at a third to a half of the lanes.  A wave64
             # instruction occupies a 16-lane SIMD for 4 cycles; 256 CUs x 4 SIMDs at 2.4 GHz.
@@ -480,7 +495,7 @@ def main():
                 out["helper_c5"] = helper_leg(sga, "c5")
         if world > 1:
             out["scaling_model"] = scaling_model(world, per_rank)
-    if use_dist and native_comm and world > 1 and args.odom_frames > 1:
+    if args.full and use_dist and native_comm and world > 1 and args.odom_frames > 1:
         r = odometry_leg(sga, args, (rank, world, ctx))
         # the other way to spread C5 over the GPUs: whole frame pairs per rank, no collective
         pairs = None
@@ -517,6 +532,16 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, result):
+    """What a caller of the timed path receives from its last step: the RegistrationResult of the last timed registration, one float64
+    .npy per field (a few hundred bytes in all).  The clouds are generated from fixed seeds, so equal arguments give equal inputs."""
+    os.makedirs(path, exist_ok=True)
+    fields = {"T_target_source": result.T_target_source, "H": result.H, "b": result.b, "error": result.error,
+              "num_inliers": result.num_inliers, "iterations": result.iterations, "converged": result.converged}
+    for name, v in fields.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def helper_leg(sga, which):

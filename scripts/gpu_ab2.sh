@@ -1,13 +1,13 @@
 #!/bin/bash
 # same-box A/B of library builds / environment settings: C3 headline, C2 and the odometry leg.  bash scripts/gpu_ab2.sh "A=1" "SGA_LIB_PATH=..." ...
-mkdir -p gpurun_out
-cd /root/repo
+cd "$(dirname "$0")/.."
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg timeout -s KILL 300 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --sustain-s 0 --no-fp64 --no-vgicp --no-policy --no-traffic --odom-frames ${ODOM:-40} > gpurun_out/ab_$i.json 2> gpurun_out/ab_$i.err
-  tail -c 300 gpurun_out/ab_$i.err
-  python - "$cfg" gpurun_out/ab_$i.json <<'PY'
+  env $cfg timeout -s KILL 300 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --sustain-s 0 --no-fp64 --no-vgicp --no-policy --no-traffic --odom-frames ${ODOM:-40} > $OUT/ab_$i.json 2> $OUT/ab_$i.err
+  tail -c 300 $OUT/ab_$i.err
+  python - "$cfg" $OUT/ab_$i.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[2]))
 r = j['roofline']

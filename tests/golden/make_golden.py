@@ -2,6 +2,8 @@
 
   c1_points.npz   raw xyz (float32) of the reference's data/target.ply and data/source.ply plus data/T_target_source.txt
                   (the GPU box has no /root/reference; the intensity channel is dropped, nothing else changes)
+  target_head.ply the reference's data/target.ply cut to its first 256 vertices (header kept, vertex count changed): the PLY
+                  reader's fixture
   c1_oracle.json  outputs of the CPU oracle (oracle/) on config C1 for every factor type: final pose, iterations,
                   num_inliers, final H/b/error and the per-iteration error trace — the 1e-4 parity anchor.
 
@@ -21,7 +23,18 @@ REF = "/root/reference/data"
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
+def write_ply_head(n=256):
+    raw = open(os.path.join(REF, "target.ply"), "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    header = raw[:end].decode("ascii")
+    count = [ln for ln in header.splitlines() if ln.startswith("element vertex ")][0]
+    with open(os.path.join(OUT, "target_head.ply"), "wb") as f:
+        f.write(header.replace(count, "element vertex %d" % n).encode("ascii"))
+        f.write(raw[end:end + 16 * n])  # 4 float properties per vertex
+
+
 def main():
+    write_ply_head()
     tgt = orc.read_ply(os.path.join(REF, "target.ply"))
     src = orc.read_ply(os.path.join(REF, "source.ply"))
     T_gt = np.loadtxt(os.path.join(REF, "T_target_source.txt"))

@@ -456,8 +456,8 @@ def test_c3_frame_invariance(c3):
 
 
 def test_bench_contract():
-    """bench.py prints one JSON line with the contract's keys plus roofline and cpu_baseline (small sizes here)."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--points", "100000", "--cpu-iters", "3"], capture_output=True, text=True, timeout=900)
+    """bench.py --full prints one JSON line with the contract's keys plus roofline and cpu_baseline (small sizes here)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--points", "100000", "--cpu-iters", "3"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     j = json.loads(line)
@@ -465,6 +465,24 @@ def test_bench_contract():
         assert key in j, key
     assert j["value"] > 0 and j["steps"] >= 20 and j["roofline"]["achieved"] > 0 and j["cpu_baseline"]["value"] > 0
     assert j["final_pose_error"]["trans_m"] < 0.02
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps, prints only the headline, and --dump-outputs writes the last timed
+    registration's result as float64 .npy files."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "25", "--warmup", "5", "--points", "100000", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in j, key
+    assert j["steps"] == 25 and j["value"] > 0 and "roofline" not in j and "cpu_baseline" not in j
+    shapes = {"T_target_source": (4, 4), "H": (6, 6), "b": (6,), "error": (), "num_inliers": (), "iterations": (), "converged": ()}
+    got = {name: np.load(tmp_path / (name + ".npy")) for name in shapes}
+    assert all(got[k].dtype == np.float64 and got[k].shape == s for k, s in shapes.items())
+    assert got["iterations"] == 4 and got["num_inliers"] > 0  # 25 steps = 2 registrations of 10 + one of 5
+    dt, _ = pose_error(got["T_target_source"], sga.synthetic.gt_transform())
+    assert dt < 0.02
 
 
 def test_scan_to_scan_odometry_matches_oracle(orc):

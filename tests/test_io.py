@@ -33,15 +33,12 @@ def test_errors_are_reported_not_raised(tmp_path, capsys):
 
 
 def test_reference_ply_matches_committed_points():
-    """The reference's data/target.ply read by this reader == the xyz committed under tests/golden (when the reference tree is present)."""
-    ply = "/root/reference/data/target.ply"
-    if not os.path.exists(ply):
-        import pytest
-
-        pytest.skip("reference tree not present")
-    pts = io.read_ply(ply)
+    """The reference's data/target.ply read by this reader == the xyz committed under tests/golden: tests/golden/target_head.ply is that
+    file's header (comments, obj_info, the intensity property) with its first 256 vertices."""
+    pts = io.read_ply(os.path.join(ROOT, "tests", "golden", "target_head.ply"))
     gold = np.load(os.path.join(ROOT, "tests", "golden", "c1_points.npz"))
-    assert pts.shape == (69088, 4) and (pts[:, :3] == gold["target"]).all()
+    assert len(gold["target"]) == 69088
+    assert pts.shape == (256, 4) and (pts[:, :3] == gold["target"][:256]).all() and (pts[:, 3] == 1).all()
 
 
 def test_trajectory_format(tmp_path):
