@@ -36,7 +36,7 @@ enum sga_status {
   SGA_ERR_INVALID = 1,     /* bad argument */
   SGA_ERR_HIP = 2,         /* a HIP runtime call failed; see sga_last_error() */
   SGA_ERR_NO_DEVICE = 3,   /* no usable gfx950 device: the product path NEVER falls back to the CPU */
-  SGA_ERR_UNSUPPORTED = 4, /* combination not available (e.g. PLANE_ICP against a voxel map) */
+  SGA_ERR_UNSUPPORTED = 4, /* combination not available (e.g. PLANE_ICP against a Gaussian voxel map) */
   SGA_ERR_CALLBACK = 5     /* a user callback returned non-zero */
 };
 
@@ -157,8 +157,25 @@ int sga_flatmap_set_setting(sga_index* flatmap, double min_sq_dist_in_cell, uint
 /* Voxels visited around the query's own (incremental_voxelmap.hpp:157-186): 1 (default), 7 or 27 — for flat AND Gaussian maps, incremental,
  * one-shot or created from host voxels; every visited Gaussian voxel offers its mean, the nearest wins (the first of equal distances). */
 int sga_voxelmap_set_search_offsets(sga_index* voxelmap, int num_offsets);
-/* coords n*3, counts n, points n*16*3 and cov6 n*16*6 (16 slots per voxel, the first counts[v] of them valid); any pointer may be NULL */
+/* coords n*3, counts n, points n*16*3 and cov6 n*16*6 (16 slots per voxel, the first counts[v] of them valid); any pointer may be NULL
+ * (a map without covariances: cov6 is filled with zeros) */
 int sga_flatmap_download(sga_context* ctx, const sga_index* flatmap, int32_t* coords, uint32_t* counts, float* points, float* cov6);
+/* The four contents of the reference's flat container (ann/flat_container.hpp:18-58, FlatContainer<HasNormals, HasCovs>; the Python names
+ * IncrementalVoxelMap / IncrementalVoxelMapNormal / IncrementalVoxelMapCov / IncrementalVoxelMapNormalCov, src/python/voxelmap.cpp:146-151):
+ * `contents` = 0 (points only), SGA_FLAT_NORMALS, SGA_FLAT_COVS or both.  A kept point's normal is R n (T.matrix() * normal, w = 0), its
+ * covariance R C R^T; the accept / reject rule depends on the points alone, so every kind keeps the same points in the same slots.
+ * sga_voxelmap_insert then needs exactly the attributes the map keeps.  Targets: ICP for every kind, PLANE_ICP where the map keeps normals
+ * (its target normal is the one stored in the matched slot), GICP where it keeps covariances.  sga_flatmap_create = SGA_FLAT_COVS. */
+enum { SGA_FLAT_NORMALS = 1, SGA_FLAT_COVS = 2 };
+int sga_flatmap_create_contents(sga_context* ctx, double leaf_size, int contents, sga_index** out);
+/* Which contents a flat map keeps (SGA_FLAT_NORMALS | SGA_FLAT_COVS bits). */
+int sga_flatmap_get_contents(const sga_index* flatmap, int* contents);
+/* sga_flatmap_download with the normals: normals n*16*3 floats.  normals / cov6 must be NULL where the map keeps none (SGA_ERR_INVALID). */
+int sga_flatmap_download_contents(sga_context* ctx, const sga_index* flatmap, int32_t* coords, uint32_t* counts, float* points, float* normals, float* cov6);
+/* sga_index_create_flatmap_from_voxels with the normals of the slots (normals3 n*16*3 doubles, NULL = none): the reference's
+ * IncrementalVoxelMap<FlatContainer<HasNormals, HasCovs>> object as it is.  The contents follow the non-NULL arrays. */
+int sga_index_create_flatmap_from_voxels_contents(sga_context* ctx, double leaf_size, const int32_t* coords, const uint32_t* counts, const double* points3, const double* normals3, const double* cov6, int search_offsets, size_t n,
+                                                   sga_index** out);
 /* traits::knn_search / nearest_neighbor_search (ann/traits.hpp:22-57) for m host queries (m*3 floats):
  * idx m*k int64 (original target indices, -1 = none), sq_dist m*k floats ascending (inf = none).
  * max_sq_dist < 0 means unbounded.  k <= 116 for kd-trees.  Voxel maps (Gaussian and flat, incremental_voxelmap.hpp:99-149): any
@@ -195,7 +212,9 @@ int sga_linearize(sga_context* ctx, sga_problem* problem, const sga_factor_param
 /* Sum_i e_i at T with the correspondences and mahalanobis cached by the last sga_linearize (gicp_factor.hpp:80-89).  With those
  * frozen the sum is a quadratic polynomial in T: sga_linearize accumulates its coefficients next to H / b (63 more sums) and this
  * call evaluates it on the host — no pass over the cloud, no device round trip.  Robust kernels (not quadratic) and calls after
- * sga_linearize_async run the error kernel. */
+ * sga_linearize_async run the error kernel.  Every factor has a fixed matrix per pair once the correspondence is frozen (GICP its cached
+ * mahalanobis, PLANE_ICP diag(n * n) of the matched target normal — also the normal of a flat map's slot, ICP I), so the model serves every
+ * (factor, target) combination sga_linearize accepts. */
 int sga_error(sga_context* ctx, sga_problem* problem, const sga_factor_params* params, const double T[16], double* e);
 /* Enqueue-only forms for multi-GPU: results stay in device memory so they can be all-reduced (RCCL) on the same stream before
  * the host reads them.  d_out30: [0..20] upper triangle of H row-wise, [21..26] b, [27] e, [28] num_inliers (as double), [29] 0.
@@ -236,7 +255,8 @@ int sga_problem_set_rejector(sga_problem* problem, sga_rejector_fn fn, void* use
 /* Factor::linearize per source point, as the reference's Python binding exposes it (src/python/factors.cpp:52-101; gicp_factor.hpp:35-73,
  * icp_factor.hpp:20-54, plane_icp_factor.hpp:19-57): runs one linearization at T, then returns for every source point (caller's order)
  * values28 n*28 doubles = [0..20] upper triangle of H_i row-wise, [21..26] b_i, [27] e_i, and inlier n bytes (0: no correspondence, all
- * values 0).  kd-tree targets; per-pair arithmetic in fp64.  A diagnostic / binding entry point, not the hot path. */
+ * values 0).  kd-tree targets, and flat voxel maps (the correspondences of that linearization); per-pair arithmetic in fp64.  A diagnostic /
+ * binding entry point, not the hot path. */
 int sga_linearize_per_point(sga_context* ctx, sga_problem* problem, const sga_factor_params* params, const double T[16], double* values28, unsigned char* inlier);
 /* Factor state in the caller's source order: target_index n int64 (-1 = outlier; voxel id for voxel maps), mahalanobis6 n*6 floats (GICP only). */
 int sga_problem_get_factors(sga_context* ctx, const sga_problem* problem, int64_t* target_index, float* mahalanobis6);

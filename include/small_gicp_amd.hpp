@@ -250,17 +250,24 @@ struct GaussianVoxelMap {
   sga_index* h = nullptr;
 };
 
-// ann/flat_container.hpp + ann/incremental_voxelmap.hpp: IncrementalVoxelMap<FlatContainerCov>, the scan-to-model GICP target
-struct FlatContainerCov {
+// ann/flat_container.hpp + ann/incremental_voxelmap.hpp: IncrementalVoxelMap<FlatContainer<HasNormals, HasCovs>>, the scan-to-model
+// targets (flat_container.hpp:18-58 and its aliases FlatContainerPoints / Normal / Cov / NormalCov).  `contents` selects what the device
+// map keeps next to the points (sga_flatmap_create_contents); an insert needs exactly those attributes.  Points: ICP; Normal: ICP and
+// PLANE_ICP (Faster-LIO's linear iVox); Cov: ICP and GICP (odometry_benchmark_small_gicp_model_omp.cpp); NormalCov: all three.
+template <int Contents>
+struct FlatContainer {
+  static constexpr int contents = Contents;
   struct Setting {
     double min_sq_dist_in_cell = 0.1 * 0.1;
     size_t max_num_points_in_cell = 10;
   };
 };
+using FlatContainerPoints = FlatContainer<0>;
+using FlatContainerNormal = FlatContainer<SGA_FLAT_NORMALS>;
+using FlatContainerCov = FlatContainer<SGA_FLAT_COVS>;
+using FlatContainerNormalCov = FlatContainer<SGA_FLAT_NORMALS | SGA_FLAT_COVS>;
 template <typename VoxelContents>
-struct IncrementalVoxelMap;
-template <>
-struct IncrementalVoxelMap<FlatContainerCov> {
+struct IncrementalVoxelMap {
   using Ptr = std::shared_ptr<IncrementalVoxelMap>;
   explicit IncrementalVoxelMap(double leaf_size) : leaf(leaf_size) {}
   IncrementalVoxelMap(const IncrementalVoxelMap&) = delete;
@@ -269,7 +276,7 @@ struct IncrementalVoxelMap<FlatContainerCov> {
   void insert(const PointCloud& points, const Isometry3d& T = Isometry3d::Identity()) {
     if (!h) {
       ctx = points.ctx;
-      check(sga_flatmap_create(ctx, leaf, &h), "sga_flatmap_create");
+      check(sga_flatmap_create_contents(ctx, leaf, VoxelContents::contents, &h), "sga_flatmap_create_contents");
       check(sga_flatmap_set_setting(h, voxel_setting.min_sq_dist_in_cell, static_cast<uint32_t>(voxel_setting.max_num_points_in_cell)), "sga_flatmap_set_setting");
       check(sga_voxelmap_set_lru(h, static_cast<uint32_t>(lru_horizon), static_cast<uint32_t>(lru_clear_cycle)), "sga_voxelmap_set_lru");
       check(sga_voxelmap_set_search_offsets(h, num_search_offsets), "sga_voxelmap_set_search_offsets");
@@ -291,7 +298,7 @@ struct IncrementalVoxelMap<FlatContainerCov> {
   static size_t point_id(size_t i) { return i & 0xffffffffull; }
   double leaf;
   size_t lru_horizon = 100, lru_clear_cycle = 10;  // set before the first insert
-  FlatContainerCov::Setting voxel_setting;          // set before the first insert
+  typename VoxelContents::Setting voxel_setting;    // set before the first insert
   int num_search_offsets = 1;
   sga_context* ctx = nullptr;
   sga_index* h = nullptr;
@@ -503,9 +510,11 @@ struct Registration {
     (void)target_tree;
     return run(target.h, source, init_T);
   }
-  /// scan-to-model GICP form (odometry_benchmark_small_gicp_model_omp.cpp:33-36)
+  /// scan-to-model forms (odometry_benchmark_small_gicp_model_omp.cpp:33-36): GICPFactor against FlatContainerCov / NormalCov,
+  /// PointToPlaneICPFactor against FlatContainerNormal / NormalCov, ICPFactor against any of the four
+  template <typename VoxelContents>
   RegistrationResult align(
-    const IncrementalVoxelMap<FlatContainerCov>& target, const PointCloud& source, const IncrementalVoxelMap<FlatContainerCov>& target_tree, const Isometry3d& init_T = Isometry3d::Identity()) const {
+    const IncrementalVoxelMap<VoxelContents>& target, const PointCloud& source, const IncrementalVoxelMap<VoxelContents>& target_tree, const Isometry3d& init_T = Isometry3d::Identity()) const {
     (void)target_tree;
     return run(target.h, source, init_T);
   }

@@ -2,7 +2,8 @@
 served by the MI355X engine (small_gicp_amd, through the C-ABI of include/small_gicp_amd.h).
 
 Scope: the subset exercised by the reference's own src/test/python_test.py and src/example/basic_registration.py
-(SURVEY.md §8f row 1): PointCloud, KdTree, GaussianVoxelMap, read_ply, voxelgrid_sampling, estimate_normals /
+(SURVEY.md §8f row 1): PointCloud, KdTree, GaussianVoxelMap, the four flat voxel maps IncrementalVoxelMap /
+IncrementalVoxelMapNormal / IncrementalVoxelMapCov / IncrementalVoxelMapNormalCov (voxelmap.cpp:146-151), read_ply, voxelgrid_sampling, estimate_normals /
 estimate_covariances / estimate_normals_covariances, preprocess_points, the three align() overloads, RegistrationResult,
 DistanceRejector and the per-point factors ICPFactor / PointToPlaneICPFactor / GICPFactor.
 
@@ -13,7 +14,16 @@ import numpy as np
 
 import small_gicp_amd.api as _api
 from small_gicp_amd import io as _io
-from small_gicp_amd.api import GaussianVoxelMap, IncrementalVoxelMapCov, KdTree, PointCloud, RegistrationResult  # noqa: F401
+from small_gicp_amd.api import (  # noqa: F401
+    GaussianVoxelMap,
+    IncrementalVoxelMap,
+    IncrementalVoxelMapCov,
+    IncrementalVoxelMapNormal,
+    IncrementalVoxelMapNormalCov,
+    KdTree,
+    PointCloud,
+    RegistrationResult,
+)
 
 _DEG01 = 0.1 * np.pi / 180.0
 
@@ -185,6 +195,6 @@ class GICPFactor(_PointFactor):
 
 
 __all__ = [
-    "PointCloud", "KdTree", "GaussianVoxelMap", "IncrementalVoxelMapCov", "RegistrationResult", "read_ply", "voxelgrid_sampling", "estimate_normals", "estimate_covariances",
+    "PointCloud", "KdTree", "GaussianVoxelMap", "IncrementalVoxelMap", "IncrementalVoxelMapNormal", "IncrementalVoxelMapCov", "IncrementalVoxelMapNormalCov", "RegistrationResult", "read_ply", "voxelgrid_sampling", "estimate_normals", "estimate_covariances",
     "estimate_normals_covariances", "preprocess_points", "align", "DistanceRejector", "ICPFactor", "PointToPlaneICPFactor", "GICPFactor",
 ]

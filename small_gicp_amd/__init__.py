@@ -9,7 +9,10 @@ from ._lib import GICP, ICP, LIB_PATH, PLANE_ICP, SgaError, load  # noqa: F401
 from .api import (  # noqa: F401
     Context,
     GaussianVoxelMap,
+    IncrementalVoxelMap,
     IncrementalVoxelMapCov,
+    IncrementalVoxelMapNormal,
+    IncrementalVoxelMapNormalCov,
     KdTree,
     MultiProblem,
     PointCloud,

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SGA_LIB_PATH") or os.path.join(_HERE, "lib", "libsmal
 
 SGA_OK = 0
 ICP, PLANE_ICP, GICP = 0, 1, 2
+FLAT_NORMALS, FLAT_COVS = 1, 2  # contents of a flat voxel map (sga_flatmap_create_contents)
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
 LEVENBERG_MARQUARDT, GAUSS_NEWTON = 0, 1
 MATH_FP32, MATH_FP64 = 0, 1
@@ -103,6 +104,10 @@ SYMBOLS = [
     ("sga_flatmap_set_setting", C.c_int, [_vp, C.c_double, C.c_uint32]),
     ("sga_voxelmap_set_search_offsets", C.c_int, [_vp, C.c_int]),
     ("sga_flatmap_download", C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _fp, _fp]),
+    ("sga_flatmap_create_contents", C.c_int, [_vp, C.c_double, C.c_int, _pvp]),
+    ("sga_flatmap_get_contents", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("sga_flatmap_download_contents", C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _fp, _fp, _fp]),
+    ("sga_index_create_flatmap_from_voxels_contents", C.c_int, [_vp, C.c_double, C.c_void_p, C.c_void_p, _dp, _dp, _dp, C.c_int, C.c_size_t, _pvp]),
     ("sga_index_knn", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_int64), _fp]),
     ("sga_index_knn_f64", C.c_int, [_vp, _vp, _dp, C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_int64), _dp]),
     ("sga_factor_params_default", None, [C.POINTER(FactorParams)]),

@@ -427,18 +427,22 @@ class GaussianVoxelMap:
         return out
 
 
-class IncrementalVoxelMapCov:
-    """small_gicp.IncrementalVoxelMapCov (src/python/voxelmap.cpp:110-140) = IncrementalVoxelMap<FlatContainerCov>: voxels keep up
-    to `max_num_points_in_cell` of the inserted points (with covariances); the scan-to-model GICP target.  `insert(cloud, T)`,
-    `set_lru`, `set_search_offsets(1 | 7 | 27)`, `size()`, `voxel_points()`, `voxel_covs()`."""
+class _FlatVoxelMap:
+    """IncrementalVoxelMap<FlatContainer<HasNormals, HasCovs>> (ann/flat_container.hpp:18-58; src/python/voxelmap.cpp:146-151): voxels keep
+    up to `max_num_points_in_cell` of the inserted points and, where the kind keeps them, the normals R n and covariances R C R^T of the
+    points they keep.  `insert(cloud, T)` (the cloud needs exactly the attributes the map keeps), `set_lru`, `set_setting`,
+    `set_search_offsets(1 | 7 | 27)`, `size()` / `len()`, `voxel_points()`, `knn_search` / `batch_knn_search`, `download()`, `from_voxels`.
+    Targets: ICP for every kind, PLANE_ICP where the map keeps normals, GICP where it keeps covariances."""
 
     FLAT_CAP = 16
+    CONTENTS = 0  # _lib.FLAT_NORMALS | _lib.FLAT_COVS bits
 
     def __init__(self, leaf_size, ctx=None):
         self.leaf = float(leaf_size)
         self.ctx = ctx or default_context()
         self.h = C.c_void_p()
-        check(load().sga_flatmap_create(self.ctx.h, self.leaf, C.byref(self.h)))
+        self.contents = self.CONTENTS
+        check(load().sga_flatmap_create_contents(self.ctx.h, self.leaf, int(self.CONTENTS), C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None) and self.h.value:
@@ -460,10 +464,7 @@ class IncrementalVoxelMapCov:
         return idx[0], d2[0]
 
     @classmethod
-    def from_voxels(cls, leaf_size, coords, counts, points, cov6=None, search_offsets=1, ctx=None):
-        """A map from voxels that exist on the host in the reference's flat order (sga_index_create_flatmap_from_voxels: what
-        ParallelReductionHIP uploads for an IncrementalVoxelMap<FlatContainer*> target): coords (V, 3), counts (V,), points (P, 3) and
-        cov6 (P, 6) with the points of voxel 0 first, then voxel 1, ... like download().  A search target only."""
+    def _from_voxels(cls, leaf_size, coords, counts, points, normals, cov6, search_offsets, ctx):
         self = cls.__new__(cls)
         self.leaf = float(leaf_size)
         self.ctx = ctx or default_context()
@@ -475,15 +476,27 @@ class IncrementalVoxelMapCov:
         if len(counts) != n or int(counts.sum()) != len(points) or (n and counts.max() > cls.FLAT_CAP):
             raise ValueError("counts must have one entry per voxel (<= %d) and sum to the number of points" % cls.FLAT_CAP)
         valid = np.arange(cls.FLAT_CAP)[None, :] < counts[:, None]
-        p16 = np.zeros((n, cls.FLAT_CAP, 3))
-        p16[valid] = points
-        c16 = None
-        if cov6 is not None:
-            c16 = np.zeros((n, cls.FLAT_CAP, 6))
-            c16[valid] = np.asarray(cov6, dtype=np.float64).reshape(-1, 6)
-        check(load().sga_index_create_flatmap_from_voxels(self.ctx.h, self.leaf, coords.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), _dp(p16), None if c16 is None else _dp(c16),
-                                                          int(search_offsets), n, C.byref(self.h)))
+
+        def slots(a, width):
+            if a is None:
+                return None
+            out = np.zeros((n, cls.FLAT_CAP, width))
+            out[valid] = np.asarray(a, dtype=np.float64).reshape(-1, np.asarray(a).shape[-1])[:, :width]
+            return out
+
+        p16, n16, c16 = slots(points, 3), slots(normals, 3), slots(cov6, 6)
+        self.contents = (_lib.FLAT_NORMALS if n16 is not None else 0) | (_lib.FLAT_COVS if c16 is not None else 0)
+        check(load().sga_index_create_flatmap_from_voxels_contents(self.ctx.h, self.leaf, coords.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), _dp(p16), None if n16 is None else _dp(n16),
+                                                                   None if c16 is None else _dp(c16), int(search_offsets), n, C.byref(self.h)))
         return self
+
+    @classmethod
+    def from_voxels(cls, leaf_size, coords, counts, points, cov6=None, search_offsets=1, ctx=None, normals=None):
+        """A map from voxels that exist on the host in the reference's flat order (sga_index_create_flatmap_from_voxels_contents: what
+        ParallelReductionHIP uploads for an IncrementalVoxelMap<FlatContainer*> target): coords (V, 3), counts (V,), points (P, 3), normals
+        (P, 3 or 4) and cov6 (P, 6) with the points of voxel 0 first, then voxel 1, ... like download().  The map keeps what is given.  A
+        search target only."""
+        return cls._from_voxels(leaf_size, coords, counts, points, normals, cov6, search_offsets, ctx)
 
     def set_setting(self, min_sq_dist_in_cell=0.01, max_num_points_in_cell=10):
         check(load().sga_flatmap_set_setting(self.h, float(min_sq_dist_in_cell), int(max_num_points_in_cell)))
@@ -498,6 +511,81 @@ class IncrementalVoxelMapCov:
 
     __len__ = size
 
+    def _download(self, normals, covs):
+        n = self.size()
+        coords = np.empty((n, 3), np.int32)
+        counts = np.empty(n, np.uint32)
+        pts = np.empty((n, self.FLAT_CAP, 3), np.float32)
+        nr = np.empty((n, self.FLAT_CAP, 3), np.float32) if normals else None
+        c6 = np.empty((n, self.FLAT_CAP, 6), np.float32) if covs else None
+        check(load().sga_flatmap_download_contents(self.ctx.h, self.h, coords.ctypes.data_as(C.POINTER(C.c_int32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(pts), None if nr is None else _fp(nr),
+                                                   None if c6 is None else _fp(c6)))
+        valid = np.arange(self.FLAT_CAP)[None, :] < counts[:, None]
+        return coords, counts, pts[valid], None if nr is None else nr[valid], None if c6 is None else c6[valid]
+
+    def download(self):
+        """coords (V,3), counts (V,), points (P,3), then normals (P,3) and cov6 (P,6) where the map keeps them: the points of voxel 0 first,
+        then voxel 1, ... (P = sum of counts)."""
+        coords, counts, pts, nr, c6 = self._download(self.contents & _lib.FLAT_NORMALS, self.contents & _lib.FLAT_COVS)
+        return (coords, counts, pts) + tuple(a for a in (nr, c6) if a is not None)
+
+    def voxel_points(self):
+        p = self._download(False, False)[2].astype(np.float64)
+        return np.concatenate([p, np.ones((len(p), 1))], axis=1)
+
+    def _voxel_normals(self):
+        nr = self._download(True, False)[3].astype(np.float64)
+        return np.concatenate([nr, np.zeros((len(nr), 1))], axis=1)
+
+    def _voxel_covs(self):
+        c6 = self._download(False, True)[4].astype(np.float64)
+        out = np.zeros((len(c6), 4, 4))
+        out[:, :3, :3] = mats_from_sym6(c6)
+        return out
+
+
+class IncrementalVoxelMap(_FlatVoxelMap):
+    """small_gicp.IncrementalVoxelMap = IncrementalVoxelMap<FlatContainerPoints>: points only, the plain scan-to-model ICP target."""
+
+    CONTENTS = 0
+
+
+class IncrementalVoxelMapNormal(_FlatVoxelMap):
+    """small_gicp.IncrementalVoxelMapNormal = IncrementalVoxelMap<FlatContainerNormal>: points with normals, the scan-to-model
+    point-to-plane target (Faster-LIO's linear iVox).  `voxel_normals()`: P x 4, w = 0."""
+
+    CONTENTS = _lib.FLAT_NORMALS
+
+    def voxel_normals(self):
+        return self._voxel_normals()
+
+
+class IncrementalVoxelMapNormalCov(_FlatVoxelMap):
+    """small_gicp.IncrementalVoxelMapNormalCov = IncrementalVoxelMap<FlatContainerNormalCov>: points with normals and covariances."""
+
+    CONTENTS = _lib.FLAT_NORMALS | _lib.FLAT_COVS
+
+    def voxel_normals(self):
+        return self._voxel_normals()
+
+    def voxel_covs(self):
+        return self._voxel_covs()
+
+
+class IncrementalVoxelMapCov(_FlatVoxelMap):
+    """small_gicp.IncrementalVoxelMapCov (src/python/voxelmap.cpp:110-140) = IncrementalVoxelMap<FlatContainerCov>: voxels keep up
+    to `max_num_points_in_cell` of the inserted points (with covariances); the scan-to-model GICP target.  `insert(cloud, T)`,
+    `set_lru`, `set_search_offsets(1 | 7 | 27)`, `size()`, `voxel_points()`, `voxel_covs()`."""
+
+    CONTENTS = _lib.FLAT_COVS
+
+    @classmethod
+    def from_voxels(cls, leaf_size, coords, counts, points, cov6=None, search_offsets=1, ctx=None):
+        """A map from voxels that exist on the host in the reference's flat order (sga_index_create_flatmap_from_voxels: what
+        ParallelReductionHIP uploads for an IncrementalVoxelMap<FlatContainer*> target): coords (V, 3), counts (V,), points (P, 3) and
+        cov6 (P, 6) with the points of voxel 0 first, then voxel 1, ... like download().  A search target only."""
+        return cls._from_voxels(leaf_size, coords, counts, points, None, cov6, search_offsets, ctx)
+
     def download(self):
         """coords (V,3), counts (V,), points (P,3), cov6 (P,6): the points of voxel 0 first, then voxel 1, ... (P = sum of counts)."""
         n = self.size()
@@ -508,10 +596,6 @@ class IncrementalVoxelMapCov:
         check(load().sga_flatmap_download(self.ctx.h, self.h, coords.ctypes.data_as(C.POINTER(C.c_int32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(pts), _fp(c6)))
         valid = np.arange(self.FLAT_CAP)[None, :] < counts[:, None]
         return coords, counts, pts[valid], c6[valid]
-
-    def voxel_points(self):
-        p = self.download()[2].astype(np.float64)
-        return np.concatenate([p, np.ones((len(p), 1))], axis=1)
 
     def voxel_covs(self):
         c6 = self.download()[3].astype(np.float64)

@@ -1433,6 +1433,7 @@ int sga_index_clone(sga_context* ctx, const sga_index* src, sga_index** out) {
   SGA_TRY(copy_buf(ctx, idx->vcov64, src->vcov64, sd));
   SGA_TRY(copy_buf(ctx, idx->vlru, src->vlru, sd));
   SGA_TRY(copy_buf(ctx, idx->fpts64, src->fpts64, sd));
+  SGA_TRY(copy_buf(ctx, idx->fnrm64, src->fnrm64, sd));
   SGA_TRY(copy_buf(ctx, idx->fcov64, src->fcov64, sd));
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
   SGA_TRY(mark_ready(ctx, idx->ready));

@@ -375,7 +375,8 @@ constexpr int kPathRecords = 10;      // pair records fetched at once by kd_push
 template <typename Real, int FACTOR, int TARGET, int PTS, bool FRESH_NN = false, bool CERT = false, bool STAGED = false>
 __device__ __forceinline__ void linearize_group(const LinParams<Real>& p, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks = nullptr);
 template <typename Real, int FACTOR>
-__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out);
+__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
+                                             const float4* nn_pre = nullptr);
 template <typename Real, int PTS>
 __device__ __forceinline__ void accumulate_moments(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3], const Real (&E)[PTS], int inliers, double* __restrict__ acc_row, int lane);
 
@@ -663,8 +664,10 @@ __host__ __device__ inline bool is_derived_col(int c) { return c < 15 || (c >= 2
 
 // M' and g of one correspondence (weighted by the robust kernel), its error, and whether it is an inlier; caches the mahalanobis
 // matrix for the error pass.  (The direct form — the 28 values of pair_system — is pair_factor below; the per-point export uses it.)
+// nn_pre (PLANE_ICP): the target normal when the caller has fetched it already (linearize_group over a flat map), else it is read here
 template <typename Real, int FACTOR>
-__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out) {
+__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
+                                             const float4* nn_pre) {
   const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
   const Real d2 = rx * rx + ry * ry + rz * rz;
   const bool inlier = (j >= 0) && within_bound && !(d2 > static_cast<Real>(p.max_sq));
@@ -680,7 +683,7 @@ __device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, in
       M = inverse_sym<Real>({Ct.xx + RCR.xx, Ct.xy + RCR.xy, Ct.xz + RCR.xz, Ct.yy + RCR.yy, Ct.yz + RCR.yz, Ct.zz + RCR.zz});
       M_out = M;  // the caller caches it for the error pass (gicp_factor.hpp:80-89)
     } else if constexpr (FACTOR == SGA_PLANE_ICP) {
-      const float4 nn = p.tgt_nrm[j];
+      const float4 nn = nn_pre != nullptr ? *nn_pre : p.tgt_nrm[j];
       M = {Real(nn.x) * Real(nn.x), Real(0), Real(0), Real(nn.y) * Real(nn.y), Real(0), Real(nn.z) * Real(nn.z)};
     } else {
       M = {Real(1), Real(0), Real(0), Real(1), Real(0), Real(1)};
@@ -965,6 +968,14 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
   }
   Sym3<Real> Mh[PTS];  // the mahalanobis matrices, stored after the last load
   bool inl[PTS];
+  // point-to-plane over a flat map: the normals of the PTS slots the search has just found, one 16-byte gather each, in flight together
+  constexpr bool kFlatNormals = TARGET == 2 && FACTOR == SGA_PLANE_ICP;
+  float4 nn4[kFlatNormals ? PTS : 1];
+  if constexpr (kFlatNormals) {
+    SGA_STAGE_PARAMS(p);
+#pragma unroll
+    for (int u = 0; u < PTS; u++) nn4[u] = act[u] && jn[u] >= 0 ? p.tgt_nrm[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   {
   SGA_STAGE_PARAMS(p);
 #pragma unroll
@@ -974,7 +985,7 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
     Mp[u] = Sym3<Real>{};
     Mh[u] = Sym3<Real>{};
     G[u][0] = G[u][1] = G[u][2] = E[u] = Real(0);
-    if (act[u]) inl[u] = pair_moments<Real, FACTOR>(p, i, jn[u], within[u], Q[u][0], Q[u][1], Q[u][2], Tg[u][0], Tg[u][1], Tg[u][2], Mp[u], G[u], E[u], Mh[u]);
+    if (act[u]) inl[u] = pair_moments<Real, FACTOR>(p, i, jn[u], within[u], Q[u][0], Q[u][1], Q[u][2], Tg[u][0], Tg[u][1], Tg[u][2], Mp[u], G[u], E[u], Mh[u], kFlatNormals ? &nn4[u] : nullptr);
     inliers += __popcll(__ballot(inl[u]));
   }
   }
@@ -1243,8 +1254,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CHECK ? SGA_
 
 // Per-point export of the same factors (the reference's Python binding exposes Factor::linearize per source point,
 // src/python/factors.cpp:52-101): the 28 values of every pair instead of their sum.  Runs after a linearize pass at the same pose
-// (the neighbours come from hint[]); not on the hot path.
-template <typename Real, int FACTOR>
+// (kd-tree: the neighbours come from hint[]; flat map, FLAT: the correspondences that pass kept in corr[], slot or -1); not on the hot path.
+template <typename Real, int FACTOR, bool FLAT = false>
 __global__ __launch_bounds__(256) void per_point_kernel(const LinParams<Real> p, double* __restrict__ out28, unsigned char* __restrict__ ok) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
@@ -1255,7 +1266,7 @@ __global__ __launch_bounds__(256) void per_point_kernel(const LinParams<Real> p,
   Real vals[28];
 #pragma unroll
   for (int k = 0; k < 28; k++) vals[k] = Real(0);
-  const int j = p.hint[i];
+  const int j = FLAT ? p.corr[i] : p.hint[i];
   Real tx = 0, ty = 0, tz = 0;
   bool within = false;
   if (j >= 0) {
@@ -1263,7 +1274,7 @@ __global__ __launch_bounds__(256) void per_point_kernel(const LinParams<Real> p,
     tx = m.x;
     ty = m.y;
     tz = m.z;
-    within = kd_dist2(m.x, m.y, m.z, static_cast<float>(qx), static_cast<float>(qy), static_cast<float>(qz)) < p.bound2;
+    within = FLAT || kd_dist2(m.x, m.y, m.z, static_cast<float>(qx), static_cast<float>(qy), static_cast<float>(qz)) < p.bound2;
   }
   const bool inlier = pair_factor<Real, FACTOR>(p, i, j, within, px, py, pz, qx, qy, qz, tx, ty, tz, vals);
   const uint32_t orig = __float_as_uint(ps4.w);  // the caller's source order
@@ -1571,7 +1582,9 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
   const bool voxel = idx->kind != SGA_INDEX_KDTREE;  // Gaussian or flat voxel map: the lookup happens inside the factor kernel
   const bool flat = idx->kind == SGA_INDEX_FLATMAP;
   if (fp->factor_kind == SGA_GICP && ((pb->n > 0 && !pb->has_covs) || (idx->n > 0 && !idx->has_covs))) return fail(SGA_ERR_INVALID, "GICP needs covariances on both source and target");
-  if (fp->factor_kind == SGA_PLANE_ICP && (voxel || (idx->n > 0 && !idx->has_normals))) return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals");
+  // PLANE_ICP: a kd-tree over a target with normals, or a flat map that keeps normals (per slot, under the slot numbering flat_nearest returns)
+  if (fp->factor_kind == SGA_PLANE_ICP && ((voxel && !flat) || ((flat || idx->n > 0) && !idx->has_normals)))
+    return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals");
   if (fp->factor_kind < 0 || fp->factor_kind > 2) return fail(SGA_ERR_INVALID, "invalid factor_kind %d", fp->factor_kind);
 
   LinParams<Real> p{};
@@ -1849,6 +1862,8 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
     if (flat) {
       if (fp->factor_kind == SGA_GICP)
         launch_linearize<Real, SGA_GICP, 2>(ctx->stream, p, blocks, pts);
+      else if (fp->factor_kind == SGA_PLANE_ICP)
+        launch_linearize<Real, SGA_PLANE_ICP, 2>(ctx->stream, p, blocks, pts);
       else
         launch_linearize<Real, SGA_ICP, 2>(ctx->stream, p, blocks, pts);
     } else if (voxel) {
@@ -2188,7 +2203,8 @@ void sga_unpack_accumulator(const double acc[SGA_ACCUM_DOUBLES], double H[36], d
 int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double* values28, unsigned char* inlier) {
   SGA_TRY(check_args(ctx, pb, fp, T));
   if (!values28 || !inlier) return fail(SGA_ERR_INVALID, "null output");
-  if (pb->target->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_UNSUPPORTED, "per-point factors need a kd-tree target");
+  const bool flat = pb->target->kind == SGA_INDEX_FLATMAP;
+  if (pb->target->kind != SGA_INDEX_KDTREE && !flat) return fail(SGA_ERR_UNSUPPORTED, "per-point factors need a kd-tree target");
   SGA_ENTER(ctx);
   double H[36], b[6], e = 0;
   uint64_t ninl = 0;
@@ -2202,7 +2218,7 @@ int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_
   p.src_pts = pb->src_pts();
   p.src_cov = pb->src_cov();
   p.n = static_cast<int>(n);
-  p.tgt_pts = idx->kd_pts.p;
+  p.tgt_pts = flat ? idx->pts.p : idx->kd_pts.p;
   p.tgt_nrm = idx->nrm.p;
   p.tgt_cov = idx->cov.p;
   p.corr = pb->corr.p;
@@ -2219,10 +2235,18 @@ int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_
   SGA_TRY(d_vals.alloc(n * 28));
   SGA_TRY(d_ok.alloc(n));
   const dim3 grid((n + 255) / 256), block(256);
-  switch (fp->factor_kind) {
-    case SGA_GICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_GICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-    case SGA_PLANE_ICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_PLANE_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-    default: hipLaunchKernelGGL((per_point_kernel<double, SGA_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+  if (flat) {
+    switch (fp->factor_kind) {
+      case SGA_GICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_GICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+      case SGA_PLANE_ICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_PLANE_ICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+      default: hipLaunchKernelGGL((per_point_kernel<double, SGA_ICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+    }
+  } else {
+    switch (fp->factor_kind) {
+      case SGA_GICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_GICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+      case SGA_PLANE_ICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_PLANE_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+      default: hipLaunchKernelGGL((per_point_kernel<double, SGA_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
+    }
   }
   SGA_HIP(hipGetLastError());
   SGA_HIP(hipMemcpyAsync(values28, d_vals.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

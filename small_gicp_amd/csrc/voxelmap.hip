@@ -188,13 +188,16 @@ __global__ void ivm_export_kernel(uint32_t n, const double* __restrict__ mean64,
   mcov[v] = o;
 }
 
-// ---- flat maps: IncrementalVoxelMap<FlatContainerCov> ---------------------------------------------------------------------------
-// One lane per voxel of the batch: FlatContainer::add for its points in insertion order (flat_container.hpp:33-51): a point is
-// kept iff the cell holds fewer than max_points and no kept point lies closer than sqrt(min_sq); kept = T p with covariance R C R^T.
+// ---- flat maps: IncrementalVoxelMap<FlatContainer<NRM, COV>> ------------------------------------------------------------------------
+// One lane per voxel of the batch: FlatContainer::add for its points in insertion order (flat_container.hpp:33-58): a point is
+// kept iff the cell holds fewer than max_points and no kept point lies closer than sqrt(min_sq); kept = T p, with the normal R n
+// (T.matrix() * normal, w = 0) and the covariance R C R^T where the map keeps them.  The decision reads the points alone: every kind of
+// contents keeps the same points in the same slots.  Kinds without covariances (normals) read no cloud covariances (normals).
+template <bool NRM, bool COV>
 __global__ void fvm_update_kernel(
   uint32_t nseg, const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_vid, uint32_t n_valid, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ order, const float4* __restrict__ pts,
-  const Cov8* __restrict__ cov, Pose12 T, uint32_t n_old, uint32_t lru_counter, uint32_t max_points, double min_sq, double* __restrict__ fpts64, double* __restrict__ fcov64, uint32_t* __restrict__ counts,
-  uint32_t* __restrict__ lru, int* __restrict__ coords, unsigned long long* __restrict__ hkeys, uint32_t* __restrict__ hvals, uint32_t hmask) {
+  const float4* __restrict__ nrm, const Cov8* __restrict__ cov, Pose12 T, uint32_t n_old, uint32_t lru_counter, uint32_t max_points, double min_sq, double* __restrict__ fpts64, double* __restrict__ fnrm64,
+  double* __restrict__ fcov64, uint32_t* __restrict__ counts, uint32_t* __restrict__ lru, int* __restrict__ coords, unsigned long long* __restrict__ hkeys, uint32_t* __restrict__ hvals, uint32_t hmask) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nseg) return;
   const uint32_t v = seg_vid[s];
@@ -203,7 +206,6 @@ __global__ void fvm_update_kernel(
   const bool is_new = v >= n_old;
   uint32_t cnt = is_new ? 0u : counts[v];
   double* P = fpts64 + static_cast<size_t>(v) * kFlatCap * 3;
-  double* C6 = fcov64 + static_cast<size_t>(v) * kFlatCap * 6;
   for (uint32_t i = first; i < n_valid && keys[i] == key; ++i) {
     if (cnt >= max_points) break;  // every further point of this batch would be rejected as well
     const uint32_t src = order[i];
@@ -220,14 +222,22 @@ __global__ void fvm_update_kernel(
     P[3 * cnt] = x;
     P[3 * cnt + 1] = y;
     P[3 * cnt + 2] = z;
-    const Cov8 q = cov[src];
-    const double Cm[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
-    double RC[3][3];
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
-    int k = 0;
-    for (int a = 0; a < 3; a++)
-      for (int b = a; b < 3; b++) C6[6 * cnt + (k++)] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+    if constexpr (NRM) {  // T.matrix() * (nx, ny, nz, 0): the translation column meets the zero w
+      const float4 q = nrm[src];
+      double* N = fnrm64 + (static_cast<size_t>(v) * kFlatCap + cnt) * 3;
+      for (int a = 0; a < 3; a++) N[a] = T.r[3 * a] * q.x + T.r[3 * a + 1] * q.y + T.r[3 * a + 2] * q.z;
+    }
+    if constexpr (COV) {
+      double* C6 = fcov64 + (static_cast<size_t>(v) * kFlatCap + cnt) * 6;
+      const Cov8 q = cov[src];
+      const double Cm[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
+      double RC[3][3];
+      for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
+      int k = 0;
+      for (int a = 0; a < 3; a++)
+        for (int b = a; b < 3; b++) C6[k++] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+    }
     cnt++;
   }
   counts[v] = cnt;
@@ -240,24 +250,32 @@ __global__ void fvm_update_kernel(
   }
 }
 
+template <bool NRM, bool COV>
 __global__ void fvm_compact_kernel(
-  uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos, const double* __restrict__ p_in, const double* __restrict__ c_in, const uint32_t* __restrict__ cnt_in, const uint32_t* __restrict__ lru_in,
-  const int* __restrict__ co_in, double* __restrict__ p_out, double* __restrict__ c_out, uint32_t* __restrict__ cnt_out, uint32_t* __restrict__ lru_out, int* __restrict__ co_out) {
+  uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos, const double* __restrict__ p_in, const double* __restrict__ n_in, const double* __restrict__ c_in, const uint32_t* __restrict__ cnt_in,
+  const uint32_t* __restrict__ lru_in, const int* __restrict__ co_in, double* __restrict__ p_out, double* __restrict__ n_out, double* __restrict__ c_out, uint32_t* __restrict__ cnt_out, uint32_t* __restrict__ lru_out,
+  int* __restrict__ co_out) {
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n || !keep[v]) return;
   const uint32_t w = pos[v];
   for (int k = 0; k < 3; k++) co_out[3 * w + k] = co_in[3 * v + k];
   const uint32_t cnt = cnt_in[v];
   for (uint32_t j = 0; j < cnt; j++) {
-    for (int k = 0; k < 3; k++) p_out[(static_cast<size_t>(w) * kFlatCap + j) * 3 + k] = p_in[(static_cast<size_t>(v) * kFlatCap + j) * 3 + k];
-    for (int k = 0; k < 6; k++) c_out[(static_cast<size_t>(w) * kFlatCap + j) * 6 + k] = c_in[(static_cast<size_t>(v) * kFlatCap + j) * 6 + k];
+    const size_t so = static_cast<size_t>(w) * kFlatCap + j, si = static_cast<size_t>(v) * kFlatCap + j;
+    for (int k = 0; k < 3; k++) p_out[so * 3 + k] = p_in[si * 3 + k];
+    if constexpr (NRM)
+      for (int k = 0; k < 3; k++) n_out[so * 3 + k] = n_in[si * 3 + k];
+    if constexpr (COV)
+      for (int k = 0; k < 6; k++) c_out[so * 6 + k] = c_in[si * 6 + k];
   }
   cnt_out[w] = cnt;
   lru_out[w] = lru_in[v];
 }
 
-// fp32 records read by the factor kernels: slot = voxel * kFlatCap + i, w = slot
-__global__ void fvm_export_kernel(uint32_t n, const uint32_t* __restrict__ counts, const double* __restrict__ fpts64, const double* __restrict__ fcov64, double ox, double oy, double oz, float4* __restrict__ pts, Cov8* __restrict__ cov) {
+// fp32 records read by the factor kernels: slot = voxel * kFlatCap + i, w = slot; normals {nx, ny, nz, 0} under the same slot numbering
+template <bool NRM, bool COV>
+__global__ void fvm_export_kernel(uint32_t n, const uint32_t* __restrict__ counts, const double* __restrict__ fpts64, const double* __restrict__ fnrm64, const double* __restrict__ fcov64, double ox, double oy, double oz,
+                                  float4* __restrict__ pts, float4* __restrict__ nrm, Cov8* __restrict__ cov) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t v = t / kFlatCap, j = t % kFlatCap;
   if (v >= n) return;
@@ -266,17 +284,32 @@ __global__ void fvm_export_kernel(uint32_t n, const uint32_t* __restrict__ count
     return;
   }
   pts[t] = make_float4(static_cast<float>(fpts64[3 * static_cast<size_t>(t)] - ox), static_cast<float>(fpts64[3 * static_cast<size_t>(t) + 1] - oy), static_cast<float>(fpts64[3 * static_cast<size_t>(t) + 2] - oz), __uint_as_float(t));
-  Cov8 o;
-  const double* c = fcov64 + 6 * static_cast<size_t>(t);
-  o.xx = static_cast<float>(c[0]);
-  o.xy = static_cast<float>(c[1]);
-  o.xz = static_cast<float>(c[2]);
-  o.yy = static_cast<float>(c[3]);
-  o.yz = static_cast<float>(c[4]);
-  o.zz = static_cast<float>(c[5]);
-  o.pad0 = o.pad1 = 0.f;
-  cov[t] = o;
+  if constexpr (NRM) {
+    const double* q = fnrm64 + 3 * static_cast<size_t>(t);
+    nrm[t] = make_float4(static_cast<float>(q[0]), static_cast<float>(q[1]), static_cast<float>(q[2]), 0.f);
+  }
+  if constexpr (COV) {
+    Cov8 o;
+    const double* c = fcov64 + 6 * static_cast<size_t>(t);
+    o.xx = static_cast<float>(c[0]);
+    o.xy = static_cast<float>(c[1]);
+    o.xz = static_cast<float>(c[2]);
+    o.yy = static_cast<float>(c[3]);
+    o.yz = static_cast<float>(c[4]);
+    o.zz = static_cast<float>(c[5]);
+    o.pad0 = o.pad1 = 0.f;
+    cov[t] = o;
+  }
 }
+
+// the instantiation for a map's contents
+#define SGA_FLAT_DISPATCH(idx, KERNEL, ...)                                                                         \
+  do {                                                                                                              \
+    if ((idx)->has_normals && (idx)->has_covs) hipLaunchKernelGGL((KERNEL<true, true>), __VA_ARGS__);              \
+    else if ((idx)->has_normals) hipLaunchKernelGGL((KERNEL<true, false>), __VA_ARGS__);                           \
+    else if ((idx)->has_covs) hipLaunchKernelGGL((KERNEL<false, true>), __VA_ARGS__);                              \
+    else hipLaunchKernelGGL((KERNEL<false, false>), __VA_ARGS__);                                                  \
+  } while (0)
 
 // origin of a device frame centred on n host points (3 doubles each)
 static void host_origin(const double* xyz, size_t n, double origin[3]) {
@@ -376,9 +409,11 @@ int sga_index_create_voxelmap_from_voxels(sga_context* ctx, double leaf, const i
 }
 
 // A flat voxel map from voxels that already exist on the host: the reference's IncrementalVoxelMap<FlatContainer*> object as it is
-// (flat order; per voxel its points and, for GICP, their covariances: flat_container.hpp:21-58), 16 slots per voxel like
-// sga_flatmap_download.  The scan-to-model target of Registration<GICPFactor, ParallelReductionHIP> (odometry_benchmark_small_gicp_model_omp.cpp).
-int sga_index_create_flatmap_from_voxels(sga_context* ctx, double leaf, const int32_t* coords, const uint32_t* counts, const double* points3, const double* cov6, int search_offsets, size_t n, sga_index** out) {
+// (flat order; per voxel its points and, where the container keeps them, their normals and covariances: flat_container.hpp:21-58), 16 slots
+// per voxel like sga_flatmap_download.  The scan-to-model target of Registration<GICPFactor | PointToPlaneICPFactor, ParallelReductionHIP>
+// (odometry_benchmark_small_gicp_model_omp.cpp).  The contents follow the arrays given.
+int sga_index_create_flatmap_from_voxels_contents(sga_context* ctx, double leaf, const int32_t* coords, const uint32_t* counts, const double* points3, const double* normals3, const double* cov6, int search_offsets, size_t n,
+                                                   sga_index** out) {
   if (!ctx || !out || (n > 0 && (!coords || !counts || !points3))) return fail(SGA_ERR_INVALID, "null argument");
   if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
   if (search_offsets != 1 && search_offsets != 7 && search_offsets != 27) return fail(SGA_ERR_INVALID, "search offsets must be 1, 7 or 27 (incremental_voxelmap.hpp:157-186)");
@@ -391,23 +426,28 @@ int sga_index_create_flatmap_from_voxels(sga_context* ctx, double leaf, const in
   idx->kind = SGA_INDEX_FLATMAP;
   idx->device = ctx->device;
   idx->leaf = leaf;
+  idx->has_normals = normals3 != nullptr;
   idx->has_covs = cov6 != nullptr;
   idx->search_offsets = search_offsets;
   idx->n = n;
   if (n > 0) {
     const size_t slots = n * kFlatCap;
-    DevBuf<double> d_pts, d_cov;
+    DevBuf<double> d_pts, d_nrm, d_cov;
     SGA_TRY(d_pts.alloc(3 * slots));
-    SGA_TRY(d_cov.alloc(6 * slots));
     SGA_TRY(idx->vcoords.alloc(3 * n));
     SGA_TRY(idx->vcounts.alloc(n));
     SGA_TRY(idx->pts.alloc(slots));
-    SGA_TRY(idx->cov.alloc(slots));
     SGA_HIP(hipMemcpyAsync(d_pts.p, points3, 3 * slots * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (cov6)
+    if (normals3) {
+      SGA_TRY(d_nrm.alloc(3 * slots));
+      SGA_TRY(idx->nrm.alloc(slots));
+      SGA_HIP(hipMemcpyAsync(d_nrm.p, normals3, 3 * slots * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (cov6) {
+      SGA_TRY(d_cov.alloc(6 * slots));
+      SGA_TRY(idx->cov.alloc(slots));
       SGA_HIP(hipMemcpyAsync(d_cov.p, cov6, 6 * slots * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    else
-      SGA_HIP(hipMemsetAsync(d_cov.p, 0, 6 * slots * sizeof(double), ctx->stream));
+    }
     SGA_HIP(hipMemcpyAsync(idx->vcoords.p, coords, 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SGA_HIP(hipMemcpyAsync(idx->vcounts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     {  // the device frame: centred on the valid points
@@ -420,7 +460,8 @@ int sga_index_create_flatmap_from_voxels(sga_context* ctx, double leaf, const in
           }
       choose_origin(lo, hi, idx->origin);
     }
-    hipLaunchKernelGGL(fvm_export_kernel, dim3((slots + 255) / 256), dim3(256), 0, ctx->stream, static_cast<uint32_t>(n), idx->vcounts.p, d_pts.p, d_cov.p, idx->origin[0], idx->origin[1], idx->origin[2], idx->pts.p, idx->cov.p);
+    SGA_FLAT_DISPATCH(idx, fvm_export_kernel, dim3((slots + 255) / 256), dim3(256), 0, ctx->stream, static_cast<uint32_t>(n), idx->vcounts.p, d_pts.p, d_nrm.p, d_cov.p, idx->origin[0], idx->origin[1], idx->origin[2], idx->pts.p,
+                      idx->nrm.p, idx->cov.p);
     SGA_HIP(hipGetLastError());
     SGA_TRY(rebuild_hash(ctx, idx.get(), n));
     SGA_HIP(hipStreamSynchronize(ctx->stream));  // the host buffers are the caller's
@@ -431,9 +472,25 @@ int sga_index_create_flatmap_from_voxels(sga_context* ctx, double leaf, const in
   return SGA_OK;
 }
 
-int sga_flatmap_create(sga_context* ctx, double leaf, sga_index** out) {
+int sga_index_create_flatmap_from_voxels(sga_context* ctx, double leaf, const int32_t* coords, const uint32_t* counts, const double* points3, const double* cov6, int search_offsets, size_t n, sga_index** out) {
+  return sga_index_create_flatmap_from_voxels_contents(ctx, leaf, coords, counts, points3, nullptr, cov6, search_offsets, n, out);
+}
+
+int sga_flatmap_create_contents(sga_context* ctx, double leaf, int contents, sga_index** out) {
+  if (contents < 0 || contents > (SGA_FLAT_NORMALS | SGA_FLAT_COVS)) return fail(SGA_ERR_INVALID, "flat map contents must be a combination of SGA_FLAT_NORMALS and SGA_FLAT_COVS");
   SGA_TRY(sga_voxelmap_create(ctx, leaf, out));
   (*out)->kind = SGA_INDEX_FLATMAP;
+  (*out)->has_normals = (contents & SGA_FLAT_NORMALS) != 0;
+  (*out)->has_covs = (contents & SGA_FLAT_COVS) != 0;
+  return SGA_OK;
+}
+
+int sga_flatmap_create(sga_context* ctx, double leaf, sga_index** out) { return sga_flatmap_create_contents(ctx, leaf, SGA_FLAT_COVS, out); }
+
+int sga_flatmap_get_contents(const sga_index* index, int* contents) {
+  if (!index || !contents) return fail(SGA_ERR_INVALID, "null argument");
+  if (index->kind != SGA_INDEX_FLATMAP) return fail(SGA_ERR_INVALID, "not a flat voxel map");
+  *contents = (index->has_normals ? SGA_FLAT_NORMALS : 0) | (index->has_covs ? SGA_FLAT_COVS : 0);
   return SGA_OK;
 }
 
@@ -453,23 +510,32 @@ int sga_voxelmap_set_search_offsets(sga_index* index, int num_offsets) {
   return SGA_OK;
 }
 
-// per voxel: coords (3 ints) and number of points; points (3 floats) and cov6 (6 floats) for kFlatCap slots per voxel
-int sga_flatmap_download(sga_context* ctx, const sga_index* index, int32_t* coords, uint32_t* counts, float* points, float* cov6) {
+// per voxel: coords (3 ints) and number of points; points (3 floats), normals (3 floats) and cov6 (6 floats) for kFlatCap slots per voxel.
+// strict: a requested attribute the map does not keep is an error; otherwise (sga_flatmap_download, cov6 only) it comes back as zeros.
+static int flatmap_download(sga_context* ctx, const sga_index* index, int32_t* coords, uint32_t* counts, float* points, float* normals, float* cov6, bool strict) {
   if (!ctx || !index) return fail(SGA_ERR_INVALID, "null argument");
   if (index->kind != SGA_INDEX_FLATMAP) return fail(SGA_ERR_INVALID, "not a flat voxel map");
+  if (strict && normals && !index->has_normals) return fail(SGA_ERR_INVALID, "the flat map keeps no normals");
+  if (strict && cov6 && !index->has_covs) return fail(SGA_ERR_INVALID, "the flat map keeps no covariances");
   const size_t n = index->n;
   if (n == 0) return SGA_OK;
   SGA_ENTER(ctx);
   SGA_TRY(wait_ready(ctx, index->ready));
-  std::vector<float4> hp;
+  std::vector<float4> hp, hn;
   std::vector<Cov8> hc;
   if (points) {
     hp.resize(n * kFlatCap);
     SGA_HIP(hipMemcpyAsync(hp.data(), index->pts.p, hp.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   }
-  if (cov6) {
+  if (normals) {
+    hn.resize(n * kFlatCap);
+    SGA_HIP(hipMemcpyAsync(hn.data(), index->nrm.p, hn.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (cov6 && index->has_covs) {
     hc.resize(n * kFlatCap);
     SGA_HIP(hipMemcpyAsync(hc.data(), index->cov.p, hc.size() * sizeof(Cov8), hipMemcpyDeviceToHost, ctx->stream));
+  } else if (cov6) {
+    hc.assign(n * kFlatCap, Cov8{});
   }
   if (coords) SGA_HIP(hipMemcpyAsync(coords, index->vcoords.p, n * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   if (counts) SGA_HIP(hipMemcpyAsync(counts, index->vcounts.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -479,6 +545,11 @@ int sga_flatmap_download(sga_context* ctx, const sga_index* index, int32_t* coor
       points[3 * i] = static_cast<float>(static_cast<double>(hp[i].x) + index->origin[0]);
       points[3 * i + 1] = static_cast<float>(static_cast<double>(hp[i].y) + index->origin[1]);
       points[3 * i + 2] = static_cast<float>(static_cast<double>(hp[i].z) + index->origin[2]);
+    }
+    if (normals) {  // (directions: no frame; the records of empty slots are undefined)
+      normals[3 * i] = hn[i].x;
+      normals[3 * i + 1] = hn[i].y;
+      normals[3 * i + 2] = hn[i].z;
     }
     if (cov6) {
       cov6[6 * i] = hc[i].xx;
@@ -492,6 +563,12 @@ int sga_flatmap_download(sga_context* ctx, const sga_index* index, int32_t* coor
   return SGA_OK;
 }
 
+int sga_flatmap_download(sga_context* ctx, const sga_index* index, int32_t* coords, uint32_t* counts, float* points, float* cov6) { return flatmap_download(ctx, index, coords, counts, points, nullptr, cov6, false); }
+
+int sga_flatmap_download_contents(sga_context* ctx, const sga_index* index, int32_t* coords, uint32_t* counts, float* points, float* normals, float* cov6) {
+  return flatmap_download(ctx, index, coords, counts, points, normals, cov6, true);
+}
+
 int sga_voxelmap_set_lru(sga_index* index, uint32_t horizon, uint32_t clear_cycle) {
   if (!index || !index->incremental) return fail(SGA_ERR_INVALID, "not an incremental voxel map");
   if (clear_cycle == 0) return fail(SGA_ERR_INVALID, "clear_cycle must be positive");
@@ -503,7 +580,10 @@ int sga_voxelmap_set_lru(sga_index* index, uint32_t horizon, uint32_t clear_cycl
 int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud, const double T16[16]) {
   if (!ctx || !idx || !cloud) return fail(SGA_ERR_INVALID, "null argument");
   if (!idx->incremental) return fail(SGA_ERR_INVALID, "not an incremental voxel map (create it with sga_voxelmap_create)");
-  if (cloud->n > 0 && !cloud->has_covs) return fail(SGA_ERR_INVALID, "GaussianVoxelMap needs point covariances");
+  if (idx->kind != SGA_INDEX_FLATMAP || idx->has_covs) {
+    if (cloud->n > 0 && !cloud->has_covs) return fail(SGA_ERR_INVALID, "GaussianVoxelMap needs point covariances");
+  }
+  if (idx->kind == SGA_INDEX_FLATMAP && idx->has_normals && cloud->n > 0 && !cloud->has_normals) return fail(SGA_ERR_INVALID, "a flat voxel map with normals needs point normals");
   if (cloud->device != ctx->device || idx->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud / map live on another device");
   SGA_ENTER(ctx);
   SGA_TRY(wait_ready(ctx, cloud->ready));
@@ -582,7 +662,8 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
         const bool flat = idx->kind == SGA_INDEX_FLATMAP;
         if (flat) {
           SGA_TRY(grow(ctx, idx->fpts64, 3 * kFlatCap * static_cast<size_t>(n_old), 3 * kFlatCap * cap));
-          SGA_TRY(grow(ctx, idx->fcov64, 6 * kFlatCap * static_cast<size_t>(n_old), 6 * kFlatCap * cap));
+          if (idx->has_normals) SGA_TRY(grow(ctx, idx->fnrm64, 3 * kFlatCap * static_cast<size_t>(n_old), 3 * kFlatCap * cap));
+          if (idx->has_covs) SGA_TRY(grow(ctx, idx->fcov64, 6 * kFlatCap * static_cast<size_t>(n_old), 6 * kFlatCap * cap));
         } else {
           SGA_TRY(grow(ctx, idx->vmean64, 3 * static_cast<size_t>(n_old), 3 * cap));
           SGA_TRY(grow(ctx, idx->vcov64, 6 * static_cast<size_t>(n_old), 6 * cap));
@@ -591,15 +672,15 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
         SGA_TRY(grow(ctx, idx->vlru, n_old, cap));
         SGA_TRY(grow(ctx, idx->vcoords, 3 * static_cast<size_t>(n_old), 3 * cap));
         SGA_TRY(grow(ctx, idx->pts, 0, flat ? kFlatCap * cap : cap));
-        SGA_TRY(grow(ctx, idx->cov, 0, flat ? kFlatCap * cap : cap));
+        if (flat && idx->has_normals) SGA_TRY(grow(ctx, idx->nrm, 0, kFlatCap * cap));
+        if (!flat || idx->has_covs) SGA_TRY(grow(ctx, idx->cov, 0, flat ? kFlatCap * cap : cap));
         idx->vcap = cap;
       }
       if (idx->hkeys.n == 0 || 2 * n_total > idx->hkeys.n) SGA_TRY(rebuild_hash(ctx, idx, n_total));
       if (n_new > 0) hipLaunchKernelGGL(ivm_assign_kernel, dim3((n_new + 255) / 256), block, 0, ctx->stream, n_new, seg_by_rank.p, n_old, seg_vid.p);
       if (idx->kind == SGA_INDEX_FLATMAP)
-        hipLaunchKernelGGL(
-          fvm_update_kernel, sgrid, block, 0, ctx->stream, nseg, seg_start.p, seg_vid.p, static_cast<uint32_t>(n), keys_sorted.p, order.p, cloud->pts.p, cloud->cov.p, T, n_old, idx->lru_counter, idx->flat_max, idx->flat_min_sq,
-          idx->fpts64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, idx->hkeys.p, idx->hvals.p, idx->hmask);
+        SGA_FLAT_DISPATCH(idx, fvm_update_kernel, sgrid, block, 0, ctx->stream, nseg, seg_start.p, seg_vid.p, static_cast<uint32_t>(n), keys_sorted.p, order.p, cloud->pts.p, cloud->nrm.p, cloud->cov.p, T, n_old,
+                          idx->lru_counter, idx->flat_max, idx->flat_min_sq, idx->fpts64.p, idx->fnrm64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, idx->hkeys.p, idx->hvals.p, idx->hmask);
       else
         hipLaunchKernelGGL(
           ivm_update_kernel, sgrid, block, 0, ctx->stream, nseg, seg_start.p, seg_vid.p, static_cast<uint32_t>(n), keys_sorted.p, order.p, cloud->pts.p, cloud->cov.p, T, n_old, idx->lru_counter, idx->vmean64.p, idx->vcov64.p,
@@ -627,23 +708,26 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
     SGA_HIP(hipStreamSynchronize(ctx->stream));
     const uint32_t kept = last_pos + last_keep;
     if (kept < nv) {
-      DevBuf<double> m2, c2;
+      DevBuf<double> m2, n2, c2;
       DevBuf<uint32_t> cnt2, lru2;
       DevBuf<int> co2;
       const bool flat = idx->kind == SGA_INDEX_FLATMAP;
       SGA_TRY(m2.alloc((flat ? 3 * kFlatCap : 3) * idx->vcap));
-      SGA_TRY(c2.alloc((flat ? 6 * kFlatCap : 6) * idx->vcap));
+      if (flat && idx->has_normals) SGA_TRY(n2.alloc(3 * kFlatCap * idx->vcap));
+      if (!flat || idx->has_covs) SGA_TRY(c2.alloc((flat ? 6 * kFlatCap : 6) * idx->vcap));
       SGA_TRY(cnt2.alloc(idx->vcap));
       SGA_TRY(lru2.alloc(idx->vcap));
       SGA_TRY(co2.alloc(3 * idx->vcap));
       if (flat)
-        hipLaunchKernelGGL(fvm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->fpts64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, c2.p, cnt2.p, lru2.p, co2.p);
+        SGA_FLAT_DISPATCH(idx, fvm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->fpts64.p, idx->fnrm64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, n2.p, c2.p,
+                          cnt2.p, lru2.p, co2.p);
       else
         hipLaunchKernelGGL(ivm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->vmean64.p, idx->vcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, c2.p, cnt2.p, lru2.p, co2.p);
       SGA_HIP(hipGetLastError());
       SGA_HIP(hipStreamSynchronize(ctx->stream));
       if (flat) {
         idx->fpts64.swap(m2);
+        idx->fnrm64.swap(n2);
         idx->fcov64.swap(c2);
       } else {
         idx->vmean64.swap(m2);
@@ -659,7 +743,8 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
   for (int k = 0; k < 3; k++) idx->origin[k] = new_origin[k];  // every fallible step is behind us: the records exported now are relative to it
   if (idx->n > 0) {
     if (idx->kind == SGA_INDEX_FLATMAP)
-      hipLaunchKernelGGL(fvm_export_kernel, dim3((idx->n * kFlatCap + 255) / 256), dim3(256), 0, ctx->stream, static_cast<uint32_t>(idx->n), idx->vcounts.p, idx->fpts64.p, idx->fcov64.p, idx->origin[0], idx->origin[1], idx->origin[2], idx->pts.p, idx->cov.p);
+      SGA_FLAT_DISPATCH(idx, fvm_export_kernel, dim3((idx->n * kFlatCap + 255) / 256), dim3(256), 0, ctx->stream, static_cast<uint32_t>(idx->n), idx->vcounts.p, idx->fpts64.p, idx->fnrm64.p, idx->fcov64.p, idx->origin[0],
+                        idx->origin[1], idx->origin[2], idx->pts.p, idx->nrm.p, idx->cov.p);
     else
       hipLaunchKernelGGL(ivm_export_kernel, dim3((idx->n + 255) / 256), dim3(256), 0, ctx->stream, static_cast<uint32_t>(idx->n), idx->vmean64.p, idx->vcov64.p, idx->origin[0], idx->origin[1], idx->origin[2], idx->pts.p, idx->cov.p);
   }

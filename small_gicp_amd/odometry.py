@@ -85,14 +85,21 @@ class ModelOdometry:
     GaussianVoxelMap accumulating every registered scan (incremental insert with the estimated pose + LRU removal of voxels the
     sensor has left behind); each new scan is registered against it starting from the previous pose, then inserted."""
 
-    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, voxel_resolution=1.0, max_correspondence_distance=1.0, ctx=None, model="gaussian"):
+    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, voxel_resolution=1.0, max_correspondence_distance=1.0, ctx=None, model="gaussian", factor="GICP"):
         """model = "gaussian": GaussianVoxelMap / VGICP (odometry_benchmark_small_vgicp_model_omp.cpp); "flat": IncrementalVoxelMap<
-        FlatContainerCov> / GICP against the stored points (odometry_benchmark_small_gicp_model_omp.cpp)."""
+        FlatContainerCov> / GICP against the stored points (odometry_benchmark_small_gicp_model_omp.cpp).  factor = "PLANE_ICP" (flat
+        model only): IncrementalVoxelMap<FlatContainerNormal> / point-to-plane ICP against the stored points and their normals (the
+        linear iVox of Faster-LIO, flat_container.hpp:15-17); the scans get normals instead of covariances."""
+        if factor not in ("GICP", "PLANE_ICP"):
+            raise ValueError("factor must be 'GICP' or 'PLANE_ICP'")
+        if factor == "PLANE_ICP" and model != "flat":
+            raise ValueError("PLANE_ICP needs the flat model: a GaussianVoxelMap keeps no normals")
         self.model = model
+        self.factor = factor
         self.res = downsampling_resolution
         self.k = num_neighbors
         self.voxel_resolution = voxel_resolution
-        self.setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
+        self.setting = api.make_setting(factor, max_correspondence_distance=max_correspondence_distance)
         self.ctx = ctx or api.default_context()
         self.voxelmap = None
         self.T_world = np.eye(4)
@@ -104,9 +111,16 @@ class ModelOdometry:
         cloud = api.voxelgrid_sampling(raw, self.res)
         self.ctx.synchronize()
         t1 = time.perf_counter()
-        api.estimate_covariances(cloud, None, self.k)
+        if self.factor == "PLANE_ICP":
+            api.estimate_normals(cloud, None, self.k)
+        else:
+            api.estimate_covariances(cloud, None, self.k)
         if self.voxelmap is None:  # the very first frame
-            self.voxelmap = (api.IncrementalVoxelMapCov if self.model == "flat" else api.GaussianVoxelMap)(self.voxel_resolution, ctx=self.ctx)
+            if self.factor == "PLANE_ICP":
+                kind = api.IncrementalVoxelMapNormal
+            else:
+                kind = api.IncrementalVoxelMapCov if self.model == "flat" else api.GaussianVoxelMap
+            self.voxelmap = kind(self.voxel_resolution, ctx=self.ctx)
             self.voxelmap.insert(cloud)
         else:
             res = api.Problem(self.voxelmap, cloud, self.T_world).align(self.setting, self.T_world)
@@ -121,7 +135,8 @@ class ModelOdometry:
 
 
 def run_synthetic_model(num_frames=20, **kw):
-    """ModelOdometry over the frozen synthetic sequence; absolute trajectory error against the generator's ground truth."""
+    """ModelOdometry over the frozen synthetic sequence (keyword arguments, model= and factor= among them, go to ModelOdometry);
+    absolute trajectory error against the generator's ground truth."""
     from . import synthetic
 
     odom = ModelOdometry(**kw)
