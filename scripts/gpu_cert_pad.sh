@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: the per-pass table of one C3 registration (scripts/diag_passes.py) under each environment setting given as an argument
-#   bash scripts/gpu_cert_pad.sh "" "SGA_CERT_PAD=0.3" "SGA_CERT_PAD=0.5 SGA_SLACK_MAX=0.03"
+#   bash scripts/gpu_cert_pad.sh "" "SGA_CERT_PAD=0.3" "SGA_CERT_PAD=0.5"
 mkdir -p gpurun_out
 cd /root/repo
 i=0

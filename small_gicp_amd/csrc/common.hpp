@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -244,9 +245,10 @@ struct sga_index {
   int kd_depth = 0;
   float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
   // the target's own length scale (notes.hpp: late notes): geometric mean of the diagonals of the tree's leaf boxes, i.e. the size of a
-  // neighbourhood of 8 points; the pass routing of linearize.hip measures motions in units of it.  0 = not known (yet)
-  mutable double spacing = 0.0;
-  mutable unsigned long long spacing_seq = 0;  // the late note that carries it; 0 = none
+  // neighbourhood of 8 points; the pass routing of linearize.hip measures motions in units of it.  0 = not known (yet).  Filled in on
+  // first use by index_spacing(), from any thread that registers against this target: spacing is stored before spacing_seq is cleared
+  mutable std::atomic<double> spacing{0.0};
+  mutable std::atomic<unsigned long long> spacing_seq{0};  // the late note that carries it; 0 = none (or read)
   // uniform cell grid over the same points (cell_grid.hpp / cell_grid.hip): the exact search of cold passes near the optimum; grid_h == 0: none
   sga::DevBuf<float4> grid_pts;       // cell order, w = kd position bits
   sga::DevBuf<uint32_t> grid_start;   // cells + 1

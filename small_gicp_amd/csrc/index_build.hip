@@ -1133,11 +1133,12 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
   SGA_TRY(idx->kd_groups.alloc(8ull << (D - (D < 2 ? D : 2))));
   SGA_TRY(idx->kd_leaf.alloc(8ull << D));
   unsigned long long* late_slot = nullptr;
-  idx->spacing_seq = late_note_begin(ctx->device, &late_slot);  // the target's length scale arrives whenever the tail kernel has run: nobody waits for it
+  const unsigned long long spacing_seq = late_note_begin(ctx->device, &late_slot);  // the target's length scale arrives whenever the tail kernel has run: nobody waits for it
   idx->spacing = 0.0;
+  idx->spacing_seq = spacing_seq;
   // gather into kd order, leaf blocks, leaf boxes + 8 levels of boxes, group headers, pair records: one launch (kd_tail_kernel)
   hipLaunchKernelGGL(kd_tail_kernel, dim3(((1u << D) + 255) / 256), block, 0, ctx->stream, cur, static_cast<uint32_t>(n), D, cloud->pts.p, cloud->has_normals ? cloud->nrm.p : nullptr, cloud->has_covs ? cloud->cov.p : nullptr, idx->kd_nodes.p,
-                     idx->kd_pts.p, idx->nrm.p, idx->cov.p, idx->kd_boxes.p, idx->kd_groups.p, reinterpret_cast<float*>(idx->kd_leaf.p), idx->kd_nodes4.p, kd_pair_count(D), ctx->d_spacing.p, late_slot, idx->spacing_seq);
+                     idx->kd_pts.p, idx->nrm.p, idx->cov.p, idx->kd_boxes.p, idx->kd_groups.p, reinterpret_cast<float*>(idx->kd_leaf.p), idx->kd_nodes4.p, kd_pair_count(D), ctx->d_spacing.p, late_slot, spacing_seq);
   for (int base = D - 8; base > 0; base -= 8) hipLaunchKernelGGL(kd_boxes_kernel, dim3(((1u << base) + 255) / 256), block, 0, ctx->stream, idx->kd_pts.p, static_cast<uint32_t>(n), D, base, idx->kd_boxes.p);
   SGA_HIP(hipGetLastError());
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
@@ -1238,14 +1239,17 @@ __global__ void count_valid_keys_kernel(const unsigned long long* __restrict__ k
 
 namespace sga {
 // the target's length scale (sga_index::spacing), once the late note of its build has arrived; 0 while it is not known
+// (a target may serve registrations on several threads at once: the note is read first, with acquire, so that a reader which finds it
+// cleared also finds the spacing stored before; two readers of the same note store the same value)
 double index_spacing(const sga_index* idx) {
-  if (idx->spacing > 0.0 || idx->spacing_seq == 0) return idx->spacing;
+  const unsigned long long seq = idx->spacing_seq.load(std::memory_order_acquire);
+  if (seq == 0) return idx->spacing.load(std::memory_order_relaxed);
   unsigned long long payload[kLateWords - 1];
-  const int r = late_note_peek(idx->spacing_seq, payload);
+  const int r = late_note_peek(seq, payload);
   if (r == 0) return 0.0;  // the build has not got there yet
-  idx->spacing_seq = 0;    // read, or lost: never asked for again
-  if (r == 1 && payload[1] > 0) idx->spacing = std::exp2(static_cast<double>(static_cast<long long>(payload[0])) / 1048576.0 / static_cast<double>(payload[1]));
-  return idx->spacing;
+  if (r == 1 && payload[1] > 0) idx->spacing.store(std::exp2(static_cast<double>(static_cast<long long>(payload[0])) / 1048576.0 / static_cast<double>(payload[1])), std::memory_order_release);
+  idx->spacing_seq.store(0, std::memory_order_release);  // read, or lost: never asked for again
+  return idx->spacing.load(std::memory_order_relaxed);
 }
 }  // namespace sga
 

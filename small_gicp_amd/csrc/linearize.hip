@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <utility>
 
 #include "common.hpp"
@@ -206,7 +207,7 @@ struct NNParams {
   Rigid<Real> T;
   float bound2;      // the walks find neighbours with kd_dist2 < bound2 (the rejector's reach + kSearchMargin)
   float within2;     // a neighbour counts for the rejector only if kd_dist2 < within2
-  float slack_min, slack_max;  // exploration slack of a re-walk = clamp(motion, slack_min, slack_max) (SGA_SLACK_MIN / SGA_SLACK_MAX)
+  float slack_min, slack_max;  // exploration slack of a re-walk = clamp(motion, slack_min, slack_max) (kSlackMin / kSlackMax)
   float cert_pad;    // headroom of the certificate check as a share of the point's motion (see certify; SGA_CERT_PAD)
   int* __restrict__ nn;
   int* __restrict__ nn2;   // the runner-up of every walk: second candidate of the certificate
@@ -1468,13 +1469,91 @@ static void launch_reduce(sga_context* ctx, const double* partials, int nrows, i
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(groups), dim3(kReduceSlices * kCols), 0, ctx->stream, partials, nrows, ncols, row_stride, stage, ctx->d_ticket.p, out, out_n, host, seq, derive ? 1 : 0, stats);
 }
 
-static bool g_lazy_maha = getenv("SGA_LAZY_MAHA") ? atoi(getenv("SGA_LAZY_MAHA")) != 0 : true;
-static int g_fuse_max = getenv("SGA_FUSE_MAX") ? atoi(getenv("SGA_FUSE_MAX")) : kFuseMaxBlocks;
-// four points per lane in the standalone factor kernel from this many points on (VGICP iterations of 140k / 200k / 300k / 500k / 1M points:
-// 32.5 / 32.7 / 36.4 / 39.0 / 45.1 us at four per lane against 25.5 / 27.0 / 30.4 / 37.0 / 45.4 us at one: the size sweep late in round 6;
-// 131072 before)
-static int g_lin_pts_min = getenv("SGA_LIN_PTS_MIN") ? atoi(getenv("SGA_LIN_PTS_MIN")) : 750000;
+// ---- the tuning table of the pass routing ------------------------------------------------------------------------------------------
+// Every threshold linearize_dispatch routes by, lengths in metres at the reference spacing (routing_unit); none changes a result, only
+// which exact kernel computes it.  The switches tests or exported setters change are read when the library loads.
+template <typename T>
+static T env_or(const char* name, T d) {  // the environment variable `name` as a T, or d if it is not set
+  const char* s = getenv(name);
+  return s == nullptr ? d : std::is_floating_point_v<T> ? static_cast<T>(atof(s)) : static_cast<T>(atoll(s));
+}
+
+// Points per lane and reduction (linearize_kernel's PTS): large clouds amortise the wave reductions over 4 points; small ones (a
+// 15k-point scan) keep one point per lane — they are bound by latency and want every workgroup they can get.  Four per lane from
+// kLinPtsMin points on (VGICP iterations of 140k / 200k / 300k / 500k / 1M points: 32.5 / 32.7 / 36.4 / 39.0 / 45.1 us at four per lane
+// against 25.5 / 27.0 / 30.4 / 37.0 / 45.4 us at one: the size sweep late in round 6; 131072 before).
+constexpr int kLinPts = 4;
+constexpr int kLinPtsMin = 750000;
+// (fp64 per-pair arithmetic keeps four per lane from 131 072 points on: its factor kernel is arithmetic-bound and loses a quarter of its rate at one —
+// 200k / 400k / 700k / 1M points 11 047 / 9 236 / 6 768 / 5 389 against 9 632 / 7 069 / 4 921 / 3 673 iterations/s)
+constexpr int kLinPtsMinF64 = 131072;
+
+// A pass runs warm (certified neighbours skip the walk) while no source point can have moved farther than this since the previous
+// linearization; beyond it hardly any certificate holds and checking them is wasted work.  Environment override SGA_WARM_DELTA,
+// run-time override sga_set_warm_limit; negative = never.
+static double g_warm_delta = env_or("SGA_WARM_DELTA", 0.1);
+
+// Search kernel selection.  SGA_SEARCH_QUEUE: 0 = one query per lane always (nn_search_kernel), 1 = queue-fed always, 2 (default) =
+// queue-fed for warm passes after a motion of at most kQueueDelta.  Measured on C3 (1 M points): when most lanes walk (cold passes,
+// the first warm pass) a wave per 64 queries and 8 waves per SIMD win — the walks are bound by the number of memory accesses in flight
+// and the queue-fed kernel starts each of them with 10 record fetches; when few lanes walk (the later passes of a registration) the
+// queue packs them into full waves: 124 -> 80, 87 -> 73, 68 -> 53 us.
+static int g_search_queue = env_or("SGA_SEARCH_QUEUE", 2);
+constexpr double kQueueDelta = 0.02;
+// tiles of 64 queries per wave of the queue-fed kernel (SGA_CHUNK_COLD / SGA_CHUNK_WARM, sga_set_search_mode)
+static int g_chunk_tiles_cold = env_or("SGA_CHUNK_COLD", 4);
+static int g_chunk_tiles_warm = env_or("SGA_CHUNK_WARM", 4);
+
+// Warm pass of a large cloud after a small motion: the certificates are checked inside the streaming factor kernel
+// (certify_linearize_kernel), whose workgroups walk their few failed points themselves.  Measured on C3 (profiles/r04_warm_split.txt):
+// it wins where few points walk (after motions of a millimetre or two: 38 - 54 us against 44 - 66) and loses where many do (the walkers
+// of a pass sit where the points moved most, i.e. in a few workgroups, which then walk alone: 121 against 99 us after a 1 cm motion),
+// hence a second limit, smaller than kQueueDelta.
+constexpr double kSplitDelta = 0.002;
+// Only from this many source points on (131072 until the size sweep late in round 6: late passes of 135k / 200k / 300k / 400k /
+// 600k-point pairs 27.3 / 29.1 / 33.8 / 35.0 / 41.0 us with this kernel against 24.6 / 26.6 / 34.2 / 38.5 / 43.2 us with the queue-fed
+// one: the crossover is near 300k): measured on C2 (100k points) and C5 (12k-point scans) the kernel — one point per lane there, the
+// row reduction folded into it (fused_tail) when the grid is small — is no faster than the queue-fed one (C2 warm pass 39.9 against
+// 40.3 us, C5 registration 0.51 against 0.48 ms/scan; with 4 points per lane 53.9 us): at those sizes a pass is a chain of launch, a
+// few dependent loads and the hand-off, whichever kernel runs it.  One point per lane at every size: the size sweep late in round 6 —
+// late passes of 300k / 600k / 700k-point pairs 34.0 / 40.4 / 42.3 us at four per lane against 31.2 / 38.8 / 40.6 us at one, C3's warm
+// passes 83.8 -> 81.2 us on average (+1.2 % on the headline).
+constexpr size_t kSplitMinPoints = 262144;
+
+// exploration slack of a re-walk = clamp(motion, kSlackMin, kSlackMax)
+constexpr float kSlackMin = 3e-4f, kSlackMax = 0.02f;
+// headroom of the certificate check (certify): a point walks unless its certificate survives PAD x its own motion beyond what this pass needs
+static const float g_cert_pad = env_or("SGA_CERT_PAD", 0.6f);
+// longest tile first (tile_order_kernel): 0 off, 1 = warm passes of the one-query-per-lane kernel (motion <= SGA_WARM_DELTA) when the
+// previous pass was such a pass too, 2 = every pass of that kernel that follows another (experiments)
+static const int g_lpt = env_or("SGA_LPT", 1);
+// 1 (default): the one-query-per-lane search kernels walk with the fast leaf scan (32-bit keys, packed fp32; exact repeat of the
+// queries it cannot decide); 0: the exact 64-bit keys throughout.
+static const int g_fast_scan = env_or("SGA_FAST_SCAN", 1);
+
+// The cell grid (cell_grid.hpp).  SGA_GRID: 0 no grid at all; 1 (default) the WALKERS of warm passes try ring 1 of the grid before they
+// walk the tree (certify_linearize_kernel) and every full search stays with the kd walk — measured on C3 whole grid passes do not beat
+// it; 2 = also the cold passes of a registration but its first (whose queries lie as far from the target as the
+// initial guess is off: there the kd walk's pruning pays) and the warm passes after a larger motion; 3 the first pass too; 4 every pass.
+// Whole grid passes only while the reach needs at most kGridMaxRings rings; if ring 1 of the last grid pass left more than kGridMaxOpen
+// of the queries open, the next cold pass walks the kd-tree instead.
+int g_grid_mode = env_or("SGA_GRID", 1);  // sga_set_grid_mode
+long long g_grid_min_points = env_or("SGA_GRID_MIN_POINTS", 65536ll);  // targets below this get no grid (cell_grid.hip)
+constexpr int kGridMaxRings = 16;
+constexpr double kGridMaxOpen = 0.5;
+// which walkers try ring 1 of the grid first (SGA_GRID_WALK, bits): 1 those of certify_linearize_kernel, 2 those of the
+// one-query-per-lane warm pass (search_linearize_kernel<CHECK>), 4 those of the queue-fed kernel, 8 certify_linearize_kernel scans ring 1
+// with a group of lanes per walker when a workgroup has few of them (grid_ring1_group); 32: a ring certificate that ends at the ring's
+// face with less than the re-walk's slack beyond the neighbour is left to the tree walk (the margin rule, certify_linearize_kernel)
+static const int g_grid_walk = env_or("SGA_GRID_WALK", 47);
+
+// trial errors from the quadratic error model of the last linearization; 0 (SGA_ERROR_MODEL, sga_set_error_model) = every error pass
+// runs the error kernel (the reference's literal procedure)
+static bool g_error_model = env_or("SGA_ERROR_MODEL", true);
+
 static int grid_blocks(int num_tiles) { return num_tiles < kMaxBlocks ? (num_tiles < 1 ? 1 : num_tiles) : kMaxBlocks; }
+static int factor_tiles(int n, int pts) { return (n + kTile * pts - 1) / (kTile * pts); }  // steps of kTile * pts points
+static int linearize_pts(int n, bool fp64) { return n >= (fp64 ? kLinPtsMinF64 : kLinPtsMin) ? kLinPts : 1; }
 
 // nearest neighbour (caller's target order) and squared distance of every source point in the caller's source order: the input of a
 // host rejector callback
@@ -1498,13 +1577,15 @@ __global__ void export_neighbours_kernel(const float4* __restrict__ src_pts, con
   out_d2[orig] = d2;
 }
 
-// Points per lane and reduction (linearize_kernel's PTS): large clouds amortise the wave reductions over 4 points; small ones (a
-// 15k-point scan) keep one point per lane — they are bound by latency and want every workgroup they can get.
-constexpr int kLinPts = 4;
-// (fp64 per-pair arithmetic keeps four per lane from 131 072 points on: its factor kernel is arithmetic-bound and loses a quarter of its rate at one —
-// 200k / 400k / 700k / 1M points 11 047 / 9 236 / 6 768 / 5 389 against 9 632 / 7 069 / 4 921 / 3 673 iterations/s)
-static int g_lin_pts_min_f64 = getenv("SGA_LIN_PTS_MIN_F64") ? atoi(getenv("SGA_LIN_PTS_MIN_F64")) : 131072;
-static int linearize_pts(int n, bool fp64) { return n >= (fp64 ? g_lin_pts_min_f64 : g_lin_pts_min) ? kLinPts : 1; }
+// f(std::integral_constant<int, K>{}) for factor kind K; the caller has validated the kind
+template <typename F>
+static void with_factor(int kind, F&& f) {
+  switch (kind) {
+    case SGA_GICP: f(std::integral_constant<int, SGA_GICP>{}); break;
+    case SGA_PLANE_ICP: f(std::integral_constant<int, SGA_PLANE_ICP>{}); break;
+    default: f(std::integral_constant<int, SGA_ICP>{}); break;
+  }
+}
 
 template <typename Real, int FACTOR, int TARGET>
 static void launch_linearize(hipStream_t st, const LinParams<Real>& p, int blocks, int pts) {
@@ -1532,7 +1613,7 @@ static double max_displacement(const double Ta[16], const double Tb[16], const f
 
 // The lengths the pass routing compares motions with are properties of the TARGET, not constants of nature: a certificate's exclusion
 // radius is a fraction of the distance between neighbouring target points, so "how far may the source have moved before the
-// certificates are gone" scales with the target's spacing.  The thresholds below were tuned in metres on the C3 scene; they are applied
+// certificates are gone" scales with the target's spacing.  The thresholds above were tuned in metres on the C3 scene; they are applied
 // multiplied by  unit = (the target's length scale) / kSpacingRef  — index_spacing(): the geometric mean of the tree's leaf diagonals,
 // computed by the build (kd_tail_kernel); kSpacingRef: that number for the C3 target — so a cloud in millimetres, or one ten times sparser,
 // routes its passes exactly as its metre-scale twin does (tests/test_scale_free.py).  unit = 1 while the length scale of a
@@ -1540,41 +1621,107 @@ static double max_displacement(const double Ta[16], const double Tb[16], const f
 constexpr double kSpacingRef = SGA_SPACING_REF;
 double index_spacing(const sga_index* idx);  // index_build.hip
 static double routing_unit(const sga_index* idx) {
-  static const bool scale_free = !(getenv("SGA_SCALE_FREE") && atoi(getenv("SGA_SCALE_FREE")) == 0);
-  const double s = scale_free ? index_spacing(idx) : 0.0;
+  const double s = index_spacing(idx);
   return s > 0.0 ? s / kSpacingRef : 1.0;
 }
 
-// A pass runs warm (certified neighbours skip the walk) while no source point can have moved farther than this since the previous
-// linearization; beyond it hardly any certificate holds and checking them is wasted work.  Environment override SGA_WARM_DELTA
-// (metres at the reference spacing, see above), run-time override sga_set_warm_limit; negative = never.  Results do not depend on it.
-static double g_warm_delta = getenv("SGA_WARM_DELTA") ? atof(getenv("SGA_WARM_DELTA")) : 0.1;
+// Which kernels run a pass, in the order plan_pass decides it
+enum class Route {
+  kFactors,     // no search: a voxel-map target (the lookup happens inside linearize_kernel) or an empty source
+  kGrid,        // a whole search pass over the target's cell grid (grid_search_pass), then linearize_kernel over nn[]
+  kCertify,     // certify_linearize_kernel: the certificates checked inside the streaming factor kernel, which walks the failed points
+  kFusedLane,   // search_linearize_kernel: one query per lane, every wave evaluates the factors of its own tile
+  kFusedQueue,  // nn_search_queue_kernel<FACTOR>: queue-fed walks, every wave evaluates the factors of its chunk
+  kQueue,       // nn_search_queue_kernel, then linearize_kernel
+  kLane,        // nn_search_kernel (one query per lane), then linearize_kernel
+};
 
-// Search kernel selection (results do not depend on it).  SGA_SEARCH_QUEUE: 0 = one query per lane always (nn_search_kernel),
-// 1 = queue-fed always, 2 (default) = queue-fed for warm passes after a motion of at most SGA_QUEUE_DELTA metres.  Measured on C3
-// (1 M points): when most lanes walk (cold passes, the first warm pass) a wave per 64 queries and 8 waves per SIMD win — the walks
-// are bound by the number of memory accesses in flight and the queue-fed kernel starts each of them with 10 record fetches; when few
-// lanes walk (the later passes of a registration) the queue packs them into full waves: 124 -> 80, 87 -> 73, 68 -> 53 us.
-static int g_search_queue = getenv("SGA_SEARCH_QUEUE") ? atoi(getenv("SGA_SEARCH_QUEUE")) : 2;
-// 1 (default): the search waves evaluate the factors of their own tiles (search_linearize_kernel); 0: always a separate factor kernel (linearize_kernel)
-static bool g_fuse_search = getenv("SGA_FUSE_SEARCH") ? atoi(getenv("SGA_FUSE_SEARCH")) != 0 : true;
-// longest tile first (tile_order_kernel): 0 off, 1 = warm passes of the one-query-per-lane kernel (motion <= SGA_WARM_DELTA) when the
-// previous pass was such a pass too, 2 = every pass of that kernel that follows another (experiments)
-static const int g_lpt = getenv("SGA_LPT") ? atoi(getenv("SGA_LPT")) : 1;
-static const float g_slack_min = getenv("SGA_SLACK_MIN") ? static_cast<float>(atof(getenv("SGA_SLACK_MIN"))) : 3e-4f;
-static const float g_slack_max = getenv("SGA_SLACK_MAX") ? static_cast<float>(atof(getenv("SGA_SLACK_MAX"))) : 0.02f;
-// headroom of the certificate check (certify): a point walks unless its certificate survives PAD x its own motion beyond what this pass needs
-static const float g_cert_pad = getenv("SGA_CERT_PAD") ? static_cast<float>(atof(getenv("SGA_CERT_PAD"))) : 0.6f;
-static double g_queue_delta = getenv("SGA_QUEUE_DELTA") ? atof(getenv("SGA_QUEUE_DELTA")) : 0.02;
-// 1 (default): the one-query-per-lane search kernels walk with the fast leaf scan (32-bit keys, packed fp32; exact repeat of the
-// queries it cannot decide); 0: the exact 64-bit keys throughout.  Results do not depend on it.
-static int g_fast_scan = getenv("SGA_FAST_SCAN") ? atoi(getenv("SGA_FAST_SCAN")) : 1;
-static int g_chunk_tiles_cold = getenv("SGA_CHUNK_COLD") ? atoi(getenv("SGA_CHUNK_COLD")) : 4;
-static const bool g_chunk_adapt = getenv("SGA_CHUNK_ADAPT") ? atoi(getenv("SGA_CHUNK_ADAPT")) != 0 : true;
-static int g_chunk_tiles_warm = getenv("SGA_CHUNK_WARM") ? atoi(getenv("SGA_CHUNK_WARM")) : 4;
+struct PassPlan {
+  Route route = Route::kFactors;
+  bool warm = false;          // the certificates of the previous pass are checked (a grid pass searches every point: cold)
+  bool grid = false;          // the target's cell grid serves the pass: ring 1 for the walkers (SGA_GRID_WALK), or all of it (kGrid)
+  int pts = 1;                // points per lane of the kernel that evaluates the factors by tiles: linearize_kernel, or 1 in certify
+  bool tail = false;          // that kernel also sums the rows (FusedTail); otherwise reduce_rows_kernel follows
+  bool order_record = false;  // kFusedLane: the waves record their durations, sorted afterwards (longest tile first, tile_order_kernel) ...
+  bool order_use = false;     // ... and the tiles start in the order the previous pass recorded
+  int chunk_tiles = 0;        // kQueue / kFusedQueue: tiles per wave
+  bool fused() const { return route == Route::kCertify || route == Route::kFusedLane || route == Route::kFusedQueue; }
+};
 
-int g_grid_mode = getenv("SGA_GRID") ? atoi(getenv("SGA_GRID")) : 1;  // what the cell grid is used for (see linearize_dispatch); sga_set_grid_mode
-long long g_grid_min_points = getenv("SGA_GRID_MIN_POINTS") ? atoll(getenv("SGA_GRID_MIN_POINTS")) : 65536;  // targets below this get no grid (cell_grid.hip)
+// The routing of one pass.  displacement: how far a source point can have moved since the previous pass (INFINITY: no previous pass
+// in the same arithmetic); unit: routing_unit.  Reads the problem, the target and the tuning table: no HIP call, no write.
+template <typename Real>
+static PassPlan plan_pass(const sga_context* ctx, const sga_problem* pb, const NNParams<Real>& q, double displacement, double unit, bool host_rejector) {
+  const sga_index* idx = pb->target;
+  PassPlan pl;
+  pl.warm = displacement <= g_warm_delta * unit;
+  pl.pts = linearize_pts(q.n, sizeof(Real) == 8);
+  if (q.n > 0 && idx->kind == SGA_INDEX_KDTREE) {
+    const bool small_warm = pl.warm && displacement <= kQueueDelta * unit;
+    const bool fuse = sizeof(Real) == 4 && !host_rejector;  // fp64 math: the fused kernels would spill (they exist for float only)
+    const int search_tiles = (q.n + kSearchBlock - 1) / kSearchBlock;
+    pl.grid = g_grid_mode != 0 && idx->grid_h > 0.f && q.bound2 < 3.0e38f && !host_rejector && q.leaves == nullptr;
+    bool use_grid = false;
+    if (pl.grid) {
+      const int rings = grid_rings_for(idx, std::sqrt(static_cast<double>(q.bound2)));
+      const bool first_pass = !pb->prev_valid;
+      use_grid = g_grid_mode >= 2 && rings > 0 && rings <= kGridMaxRings &&
+                 (g_grid_mode >= 4 || (!small_warm && (g_grid_mode == 3 || (!first_pass && pb->grid_open_frac <= kGridMaxOpen))));
+    }
+    const bool queue = g_search_queue == 1 || (g_search_queue == 2 && small_warm);
+    if (use_grid) {
+      pl.route = Route::kGrid;
+      pl.warm = false;
+    } else if (g_search_queue == 2 && small_warm && displacement <= kSplitDelta * unit && fuse && pb->n >= kSplitMinPoints && q.leaves == nullptr) {
+      pl.route = Route::kCertify;
+      pl.pts = 1;
+    } else if (fuse && !queue) {
+      pl.route = Route::kFusedLane;
+      pl.order_record = g_lpt != 0 && search_tiles >= 8192;  // fewer tiles than wave slots: all waves start at once, the order means nothing
+      // (the order was written behind the previous pass's hand-off on that pass's stream: a pass issued on another stream could read it half-written)
+      pl.order_use = pl.order_record && pb->order_tiles == static_cast<unsigned>(search_tiles) && pb->order_stream == ctx->stream && (g_lpt == 2 || pl.warm);
+    } else if (queue) {
+      pl.route = fuse && pl.warm ? Route::kFusedQueue : Route::kQueue;
+      pl.chunk_tiles = std::max(1, pl.warm ? g_chunk_tiles_warm : g_chunk_tiles_cold);
+      // a wave works through its chunk serially (two dependent round trips per tile): small clouds get shorter chunks, down to one tile,
+      // as long as that leaves no more than ~4 waves per SIMD (kWaveSlots4 = 256 CUs x 4 SIMDs x 4); C3 keeps its 4 tiles
+      if (pl.warm) pl.chunk_tiles = std::min(pl.chunk_tiles, std::max(1, (search_tiles + 4095) / 4096));
+    } else {
+      pl.route = Route::kLane;
+    }
+  }
+  // the search kernels that evaluate the factors leave one row per tile or chunk: reduce_rows_kernel sums them.  (certify: never at its
+  // sizes since kFuseMaxBlocks is 32: 128 - 256 workgroups taking the tail's ticket one after the other cost the late passes of a
+  // 250k-point source 28 us, 59 against 31: scripts/diag_shards.py, N = 4)
+  pl.tail = pl.route != Route::kFusedLane && pl.route != Route::kFusedQueue && q.n > 0 && grid_blocks(factor_tiles(q.n, pl.pts)) <= kFuseMaxBlocks;
+  return pl;
+}
+
+// the factor stage's view of the problem that every kind of pass shares: clouds, correspondences, pose, rejector and robust kernel
+// (a host rejector sees every nearest neighbour: no distance rejection of its own)
+template <typename Real>
+static LinParams<Real> factor_params(const sga_problem* pb, const sga_factor_params* fp, const double T[16], bool host_rejector) {
+  const sga_index* idx = pb->target;
+  LinParams<Real> p{};
+  p.src_pts = pb->src_pts();
+  p.src_cov = pb->src_cov();
+  p.n = static_cast<int>(pb->n);
+  p.tgt_pts = idx->kind != SGA_INDEX_KDTREE ? idx->pts.p : idx->kd_pts.p;
+  p.tgt_nrm = idx->nrm.p;
+  p.tgt_cov = idx->cov.p;
+  p.corr = pb->corr.p;
+  p.hint = pb->hint.p;
+  if constexpr (sizeof(Real) == 4)
+    p.maha = pb->maha.p;
+  else
+    p.maha = pb->maha64.p;
+  p.T = rigid_from_colmajor<Real>(T);
+  p.max_sq = (fp->max_dist_sq < 0 || host_rejector) ? INFINITY : static_cast<float>(fp->max_dist_sq);
+  p.bound2 = p.max_sq < 3.0e38f ? p.max_sq * 1.0000002f : INFINITY;  // d2 == max_sq must still be found (strict '>' rejector)
+  p.robust_kind = fp->robust_kind;
+  p.robust_c = static_cast<Real>(fp->robust_c);
+  return p;
+}
 
 template <typename Real>
 static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double* d_out30, double* host, unsigned long long seq, bool with_model = false) {
@@ -1587,15 +1734,10 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
     return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals");
   if (fp->factor_kind < 0 || fp->factor_kind > 2) return fail(SGA_ERR_INVALID, "invalid factor_kind %d", fp->factor_kind);
 
-  LinParams<Real> p{};
-  p.src_pts = pb->src_pts();
-  p.src_cov = pb->src_cov();
-  p.n = static_cast<int>(pb->n);
-  const int pts = linearize_pts(p.n, sizeof(Real) == 8);
-  p.num_tiles = (p.n + kTile * pts - 1) / (kTile * pts);  // steps of kTile * pts points
-  p.tgt_pts = voxel ? idx->pts.p : idx->kd_pts.p;
-  p.tgt_nrm = idx->nrm.p;
-  p.tgt_cov = idx->cov.p;
+  if constexpr (sizeof(Real) == 8)
+    if (pb->maha64.n < pb->n * 6) SGA_TRY(pb->maha64.alloc(pb->n * 6));
+  const bool host_rejector = pb->rejector_fn != nullptr && !voxel;
+  LinParams<Real> p = factor_params<Real>(pb, fp, T, host_rejector);
   if (flat) {
     p.flat.hkeys = idx->hkeys.p;
     p.flat.hvals = idx->hvals.p;
@@ -1614,220 +1756,120 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
   } else {
     p.kd = make_kd_view(idx);
   }
-  p.corr = pb->corr.p;
-  p.hint = pb->hint.p;
   p.cert_nn2 = (!voxel && sizeof(Real) == 8) ? pb->hint2.p : nullptr;  // fp64 arithmetic: the factor kernel measures the walk's two candidates again, in double
-  if constexpr (sizeof(Real) == 4) {
-    p.maha = pb->maha.p;
-  } else {
-    if (pb->maha64.n < pb->n * 6) SGA_TRY(pb->maha64.alloc(pb->n * 6));
-    p.maha = pb->maha64.p;
-  }
-  p.T = rigid_from_colmajor<Real>(T);
-  p.store_maha = (fp->robust_kind != SGA_ROBUST_NONE || !g_lazy_maha) ? 1 : 0;  // the error passes of a robust factor run the error kernel
-  const bool host_rejector = pb->rejector_fn != nullptr && !voxel;
-  p.max_sq = (fp->max_dist_sq < 0 || host_rejector) ? INFINITY : static_cast<float>(fp->max_dist_sq);  // a user rejector sees every nearest neighbour
-  p.bound2 = p.max_sq < 3.0e38f ? p.max_sq * 1.0000002f : INFINITY;  // d2 == max_sq must still be found (strict '>' rejector)
-  p.robust_kind = fp->robust_kind;
-  p.robust_c = static_cast<Real>(fp->robust_c);
+  p.store_maha = fp->robust_kind != SGA_ROBUST_NONE ? 1 : 0;  // the error passes of a robust factor run the error kernel
   p.partials = pb->partials.p;
-  const int blocks = grid_blocks(p.num_tiles);
-  const bool fuse = p.n > 0 && blocks <= g_fuse_max;
   const int ncols = kModelCols, out_n = with_model ? kRow : SGA_ACCUM_DOUBLES;  // the caller's buffer: the system, or the system + its moments
-  p.tail = FusedTail{fuse ? 1 : 0, ctx->d_ticket.p, d_out30, out_n, host, seq};
 
   // warm pass?  Only with certificates from a previous pass in the same arithmetic (the queries must be bit-identical), and only
   // while no source point can have moved farther than the certificates can possibly cover.
   const int math = sizeof(Real) == 4 ? SGA_MATH_FP32 : SGA_MATH_FP64;
   const double displacement = (!voxel && p.n > 0 && pb->prev_valid && pb->prev_math == math) ? max_displacement(T, pb->T_prev, pb->bbox_lo, pb->bbox_hi) : INFINITY;
   const double unit = voxel ? 1.0 : routing_unit(idx);  // the target's own length scale relative to the scene the thresholds were tuned on
-  bool warm = displacement <= g_warm_delta * unit;
-  // The cell grid (cell_grid.hpp).  SGA_GRID: 0 no grid at all; 1 (default) the WALKERS of warm passes try ring 1 of the grid before they
-  // walk the tree (certify_linearize_kernel) and every full search stays with the kd walk — measured on C3 whole grid passes do not beat
-  // it; 2 = also the cold passes of a registration but its first (whose queries lie as far from the target as the
-  // initial guess is off: there the kd walk's pruning pays) and the warm passes after a larger motion; 3 the first pass too; 4 every pass.
-  // If ring 1 of the last grid pass left more than SGA_GRID_MAX_OPEN of the queries open, the next cold pass walks the kd-tree instead.
-  const int grid_mode = g_grid_mode;
-  static const int grid_max_rings = getenv("SGA_GRID_MAX_RINGS") ? atoi(getenv("SGA_GRID_MAX_RINGS")) : 16;
-  static const double grid_max_open = getenv("SGA_GRID_MAX_OPEN") ? atof(getenv("SGA_GRID_MAX_OPEN")) : 0.5;
-  const bool first_pass = !pb->prev_valid;
-  bool use_grid = false;
+  NNParams<Real> q{};
+  q.src_pts = pb->src_pts();
+  q.n = p.n;
+  q.kd = p.kd;
+  q.T = p.T;
+  q.within2 = p.bound2;
+  q.slack_min = static_cast<float>(kSlackMin * unit), q.slack_max = static_cast<float>(kSlackMax * unit);
+  q.cert_pad = std::max(g_cert_pad, 0.f);
+  q.bound2 = p.bound2 * (1.f + kSearchMargin) * (1.f + kSearchMargin);
+  q.nn = pb->hint.p, q.nn2 = pb->hint2.p, q.rex = pb->rex.p, q.walked = pb->walked.p;
+  q.fast = g_fast_scan;
+  q.leaves = pb->dbg_leaves.n >= pb->n ? pb->dbg_leaves.p : nullptr;
+
+  const PassPlan plan = plan_pass<Real>(ctx, pb, q, displacement, unit, host_rejector);
+  p.num_tiles = factor_tiles(p.n, plan.pts);
+  const int blocks = grid_blocks(p.num_tiles);
+  p.tail = FusedTail{plan.tail ? 1 : 0, ctx->d_ticket.p, d_out30, out_n, host, seq};
+  q.check = plan.warm ? 1 : 0;
+  if (plan.warm) q.T_prev = rigid_from_colmajor<Real>(pb->T_prev);
+  if (plan.grid) {
+    q.grid_walk = g_grid_walk;
+    q.grid = make_grid_view(idx);
+  }
+  q.chunk_tiles = plan.chunk_tiles;
 
   const bool timed = ctx->profiling && (ctx->lin_seq++ % ctx->profile_period) == 0;  // sampled: event records cost ~7 us each
   if (timed) {
     sga_profile_collect_pending(ctx);
     (void)hipEventRecord(ctx->ev0, ctx->stream);
-    ctx->pending_warm = warm;
+    ctx->pending_warm = plan.warm;
   }
-  bool split_fused_tail = false;  // certify_linearize_kernel of a small grid: the row reduction and the hand-off happen inside it
-  bool fused_search = false;  // the search kernel evaluates the factors itself ...
-  bool record_tiles = false;  // ... and records the duration of every tile's wave (longest tile first, tile_order_kernel)
-  int fused_rows = 0;         // ... and leaves this many partial rows
+  int rows = p.n > 0 ? blocks : 0;  // partial rows left for reduce_rows_kernel
   // The search kernels rewrite hint / hint2 / rex for THIS pose: until the pass has been launched completely the certificates belong
   // to no pose the host knows, so an early return below (allocation, rejector callback, launch error) must not leave them marked
   // valid for T_prev.
+  const bool first_pass = !pb->prev_valid;
   if (!voxel) pb->prev_valid = false;
   pb->state_fresh = false;
-  if (p.n > 0 && !voxel) {
-    NNParams<Real> q{};
-    q.src_pts = pb->src_pts();
-    q.n = p.n;
-    q.kd = p.kd;
-    q.T = p.T;
-    q.within2 = p.bound2;
-    q.slack_min = static_cast<float>(g_slack_min * unit), q.slack_max = static_cast<float>(g_slack_max * unit);
-    q.cert_pad = std::max(g_cert_pad, 0.f);
-    q.bound2 = p.bound2 * (1.f + kSearchMargin) * (1.f + kSearchMargin);
-    q.nn = pb->hint.p;
-    q.nn2 = pb->hint2.p;
-    q.rex = pb->rex.p;
-    q.check = warm ? 1 : 0;
-    q.fast = g_fast_scan;
-    if (warm) q.T_prev = rigid_from_colmajor<Real>(pb->T_prev);
-    q.walked = pb->walked.p;
-    q.leaves = pb->dbg_leaves.n >= pb->n ? pb->dbg_leaves.p : nullptr;
+  if (plan.route != Route::kFactors) {
     if (q.leaves != nullptr) SGA_HIP(hipMemsetAsync(q.leaves, 0, pb->n * sizeof(int), ctx->stream));
+    if (plan.grid && (first_pass || (plan.route != Route::kGrid && !plan.warm))) pb->grid_open_frac = 0.0;  // a kd pass in between: the grid gets another chance afterwards
+    pb->order_tiles = 0;  // (set again below when this pass records its tiles' durations)
     const size_t words = static_cast<size_t>(p.kd.depth);  // traversal stack rows
     const dim3 sgrid((p.n + kSearchBlock - 1) / kSearchBlock), sblock(kSearchBlock);
-    if (grid_mode != 0 && idx->grid_h > 0.f && q.bound2 < 3.0e38f && !host_rejector && q.leaves == nullptr) {
-      const int rings = grid_rings_for(idx, std::sqrt(static_cast<double>(q.bound2)));
-      const bool small_warm = warm && displacement <= g_queue_delta * unit;
-      use_grid = grid_mode >= 2 && rings > 0 && rings <= grid_max_rings &&
-                 (grid_mode >= 4 || (!small_warm && (grid_mode == 3 || (!first_pass && pb->grid_open_frac <= grid_max_open))));
-      // which walkers try ring 1 of the grid first (SGA_GRID_WALK, bits): 1 those of certify_linearize_kernel, 2 those of the
-      // one-query-per-lane warm pass (search_linearize_kernel<CHECK>), 4 those of the queue-fed kernel, 8 certify_linearize_kernel scans ring 1
-      // with a group of lanes per walker when a workgroup has few of them (grid_ring1_group); 32: a ring certificate that ends at the ring's
-      // face with less than the re-walk's slack beyond the neighbour is left to the tree walk (the margin rule, certify_linearize_kernel)
-      static const int grid_walk_bits = getenv("SGA_GRID_WALK") ? atoi(getenv("SGA_GRID_WALK")) : 47;
-      q.grid_walk = grid_walk_bits;
-      q.grid = make_grid_view(idx);
-      if (first_pass || (!use_grid && !warm)) pb->grid_open_frac = 0.0;  // a kd pass in between: the grid gets another chance afterwards
-    }
-    if (use_grid) {
-      warm = false;  // a full search of every point: the pass counts as cold
-      if (timed) ctx->pending_warm = false;
-      if (pb->grid_stats.n < 4) {
-        SGA_TRY(pb->grid_stats.alloc(4));
-        SGA_HIP(hipMemsetAsync(pb->grid_stats.p, 0, 4 * sizeof(uint32_t), ctx->stream));
-      }
-      SGA_TRY(grid_search_pass<Real>(ctx, idx, pb->src_pts(), p.n, p.T, q.bound2, pb->hint.p, pb->hint2.p, pb->rex.p, pb->grid_stats.p));
-      pb->order_tiles = 0;
-      pb->grid_passes++;
-    }
-    const bool queue = !use_grid && (g_search_queue == 1 || (g_search_queue == 2 && warm && displacement <= g_queue_delta * unit));
-    // Warm pass of a large cloud after a small motion: the certificates are checked inside the streaming factor kernel
-    // (certify_linearize_kernel), whose workgroups walk their few failed points themselves.  SGA_WARM_SPLIT=0: the older form
-    // (certificate check, queue-fed walks and factors per chunk in nn_search_queue_kernel).
-    static const bool warm_split = getenv("SGA_WARM_SPLIT") ? atoi(getenv("SGA_WARM_SPLIT")) != 0 : true;
-    // Measured on C3 (profiles/r04_warm_split.txt): it wins where few points walk (after motions of a millimetre or two: 38 - 54 us
-    // against 44 - 66) and loses where many do (the walkers of a pass sit where the points moved most, i.e. in a few workgroups, which
-    // then walk alone: 121 against 99 us after a 1 cm motion), hence the second, smaller limit SGA_SPLIT_DELTA.
-    static const double split_delta = getenv("SGA_SPLIT_DELTA") ? atof(getenv("SGA_SPLIT_DELTA")) : 0.002;
-    // Only from SGA_SPLIT_MIN_POINTS source points on (default 262144; 131072 until the size sweep late in round 6: late passes of 135k / 200k /
-    // 300k / 400k / 600k-point pairs 27.3 / 29.1 / 33.8 / 35.0 / 41.0 us with this kernel against 24.6 / 26.6 / 34.2 / 38.5 / 43.2 us with the
-    // queue-fed one: the crossover is near 300k): measured on C2 (100k points) and C5 (12k-point
-    // scans) the kernel — one point per lane there, the row reduction folded into it (fused_tail) when the grid is small — is no faster
-    // than the queue-fed one (C2 warm pass 39.9 against 40.3 us, C5 registration 0.51 against 0.48 ms/scan; with 4 points per lane 53.9 us):
-    // at those sizes a pass is a chain of launch, a few dependent loads and the hand-off, whichever kernel runs it.
-    static const size_t split_min_points = getenv("SGA_SPLIT_MIN_POINTS") ? static_cast<size_t>(atoll(getenv("SGA_SPLIT_MIN_POINTS"))) : 262144;
-    static const int split_pts_env = getenv("SGA_SPLIT_PTS") ? atoi(getenv("SGA_SPLIT_PTS")) : 0;
-    const bool split = warm_split && queue && warm && displacement <= split_delta * unit && g_search_queue == 2 && g_fuse_search && !host_rejector && sizeof(Real) == 4 && pb->n >= split_min_points && q.leaves == nullptr;
-    fused_search = !use_grid && g_fuse_search && !host_rejector && !queue && sizeof(Real) == 4;  // fp64 math: the fused kernel would spill
-    const unsigned order_tiles_before = pb->order_tiles;
-    pb->order_tiles = 0;  // (set again below when this pass records its tiles' durations)
-    if (use_grid) {
-      // searched above; the factors follow as linearize_kernel over nn[]
-    } else if (split) {
-      // one point per lane unless told otherwise (SGA_SPLIT_PTS=4): the size sweep late in round 6 — late passes of 300k / 600k / 700k-point pairs
-      // 34.0 / 40.4 / 42.3 us at four per lane against 31.2 / 38.8 / 40.6 us at one, C3's warm passes 83.8 -> 81.2 us on average (+1.2 % on the headline)
-      const int spts = split_pts_env == 1 || split_pts_env == 4 ? split_pts_env : 1;
-      LinParams<Real>& pc = p;
-      pc.num_tiles = (p.n + kTile * spts - 1) / (kTile * spts);
-      const int cblocks = grid_blocks(pc.num_tiles);
-      // (never at its sizes since kFuseMaxBlocks is 32: 128 - 256 workgroups taking the tail's ticket one after the other cost the late passes
-      // of a 250k-point source 28 us, 59 against 31: scripts/diag_shards.py, N = 4)
-      const bool cfuse = cblocks <= g_fuse_max;
-      pc.tail = FusedTail{cfuse ? 1 : 0, ctx->d_ticket.p, d_out30, out_n, host, seq};
-      split_fused_tail = cfuse;
-      p.cert_nn = pb->hint.p;
-      p.cert_nn2 = pb->hint2.p;
-      p.cert_rex = pb->rex.p;
-      p.cert_walked = pb->walked.p;
-      p.T_prev = q.T_prev;
-      p.cert_within2 = q.within2;
-      p.cert_slack_min = q.slack_min, p.cert_slack_max = q.slack_max;
-      p.cert_pad = q.cert_pad;
-      const size_t lds = std::max<size_t>(words, 1) * 64 * sizeof(uint32_t) * (kTile / 64);
-#define SGA_CERTIFY(F)                                                                                                                      \
-  do {                                                                                                                                      \
-    if (spts == kLinPts)                                                                                                                    \
-      hipLaunchKernelGGL((certify_linearize_kernel<Real, F, kLinPts>), dim3(cblocks), dim3(kTile), lds, ctx->stream, p, q);  \
-    else                                                                                                                                    \
-      hipLaunchKernelGGL((certify_linearize_kernel<Real, F, 1>), dim3(cblocks), dim3(kTile), lds, ctx->stream, p, q);        \
-  } while (0)
-      switch (fp->factor_kind) {
-        case SGA_GICP: SGA_CERTIFY(SGA_GICP); break;
-        case SGA_PLANE_ICP: SGA_CERTIFY(SGA_PLANE_ICP); break;
-        default: SGA_CERTIFY(SGA_ICP); break;
-      }
-#undef SGA_CERTIFY
-      fused_search = true;
-      fused_rows = cblocks;
-    } else if (fused_search) {
-      // every search wave evaluates the factors of its own tile: one partial row per tile of 64 points, summed by reduce_rows_kernel
-      p.tail.enabled = 0;
-      fused_rows = static_cast<int>(sgrid.x);
-      const dim3 cgrid(sgrid.x);
-      if (g_lpt != 0 && sgrid.x >= 8192) {  // fewer tiles than wave slots: all waves start at once, the order means nothing
-        SGA_TRY(pb->tile_cost.reserve(sgrid.x));
-        SGA_TRY(pb->tile_order.reserve(sgrid.x));
-        q.tile_cost = pb->tile_cost.p;
-        // (the order was written behind the previous pass's hand-off on that pass's stream: a pass issued on another stream could read it half-written)
-        if (order_tiles_before == sgrid.x && pb->order_stream == ctx->stream && (g_lpt == 2 || warm)) q.tile_order = pb->tile_order.p;
-        record_tiles = true;
-      }
-      static const size_t lds_pad = getenv("SGA_LDS_PAD") ? static_cast<size_t>(atoi(getenv("SGA_LDS_PAD"))) : 0;  // experiments: bytes of unused LDS per wave (lowers the occupancy)
-      const size_t lds = std::max<size_t>(words, 3) * 64 * sizeof(uint32_t) + lds_pad;
-      switch (fp->factor_kind) {
-        case SGA_GICP:
-          if (warm) hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_GICP, true>), cgrid, sblock, lds, ctx->stream, q, p);
-          else hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_GICP, false>), cgrid, sblock, lds, ctx->stream, q, p);
-          break;
-        case SGA_PLANE_ICP:
-          if (warm) hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_PLANE_ICP, true>), cgrid, sblock, lds, ctx->stream, q, p);
-          else hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_PLANE_ICP, false>), cgrid, sblock, lds, ctx->stream, q, p);
-          break;
-        default:
-          if (warm) hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_ICP, true>), cgrid, sblock, lds, ctx->stream, q, p);
-          else hipLaunchKernelGGL((search_linearize_kernel<Real, SGA_ICP, false>), cgrid, sblock, lds, ctx->stream, q, p);
-          break;
-      }
-    } else if (queue) {
-      q.inv_leaf = p.kd.n > 0 ? std::ldexp(1.0, p.kd.depth) / static_cast<double>(p.kd.n) : 0.0;
-      q.chunk_tiles = std::max(1, warm ? g_chunk_tiles_warm : g_chunk_tiles_cold);
-      // a wave works through its chunk serially (two dependent round trips per tile): small clouds get shorter chunks, down to one tile,
-      // as long as that leaves no more than ~4 waves per SIMD (kWaveSlots4 = 256 CUs x 4 SIMDs x 4); C3 keeps its 4 tiles
-      if (warm && g_chunk_adapt) q.chunk_tiles = std::min(q.chunk_tiles, std::max(1, (static_cast<int>(sgrid.x) + 4095) / 4096));
-      const dim3 qgrid((sgrid.x + q.chunk_tiles - 1) / q.chunk_tiles);
-      const size_t lds = std::max<size_t>(words, 3) * 64 * sizeof(uint32_t);
-      fused_search = g_fuse_search && !host_rejector && warm && sizeof(Real) == 4;
-      if (fused_search) {  // the chunk's wave evaluates the factors as well: one partial row per chunk
-        p.tail.enabled = 0;
-        fused_rows = static_cast<int>(qgrid.x);
-        const dim3 cgrid(qgrid.x);
-        switch (fp->factor_kind) {
-          case SGA_GICP: hipLaunchKernelGGL((nn_search_queue_kernel<Real, true, SGA_GICP>), cgrid, sblock, lds, ctx->stream, q, p); break;
-          case SGA_PLANE_ICP: hipLaunchKernelGGL((nn_search_queue_kernel<Real, true, SGA_PLANE_ICP>), cgrid, sblock, lds, ctx->stream, q, p); break;
-          default: hipLaunchKernelGGL((nn_search_queue_kernel<Real, true, SGA_ICP>), cgrid, sblock, lds, ctx->stream, q, p); break;
+    switch (plan.route) {
+      case Route::kGrid:  // the factors follow as linearize_kernel over nn[]
+        if (pb->grid_stats.n < 4) {
+          SGA_TRY(pb->grid_stats.alloc(4));
+          SGA_HIP(hipMemsetAsync(pb->grid_stats.p, 0, 4 * sizeof(uint32_t), ctx->stream));
         }
-      } else if (warm)
-        hipLaunchKernelGGL((nn_search_queue_kernel<Real, true>), qgrid, sblock, lds, ctx->stream, q, p);
-      else
-        hipLaunchKernelGGL((nn_search_queue_kernel<Real, false>), qgrid, sblock, lds, ctx->stream, q, p);
-    } else if (warm)
-      hipLaunchKernelGGL((nn_search_kernel<Real, kSearchBlock, true>), sgrid, sblock, words * kSearchBlock * sizeof(uint32_t), ctx->stream, q);
-    else
-      hipLaunchKernelGGL((nn_search_kernel<Real, kSearchBlock, false>), sgrid, sblock, words * kSearchBlock * sizeof(uint32_t), ctx->stream, q);
+        SGA_TRY(grid_search_pass<Real>(ctx, idx, pb->src_pts(), p.n, p.T, q.bound2, pb->hint.p, pb->hint2.p, pb->rex.p, pb->grid_stats.p));
+        pb->grid_passes++;
+        break;
+      case Route::kCertify:
+        if constexpr (sizeof(Real) == 4) {
+          p.cert_nn = q.nn, p.cert_nn2 = q.nn2, p.cert_rex = q.rex, p.cert_walked = q.walked;
+          p.T_prev = q.T_prev, p.cert_within2 = q.within2, p.cert_pad = q.cert_pad;
+          p.cert_slack_min = q.slack_min, p.cert_slack_max = q.slack_max;
+          const size_t lds = std::max<size_t>(words, 1) * 64 * sizeof(uint32_t) * (kTile / 64);
+          with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((certify_linearize_kernel<Real, decltype(f)::value, 1>), dim3(blocks), dim3(kTile), lds, ctx->stream, p, q); });
+        }
+        break;
+      case Route::kFusedLane:
+        if constexpr (sizeof(Real) == 4) {  // one partial row per tile of 64 points
+          rows = static_cast<int>(sgrid.x);
+          if (plan.order_record) {
+            SGA_TRY(pb->tile_cost.reserve(sgrid.x));
+            SGA_TRY(pb->tile_order.reserve(sgrid.x));
+            q.tile_cost = pb->tile_cost.p;
+            if (plan.order_use) q.tile_order = pb->tile_order.p;
+          }
+          const size_t lds = std::max<size_t>(words, 3) * 64 * sizeof(uint32_t);
+          with_factor(fp->factor_kind, [&](auto f) {
+            if (plan.warm)
+              hipLaunchKernelGGL((search_linearize_kernel<Real, decltype(f)::value, true>), sgrid, sblock, lds, ctx->stream, q, p);
+            else
+              hipLaunchKernelGGL((search_linearize_kernel<Real, decltype(f)::value, false>), sgrid, sblock, lds, ctx->stream, q, p);
+          });
+        }
+        break;
+      case Route::kFusedQueue:
+      case Route::kQueue: {
+        q.inv_leaf = p.kd.n > 0 ? std::ldexp(1.0, p.kd.depth) / static_cast<double>(p.kd.n) : 0.0;
+        const dim3 qgrid((sgrid.x + q.chunk_tiles - 1) / q.chunk_tiles);
+        const size_t lds = std::max<size_t>(words, 3) * 64 * sizeof(uint32_t);
+        if (plan.route == Route::kFusedQueue) {
+          if constexpr (sizeof(Real) == 4) {  // one partial row per chunk
+            rows = static_cast<int>(qgrid.x);
+            with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((nn_search_queue_kernel<Real, true, decltype(f)::value>), qgrid, sblock, lds, ctx->stream, q, p); });
+          }
+        } else if (plan.warm)
+          hipLaunchKernelGGL((nn_search_queue_kernel<Real, true>), qgrid, sblock, lds, ctx->stream, q, p);
+        else
+          hipLaunchKernelGGL((nn_search_queue_kernel<Real, false>), qgrid, sblock, lds, ctx->stream, q, p);
+        break;
+      }
+      case Route::kLane:
+        if (plan.warm)
+          hipLaunchKernelGGL((nn_search_kernel<Real, kSearchBlock, true>), sgrid, sblock, words * kSearchBlock * sizeof(uint32_t), ctx->stream, q);
+        else
+          hipLaunchKernelGGL((nn_search_kernel<Real, kSearchBlock, false>), sgrid, sblock, words * kSearchBlock * sizeof(uint32_t), ctx->stream, q);
+        break;
+      case Route::kFactors: break;
+    }
     if (timed) {
       (void)hipEventRecord(ctx->ev_mid, ctx->stream);
       ctx->mid_recorded = true;
@@ -1858,42 +1900,28 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
       p.reject = pb->reject.p;
     }
   }
-  if (p.n > 0 && !fused_search) {
-    if (flat) {
-      if (fp->factor_kind == SGA_GICP)
-        launch_linearize<Real, SGA_GICP, 2>(ctx->stream, p, blocks, pts);
-      else if (fp->factor_kind == SGA_PLANE_ICP)
-        launch_linearize<Real, SGA_PLANE_ICP, 2>(ctx->stream, p, blocks, pts);
-      else
-        launch_linearize<Real, SGA_ICP, 2>(ctx->stream, p, blocks, pts);
-    } else if (voxel) {
-      if (fp->factor_kind == SGA_GICP)
-        launch_linearize<Real, SGA_GICP, 1>(ctx->stream, p, blocks, pts);
-      else
-        launch_linearize<Real, SGA_ICP, 1>(ctx->stream, p, blocks, pts);
-    } else {
-      switch (fp->factor_kind) {
-        case SGA_GICP: launch_linearize<Real, SGA_GICP, 0>(ctx->stream, p, blocks, pts); break;
-        case SGA_PLANE_ICP: launch_linearize<Real, SGA_PLANE_ICP, 0>(ctx->stream, p, blocks, pts); break;
-        default: launch_linearize<Real, SGA_ICP, 0>(ctx->stream, p, blocks, pts); break;
-      }
-    }
+  if (p.n > 0 && !plan.fused()) {
+    with_factor(fp->factor_kind, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      if (flat)
+        launch_linearize<Real, F, 2>(ctx->stream, p, blocks, plan.pts);
+      else if (voxel) {
+        if constexpr (F != SGA_PLANE_ICP) launch_linearize<Real, F, 1>(ctx->stream, p, blocks, plan.pts);  // (a Gaussian map refuses PLANE_ICP above)
+      } else
+        launch_linearize<Real, F, 0>(ctx->stream, p, blocks, plan.pts);
+    });
   }
-  if (fused_search && split_fused_tail) {
-    // (done inside the kernel: fused tail of a small grid)
-  } else if (fused_search) {
-    launch_reduce(ctx, pb->partials.p, fused_rows, ncols, kRow, pb->partials.p + partial_rows(pb->n) * kRow, d_out30, out_n, host, seq, true);
-  }
-  else if (!fuse)
-    launch_reduce(ctx, pb->partials.p, p.n > 0 ? blocks : 0, ncols, kRow, pb->partials.p + partial_rows(pb->n) * kRow, d_out30, out_n, host, seq, true, use_grid ? pb->grid_stats.p : nullptr);
-  pb->grid_stats_pending = use_grid && !fuse && out_n > kStatsCol + 1;
+  // the sum of the rows: inside the factor kernel (tail), or reduce_rows_kernel over the rows of the fused search or of the factor
+  // kernel's workgroups (a grid pass's search statistics ride along)
+  if (!plan.tail) launch_reduce(ctx, pb->partials.p, rows, ncols, kRow, pb->partials.p + partial_rows(pb->n) * kRow, d_out30, out_n, host, seq, true, plan.route == Route::kGrid ? pb->grid_stats.p : nullptr);
+  pb->grid_stats_pending = plan.route == Route::kGrid && !plan.tail && out_n > kStatsCol + 1;
   if (timed) {  // the whole GPU side of the pass: search + factors + the sum of the rows
     (void)hipEventRecord(ctx->ev1, ctx->stream);
     ctx->pending |= 1;
   }
-  if (record_tiles) {  // after the reduction has handed the result to the host: the tiles are sorted while the host solves
-    hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(1024), 0, ctx->stream, pb->tile_cost.p, pb->tile_order.p, fused_rows);
-    pb->order_tiles = static_cast<unsigned>(fused_rows);
+  if (plan.order_record) {  // after the reduction has handed the result to the host: the tiles are sorted while the host solves
+    hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(1024), 0, ctx->stream, pb->tile_cost.p, pb->tile_order.p, rows);
+    pb->order_tiles = static_cast<unsigned>(rows);
     pb->order_stream = ctx->stream;
   }
   SGA_HIP(hipGetLastError());
@@ -1905,7 +1933,7 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
     memcpy(pb->T_prev, T, sizeof(pb->T_prev));
     pb->prev_valid = true;
     pb->prev_math = math;
-    if (warm)
+    if (plan.warm)
       pb->warm_passes++;
     else
       pb->cold_passes++;
@@ -1970,7 +1998,7 @@ static int error_dispatch(sga_context* ctx, sga_problem* pb, const sga_factor_pa
   p.robust_c = static_cast<Real>(fp->robust_c);
   p.partials = pb->partials.p;
   const int blocks = grid_blocks(p.num_tiles);
-  const bool fuse = p.n > 0 && blocks <= g_fuse_max;
+  const bool fuse = p.n > 0 && blocks <= kFuseMaxBlocks;
   p.tail = FusedTail{fuse ? 1 : 0, ctx->d_ticket.p, d_out1, 1, host, seq};
   if (fp->factor_kind == SGA_PLANE_ICP && !idx->has_normals) return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs target normals");
   const bool timed = ctx->profiling && (ctx->err_seq++ % ctx->profile_period) == 0;
@@ -1979,12 +2007,8 @@ static int error_dispatch(sga_context* ctx, sga_problem* pb, const sga_factor_pa
     (void)hipEventRecord(ctx->ev2, ctx->stream);
   }
   if (p.n > 0) {
-    switch (fp->factor_kind) {
-      case SGA_GICP: hipLaunchKernelGGL((error_kernel<Real, SGA_GICP>), dim3(blocks), dim3(kTile), 0, ctx->stream, p); break;
-      case SGA_PLANE_ICP: hipLaunchKernelGGL((error_kernel<Real, SGA_PLANE_ICP>), dim3(blocks), dim3(kTile), 0, ctx->stream, p); break;
-      case SGA_ICP: hipLaunchKernelGGL((error_kernel<Real, SGA_ICP>), dim3(blocks), dim3(kTile), 0, ctx->stream, p); break;
-      default: return fail(SGA_ERR_INVALID, "invalid factor_kind %d", fp->factor_kind);
-    }
+    if (fp->factor_kind < 0 || fp->factor_kind > 2) return fail(SGA_ERR_INVALID, "invalid factor_kind %d", fp->factor_kind);
+    with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((error_kernel<Real, decltype(f)::value>), dim3(blocks), dim3(kTile), 0, ctx->stream, p); });
   }
   if (timed) {
     (void)hipEventRecord(ctx->ev3, ctx->stream);
@@ -2180,8 +2204,6 @@ int problem_check_shard_frames(sga_context* ctx, sga_problem* pb) {
 
 using namespace sga;
 
-static bool g_error_model = getenv("SGA_ERROR_MODEL") ? atoi(getenv("SGA_ERROR_MODEL")) != 0 : true;
-
 extern "C" {
 
 void sga_debug_shard_frame_pack(const double origin[3], double out[SGA_FRAME_CHECK_DOUBLES]) { shard_frame_pack(origin, out); }
@@ -2213,41 +2235,19 @@ int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_
   SGA_TRY(sga_linearize(ctx, pb, &f32, T, H, b, &e, &ninl));  // neighbours + factor state at T
   const size_t n = pb->n;
   if (n == 0) return SGA_OK;
-  const sga_index* idx = pb->target;
-  LinParams<double> p{};
-  p.src_pts = pb->src_pts();
-  p.src_cov = pb->src_cov();
-  p.n = static_cast<int>(n);
-  p.tgt_pts = flat ? idx->pts.p : idx->kd_pts.p;
-  p.tgt_nrm = idx->nrm.p;
-  p.tgt_cov = idx->cov.p;
-  p.corr = pb->corr.p;
-  p.hint = pb->hint.p;
-  p.maha = pb->maha64.p;
   double Td[16];
-  p.T = rigid_from_colmajor<double>(problem_pose(pb, T, Td));
-  p.max_sq = fp->max_dist_sq < 0 ? INFINITY : static_cast<float>(fp->max_dist_sq);
-  p.bound2 = p.max_sq < 3.0e38f ? p.max_sq * 1.0000002f : INFINITY;
-  p.robust_kind = fp->robust_kind;
-  p.robust_c = fp->robust_c;
+  const LinParams<double> p = factor_params<double>(pb, fp, problem_pose(pb, T, Td), false);
   DevBuf<double> d_vals;
   DevBuf<unsigned char> d_ok;
   SGA_TRY(d_vals.alloc(n * 28));
   SGA_TRY(d_ok.alloc(n));
   const dim3 grid((n + 255) / 256), block(256);
-  if (flat) {
-    switch (fp->factor_kind) {
-      case SGA_GICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_GICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-      case SGA_PLANE_ICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_PLANE_ICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-      default: hipLaunchKernelGGL((per_point_kernel<double, SGA_ICP, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-    }
-  } else {
-    switch (fp->factor_kind) {
-      case SGA_GICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_GICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-      case SGA_PLANE_ICP: hipLaunchKernelGGL((per_point_kernel<double, SGA_PLANE_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-      default: hipLaunchKernelGGL((per_point_kernel<double, SGA_ICP>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); break;
-    }
-  }
+  with_factor(fp->factor_kind, [&](auto f) {
+    if (flat)
+      hipLaunchKernelGGL((per_point_kernel<double, decltype(f)::value, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p);
+    else
+      hipLaunchKernelGGL((per_point_kernel<double, decltype(f)::value>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p);
+  });
   SGA_HIP(hipGetLastError());
   SGA_HIP(hipMemcpyAsync(values28, d_vals.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SGA_HIP(hipMemcpyAsync(inlier, d_ok.p, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2539,7 +2539,6 @@ void preload_hot_kernels() {
   SGA_PRELOAD(search_linearize_kernel<float, F, false>);            \
   SGA_PRELOAD(search_linearize_kernel<float, F, true>);             \
   SGA_PRELOAD(nn_search_queue_kernel<float, true, F>);              \
-  SGA_PRELOAD(certify_linearize_kernel<float, F, kLinPts>);         \
   SGA_PRELOAD(certify_linearize_kernel<float, F, 1>);               \
   SGA_PRELOAD(linearize_kernel<float, F, 0, kLinPts>);              \
   SGA_PRELOAD(linearize_kernel<float, F, 0, 1>)
