@@ -17,6 +17,12 @@ int sga_problem_set_search_stats(sga_context* ctx, sga_problem* pb, int enabled)
 int sga_problem_get_search_stats(sga_context* ctx, const sga_problem* pb, int* leaves_per_point);
 /* The source points in the engine's order (n x 4 floats: x, y, z, original index as bits). */
 int sga_problem_get_sorted_points(sga_context* ctx, const sga_problem* pb, float* xyzw);
+/* The plan of the last linearization pass of this problem (csrc/linearize.hip: PassPlan, plan_pass): out[0] = the route (enum class Route:
+ * 0 factors, 1 grid, 2 certify, 3 fused lane, 4 fused queue, 5 queue, 6 lane), out[1] = warm, out[2] = the cell grid serves the pass,
+ * out[3] = points per lane of the factor kernel, out[4] = that kernel also summed the rows, out[5] = tiles per wave of the queue-fed
+ * kernels, out[6] = partial rows given to reduce_rows_kernel and out[7] = its workgroups (both 0 when the factor kernel summed the rows).
+ * All 0 before the first pass. */
+int sga_problem_get_last_plan(const sga_problem* pb, int out[8]);
 /* Cell-grid passes (cell_grid.hip) since the problem was created: out[0] = passes searched through the grid, out[1] = queries their
  * first ring left open (finished by the second kernel), out[2] = sum of the rings those queries then scanned, out[3] = cell edge in
  * micrometres (0: the target has no grid); out[4], out[5]: always 0 (counters of experiments removed in round 6). */

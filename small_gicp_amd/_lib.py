@@ -139,6 +139,7 @@ SYMBOLS = [
     ("sga_problem_get_search_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("sga_problem_get_sorted_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("sga_problem_get_grid_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("sga_problem_get_last_plan", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("sga_set_grid_mode", None, [C.c_int, C.c_longlong]),
     ("sga_host_alloc", C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     ("sga_host_free", C.c_int, [C.c_void_p]),

@@ -747,6 +747,16 @@ class Problem:
         check(load().sga_problem_get_factors(self.ctx.h, self.h, ti.ctypes.data_as(C.POINTER(C.c_int64)), _fp(m6)))
         return ti, m6
 
+    ROUTES = ("factors", "grid", "certify", "fused_lane", "fused_queue", "queue", "lane")  # enum class Route (csrc/linearize.hip)
+
+    def last_plan(self):
+        """Diagnostics (sga_problem_get_last_plan): the plan of the last linearization pass — its route by name, warm, grid, points per
+        lane, tail, chunk_tiles, and the rows and workgroups of the row reduction (0 when the factor kernel summed the rows itself)."""
+        out = (C.c_int * 8)()
+        check(load().sga_problem_get_last_plan(self.h, out))
+        v = list(out)
+        return {"route": self.ROUTES[v[0]], "warm": bool(v[1]), "grid": bool(v[2]), "pts": v[3], "tail": bool(v[4]), "chunk_tiles": v[5], "reduce_rows": v[6], "reduce_groups": v[7]}
+
     def align(self, setting, init_T=None):
         res = ResultC()
         t16 = _T16(init_T)

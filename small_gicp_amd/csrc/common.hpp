@@ -334,6 +334,7 @@ struct sga_problem {
   bool model_valid = false;
   double model[96] = {0};        // the reduced row: system + model sums
   double model_T[16] = {0};      // its pose
+  int last_plan[8] = {0};        // the PassPlan of the last linearize_dispatch (sga_problem_get_last_plan, small_gicp_amd_debug.h)
   // reduction scratch
   sga::DevBuf<double> partials;  // partial rows + the stage rows of reduce_rows_kernel
 };

@@ -134,7 +134,7 @@ struct LinParams {
   Real* __restrict__ maha;  // n*6
   int store_maha;  // cache the mahalanobis matrices for the error kernel (robust factors); otherwise they are recomputed if ever asked for
   Rigid<Real> T;
-  float max_sq;  // INFINITY = no rejector
+  Real max_sq;   // INFINITY = no rejector; in the pair arithmetic's type: fp64 passes compare double distances with the double threshold (rejector.hpp)
   float bound2;  // a neighbour counts only if kd_dist2 < bound2 (max_sq nudged up by an ulp, or INFINITY); the walks reach a little farther
   int robust_kind;
   Real robust_c;
@@ -593,7 +593,7 @@ __device__ __forceinline__ bool pair_factor(const LinParams<Real>& p, int i, int
                                             Real* g_out = nullptr) {
   const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
   const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && !(d2 > static_cast<Real>(p.max_sq));
+  const bool inlier = (j >= 0) && within_bound && !(d2 > p.max_sq);
   if (inlier) {
     Sym3<Real> M;
     if constexpr (FACTOR == SGA_GICP) {
@@ -671,7 +671,7 @@ __device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, in
                                              const float4* nn_pre) {
   const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
   const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && !(d2 > static_cast<Real>(p.max_sq));
+  const bool inlier = (j >= 0) && within_bound && !(d2 > p.max_sq);
   Mp = Sym3<Real>{};
   g[0] = g[1] = g[2] = Real(0);
   e = Real(0);
@@ -947,7 +947,7 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
               m4[u] = c;
             }
           }
-          within[u] = d1 <= static_cast<double>(p.max_sq);
+          within[u] = d1 <= p.max_sq;
           if (p.reject != nullptr) within[u] = within[u] && p.reject[__float_as_uint(ps4[u].w)] == 0;
           decided64[u] = true;
         }
@@ -1464,8 +1464,10 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __rest
 // the stage-1 rows of the reduction follow them
 static size_t partial_rows(size_t n) { return std::max<size_t>(kMaxBlocks, (n + 63) / 64); }
 
+static int reduce_groups(int nrows) { return nrows > 256 ? std::min(kReduceGroups, std::max(8, nrows / 128)) : 1; }  // <= 256 rows: one workgroup, no hand-off between workgroups
+
 static void launch_reduce(sga_context* ctx, const double* partials, int nrows, int ncols, int row_stride, double* stage, double* out, int out_n, double* host, unsigned long long seq, bool derive = false, const uint32_t* stats = nullptr) {
-  const int groups = nrows > 256 ? std::min(kReduceGroups, std::max(8, nrows / 128)) : 1;  // <= 256 rows: one workgroup, no hand-off between workgroups
+  const int groups = reduce_groups(nrows);
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(groups), dim3(kReduceSlices * kCols), 0, ctx->stream, partials, nrows, ncols, row_stride, stage, ctx->d_ticket.p, out, out_n, host, seq, derive ? 1 : 0, stats);
 }
 
@@ -1716,8 +1718,12 @@ static LinParams<Real> factor_params(const sga_problem* pb, const sga_factor_par
   else
     p.maha = pb->maha64.p;
   p.T = rigid_from_colmajor<Real>(T);
-  p.max_sq = (fp->max_dist_sq < 0 || host_rejector) ? INFINITY : static_cast<float>(fp->max_dist_sq);
-  p.bound2 = p.max_sq < 3.0e38f ? p.max_sq * 1.0000002f : INFINITY;  // d2 == max_sq must still be found (strict '>' rejector)
+  const bool rejects = !(fp->max_dist_sq < 0 || host_rejector);
+  p.max_sq = rejects ? static_cast<Real>(fp->max_dist_sq) : static_cast<Real>(INFINITY);
+  // the walks stay fp32: d2 == max_sq must still be found (strict '>' rejector), and the nudge also reaches past a double threshold
+  // that float(max_dist_sq) rounded down
+  const float max_sq_f = rejects ? static_cast<float>(fp->max_dist_sq) : INFINITY;
+  p.bound2 = max_sq_f < 3.0e38f ? max_sq_f * 1.0000002f : INFINITY;
   p.robust_kind = fp->robust_kind;
   p.robust_c = static_cast<Real>(fp->robust_c);
   return p;
@@ -1915,6 +1921,10 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
   // kernel's workgroups (a grid pass's search statistics ride along)
   if (!plan.tail) launch_reduce(ctx, pb->partials.p, rows, ncols, kRow, pb->partials.p + partial_rows(pb->n) * kRow, d_out30, out_n, host, seq, true, plan.route == Route::kGrid ? pb->grid_stats.p : nullptr);
   pb->grid_stats_pending = plan.route == Route::kGrid && !plan.tail && out_n > kStatsCol + 1;
+  {  // what sga_problem_get_last_plan reports
+    const int lp[8] = {static_cast<int>(plan.route), plan.warm, plan.grid, plan.pts, plan.tail, plan.chunk_tiles, plan.tail ? 0 : rows, plan.tail ? 0 : reduce_groups(rows)};
+    std::copy(lp, lp + 8, pb->last_plan);
+  }
   if (timed) {  // the whole GPU side of the pass: search + factors + the sum of the rows
     (void)hipEventRecord(ctx->ev1, ctx->stream);
     ctx->pending |= 1;
@@ -2496,6 +2506,13 @@ int sga_problem_get_sorted_points(sga_context* ctx, const sga_problem* pb, float
   SGA_ENTER(ctx);
   SGA_HIP(hipMemcpyAsync(xyzw, pb->src_pts(), pb->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   SGA_HIP(hipStreamSynchronize(ctx->stream));
+  return SGA_OK;
+}
+// diagnostics: the PassPlan of the last linearize_dispatch (route, warm, grid, points per lane, tail, chunk tiles, rows and workgroups
+// of reduce_rows_kernel)
+int sga_problem_get_last_plan(const sga_problem* pb, int out[8]) {
+  if (!pb || !out) return fail(SGA_ERR_INVALID, "null argument");
+  std::copy(pb->last_plan, pb->last_plan + 8, out);
   return SGA_OK;
 }
 int sga_problem_get_search_stats(sga_context* ctx, const sga_problem* pb, int* leaves_per_point) {

@@ -103,8 +103,12 @@ constexpr int kKnnBlock = 64;
 constexpr int kKnnMaxK = 116;  // (k * 8 + 96) * 64 bytes of LDS per workgroup must stay below 64 KB
 
 // queries64 / out_d2_64 (optional): the squared distances of the neighbours found are re-evaluated in double against the double
-// query — the coordinates stored on the device are fp32, the reference returns double distances (ann/kdtree.hpp:193-233)
-__global__ __launch_bounds__(kKnnBlock) void knn_kernel(const KdView t, const float* __restrict__ queries, size_t m, int k, float max_sq, long long* __restrict__ out_idx, float* __restrict__ out_d2, const double* __restrict__ queries64, double* __restrict__ out_d2_64) {
+// query — the coordinates stored on the device are fp32, the reference returns double distances (ann/kdtree.hpp:193-233).
+// F64 (queries64 / out_d2_64 given): the rejection compares that double distance with the double threshold max_sq64, as the reference
+// does (knn_result.hpp); the walk's fp32 bound is max_sq nudged up, which reaches past it.
+template <bool F64>
+__global__ __launch_bounds__(kKnnBlock) void knn_kernel(const KdView t, const float* __restrict__ queries, size_t m, int k, float max_sq, long long* __restrict__ out_idx, float* __restrict__ out_d2, const double* __restrict__ queries64, double* __restrict__ out_d2_64,
+                                                        double max_sq64) {
   extern __shared__ float sh[];  // k*64 distances, k*64 indices, kKdMaxDepth*64 stack words
   const int kpad = (k + 3) & ~3;  // kd_knn sweeps the list four slots at a time
   float* sd = sh;
@@ -123,6 +127,16 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const KdView t, const fl
   for (int j = 0; j < k; j++) {
     const float d2 = sd[j * kKnnBlock + lane];
     const int id = si[j * kKnnBlock + lane];
+    if constexpr (F64) {
+      const float4 c = id >= 0 ? t.pts[id] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const double dx = static_cast<double>(c.x) - queries64[3 * qi], dy = static_cast<double>(c.y) - queries64[3 * qi + 1], dz = static_cast<double>(c.z) - queries64[3 * qi + 2];
+      const double d64 = dx * dx + dy * dy + dz * dz;
+      const bool ok = id >= 0 && !(d64 > max_sq64);
+      out_idx[qi * k + j] = ok ? static_cast<long long>(__float_as_uint(c.w)) : -1ll;
+      out_d2[qi * k + j] = ok ? d2 : INFINITY;
+      out_d2_64[qi * k + j] = ok ? d64 : INFINITY;
+      continue;
+    }
     const bool ok = id >= 0 && !(d2 > max_sq);
     const float4 c = ok ? t.pts[id] : make_float4(0.f, 0.f, 0.f, 0.f);
     out_idx[qi * k + j] = ok ? static_cast<long long>(__float_as_uint(c.w)) : -1ll;
@@ -440,7 +454,11 @@ static int index_knn_impl(sga_context* ctx, const sga_index* index, const float*
     if (k > kKnnMaxK) return fail(SGA_ERR_INVALID, "k must be <= %d for a kd-tree (LDS per workgroup)", kKnnMaxK);
     const size_t shmem = (static_cast<size_t>((k + 3) & ~3) * 8 + kKdMaxDepth * 4) * kKnnBlock;
     KdView kv = make_kd_view(index);
-    hipLaunchKernelGGL(knn_kernel, dim3((m + kKnnBlock - 1) / kKnnBlock), dim3(kKnnBlock), shmem, ctx->stream, kv, d_q.p, m, k, max_sq, d_i.p, d_d.p, want64 ? d_q64.p : nullptr, want64 ? d_d64.p : nullptr);
+    const dim3 kgrid((m + kKnnBlock - 1) / kKnnBlock), kblock(kKnnBlock);
+    if (want64)
+      hipLaunchKernelGGL(knn_kernel<true>, kgrid, kblock, shmem, ctx->stream, kv, d_q.p, m, k, max_sq, d_i.p, d_d.p, d_q64.p, d_d64.p, max_sq_dist < 0 ? static_cast<double>(INFINITY) : max_sq_dist);
+    else
+      hipLaunchKernelGGL(knn_kernel<false>, kgrid, kblock, shmem, ctx->stream, kv, d_q.p, m, k, max_sq, d_i.p, d_d.p, nullptr, nullptr, 0.0);
   }
   SGA_HIP(hipGetLastError());
   SGA_HIP(hipMemcpyAsync(idx, d_i.p, m * k * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
