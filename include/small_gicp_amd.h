@@ -187,6 +187,24 @@ int sga_index_knn(sga_context* ctx, const sga_index* index, const float* queries
  * Python tests compare them with scipy to 1e-6 at ranges where fp32 resolves 1e-4, src/test/python_test.py:194-257). */
 int sga_index_knn_f64(sga_context* ctx, const sga_index* index, const double* queries, size_t m, int k, double max_sq_dist, int64_t* idx, double* sq_dist);
 
+/* Replaces ProjectiveSearch<PointCloud>(width, height, target) (ann/projective_search.hpp:161-163, UnsafeProjectiveSearch :49-62):
+ * the equirectangular index image of `cloud` (EquirectangularProjection :13-27; y down, z forward), one pixel per point, the highest
+ * index owning a pixel; points whose pixel lies out of the image (u == width) are dropped, non-finite points are skipped (undefined in
+ * the reference).  Search window 10 / 5, BorderRepeat horizontally and BorderClamp vertically (:42, :49).  A target for
+ * sga_problem_create / sga_align (ICP, PLANE_ICP with target normals, GICP with target covariances; correspondences and kNN indices are
+ * the cloud's own indices) and for sga_index_knn / _f64 (any k <= 128; the scan of :107-140 with KnnResult::push, duplicates of a column
+ * visited twice kept; the _f64 form measures double distances, sga_index_knn float ones).  Not usable as a source index, with a host
+ * rejector, for per-point factors or for normal / covariance estimation (SGA_ERR_UNSUPPORTED). */
+int sga_index_build_projective(sga_context* ctx, const sga_cloud* cloud, int width, int height, sga_index** out);
+/* search_window_h / search_window_v (:153-154), read at each search; each in [0, 65535]. */
+int sga_projective_set_search_window(sga_index* index, int h, int v);
+/* BorderModeH / BorderModeV (:41-42): non-zero = BorderRepeat (wraps once), 0 = BorderClamp (out-of-range rows / columns are skipped). */
+int sga_projective_set_border_modes(sga_index* index, int repeat_h, int repeat_v);
+/* {width, height, window h, window v, repeat_h, repeat_v} */
+int sga_projective_get_params(const sga_index* index, int out[6]);
+/* index_map (:152) in the reference's layout: out[v * width + u] = index_map(v, u), 0xFFFFFFFF = invalid_index. */
+int sga_projective_download_map(sga_context* ctx, const sga_index* index, uint32_t* out);
+
 /* ---- the hot path: Reduction::linearize / Reduction::error (registration/reduction_omp.hpp:24-70) ------------------------- */
 typedef struct sga_factor_params {
   int factor_kind;    /* sga_factor_kind */

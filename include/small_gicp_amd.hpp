@@ -202,6 +202,43 @@ struct KdTree {
   sga_index* h = nullptr;
 };
 
+/// ann/projective_search.hpp:158-183 ProjectiveSearch<PointCloud>(width, height, points): the equirectangular index image of the points
+/// (y down, z forward), searched over the (2 h + 1) x (2 v + 1) window around the query's pixel, BorderRepeat horizontally and
+/// BorderClamp vertically.  search_window_h / search_window_v are public as in the reference (:153-154) and honoured at every search
+/// and align.  Indices are the cloud's own; distances are double (sga_index_knn_f64).
+struct ProjectiveSearch {
+  using Ptr = std::shared_ptr<ProjectiveSearch>;
+  using ConstPtr = std::shared_ptr<const ProjectiveSearch>;
+  ProjectiveSearch(int width, int height, std::shared_ptr<const PointCloud> pts) : points(std::move(pts)) {
+    check(sga_index_build_projective(points->ctx, points->h, width, height, &h), "sga_index_build_projective");
+  }
+  ProjectiveSearch(const ProjectiveSearch&) = delete;
+  ProjectiveSearch& operator=(const ProjectiveSearch&) = delete;
+  ~ProjectiveSearch() { sga_index_destroy(h); }
+  /// the public window, pushed to the index before it is used
+  void sync() const { check(sga_projective_set_search_window(h, search_window_h, search_window_v), "sga_projective_set_search_window"); }
+  size_t knn_search(const double* pt, size_t k, size_t* k_indices, double* k_sq_dists) const {
+    sync();
+    std::vector<int64_t> idx(k);
+    std::vector<double> d2(k);
+    check(sga_index_knn_f64(points->ctx, h, pt, 1, static_cast<int>(k), -1.0, idx.data(), d2.data()), "sga_index_knn_f64");
+    size_t found = 0;
+    for (size_t j = 0; j < k; j++)
+      if (idx[j] >= 0) {
+        k_indices[found] = static_cast<size_t>(idx[j]);
+        k_sq_dists[found] = d2[j];
+        found++;
+      }
+    return found;
+  }
+  size_t nearest_neighbor_search(const double* pt, size_t* k_index, double* k_sq_dist) const { return knn_search(pt, 1, k_index, k_sq_dist); }
+
+  std::shared_ptr<const PointCloud> points;
+  sga_index* h = nullptr;
+  int search_window_h = 10;
+  int search_window_v = 5;
+};
+
 /// traits::knn_search / nearest_neighbor_search of a voxel map (ann/incremental_voxelmap.hpp:99-149) for one query: global indices
 /// (voxel_id << 32) | point_id, squared distances ascending; returns the number found
 inline size_t voxelmap_knn_search(sga_context* ctx, const sga_index* h, const double* pt, size_t k, size_t* k_indices, double* k_sq_dists) {
@@ -504,6 +541,13 @@ struct Registration {
     sga_problem_destroy(pb);
     check(rc, "sga_align_problem");
     return to_result(r);
+  }
+  /// target_tree: ProjectiveSearch (ICP / PLANE_ICP / GICP), its search window as the members say at this call
+  RegistrationResult align(const PointCloud& target, const PointCloud& source, const ProjectiveSearch& target_tree, const Isometry3d& init_T = Isometry3d::Identity()) const {
+    (void)target;
+    target_tree.sync();
+    check(sga_index_refresh_attributes(source.ctx, target_tree.h, target_tree.points->h), "sga_index_refresh_attributes");
+    return run(target_tree.h, source, init_T);
   }
   /// VGICP form (registration_helper.cpp:136: the voxel map is both target cloud and search structure)
   RegistrationResult align(const GaussianVoxelMap& target, const PointCloud& source, const GaussianVoxelMap& target_tree, const Isometry3d& init_T = Isometry3d::Identity()) const {

@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
     MultiProblem,
     PointCloud,
     Problem,
+    ProjectiveSearch,
     RegistrationResult,
     align,
     default_context,

@@ -110,6 +110,11 @@ SYMBOLS = [
     ("sga_index_create_flatmap_from_voxels_contents", C.c_int, [_vp, C.c_double, C.c_void_p, C.c_void_p, _dp, _dp, _dp, C.c_int, C.c_size_t, _pvp]),
     ("sga_index_knn", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_int64), _fp]),
     ("sga_index_knn_f64", C.c_int, [_vp, _vp, _dp, C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_int64), _dp]),
+    ("sga_index_build_projective", C.c_int, [_vp, _vp, C.c_int, C.c_int, _pvp]),
+    ("sga_projective_set_search_window", C.c_int, [_vp, C.c_int, C.c_int]),
+    ("sga_projective_set_border_modes", C.c_int, [_vp, C.c_int, C.c_int]),
+    ("sga_projective_get_params", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("sga_projective_download_map", C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     ("sga_factor_params_default", None, [C.POINTER(FactorParams)]),
     ("sga_problem_create", C.c_int, [_vp, _vp, _vp, _dp, _pvp]),
     ("sga_problem_create_from_index", C.c_int, [_vp, _vp, _vp, _dp, _pvp]),

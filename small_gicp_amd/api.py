@@ -347,6 +347,83 @@ class KdTree:
         return (1 if idx[0] >= 0 else 0), int(idx[0]), float(d2[0])
 
 
+class ProjectiveSearch:
+    """ProjectiveSearch<PointCloud>(width, height, points) (ann/projective_search.hpp:158-183): the equirectangular index image of the
+    points (y down, z forward), searched over a window of (2 h + 1) x (2 v + 1) pixels around the query's pixel (sga_index_build_projective).
+    border_h / border_v: "repeat" (BorderRepeat, wraps once) or "clamp" (BorderClamp, out-of-range pixels skipped).  A target for
+    Problem / align like a KdTree; indices are the cloud's own."""
+
+    _BORDERS = {"repeat": 1, "clamp": 0}
+
+    def __init__(self, points, width, height, search_window_h=10, search_window_v=5, border_h="repeat", border_v="clamp"):
+        if not isinstance(points, PointCloud):
+            points = PointCloud(points)
+        if border_h not in self._BORDERS or border_v not in self._BORDERS:
+            raise ValueError("border modes are 'repeat' or 'clamp'")
+        self.cloud = points
+        self.ctx = points.ctx
+        self.width, self.height = int(width), int(height)
+        self.h = C.c_void_p()
+        check(load().sga_index_build_projective(self.ctx.h, points.h, self.width, self.height, C.byref(self.h)))
+        self.set_search_window(search_window_h, search_window_v)
+        self.set_border_modes(border_h, border_v)
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            load().sga_index_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def set_search_window(self, h, v):
+        check(load().sga_projective_set_search_window(self.h, int(h), int(v)))
+        self.search_window_h, self.search_window_v = int(h), int(v)
+
+    def set_border_modes(self, border_h, border_v):
+        check(load().sga_projective_set_border_modes(self.h, self._BORDERS[border_h], self._BORDERS[border_v]))
+        self.border_h, self.border_v = border_h, border_v
+
+    def size(self):
+        n = C.c_size_t()
+        check(load().sga_index_size(self.h, C.byref(n)))
+        return n.value
+
+    __len__ = size
+
+    def origin(self):
+        o = np.empty(3)
+        check(load().sga_index_origin(self.h, _dp(o)))
+        return o
+
+    def index_map(self):
+        """index_map (projective_search.hpp:152): (height, width) uint32, [v][u] = the point owning pixel (u, v), 0xFFFFFFFF = none."""
+        out = np.empty((self.height, self.width), np.uint32)
+        check(load().sga_projective_download_map(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def refresh_attributes(self):
+        """Pull the cloud's current normals / covariances into the index (needed when they were set after the index was built)."""
+        check(load().sga_index_refresh_attributes(self.ctx.h, self.h, self.cloud.h))
+
+    def batch_knn_search(self, pts, k, max_sq_dist=-1.0, num_threads=1):
+        """(indices (m,k) int64, squared distances (m,k) float64): the reference's scan with double distances (sga_index_knn_f64); -1 / inf = none."""
+        q = np.ascontiguousarray(np.asarray(pts, dtype=np.float64).reshape(-1, np.shape(pts)[-1])[:, :3])
+        idx = np.empty((len(q), k), np.int64)
+        d2 = np.empty((len(q), k), np.float64)
+        check(load().sga_index_knn_f64(self.ctx.h, self.h, _dp(q), len(q), int(k), float(max_sq_dist), idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(d2)))
+        return idx, d2
+
+    def batch_nearest_neighbor_search(self, pts, num_threads=1):
+        idx, d2 = self.batch_knn_search(pts, 1)
+        return idx[:, 0], d2[:, 0]
+
+    def knn_search(self, pt, k):
+        idx, d2 = self.batch_knn_search(np.asarray(pt, dtype=np.float64).reshape(1, -1), k)
+        return idx[0], d2[0]
+
+    def nearest_neighbor_search(self, pt):
+        idx, d2 = self.knn_search(pt, 1)
+        return (1 if idx[0] >= 0 else 0), int(idx[0]), float(d2[0])
+
+
 class GaussianVoxelMap:
     """small_gicp.GaussianVoxelMap (src/python/voxelmap.cpp:20-140): `GaussianVoxelMap(leaf_size)`, then any number of
     `insert(cloud_with_covs, T)`; `set_lru(horizon, clear_cycle)`; `size()`, `voxel_points()`, `voxel_covs()`.
@@ -673,7 +750,7 @@ class Problem:
         self.ctx = ctx or source.ctx  # a problem may run on another context (stream) of the same device than the one that built its inputs
         self.h = C.c_void_p()
         t16 = _T16(init_T)
-        if isinstance(source, KdTree):  # the source by its own index: its kd order is taken as it is (no sort)
+        if isinstance(source, (KdTree, ProjectiveSearch)):  # the source by its own index: its kd order is taken as it is (no sort; a projective search is refused)
             check(load().sga_problem_create_from_index(self.ctx.h, target.h, source.h, _dp(t16), C.byref(self.h)))
         else:
             check(load().sga_problem_create(self.ctx.h, target.h, source.h, _dp(t16), C.byref(self.h)))

@@ -223,7 +223,7 @@ struct sga_cloud {
   sga::DevBuf<sga::Cov8> cov;
 };
 
-enum { SGA_INDEX_KDTREE = 0, SGA_INDEX_VOXELMAP = 1, SGA_INDEX_FLATMAP = 2 };
+enum { SGA_INDEX_KDTREE = 0, SGA_INDEX_VOXELMAP = 1, SGA_INDEX_FLATMAP = 2, SGA_INDEX_PROJECTIVE = 3 };
 constexpr int kFlatCap = 16;  // point slots per voxel of a flat map (max_num_points_in_cell <= 16)
 struct sga_index {
   int kind = SGA_INDEX_KDTREE;
@@ -279,6 +279,13 @@ struct sga_index {
   uint32_t flat_max = 10;                 // flat_container.hpp:20
   double flat_min_sq = 0.1 * 0.1;         // flat_container.hpp:19
   int search_offsets = 1;                 // 1, 7 or 27 (incremental_voxelmap.hpp:157-186)
+  // projective search (projective.hip; ann/projective_search.hpp): pts / nrm / cov hold the target in its ORIGINAL order (w = index bits),
+  // proj_img the equirectangular index image u-major (pixel u * proj_h + v: the 2 v + 1 rows of a window column are contiguous), each
+  // entry the index + 1 of the point that owns the pixel, 0 = none.  The window and the border modes are host-side, read at each dispatch
+  sga::DevBuf<uint32_t> proj_img;
+  int proj_w = 0, proj_h = 0;
+  int proj_win_h = 10, proj_win_v = 5;        // projective_search.hpp:49
+  int proj_repeat_h = 1, proj_repeat_v = 0;   // BorderRepeat horizontally, BorderClamp vertically (projective_search.hpp:42)
 };
 
 struct sga_problem {

@@ -1417,6 +1417,9 @@ int sga_index_clone(sga_context* ctx, const sga_index* src, sga_index** out) {
   idx->flat_max = src->flat_max;
   idx->flat_min_sq = src->flat_min_sq;
   idx->search_offsets = src->search_offsets;
+  idx->proj_w = src->proj_w, idx->proj_h = src->proj_h;
+  idx->proj_win_h = src->proj_win_h, idx->proj_win_v = src->proj_win_v;
+  idx->proj_repeat_h = src->proj_repeat_h, idx->proj_repeat_v = src->proj_repeat_v;
   const int sd = src->device;
   SGA_TRY(copy_buf(ctx, idx->kd_pts, src->kd_pts, sd));
   SGA_TRY(copy_buf(ctx, idx->nrm, src->nrm, sd));
@@ -1439,6 +1442,7 @@ int sga_index_clone(sga_context* ctx, const sga_index* src, sga_index** out) {
   SGA_TRY(copy_buf(ctx, idx->fpts64, src->fpts64, sd));
   SGA_TRY(copy_buf(ctx, idx->fnrm64, src->fnrm64, sd));
   SGA_TRY(copy_buf(ctx, idx->fcov64, src->fcov64, sd));
+  SGA_TRY(copy_buf(ctx, idx->proj_img, src->proj_img, sd));
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
   SGA_TRY(mark_ready(ctx, idx->ready));
   *out = idx.release();

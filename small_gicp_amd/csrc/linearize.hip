@@ -26,6 +26,7 @@
 #include "device_math.hpp"
 #include "cell_grid.hpp"
 #include "kd_search.hpp"
+#include "projective.hpp"
 #include "voxel_hash.hpp"
 
 void sga_profile_collect_pending(sga_context* ctx);
@@ -374,8 +375,9 @@ constexpr int kQueueCap = 128;        // entries; a tile is staged while at most
 constexpr int kPathRecords = 10;      // pair records fetched at once by kd_push_path: covers depth 20 (8 M points); deeper trees take a second batch
 
 template <typename Real, int FACTOR, int TARGET, int PTS, bool FRESH_NN = false, bool CERT = false, bool STAGED = false>
-__device__ __forceinline__ void linearize_group(const LinParams<Real>& p, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks = nullptr);
-template <typename Real, int FACTOR>
+__device__ __forceinline__ void linearize_group(const LinParams<Real>& p, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks = nullptr,
+                                                const ProjView* __restrict__ proj = nullptr);
+template <typename Real, int FACTOR, bool OWN_D2 = true>
 __device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
                                              const float4* nn_pre = nullptr);
 template <typename Real, int PTS>
@@ -665,13 +667,14 @@ __host__ __device__ inline bool is_derived_col(int c) { return c < 15 || (c >= 2
 
 // M' and g of one correspondence (weighted by the robust kernel), its error, and whether it is an inlier; caches the mahalanobis
 // matrix for the error pass.  (The direct form — the 28 values of pair_system — is pair_factor below; the per-point export uses it.)
-// nn_pre (PLANE_ICP): the target normal when the caller has fetched it already (linearize_group over a flat map), else it is read here
-template <typename Real, int FACTOR>
+// nn_pre (PLANE_ICP): the target normal when the caller has fetched it already (linearize_group over a flat map), else it is read here.
+// OWN_D2 = false: the caller's within_bound already is the rejector's verdict on the search's own distance (a projective target)
+template <typename Real, int FACTOR, bool OWN_D2>
 __device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
                                              const float4* nn_pre) {
   const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
   const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && !(d2 > p.max_sq);
+  const bool inlier = (j >= 0) && within_bound && (!OWN_D2 || !(d2 > p.max_sq));
   Mp = Sym3<Real>{};
   g[0] = g[1] = g[2] = Real(0);
   e = Real(0);
@@ -803,14 +806,15 @@ __device__ __forceinline__ const LinParams<Real>& kernarg_lin_params() {
   return *(const LinParams<Real>*)a;
 }
 
-// The factor stage as a kernel of its own.  TARGET: 0 kd-tree (the neighbours come from the search kernel), 1 Gaussian voxel map, 2 flat voxel map (the lookup of a
-// voxel target happens right here).  Streaming + two gathers; a lane handles PTS points (PTS x kTile consecutive points per
+// The factor stage as a kernel of its own.  TARGET: 0 kd-tree (the neighbours come from the search kernel), 1 Gaussian voxel map, 2 flat voxel map, 3 projective
+// search (`proj`: ann/projective_search.hpp; the lookup of these targets happens right here).  Streaming + two gathers; a lane handles PTS points (PTS x kTile consecutive points per
 // workgroup step), their products are added up in registers, reduced with DPP inside the wave, in fp64 across waves.
 // The factors of PTS points per lane — points first, first + stride, ... below `limit` — added to the wave's row.
 // FRESH_NN: hint[] was written earlier in this very kernel (by any lane of this wave): read it past the vector L1.
 // STAGED (the caller is a kernel whose first argument is `p0` itself): every stage reads the parameters it uses afresh (kernarg_lin_params).
 template <typename Real, int FACTOR, int TARGET, int PTS, bool FRESH_NN, bool CERT, bool STAGED>
-__device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks) {
+__device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks,
+                                                const ProjView* __restrict__ proj) {
 #define SGA_STAGE_PARAMS(name) const LinParams<Real>& name = STAGED ? kernarg_lin_params<Real>() : p0
   SGA_STAGE_PARAMS(p);
   Real P[PTS][3], G[PTS][3], E[PTS];
@@ -850,6 +854,16 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
         jn[u] = flat_nearest<Real>(p.flat, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2], m);
         Tg[u][0] = m.x, Tg[u][1] = m.y, Tg[u][2] = m.z;
       }
+    } else if constexpr (TARGET == 3) {
+      // the windowed scan of projective_search.hpp:107-140 (projective.hpp); the rejector (rejector.hpp:19-28) judges the scan's own
+      // distance, in Real, so pair_moments does not measure the pair again
+      if (act[u]) {
+        Real d2 = Real(0);
+        jn[u] = projective_nearest<Real>(*proj, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2], d2);
+        within[u] = jn[u] >= 0 && !(d2 > p.max_sq);
+        const float4 m = jn[u] >= 0 ? p.tgt_pts[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
+        Tg[u][0] = m.x, Tg[u][1] = m.y, Tg[u][2] = m.z;
+      }
     } else if constexpr (TARGET == 1) {
       if (act[u]) {
         if (p.vox.offsets == 1)  // (wave-uniform) the default: the query's own voxel, no distance to compare
@@ -860,7 +874,7 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
     }
   }
   }
-  if constexpr (TARGET != 2) {
+  if constexpr (TARGET != 2 && TARGET != 3) {
     float4 m4[PTS];
     if constexpr (CERT && TARGET == 0) {
       // The certificate check of the warm pass (search_lane / nn_search_queue_kernel: the same arithmetic, bit for bit) on the way through:
@@ -986,7 +1000,7 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
     Mp[u] = Sym3<Real>{};
     Mh[u] = Sym3<Real>{};
     G[u][0] = G[u][1] = G[u][2] = E[u] = Real(0);
-    if (act[u]) inl[u] = pair_moments<Real, FACTOR>(p, i, jn[u], within[u], Q[u][0], Q[u][1], Q[u][2], Tg[u][0], Tg[u][1], Tg[u][2], Mp[u], G[u], E[u], Mh[u], kFlatNormals ? &nn4[u] : nullptr);
+    if (act[u]) inl[u] = pair_moments<Real, FACTOR, TARGET != 3>(p, i, jn[u], within[u], Q[u][0], Q[u][1], Q[u][2], Tg[u][0], Tg[u][1], Tg[u][2], Mp[u], G[u], E[u], Mh[u], kFlatNormals ? &nn4[u] : nullptr);
     inliers += __popcll(__ballot(inl[u]));
   }
   }
@@ -1020,6 +1034,32 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(4))) void
   tile_schedule(p.num_tiles, tile, stride, tile_end);
   for (; tile < tile_end; tile += stride) {
     linearize_group<Real, FACTOR, TARGET, PTS>(p, tile * PTS * kTile + static_cast<int>(threadIdx.x), kTile, p.n, acc_row, lane);
+  }
+  __syncthreads();
+  if (threadIdx.x < kRow) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kTile / 64; w++) t += sh_acc[w][threadIdx.x];
+    if (p.tail.enabled)
+      __hip_atomic_store(&p.partials[static_cast<size_t>(blockIdx.x) * kRow + threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      p.partials[static_cast<size_t>(blockIdx.x) * kRow + threadIdx.x] = t;
+  }
+  if (p.tail.enabled) fused_tail(p.tail, p.partials, gridDim.x, kModelCols, kRow, true);
+}
+
+// linearize_kernel over a projective search target (TARGET 3): the index's view travels as an argument of its own, behind the LinParams.
+// One query per lane (PTS = 1): the lane scans its (2 h + 1) x (2 v + 1) window, column by column
+template <typename Real, int FACTOR, int PTS>
+__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(4))) void projective_linearize_kernel(const LinParams<Real> p, const ProjView pv) {
+  __shared__ double sh_acc[kTile / 64][kRow];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = lane; c < kRow; c += 64) sh_acc[wave][c] = 0.0;
+  double* acc_row = sh_acc[wave];
+  int tile, stride, tile_end;
+  tile_schedule(p.num_tiles, tile, stride, tile_end);
+  for (; tile < tile_end; tile += stride) {
+    linearize_group<Real, FACTOR, 3, PTS>(p, tile * PTS * kTile + static_cast<int>(threadIdx.x), kTile, p.n, acc_row, lane, nullptr, &pv);
   }
   __syncthreads();
   if (threadIdx.x < kRow) {
@@ -1622,6 +1662,7 @@ static double max_displacement(const double Ta[16], const double Tb[16], const f
 // target is not known (only ever before the first result of a problem has come back: the first pass is cold anyway).
 constexpr double kSpacingRef = SGA_SPACING_REF;
 double index_spacing(const sga_index* idx);  // index_build.hip
+ProjView make_proj_view(const sga_index* idx);  // projective.hip
 static double routing_unit(const sga_index* idx) {
   const double s = index_spacing(idx);
   return s > 0.0 ? s / kSpacingRef : 1.0;
@@ -1658,6 +1699,7 @@ static PassPlan plan_pass(const sga_context* ctx, const sga_problem* pb, const N
   PassPlan pl;
   pl.warm = displacement <= g_warm_delta * unit;
   pl.pts = linearize_pts(q.n, sizeof(Real) == 8);
+  if (idx->kind == SGA_INDEX_PROJECTIVE) pl.pts = 1;  // the window scan is the work: four points per lane would only spill
   if (q.n > 0 && idx->kind == SGA_INDEX_KDTREE) {
     const bool small_warm = pl.warm && displacement <= kQueueDelta * unit;
     const bool fuse = sizeof(Real) == 4 && !host_rejector;  // fp64 math: the fused kernels would spill (they exist for float only)
@@ -1732,11 +1774,16 @@ static LinParams<Real> factor_params(const sga_problem* pb, const sga_factor_par
 template <typename Real>
 static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double* d_out30, double* host, unsigned long long seq, bool with_model = false) {
   const sga_index* idx = pb->target;
-  const bool voxel = idx->kind != SGA_INDEX_KDTREE;  // Gaussian or flat voxel map: the lookup happens inside the factor kernel
+  // Gaussian, flat voxel map or projective search: the lookup happens inside the factor kernel, no certificates, no warm passes, no cell
+  // grid, no fp64 re-decision of a runner-up, routing unit 1
+  const bool voxel = idx->kind != SGA_INDEX_KDTREE;
   const bool flat = idx->kind == SGA_INDEX_FLATMAP;
+  const bool proj = idx->kind == SGA_INDEX_PROJECTIVE;
   if (fp->factor_kind == SGA_GICP && ((pb->n > 0 && !pb->has_covs) || (idx->n > 0 && !idx->has_covs))) return fail(SGA_ERR_INVALID, "GICP needs covariances on both source and target");
-  // PLANE_ICP: a kd-tree over a target with normals, or a flat map that keeps normals (per slot, under the slot numbering flat_nearest returns)
-  if (fp->factor_kind == SGA_PLANE_ICP && ((voxel && !flat) || ((flat || idx->n > 0) && !idx->has_normals)))
+  // PLANE_ICP: a kd-tree or a projective search over a target with normals, or a flat map that keeps normals (per slot, under the slot
+  // numbering flat_nearest returns)
+  if (fp->factor_kind == SGA_PLANE_ICP && proj && idx->n > 0 && !idx->has_normals) return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a projective search over a target with normals");
+  if (fp->factor_kind == SGA_PLANE_ICP && !proj && ((voxel && !flat) || ((flat || idx->n > 0) && !idx->has_normals)))
     return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals");
   if (fp->factor_kind < 0 || fp->factor_kind > 2) return fail(SGA_ERR_INVALID, "invalid factor_kind %d", fp->factor_kind);
 
@@ -1752,6 +1799,8 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
     p.flat.vnum = idx->vcounts.p;
     p.flat.offsets = idx->search_offsets;
     for (int k = 0; k < 3; k++) p.flat.org[k] = idx->origin[k];
+  } else if (proj) {
+    // (the view is an argument of projective_linearize_kernel of its own)
   } else if (voxel) {
     p.vox.hkeys = idx->hkeys.p;
     p.vox.hvals = idx->hvals.p;
@@ -1911,7 +1960,9 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
       constexpr int F = decltype(f)::value;
       if (flat)
         launch_linearize<Real, F, 2>(ctx->stream, p, blocks, plan.pts);
-      else if (voxel) {
+      else if (proj) {
+        hipLaunchKernelGGL((projective_linearize_kernel<Real, F, 1>), dim3(blocks), dim3(kTile), 0, ctx->stream, p, make_proj_view(idx));  // (plan.pts == 1)
+      } else if (voxel) {
         if constexpr (F != SGA_PLANE_ICP) launch_linearize<Real, F, 1>(ctx->stream, p, blocks, plan.pts);  // (a Gaussian map refuses PLANE_ICP above)
       } else
         launch_linearize<Real, F, 0>(ctx->stream, p, blocks, plan.pts);

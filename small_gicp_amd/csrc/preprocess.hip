@@ -595,6 +595,21 @@ int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf, s
 
 int sga_index_refresh_attributes(sga_context* ctx, sga_index* index, const sga_cloud* cloud) {
   if (!ctx || !index || !cloud) return fail(SGA_ERR_INVALID, "null argument");
+  if (index->kind == SGA_INDEX_PROJECTIVE) {  // original order: the cloud's attributes are the index's as they are
+    if (index->n != cloud->n) return fail(SGA_ERR_INVALID, "index was built over a cloud of %zu points, got %zu", index->n, cloud->n);
+    SGA_ENTER(ctx);
+    SGA_TRY(wait_ready(ctx, index->ready));
+    SGA_TRY(wait_ready(ctx, cloud->ready));
+    const size_t n = index->n;
+    if (cloud->has_normals && index->nrm.n < n) SGA_TRY(index->nrm.alloc(n));
+    if (cloud->has_covs && index->cov.n < n) SGA_TRY(index->cov.alloc(n));
+    if (n > 0 && cloud->has_normals) SGA_HIP(hipMemcpyAsync(index->nrm.p, cloud->nrm.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    if (n > 0 && cloud->has_covs) SGA_HIP(hipMemcpyAsync(index->cov.p, cloud->cov.p, n * sizeof(Cov8), hipMemcpyDeviceToDevice, ctx->stream));
+    SGA_HIP(hipStreamSynchronize(ctx->stream));
+    index->has_normals = cloud->has_normals;
+    index->has_covs = cloud->has_covs;
+    return SGA_OK;
+  }
   if (index->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_INVALID, "not a kd-tree index");
   if (index->n != cloud->n) return fail(SGA_ERR_INVALID, "index was built over a cloud of %zu points, got %zu", index->n, cloud->n);
   SGA_ENTER(ctx);
@@ -629,6 +644,7 @@ int sga_estimate_normals_covariances(sga_context* ctx, sga_cloud* cloud, const s
     SGA_TRY(sga_index_build_kdtree(ctx, cloud, &temp));
     index = temp;
   } else {
+    if (index->kind == SGA_INDEX_PROJECTIVE) return fail(SGA_ERR_UNSUPPORTED, "normal / covariance estimation needs a kd-tree index, not a projective search");
     if (index->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_INVALID, "a kd-tree index is required");
     if (index->n != n) return fail(SGA_ERR_INVALID, "index was built over a cloud of %zu points, got %zu", index->n, n);
     for (int a = 0; a < 3; a++)

@@ -18,6 +18,9 @@ int ensure_temp(sga_context* ctx, size_t bytes);
 size_t problem_partials_doubles(size_t n);
 int problem_ensure_maha(sga_context* ctx, sga_problem* pb);
 int cloud_bbox(sga_context* ctx, const float4* pts, size_t n, float lo[3], float hi[3]);
+// projective.hip
+int projective_source_keys(sga_context* ctx, const sga_index* idx, const float4* pts, size_t n, const double T_dev[16], unsigned long long* keys, uint32_t* vals);
+int projective_index_knn(sga_context* ctx, const sga_index* index, const float* queries, const double* queries64, size_t m, int k, double max_sq_dist, int64_t* idx, float* sq_dist, double* sq_dist64);
 
 __device__ __forceinline__ unsigned long long spread3(unsigned long long v) {
   v &= 0x1fffffull;
@@ -261,6 +264,7 @@ static int problem_alloc_state(sga_context* ctx, sga_problem* pb, size_t n, bool
 int sga_problem_create_from_index(sga_context* ctx, const sga_index* target, const sga_index* source, const double init_T[16], sga_problem** out) {
   if (!ctx || !target || !source || !out) return fail(SGA_ERR_INVALID, "null argument");
   if (target->device != ctx->device || source->device != ctx->device) return fail(SGA_ERR_INVALID, "target/source live on another device");
+  if (source->kind == SGA_INDEX_PROJECTIVE) return fail(SGA_ERR_UNSUPPORTED, "a projective search cannot serve as the source index: pass its cloud");
   if (source->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_INVALID, "the source index must be a kd-tree");
   (void)init_T;  // the kd order does not depend on the initial guess
   *out = nullptr;
@@ -321,10 +325,12 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
       oz = target->bbox_lo[2];
       const float ext = fmaxf(fmaxf(target->bbox_hi[0] - ox, target->bbox_hi[1] - oy), fmaxf(target->bbox_hi[2] - oz, 1e-6f));
       inv = 512.f / ext;  // 10-bit Morton cells over the target's extent refine the kd-leaf key
-    } else {
+    } else if (target->kind != SGA_INDEX_PROJECTIVE) {
       inv = static_cast<float>(4.0 / target->leaf);  // quarter-voxel cells: neighbouring lanes probe the same voxel
     }
-    if (target->kind == SGA_INDEX_KDTREE && target->n > 0) {
+    if (target->kind == SGA_INDEX_PROJECTIVE) {
+      SGA_TRY(projective_source_keys(ctx, target, source->pts.p, n, T, keys.p, vals.p));  // u-major pixel: neighbouring lanes scan overlapping windows
+    } else if (target->kind == SGA_INDEX_KDTREE && target->n > 0) {
       KdView kv = make_kd_view(target);
       hipLaunchKernelGGL(source_kd_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, source->pts.p, n, rigid_from_colmajor<float>(T), kv, ox, oy, oz, inv, keys.p, vals.p);
     } else {
@@ -406,6 +412,7 @@ static int index_knn_impl(sga_context* ctx, const sga_index* index, const float*
   if (m == 0) return SGA_OK;
   SGA_ENTER(ctx);
   SGA_TRY(wait_ready(ctx, index->ready));
+  if (index->kind == SGA_INDEX_PROJECTIVE) return projective_index_knn(ctx, index, queries, queries64, m, k, max_sq_dist, idx, sq_dist, sq_dist64);
   std::vector<float> qf;
   std::vector<double> qd;
   const bool framed = !origin_is_zero(index->origin);
