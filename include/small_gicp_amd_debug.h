@@ -35,7 +35,7 @@ int sga_problem_get_grid_stats(const sga_problem* pb, uint64_t out[6]);
 void sga_set_grid_mode(int mode, long long min_points);
 /* Normal / covariance estimation: clouds of at most max_points points search their neighbours with one wave per query (csrc/knn_wave.hpp:
  * the form for clouds that do not fill the chip), larger ones with one query per lane.  Both are exact; the tests compare them.
- * Default 32768 (environment: SGA_KNN_WAVE_MAX); 0 = never. */
+ * Default 81920 (environment: SGA_KNN_WAVE_MAX); 0 = never. */
 void sga_set_knn_wave_max(long long max_points);
 /* The length scale of a kd-tree index: the geometric mean of the diagonals of its leaf boxes (a leaf = a neighbourhood of <= 8 points),
  * computed by the build.  The pass routing of the linearization measures the source's motion in units of it (csrc/linearize.hip:

@@ -1766,6 +1766,22 @@ static LinParams<Real> factor_params(const sga_problem* pb, const sga_factor_par
   // that float(max_dist_sq) rounded down
   const float max_sq_f = rejects ? static_cast<float>(fp->max_dist_sq) : INFINITY;
   p.bound2 = max_sq_f < 3.0e38f ? max_sq_f * 1.0000002f : INFINITY;
+  if constexpr (sizeof(Real) == 8) {
+    // fp64 keeps a pair on its double distance from the double query q, but the walks and the `within` tests measure kd_dist2 from
+    // fl32(q): a target within r = sqrt(max_dist_sq) of q lies within r + |q - fl32(q)| of fl32(q), and kd_dist2 rounds that by less
+    // than 6 ulp (the factor 1 + 2^-20 covers it and the cast).  |q_a - fl32(q_a)| <= 2^-24 |q_a|, and every query T s of the source box
+    // has |q_a| <= |t_a| + sum_b |R_ab| max(|lo_b|, |hi_b|) (device frames, column-major T).
+    if (rejects && p.n > 0 && max_sq_f < 3.0e38f) {
+      double m2 = 0.0;
+      for (int a = 0; a < 3; a++) {
+        double ma = std::fabs(T[12 + a]);
+        for (int b = 0; b < 3; b++) ma += std::fabs(T[4 * b + a]) * std::max(std::fabs(static_cast<double>(pb->bbox_lo[b])), std::fabs(static_cast<double>(pb->bbox_hi[b])));
+        m2 += ma * ma;
+      }
+      const double r = std::sqrt(fp->max_dist_sq) + 0x1p-24 * (1.0 + 1e-6) * std::sqrt(m2);
+      p.bound2 = std::max(p.bound2, static_cast<float>(r * r * (1.0 + 0x1p-20)));
+    }
+  }
   p.robust_kind = fp->robust_kind;
   p.robust_c = static_cast<Real>(fp->robust_c);
   return p;

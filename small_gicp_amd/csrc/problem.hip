@@ -108,7 +108,10 @@ constexpr int kKnnMaxK = 116;  // (k * 8 + 96) * 64 bytes of LDS per workgroup m
 // queries64 / out_d2_64 (optional): the squared distances of the neighbours found are re-evaluated in double against the double
 // query — the coordinates stored on the device are fp32, the reference returns double distances (ann/kdtree.hpp:193-233).
 // F64 (queries64 / out_d2_64 given): the rejection compares that double distance with the double threshold max_sq64, as the reference
-// does (knn_result.hpp); the walk's fp32 bound is max_sq nudged up, which reaches past it.
+// does (knn_result.hpp).  The walk measures from the query's fp32 rounding q32, so its bound is widened by that rounding: a point within
+// r = sqrt(max_sq64) of the double query lies within r + |q64 - q32| of q32, and kd_dist2 rounds that by less than 6 ulp (the factor
+// 1 + 2^-20 covers it and the cast to float).  The kept entries are then ordered by (double distance, kd position) and packed to the
+// front of the row: the fp32 order of the walk is not the double order, and a rejected entry leaves no hole.
 template <bool F64>
 __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const KdView t, const float* __restrict__ queries, size_t m, int k, float max_sq, long long* __restrict__ out_idx, float* __restrict__ out_d2, const double* __restrict__ queries64, double* __restrict__ out_d2_64,
                                                         double max_sq64) {
@@ -125,21 +128,49 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const KdView t, const fl
   }
   if (qi >= m) return;
   const float qx = queries[3 * qi], qy = queries[3 * qi + 1], qz = queries[3 * qi + 2];
-  const float bound2 = max_sq < 3.0e38f ? max_sq * 1.0000002f : INFINITY;
+  float bound2 = max_sq < 3.0e38f ? max_sq * 1.0000002f : INFINITY;
+  if constexpr (F64) {
+    const double q0 = queries64[3 * qi], q1 = queries64[3 * qi + 1], q2 = queries64[3 * qi + 2];
+    const double ex = q0 - qx, ey = q1 - qy, ez = q2 - qz;
+    const double r = sqrt(max_sq64) + sqrt(ex * ex + ey * ey + ez * ez);
+    bound2 = max_sq64 < static_cast<double>(INFINITY) ? static_cast<float>(r * r * (1.0 + 0x1p-20)) : INFINITY;
+  }
   kd_knn<kKnnBlock>(t, qx, qy, qz, k, bound2, sd, si, stack, lane);
+  if constexpr (F64) {
+    // insertion into the output row by (d64, kd position), nearly linear: the walk's fp32 order is the double order but for near-ties
+    long long* __restrict__ oi = out_idx + qi * k;
+    double* __restrict__ od = out_d2_64 + qi * k;
+    const double q0 = queries64[3 * qi], q1 = queries64[3 * qi + 1], q2 = queries64[3 * qi + 2];
+    int kept = 0;
+    for (int j = 0; j < k; j++) {
+      const int id = si[j * kKnnBlock + lane];
+      if (id < 0) continue;
+      const float4 c = t.pts[id];
+      const double dx = static_cast<double>(c.x) - q0, dy = static_cast<double>(c.y) - q1, dz = static_cast<double>(c.z) - q2;
+      const double d64 = dx * dx + dy * dy + dz * dz;
+      if (d64 > max_sq64) continue;
+      int s = kept++;
+      for (; s > 0 && (od[s - 1] > d64 || (od[s - 1] == d64 && oi[s - 1] > id)); s--) {
+        od[s] = od[s - 1];
+        oi[s] = oi[s - 1];
+      }
+      od[s] = d64;
+      oi[s] = id;
+    }
+    for (int j = 0; j < kept; j++) {  // kd positions -> original indices
+      oi[j] = static_cast<long long>(__float_as_uint(t.pts[oi[j]].w));
+      out_d2[qi * k + j] = static_cast<float>(od[j]);
+    }
+    for (int j = kept; j < k; j++) {  // the rest of the row: none
+      oi[j] = -1ll;
+      od[j] = INFINITY;
+      out_d2[qi * k + j] = INFINITY;
+    }
+    return;
+  }
   for (int j = 0; j < k; j++) {
     const float d2 = sd[j * kKnnBlock + lane];
     const int id = si[j * kKnnBlock + lane];
-    if constexpr (F64) {
-      const float4 c = id >= 0 ? t.pts[id] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const double dx = static_cast<double>(c.x) - queries64[3 * qi], dy = static_cast<double>(c.y) - queries64[3 * qi + 1], dz = static_cast<double>(c.z) - queries64[3 * qi + 2];
-      const double d64 = dx * dx + dy * dy + dz * dz;
-      const bool ok = id >= 0 && !(d64 > max_sq64);
-      out_idx[qi * k + j] = ok ? static_cast<long long>(__float_as_uint(c.w)) : -1ll;
-      out_d2[qi * k + j] = ok ? d2 : INFINITY;
-      out_d2_64[qi * k + j] = ok ? d64 : INFINITY;
-      continue;
-    }
     const bool ok = id >= 0 && !(d2 > max_sq);
     const float4 c = ok ? t.pts[id] : make_float4(0.f, 0.f, 0.f, 0.f);
     out_idx[qi * k + j] = ok ? static_cast<long long>(__float_as_uint(c.w)) : -1ll;

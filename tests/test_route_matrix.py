@@ -473,3 +473,52 @@ def test_fp64_rejector_threshold_is_double():
     _, n32, ok32, _ = verdict(sga.Problem(tree, src), st32, "fp32")
     clear = np.abs(d2 - 0.01) > 1e-6 * 0.01
     assert (ok32[clear] == inl_ref[clear]).all() and n32 == ok32.sum()
+    # a posed case: T s is no longer exact in fp32, so the walks measure from a query up to 2^-24 |q| per axis away from the double one
+    # the factor kernel tests (40 m: ~1e-6 m, 5e-5 of d2 at d = 0.1 m — far beyond the fp32 nudge).  The routes re-decide the pair in
+    # double; the per-point export (sga_linearize_per_point, fp64) tests the search's own reach, widened by the query's rounding.
+    Tp, tp2, sp2, d2p = posed_edge_pairs()
+    inl_p = d2p <= 0.01
+    assert 0 < inl_p.sum() < len(d2p)
+    sga.set_grid_mode(4, 16)
+    tree_p = sga.KdTree(sga.PointCloud(tp2))
+    src_p = sga.PointCloud(sp2)
+    got = []
+    sga.set_grid_mode(1)
+    pb = sga.Problem(tree_p, src_p)
+    _, _, _, n = pb.linearize(st64.factor, Tp)
+    got.append(("posed lane", n, pb.factors()[0] >= 0, pb.last_plan()["route"], "lane"))
+    _, _, _, n = pb.linearize(st64.factor, Tp)
+    got.append(("posed queue warm", n, pb.factors()[0] >= 0, pb.last_plan()["route"], "queue"))
+    sga.set_grid_mode(4)
+    pb = sga.Problem(tree_p, src_p)
+    _, _, _, n = pb.linearize(st64.factor, Tp)
+    got.append(("posed grid", n, pb.factors()[0] >= 0, pb.last_plan()["route"], "grid"))
+    sga.set_grid_mode(1)
+    for label, n, ok, route, want in got:
+        assert route == want, (label, route)
+        assert n == inl_p.sum() and (ok == inl_p).all(), (label, n, inl_p.sum(), np.flatnonzero(ok != inl_p)[:8], (d2p[ok != inl_p] / 0.01 - 1)[:8])
+    okp = sga.Problem(tree_p, src_p).linearize_per_point(st64.factor, Tp)[0]
+    assert (okp == inl_p).all(), ("posed per-point export", okp.sum(), inl_p.sum(), np.flatnonzero(okp != inl_p)[:8], (d2p[okp != inl_p] / 0.01 - 1)[:8])
+
+
+def posed_edge_pairs(max_sq=0.01, seed=7):
+    """(T, target (m, 3) float32, source (m, 3) float32, d2 (m,)): source points whose transformed positions q = T s (in double, as fp64
+    passes form them) lie 20 - 45 m from the origin, each with one target point at d2 = (1 + delta) max_sq, |delta| <= 3e-5, from q; the
+    pairs sit on a 1 m lattice, so each q's nearest target is its own.  d2 is the float64 distance the reference's rejector compares."""
+    rng = np.random.default_rng(seed)
+    a = np.deg2rad(20.0)
+    k = np.array([0.3, -0.5, 0.8]) / np.linalg.norm([0.3, -0.5, 0.8])
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
+    T[:3, 3] = [0.3, -0.2, 0.5]
+    g = np.stack(np.meshgrid(np.arange(6), np.arange(8), np.arange(5), indexing="ij"), -1).reshape(-1, 3) + [20.0, -30.0, 5.0]
+    Ti = np.linalg.inv(T)
+    s = (g @ Ti[:3, :3].T + Ti[:3, 3]).astype(np.float32)
+    q = s.astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    u = rng.normal(size=q.shape)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    t = (q + u * np.sqrt(max_sq * (1 + rng.uniform(-3e-5, 3e-5, len(q))))[:, None]).astype(np.float32)
+    d2 = ((t.astype(np.float64) - q) ** 2).sum(1)
+    assert np.abs(d2 - max_sq).min() > 1e-12  # clear of the few-ulp differences of the device's double transform
+    return T, t, s, d2
