@@ -42,6 +42,10 @@ void sga_set_knn_wave_max(long long max_points);
  * routing_unit), so that the choice between the exact search kernels does not depend on the unit of length or the density of the cloud.
  * 0 while the build's kernels have not run yet (the value arrives as a late note, csrc/notes.hpp) or for other kinds of index. */
 int sga_index_spacing(const sga_index* index, double* spacing);
+/* A kd-tree index as built: depth = D (leaves of at most 8 points); nodes = 2^D x {threshold, axis as int bits} (entry 2^d + k is node k
+ * of depth d; entry 0 unused, never written); xyzw = the n points in kd order (device frame, w = original index as bits).  nodes / xyzw may be null
+ * (depth only).  Other kinds of index are refused. */
+int sga_debug_kd_tree(sga_context* ctx, const sga_index* index, int* depth, float* nodes, float* xyzw);
 /* GPU time (HIP events) between two points of the context's stream: start() records an event, stop() records another, waits for it and
  * returns the milliseconds in between — the kernel times of bench.py's per-stage roofline lines (voxel grid, index build, covariances). */
 int sga_debug_timer_start(sga_context* ctx);

@@ -23,7 +23,7 @@ sga.set_search_mode(0)
 pb = sga.Problem(tree, src)
 lib = _lib.load()
 lib.sga_debug_kd_trips.restype = C.c_int
-names = ["uniform level", "pair step", "group header", "leaf scan", "pop iteration", "outer iteration", "leaf scan of the first group (SGA_KD_STALE builds)"]
+names = ["uniform level", "pair step", "group header", "leaf scan", "pop iteration", "outer iteration"]
 k = [0]
 buf = (C.c_ulonglong * 16)()
 lib.sga_debug_kd_trips(buf)

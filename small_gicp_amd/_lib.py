@@ -150,6 +150,7 @@ SYMBOLS = [
     ("sga_host_free", C.c_int, [C.c_void_p]),
     ("sga_index_spacing", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("sga_set_knn_wave_max", None, [C.c_longlong]),
+    ("sga_debug_kd_tree", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     ("sga_debug_timer_start", C.c_int, [C.c_void_p]),
     ("sga_debug_timer_stop", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("sga_debug_shard_frame_pack", None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -321,6 +321,16 @@ class KdTree:
         check(load().sga_index_spacing(self.h, C.byref(v)))
         return v.value
 
+    def _tree(self):
+        """Diagnostics (sga_debug_kd_tree): (depth D, thresholds (2^D,) float32, axes (2^D,) int32 — entry 2^d + k is node k of depth d,
+        entry 0 unused, never written —, points (n, 3) float32 in kd order and in the cloud's device frame, order (n,) int64: their original indices)."""
+        lib, depth = load(), C.c_int()
+        check(lib.sga_debug_kd_tree(self.ctx.h, self.h, C.byref(depth), None, None))
+        nodes = np.zeros((1 << depth.value, 2), np.float32)
+        xyzw = np.zeros((self.size(), 4), np.float32)
+        check(lib.sga_debug_kd_tree(self.ctx.h, self.h, C.byref(depth), nodes.ctypes.data_as(C.c_void_p), xyzw.ctypes.data_as(C.c_void_p)))
+        return depth.value, nodes[:, 0].copy(), nodes[:, 1].view(np.int32).copy(), xyzw[:, :3].copy(), xyzw[:, 3].view(np.uint32).astype(np.int64)
+
     def refresh_attributes(self):
         """Pull the cloud's current normals / covariances into the index (needed when they were set after the index was built)."""
         check(load().sga_index_refresh_attributes(self.ctx.h, self.h, self.cloud.h))

@@ -67,9 +67,12 @@ int cloud_bbox(sga_context* ctx, const float4* pts, size_t n, float lo[3], float
 }
 
 // ---- implicit balanced kd-tree (see kd_search.hpp for the layout) ----------------------------------------------------------------
-// Built top-down, one level per pass: per-segment bounding box -> split axis = longest extent -> sort by (segment, coordinate)
-// -> threshold = coordinate of the first point of the right half.  (The reference picks the axis of largest sampled
-// variance, projection.hpp:31-50; any axis gives an exact search.)
+// Built top-down, one level at a time.  Every node of depth d owns the segment [B(d, k), B(d, k + 1)) of positions (kd_bound); its
+// split axis is the longest extent of the segment's own points, and its points are PARTITIONED so that the left child's segment
+// [B(d, k), m), m = B(d + 1, 2k + 1), holds the m - B(d, k) smallest coordinates along that axis.  The threshold is the coordinate of
+// the first point of the right half (the median); left coordinates are <= it, right ones >= it.  The order inside a half need not
+// be sorted (a kd-tree needs the halves only); it is fixed by the level's kernel, so the build is deterministic.  (The reference
+// picks the axis of largest sampled variance, projection.hpp:31-50; any axis gives an exact search.)
 __device__ __forceinline__ uint32_t kd_bound_d(uint32_t n, int d, uint32_t k) { return kd_bound(n, d, k); }
 
 __device__ __forceinline__ uint32_t kd_segment_of(uint32_t i, uint32_t n, int d) {
@@ -84,70 +87,7 @@ __device__ __forceinline__ int ordered_from_float(float f) {
   return i >= 0 ? i : i ^ 0x7fffffff;
 }
 
-// seg_box: 6 ints per segment (min xyz, max xyz) in the order-preserving int encoding.  Only the top levels of the build come here
-// (segments of more than kFinishCap points), so a workgroup of 1024 consecutive points nearly always lies inside one segment: it
-// reduces in registers + LDS and issues six atomics; mixed workgroups fall back to per-wave / per-lane atomics.
-__global__ __launch_bounds__(1024) void kd_segment_box_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm, uint32_t n, int d, int* __restrict__ seg_box) {
-  __shared__ float sh_lo[16][3], sh_hi[16][3];
-  __shared__ uint32_t sh_seg[16];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const bool valid = i < n;
-  const uint32_t seg = kd_segment_of(valid ? i : n - 1, n, d);  // tail lanes join the last segment with neutral values
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  if (valid) {
-    const float4 p = pts[perm[i]];
-    lo[0] = hi[0] = p.x;
-    lo[1] = hi[1] = p.y;
-    lo[2] = hi[2] = p.z;
-  }
-  const uint32_t seg0 = __shfl(seg, 0);
-  const bool wave_uniform = __all(seg == seg0);
-  if (wave_uniform) {
-    for (int k = 0; k < 3; k++)
-      for (int off = 32; off > 0; off >>= 1) {
-        lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-        hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-      }
-  }
-  if (lane == 0) {
-    sh_seg[wave] = wave_uniform ? seg0 : 0xffffffffu;
-    for (int k = 0; k < 3; k++) {
-      sh_lo[wave][k] = lo[k];
-      sh_hi[wave][k] = hi[k];
-    }
-  }
-  __syncthreads();
-  bool block_uniform = true;
-  for (int w = 0; w < nwaves; w++) block_uniform = block_uniform && sh_seg[w] == sh_seg[0] && sh_seg[0] != 0xffffffffu;
-  if (block_uniform) {
-    if (threadIdx.x < 3) {
-      const int k = threadIdx.x;
-      float l = INFINITY, h = -INFINITY;
-      for (int w = 0; w < nwaves; w++) {
-        l = fminf(l, sh_lo[w][k]);
-        h = fmaxf(h, sh_hi[w][k]);
-      }
-      if (l <= h) {
-        atomicMin(&seg_box[6 * sh_seg[0] + k], ordered_from_float(l));
-        atomicMax(&seg_box[6 * sh_seg[0] + 3 + k], ordered_from_float(h));
-      }
-    }
-  } else if (wave_uniform) {
-    if (lane == 0 && lo[0] <= hi[0]) {
-      for (int k = 0; k < 3; k++) {
-        atomicMin(&seg_box[6 * seg0 + k], ordered_from_float(lo[k]));
-        atomicMax(&seg_box[6 * seg0 + 3 + k], ordered_from_float(hi[k]));
-      }
-    }
-  } else if (valid) {
-    for (int k = 0; k < 3; k++) {
-      atomicMin(&seg_box[6 * seg + k], ordered_from_float(lo[k]));
-      atomicMax(&seg_box[6 * seg + 3 + k], ordered_from_float(hi[k]));
-    }
-  }
-}
-
+// seg_box: 6 ints per segment (min xyz, max xyz) in the order-preserving int encoding, reset to the empty box
 __global__ void kd_init_box_kernel(int* __restrict__ seg_box, uint32_t nseg) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nseg) return;
@@ -159,62 +99,25 @@ __global__ void kd_init_box_kernel(int* __restrict__ seg_box, uint32_t nseg) {
 
 __device__ __forceinline__ float float_from_ordered(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
-// keys for the sort of one level: (segment, coordinate along the segment's split axis)
+// split axis of a segment: the longest extent of its box (ties: the lower axis)
 __device__ __forceinline__ int kd_longest_axis(const int* __restrict__ box6) {
   float v[3];
   for (int a = 0; a < 3; a++) v[a] = float_from_ordered(box6[3 + a]) - float_from_ordered(box6[a]);
   return v[0] >= v[1] ? (v[0] >= v[2] ? 0 : 2) : (v[1] >= v[2] ? 1 : 2);
 }
 
-// split axis of every segment = longest extent of its box (each lane derives it from the six box words; the first lane of a
-// segment records it for kd_nodes_kernel) + the sort key of every point
-__global__ void kd_keys_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm, uint32_t n, int d, const int* __restrict__ seg_box, int* __restrict__ axis_of_seg, unsigned long long* __restrict__ keys) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t seg = kd_segment_of(i, n, d);
-  const int axis = kd_longest_axis(seg_box + 6 * seg);
-  if (i == kd_bound_d(n, d, seg)) axis_of_seg[seg] = axis;
-  const float4 p = pts[perm[i]];
-  const float c = axis == 0 ? p.x : (axis == 1 ? p.y : p.z);
-  const uint32_t oc = static_cast<uint32_t>(ordered_from_float(c)) ^ 0x80000000u;  // unsigned order
-  keys[i] = (static_cast<unsigned long long>(seg) << 32) | oc;
-}
-
-// thresholds of level d; also resets the boxes of the 2^(d+1) segments of the next level (nobody reads this level's boxes any more)
-__global__ void kd_nodes_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm, uint32_t n, int d, const int* __restrict__ axis_of_seg, float2* __restrict__ nodes, int* __restrict__ next_box) {
-  const uint32_t seg = blockIdx.x * blockDim.x + threadIdx.x;
-  if (seg >= (1u << d)) return;
-  const int axis = axis_of_seg[seg];
-  const uint32_t first = kd_bound_d(n, d, seg), end = kd_bound_d(n, d, seg + 1);
-  const uint32_t m = kd_bound_d(n, d + 1, 2 * seg + 1);  // first point of the right child
-  float thr = 0.f;
-  if (first < end) {
-    const float4 p = pts[perm[min(m, end - 1)]];
-    thr = axis == 0 ? p.x : (axis == 1 ? p.y : p.z);
-  }
-  nodes[(1u << d) + seg] = make_float2(thr, __int_as_float(axis));
-  if (next_box != nullptr)
-    for (uint32_t c = 2 * seg; c < 2 * seg + 2; c++)
-      for (int k = 0; k < 3; k++) {
-        next_box[6 * c + k] = 0x7f800000;                                       // +inf
-        next_box[6 * c + 3 + k] = static_cast<int>(0xff800000u) ^ 0x7fffffff;  // -inf
-      }
-}
-
 // ---- bottom levels of the build inside LDS ----------------------------------------------------------------------------------------
-// Once a segment holds at most kFinishCap points, ONE workgroup finishes its whole sub-tree: the points' coordinates are loaded
-// into LDS once, and every remaining level is (per sub-segment box -> longest extent -> sort by (sub-segment, coordinate) ->
+// Once a segment holds at most CAP (= kSplitFinish) points, ONE workgroup finishes its whole sub-tree: the points' coordinates are
+// loaded into LDS once, and every remaining level is (per sub-segment box -> longest extent -> sort by (sub-segment, coordinate) ->
 // threshold) without touching global memory or launching anything.  The sort is a rank sort over 64-bit keys
-// (sub-segment | ordered coordinate | current position); the position field makes it reproduce the STABLE order of the
-// radix sorts of the top levels, so the tree is the same whichever path builds a level.
-constexpr int kFinishCap = 2048;      // points per workgroup, large clouds (small ones: 1024, to spread over more CUs)
-constexpr int kFinishThreads = 512;
-constexpr int kFinishMaxSub = 256;    // sub-segments at the last level: kFinishCap / 8
+// (sub-segment | ordered coordinate | current position); the position field makes the keys distinct, so every element gets a rank
+// of its own, and breaks ties between equal coordinates by the current position: a stable, deterministic order.
+constexpr int kFinishMaxSub = 256;  // sub-segments at the last level; 32 would do at CAP = 256, but this sizes the LDS arrays (and so the occupancy) as measured
 
 __device__ __forceinline__ uint32_t ordered_u32(float c) { return static_cast<uint32_t>(ordered_from_float(c)) ^ 0x80000000u; }
 
-// THREADS: workgroup size (a sub-tree of <= 256 points keeps 256 threads busy, not 512: twice the workgroups per CU)
-template <int CAP, int THREADS = kFinishThreads>
+// CAP: points per workgroup; THREADS: workgroup size (built as <kSplitFinish, kSplitFinish>: one thread per point)
+template <int CAP, int THREADS>
 __global__ __launch_bounds__(THREADS) void kd_finish_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in, uint32_t* __restrict__ perm_out, uint32_t n, int dA, int D, float2* __restrict__ nodes) {
   __shared__ float cx[CAP], cy[CAP], cz[CAP];
   __shared__ uint32_t gidx[CAP];
@@ -317,8 +220,8 @@ __global__ __launch_bounds__(THREADS) void kd_finish_kernel(const float4* __rest
 }
 
 // ---- top levels of SMALL clouds: one launch per level, one workgroup per segment --------------------------------------------------
-// A 15k-point scan (the odometry workload) is launch-bound: a level of the sort-based build above is a box kernel, a key kernel, a
-// rocPRIM sort (3 - 6 launches at this size) and a node kernel, ~45 us for 15k points that a single workgroup can hold in registers.
+// A 15k-point scan (the odometry workload) is launch-bound: a sort-based level (a box kernel, a key kernel, a rocPRIM sort of 3 - 6
+// launches and a node kernel; rounds 1 - 5) took ~45 us for 15k points that a single workgroup can hold in registers.
 // Here one workgroup (1024 threads, or 256 for segments of at most 8192 points: cheaper barriers) owns one segment (<= kSplitKeys
 // points per thread) and does the whole level:
 // bounding box -> longest axis -> the median by a three-round radix SELECT over the order-preserving keys (LDS histograms of 11 / 11
@@ -484,10 +387,12 @@ __global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* _
 }
 
 // ---- top levels of LARGE clouds: the same select + partition, a segment spread over many workgroups (round 6) -------------------------
-// A segment of more than kSplitMaxPoints points does not fit one workgroup's registers.  The sort-based level above orders ALL n (segment,
-// coordinate) keys to learn one median per segment: ~260 us per level at 1M points, 47 rocPRIM launches — most of a 1M-point build.  Here the
-// level is what kd_split_level_kernel does, with the segment cut into chunks of kTopChunk (4096) points (grid = chunks x segments) and the
-// histograms of the three select rounds accumulated in global memory (LDS first, the non-empty bins flushed with atomics):
+// A segment of more than kTopSegMin points is left to many workgroups: the split kernel's 32-key form runs 136 us for 32 segments of
+// 31k points (32 workgroups on 256 CUs), its 16-key form 53 us, while these levels take ~55 us at 1M whatever the number of segments.
+// (A sort-based level, rounds 1 - 5, ordered ALL n (segment, coordinate) keys to learn one median per segment: ~260 us per level at 1M
+// points, 47 rocPRIM launches.)  Here the level is what kd_split_level_kernel does, with the segment cut into chunks of kTopChunk
+// (4096) points (grid = chunks x segments) and the histograms of the three select rounds accumulated in global memory (LDS first, the
+// non-empty bins flushed with atomics):
 //   box   -> the segment's box (6 atomics per workgroup)                                           kd_top_box_kernel
 //   hist0 -> axis = longest extent; the keys (order-preserving coordinate) are stored once; top 11 bits   kd_top_hist_kernel<0>
 //   hist1, hist2 -> every workgroup re-derives the buckets chosen so far from the finished histograms (2048 bins: one scan), then counts
@@ -496,13 +401,10 @@ __global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* _
 //   scatter -> [keys < median][`rank` of the equal ones] | [the other equal ones][keys > median], chunks in order, inside a chunk
 //            thread-major: a fixed order.  The POINTS move with the permutation (ping-pong copies), so that every pass of the next
 //            level streams instead of gathering through the permutation                               kd_top_scatter_kernel
-// Six passes over 4 - 20 bytes per point instead of a 64-bit key-value sort of the whole cloud.  The tree is another valid one over the
-// same points (like the split path's): the halves are the same SETS as the sort's whenever the median key is unique, the order inside
-// them is not the sorted one.
-#ifndef SGA_TOP_ITEMS
-#define SGA_TOP_ITEMS 4  // items per thread: chunks of 4096 points (measured: 2 / 4 / 8 / 16 items -> 1M-point build 1.29 / 1.23 / 1.26 / 1.42 ms, 400k 0.80 / 0.80 / 0.85 / 0.98)
-#endif
-constexpr uint32_t kTopItems = SGA_TOP_ITEMS, kTopThreads = 1024, kTopChunk = kTopItems * kTopThreads;
+// Six passes over 4 - 20 bytes per point instead of a 64-bit key-value sort of the whole cloud.
+constexpr uint32_t kTopSegMin = 16384;  // segments of more than this many points (clouds of more than kSplitMaxPoints) take these levels
+constexpr uint32_t kTopItems = 4;  // items per thread: chunks of 4096 points (measured: 2 / 4 / 8 / 16 items -> 1M-point build 1.29 / 1.23 / 1.26 / 1.42 ms, 400k 0.80 / 0.80 / 0.85 / 0.98)
+constexpr uint32_t kTopThreads = 1024, kTopChunk = kTopItems * kTopThreads;
 struct TopSel {
   uint32_t median, below, rank, eq_total;  // the median key; keys below it; how many of the equal keys complete the left half; equal keys
 };
@@ -983,12 +885,9 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
   if (D > 24) return fail(SGA_ERR_INVALID, "target too large for the kd-tree (%zu points)", n);
   idx->kd_depth = D;
   DevBuf<uint32_t> perm, perm2;
-  DevBuf<unsigned long long> keys, keys2;
   DevBuf<int> seg_box;
   SGA_TRY(perm.alloc(n));
   SGA_TRY(perm2.alloc(n));
-  SGA_TRY(keys.alloc(n));
-  SGA_TRY(keys2.alloc(n));
   SGA_TRY(seg_box.alloc(6ull << (D > 0 ? D - 1 : 0)));
   SGA_TRY(idx->kd_nodes.alloc(1ull << D));
   SGA_TRY(idx->kd_nodes4.alloc(kd_pair_count(D)));
@@ -998,34 +897,17 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
   DevBuf<int> axis_of_seg;
   SGA_TRY(axis_of_seg.alloc(1ull << (D > 0 ? D - 1 : 0)));
   // Three regimes, top down — every level a median select + partition, nothing is sorted (round 6):
-  //   [0, dS)   segments of more than 16 384 points (clouds of more than kSplitMaxPoints): the segment spread over many workgroups, six
-  //             launches per level, the points moving with the permutation (kd_top_*_kernel);
+  //   [0, dS)   segments of more than kTopSegMin points (clouds of more than kSplitMaxPoints): the segment spread over many workgroups,
+  //             six launches per level, the points moving with the permutation (kd_top_*_kernel);
   //   [dS, dA)  one launch per level, one workgroup per segment (kd_split_level_kernel), gathering from the copy the levels above left;
-  //   [dA, D)   the rest of every sub-tree in LDS (kd_finish_kernel<kSplitFinish>).
-  // The older paths stay for the tests that compare them: SGA_KD_TOP=0: [0, dS) (then: segments of more than kSplitMaxPoints points) by a
-  // box pass, a key pass, a key-value sort of the whole cloud and a node pass per level; SGA_KD_SPLIT=0: no split levels (sort-based down to
-  // kFinishCap, then the large LDS finish); SGA_KD_FINISH=0: sort-based throughout.
-  const bool lds_finish = !(getenv("SGA_KD_FINISH") && atoi(getenv("SGA_KD_FINISH")) == 0);  // read per build: the tests compare the paths
-  const bool split_levels = lds_finish && !(getenv("SGA_KD_SPLIT") && atoi(getenv("SGA_KD_SPLIT")) == 0);
+  //   [dA, D)   the rest of every sub-tree in LDS (kd_finish_kernel<kSplitFinish, kSplitFinish>).
   auto seg_max_at = [&](int d) { return (n + (1ull << d) - 1) >> d; };
-  const int cap = n >= 400000 ? kFinishCap : kFinishCap / 2;
-  int dS = 0, dA = 0;
-  if (split_levels) {
-    // the many-workgroup levels (kd_top_*_kernel, ~55 us per level at 1M whatever the number of segments) also take the first levels the split
-    // kernel could hold: its 32-key form runs 136 us for 32 segments of 31k points (32 workgroups on 256 CUs), its 16-key form 53 us
-    static const size_t top_min = getenv("SGA_KD_TOP_MIN") ? static_cast<size_t>(atoll(getenv("SGA_KD_TOP_MIN"))) : 16384;
-    const bool top_on = !(getenv("SGA_KD_TOP") && atoi(getenv("SGA_KD_TOP")) == 0);
-    const size_t reach = (top_on && n > kSplitMaxPoints) ? std::min<size_t>(top_min, kSplitMaxPoints) : kSplitMaxPoints;  // (clouds the split kernel holds whole stay with it)
-    while (dS < D && seg_max_at(dS) > reach) dS++;
-    dA = dS;
-    while (dA < D && seg_max_at(dA) > static_cast<size_t>(kSplitFinish)) dA++;
-  } else {
-    while (dS < D && seg_max_at(dS) > static_cast<size_t>(cap)) dS++;
-    if (!lds_finish || D - dS > 8) dS = D;
-    dA = dS;
-  }
-  // SGA_KD_TOP=0: the levels above the split kernel's reach through the key-value sort (rounds 1 - 5); default: select + partition over many workgroups
-  const bool top_levels = split_levels && dS > 0 && !(getenv("SGA_KD_TOP") && atoi(getenv("SGA_KD_TOP")) == 0);
+  const size_t reach = n > kSplitMaxPoints ? kTopSegMin : kSplitMaxPoints;  // (clouds the split kernel holds whole stay with it)
+  int dS = 0;
+  while (dS < D && seg_max_at(dS) > reach) dS++;
+  int dA = dS;
+  while (dA < D && seg_max_at(dA) > static_cast<size_t>(kSplitFinish)) dA++;
+  const bool top_levels = dS > 0;
   if (dS > 0 || dA == 0) {  // (otherwise the root split level below hands over the box and reads the identity permutation)
     SGA_TRY(cloud_bbox_enqueue(ctx, cloud->pts.p, n, box_seq));
     if (!top_levels) hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, perm.p, n);
@@ -1076,22 +958,6 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
     // 64-byte sector of a 16 MB array per point).  Their result — positions in the moved copy — is composed with top_perm at the end.
     base_pts = pin;
   }
-  for (int d = 0; d < dS && !top_levels; d++) {
-    const uint32_t nseg = 1u << d;
-    const dim3 sgrid((nseg + 255) / 256);
-    const unsigned end_bit = 32 + (d > 0 ? d : 1);
-    if (d == 0) hipLaunchKernelGGL(kd_init_box_kernel, sgrid, block, 0, ctx->stream, seg_box.p, nseg);  // later levels: reset by kd_nodes_kernel
-    {
-      // six atomics per workgroup on a handful of addresses: large workgroups for large clouds (fewer atomics), small ones for
-      // small clouds (a 15k-point scan in 1024-thread workgroups would occupy 15 CUs)
-      const unsigned bs = n > 200000 ? 1024u : 256u;
-      hipLaunchKernelGGL(kd_segment_box_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, ctx->stream, cloud->pts.p, cur, static_cast<uint32_t>(n), d, seg_box.p);
-    }
-    hipLaunchKernelGGL(kd_keys_kernel, grid, block, 0, ctx->stream, cloud->pts.p, cur, static_cast<uint32_t>(n), d, seg_box.p, axis_of_seg.p, keys.p);
-    SGA_TRY(sort_pairs(ctx, keys.p, keys2.p, cur, nxt, n, 0, end_bit));
-    std::swap(cur, nxt);
-    hipLaunchKernelGGL(kd_nodes_kernel, sgrid, block, 0, ctx->stream, cloud->pts.p, cur, static_cast<uint32_t>(n), d, axis_of_seg.p, idx->kd_nodes.p, d + 1 < dS ? seg_box.p : static_cast<int*>(nullptr));
-  }
   for (int d = dS; d < dA; d++) {
     const size_t seg_max = seg_max_at(d);
     unsigned long long* note_slot = nullptr;
@@ -1111,14 +977,8 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
     std::swap(cur, nxt);
   }
   if (top_levels && dA == dS) hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, cur, n);  // (no split level ran: the finish reads the identity)
-  if (dA < D && split_levels) {
+  if (dA < D) {
     hipLaunchKernelGGL((kd_finish_kernel<kSplitFinish, kSplitFinish>), dim3(1u << dA), dim3(kSplitFinish), 0, ctx->stream, base_pts, cur, nxt, static_cast<uint32_t>(n), dA, D, idx->kd_nodes.p);
-    std::swap(cur, nxt);
-  } else if (dA < D) {
-    if (cap == kFinishCap)
-      hipLaunchKernelGGL(kd_finish_kernel<kFinishCap>, dim3(1u << dA), dim3(kFinishThreads), 0, ctx->stream, cloud->pts.p, cur, nxt, static_cast<uint32_t>(n), dA, D, idx->kd_nodes.p);
-    else
-      hipLaunchKernelGGL(kd_finish_kernel<kFinishCap / 2>, dim3(1u << dA), dim3(kFinishThreads), 0, ctx->stream, cloud->pts.p, cur, nxt, static_cast<uint32_t>(n), dA, D, idx->kd_nodes.p);
     std::swap(cur, nxt);
   }
   if (top_levels) {  // positions in the moved copy -> indices of the cloud
@@ -1460,6 +1320,20 @@ int sga_index_destroy(sga_index* index) {
 int sga_index_size(const sga_index* index, size_t* n) {
   if (!index || !n) return fail(SGA_ERR_INVALID, "null argument");
   *n = index->n;
+  return SGA_OK;
+}
+
+// diagnostics: the kd-tree as built (the split nodes and the points in kd order), for the tests that check it against its definition
+int sga_debug_kd_tree(sga_context* ctx, const sga_index* index, int* depth, float* nodes, float* xyzw) {
+  if (!ctx || !index || !depth) return fail(SGA_ERR_INVALID, "null argument");
+  if (index->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_INVALID, "not a kd-tree");
+  *depth = index->kd_depth;
+  if (index->n == 0 || (!nodes && !xyzw)) return SGA_OK;
+  SGA_ENTER(ctx);
+  SGA_TRY(wait_ready(ctx, index->ready));
+  if (nodes) SGA_HIP(hipMemcpyAsync(nodes, index->kd_nodes.p, (sizeof(float2) << index->kd_depth), hipMemcpyDeviceToHost, ctx->stream));
+  if (xyzw) SGA_HIP(hipMemcpyAsync(xyzw, index->kd_pts.p, index->n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  SGA_HIP(hipStreamSynchronize(ctx->stream));
   return SGA_OK;
 }
 

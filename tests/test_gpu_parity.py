@@ -15,6 +15,7 @@ import pytest
 
 import small_gicp_amd as sga
 from conftest import ROOT, pose_error
+from kd_ref import check_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -396,7 +397,7 @@ def c3():
     sga.estimate_covariances(tgt, None, 20)
     sga.estimate_covariances(src, None, 20)
     tree = sga.KdTree(tgt)
-    return dict(tgt=tgt, src=src, tree=tree, T_gt=T_gt, source=source, src_cov=src.covs()[:, :3, :3].astype(np.float32))
+    return dict(tgt=tgt, src=src, tree=tree, T_gt=T_gt, target=target, source=source, src_cov=src.covs()[:, :3, :3].astype(np.float32))
 
 
 def test_c3_properties(c3):
@@ -882,46 +883,60 @@ def test_c4_vgicp_1m_properties(c3):
 
 
 # ---- the search structure itself ------------------------------------------------------------------------------------------------
-def test_kd_build_paths_give_the_same_tree(monkeypatch):
-    """Bottom levels finished in LDS (kd_finish_kernel) vs every level through the global radix-sort path: identical trees, hence
-    bit-identical linearizations and identical kNN answers (index_build.hip).  Small clouds are built by a third path — one launch per
-    level, radix select + partition (kd_split_level_kernel): another valid tree over the same points (the order inside a half is not
-    the sorted one), so the same neighbour DISTANCES, inliers and sums to rounding."""
+def _checked_tree(pts, cloud=None):
+    """A kd-tree over pts ((n, 3) float32) and its download (KdTree._tree), checked node by node against the tree's definition
+    (tests/kd_ref.py: check_tree); its points must be exactly the cloud's stored fp32 records (fl32(p - origin)) in kd order."""
+    assert pts.dtype == np.float32
+    cloud = sga.PointCloud(pts) if cloud is None else cloud
+    tree = sga.KdTree(cloud)
+    t = tree._tree()
+    depth, thr, axis, pk, order = t
+    check_tree(pk, order, depth, thr, axis, len(pts))
+    o = cloud.origin()
+    stored = (pts.astype(np.float64) - o).astype(np.float32) if o.any() else pts
+    assert np.array_equal(pk.view(np.uint32), stored[order].view(np.uint32))
+    return tree, t
+
+
+def _same_tree(a, b):
+    """Two downloads byte for byte: depth, thresholds and axes of nodes 1 .. 2^D - 1 (entry 0 is never written), points, order."""
+    return a[0] == b[0] and all(x[1:].tobytes() == y[1:].tobytes() for x, y in zip(a[1:3], b[1:3])) and all(x.tobytes() == y.tobytes() for x, y in zip(a[3:], b[3:]))
+
+
+def test_kd_build_is_valid_and_repeatable(c3):
+    """Every tree meets its definition (kd_ref.check_tree) and a second build of the same cloud is the same tree, byte for byte — hence
+    bit-identical linearizations and identical kNN rows.  The sizes cover every regime of the build (index_build.hip: build_kdtree): one
+    workgroup (1500), the split levels (20k), the many-workgroup top levels (40k, 600k) and the benchmark's 1M-point target (C3).  A
+    fiftieth of every target is duplicated: equal keys at every level."""
     rng = np.random.default_rng(11)
-    for n in (1500, 20_000, 40_000, 600_000):  # one workgroup / the split path's range / small-cloud capacity / large-cloud capacity
+    for n in (1500, 20_000, 40_000, 600_000):
         target, source, _ = sga.synthetic.registration_pair(n)
         target = target.copy()
-        target[: n // 50] = target[n // 50 : 2 * (n // 50)]  # duplicates: the stable tie order must be reproduced too
+        target[: n // 50] = target[n // 50 : 2 * (n // 50)]
         st = sga.make_setting("ICP")
         T = se3([0.2, 0.3, 0.93], np.deg2rad(1.0), [0.1, -0.1, 0.0])
         q = np.concatenate([source[rng.choice(n, 300, replace=False)], rng.uniform(-60, 60, (100, 3)).astype(np.float32)])
+        src = sga.PointCloud(source)
 
         def run():
-            tree = sga.KdTree(sga.PointCloud(target))
-            H, b, e, inl = sga.Problem(tree, sga.PointCloud(source)).linearize(st.factor, T)
+            tree, t = _checked_tree(target)
+            H, b, e, inl = sga.Problem(tree, src).linearize(st.factor, T)
             idx, d2 = tree.batch_knn_search(q, 10)
-            return H, b, e, inl, idx, d2
+            return t, H, b, e, inl, idx, d2
 
-        out = []
-        monkeypatch.setenv("SGA_KD_SPLIT", "0")
-        for finish in ("1", "0"):
-            monkeypatch.setenv("SGA_KD_FINISH", finish)
-            out.append(run())
-        a, c = out
-        assert (a[0] == c[0]).all() and (a[1] == c[1]).all() and a[2] == c[2] and a[3] == c[3], n
-        assert (a[4] == c[4]).all() and (a[5] == c[5]).all(), n
-        monkeypatch.delenv("SGA_KD_SPLIT")
-        monkeypatch.setenv("SGA_KD_FINISH", "1")
-        s = run()  # n <= 32768: the split path
-        assert s[3] == a[3] and (s[5] == a[5]).all(), n
-        assert np.abs(s[0] - a[0]).max() <= 1e-5 * np.abs(a[0]).max() and abs(s[2] - a[2]) <= 1e-5 * abs(a[2]), n
+        a, c = run(), run()
+        assert _same_tree(a[0], c[0]), n
+        assert (a[1] == c[1]).all() and (a[2] == c[2]).all() and a[3] == c[3] and a[4] == c[4], n
+        assert (a[5] == c[5]).all() and (a[6] == c[6]).all(), n
+    _, t = _checked_tree(c3["target"], c3["tgt"])
+    assert _same_tree(t, c3["tree"]._tree())
 
 
-def test_kd_split_path_on_degenerate_clouds(monkeypatch):
+def test_kd_split_path_on_degenerate_clouds():
     """kd_split_level_kernel (radix select + partition, clouds <= 32768 points) on inputs that stress the select: all points identical, a
     line, two distinct points, a lattice with triplicates, coordinates up to 1e6 with ties, and sizes around the kernel's segment classes
-    (256 / 1024 threads x 2 ... 32 keys).  The kNN DISTANCES must equal those of the sort-based build (another valid tree over the same
-    points) and brute force."""
+    (256 / 1024 threads x 2 ... 32 keys).  Every tree meets its definition, two builds give the same tree and the same kNN rows, and the
+    kNN distances equal brute force."""
     rng = np.random.default_rng(21)
     g = np.arange(16, dtype=np.float32)
     lattice = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
@@ -937,24 +952,26 @@ def test_kd_split_path_on_degenerate_clouds(monkeypatch):
     for name, pts in clouds.items():
         q = np.concatenate([pts[rng.choice(len(pts), min(200, len(pts)), replace=False)] + rng.normal(0, 0.3, (min(200, len(pts)), 3)).astype(np.float32), rng.uniform(-20, 20, (50, 3)).astype(np.float32)])
         k = min(5, len(pts))
-        res = []
-        for split in ("1", "0"):
-            monkeypatch.setenv("SGA_KD_SPLIT", split)
-            tree = sga.KdTree(sga.PointCloud(pts))
-            res.append(tree.batch_knn_search(q, k)[1])
-        monkeypatch.delenv("SGA_KD_SPLIT")
+        res, trees = [], []
+        for _ in range(2):
+            tree, t = _checked_tree(pts)
+            trees.append(t)
+            res.append(tree.batch_knn_search(q, k))
+        assert _same_tree(*trees), name
+        assert np.array_equal(res[0][0], res[1][0]), name
+        res = [r[1] for r in res]
         assert np.array_equal(res[0], res[1]), name
         d = ((q[:, None, :].astype(np.float64) - pts[None, : min(len(pts), 40000), :].astype(np.float64)) ** 2).sum(-1)
         brute = np.sort(d, axis=1)[:, :k]
         assert np.abs(res[0] - brute).max() <= 1e-5 * max(1.0, float(brute.max())), name
 
 
-def test_kd_top_levels_on_degenerate_clouds(monkeypatch):
-    """The levels above the split kernel's reach (segments of more than 32768 points: kd_top_*_kernel — select + partition with a segment
+def test_kd_top_levels_on_degenerate_clouds():
+    """The levels above the split kernel's reach (segments of more than 16384 points: kd_top_*_kernel — select + partition with a segment
     spread over many workgroups, the points moving with the permutation) on inputs that stress the select across chunks: all points
     identical, a line, two distinct points, a lattice with many copies (median keys shared by thousands of points in several chunks),
-    large coordinates with ties, and sizes around the chunk (4096) and segment boundaries.  The kNN DISTANCES must equal those of the
-    sort-based levels (SGA_KD_TOP=0: another valid tree over the same points) and brute force."""
+    large coordinates with ties, and sizes around the chunk (4096) and segment boundaries.  Every tree meets its definition, two builds
+    give the same tree and the same kNN rows, and the kNN distances equal brute force."""
     rng = np.random.default_rng(33)
     g = np.arange(16, dtype=np.float32)
     lattice = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
@@ -970,12 +987,14 @@ def test_kd_top_levels_on_degenerate_clouds(monkeypatch):
     for name, pts in clouds.items():
         q = np.concatenate([pts[rng.choice(len(pts), 150, replace=False)] + rng.normal(0, 0.3, (150, 3)).astype(np.float32), rng.uniform(-20, 20, (50, 3)).astype(np.float32)])
         k = 5
-        res = []
-        for top in ("1", "0"):
-            monkeypatch.setenv("SGA_KD_TOP", top)
-            tree = sga.KdTree(sga.PointCloud(pts))
-            res.append(tree.batch_knn_search(q, k)[1])
-        monkeypatch.delenv("SGA_KD_TOP")
+        res, trees = [], []
+        for _ in range(2):
+            tree, t = _checked_tree(pts)
+            trees.append(t)
+            res.append(tree.batch_knn_search(q, k))
+        assert _same_tree(*trees), name
+        assert np.array_equal(res[0][0], res[1][0]), name
+        res = [r[1] for r in res]
         assert np.array_equal(res[0], res[1]), name
         brute = np.empty((len(q), k))
         p64 = pts.astype(np.float64)
