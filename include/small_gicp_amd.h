@@ -344,6 +344,35 @@ int sga_align(sga_context* ctx, const sga_index* target, const sga_cloud* source
 /* Same, on an existing problem (re-uses the sorted source and the factor buffers). */
 int sga_align_problem(sga_context* ctx, sga_problem* problem, const double init_T[16], const sga_registration_setting* setting, sga_result* out);
 
+/* ---- several independent registrations in one chain of launches ---------------------------------------------------------------------
+ * A batch pairs `count` existing problems of ONE context (it borrows them: the caller keeps ownership and destroys the batch first).
+ * One linearization of the batch is ONE search + factor launch over the tiles of all its active pairs, ONE row reduction and ONE
+ * hand-off to the host, whatever `count` is: the throughput form for many small clouds (a 11k-point scan fills 2 % of an MI355X).
+ * Every pair has its own pose and its own device frames; its sums do not depend on the company it keeps, bit for bit.
+ * Scope: kd-tree targets (voxel maps, flat maps, projective indexes: SGA_ERR_UNSUPPORTED at creation); one factor kind per call (ICP,
+ * PLANE_ICP, GICP), distance or null rejector; SGA_MATH_FP32, SGA_ROBUST_NONE, the error model on (sga_set_error_model) and no host
+ * rejector on any member — otherwise SGA_ERR_UNSUPPORTED before any device work.  count == 0 is SGA_OK and does nothing.  A problem
+ * is in one batch at a time and is not used through the lone entry points while a batch call runs; after a batch call it holds what a
+ * lone pass at the same pose leaves (sga_problem_get_factors, sga_linearize_per_point, sga_error keep working on it). */
+typedef struct sga_batch sga_batch;
+int sga_batch_create(sga_context* ctx, sga_problem* const* problems, size_t count, sga_batch** out);
+int sga_batch_destroy(sga_batch* batch);
+int sga_batch_size(const sga_batch* batch, size_t* count);
+/* Reduction::linearize (reduction_omp.hpp:24-58) for every pair with active[k] != 0 (active == NULL: all).  T: count x 16, H: count x 36,
+ * b: count x 6, e / num_inliers (may be NULL): count.  Entries of inactive pairs are left untouched. */
+int sga_batch_linearize(sga_context* ctx, sga_batch* batch, const sga_factor_params* params, const double* T, const unsigned char* active, double* H, double* b, double* e, uint64_t* num_inliers);
+/* Registration<>::align (registration.hpp:33-54) for every pair, LM or GN on the host in lock-step rounds: a round linearizes the pairs
+ * that are not done, each then runs its LM inner loop against its error model.  init_T: count x 16 or NULL (identity); out: count.
+ * Per pair the result is that of the same loop run on the pair alone; like sga_align_problem, no search state of earlier calls is used. */
+int sga_align_batch(sga_context* ctx, sga_batch* batch, const double* init_T, const sga_registration_setting* setting, sga_result* out);
+/* The host loop alone over caller-supplied batched reductions (the batched form of sga_optimize, no device involved): each callback
+ * serves the pairs with active[k] != 0 (T: count x 16 and the outputs laid out as above, entries of the others untouched) and returns 0
+ * on success.  For every pair the sequence of linearize / error requests and the sga_result are exactly those of sga_optimize run on
+ * that pair alone; verbose lines carry the pair's number. */
+typedef int (*sga_batch_linearize_fn)(void* user, size_t count, const unsigned char* active, const double* T, double* H, double* b, double* e, uint64_t* num_inliers);
+typedef int (*sga_batch_error_fn)(void* user, size_t count, const unsigned char* active, const double* T, double* e);
+int sga_optimize_batch(const sga_registration_setting* setting, size_t count, const double* init_T, sga_batch_linearize_fn linearize, sga_batch_error_fn error, void* user, sga_result* out);
+
 /* ---- one registration over several GPUs of THIS process ------------------------------------------------------------------------
  * The single-process form of the sharded path and the analogue of ParallelReductionOMP::num_threads (registration/reduction_omp.hpp:22,72:
  * the loop over the source points, :32-58, is what gets partitioned).  Shard g owns the source points [g n / G, (g + 1) n / G) of the

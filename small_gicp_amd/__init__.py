@@ -7,6 +7,7 @@ synthetic workloads of the benchmark configs (synthetic).
 from . import api, synthetic  # noqa: F401
 from ._lib import GICP, ICP, LIB_PATH, PLANE_ICP, SgaError, load  # noqa: F401
 from .api import (  # noqa: F401
+    BatchProblem,
     Context,
     GaussianVoxelMap,
     IncrementalVoxelMap,
@@ -20,6 +21,7 @@ from .api import (  # noqa: F401
     ProjectiveSearch,
     RegistrationResult,
     align,
+    align_batch,
     default_context,
     estimate_covariances,
     estimate_normals,
@@ -32,6 +34,7 @@ from .api import (  # noqa: F401
     set_warm_limit,
     make_setting,
     optimize,
+    optimize_batch,
     pinned_copy,
     pinned_empty,
     preprocess_points,

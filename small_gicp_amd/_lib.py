@@ -60,6 +60,10 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_
 LINEARIZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64))
 ERROR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
+# sga_batch_linearize_fn / sga_batch_error_fn: (user, count, active, T, H, b, e, num_inliers) / (user, count, active, T, e)
+BATCH_LINEARIZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64))
+BATCH_ERROR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), C.POINTER(C.c_double))
+
 # every symbol include/small_gicp_amd.h and include/small_gicp_amd_debug.h declare: (name, restype, argtypes)
 _vp, _dp, _fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float)
 _pvp = C.POINTER(C.c_void_p)
@@ -181,6 +185,12 @@ SYMBOLS = [
     ("sga_multi_align", C.c_int, [_vp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(ResultC)]),
     ("sga_multi_reset_search_state", C.c_int, [_vp]),
     ("sga_multi_get_factors", C.c_int, [_vp, C.c_void_p, C.c_void_p]),
+    ("sga_batch_create", C.c_int, [_vp, _pvp, C.c_size_t, _pvp]),
+    ("sga_batch_destroy", C.c_int, [_vp]),
+    ("sga_batch_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    ("sga_batch_linearize", C.c_int, [_vp, _vp, C.POINTER(FactorParams), _dp, C.POINTER(C.c_ubyte), _dp, _dp, _dp, C.POINTER(C.c_uint64)]),
+    ("sga_align_batch", C.c_int, [_vp, _vp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(ResultC)]),
+    ("sga_optimize_batch", C.c_int, [C.POINTER(RegistrationSettingC), C.c_size_t, _dp, BATCH_LINEARIZE_FN, BATCH_ERROR_FN, _vp, C.POINTER(ResultC)]),
     ("sga_optimize", C.c_int, [C.POINTER(RegistrationSettingC), _dp, LINEARIZE_FN, ERROR_FN, _vp, C.POINTER(ResultC)]),
     ("sga_se3_exp", None, [_dp, _dp]),
 ]

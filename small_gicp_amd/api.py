@@ -876,6 +876,112 @@ class Problem:
                 "adj_queries": g[4], "adj_unsettled": g[5]}
 
 
+def _T16s(Ts, count):
+    """count poses (None: identities) as a contiguous (count, 16) array, each column-major"""
+    if Ts is None:
+        Ts = [None] * count
+    if len(Ts) != count:
+        raise ValueError(f"{len(Ts)} poses for {count} pairs")
+    return np.ascontiguousarray(np.stack([_T16(T) for T in Ts]).reshape(count, 16)) if count else np.zeros((0, 16))
+
+
+class BatchProblem:
+    """sga_batch: several independent Problems of ONE context linearized by one search + factor launch, one row reduction and one
+    hand-off to the host per round, each pair at its own pose (small_gicp_amd.h).  kd-tree targets; ICP, PLANE_ICP or GICP in fp32
+    arithmetic, no robust kernel, no host rejector.  The problems are borrowed: after a call each holds what a lone pass leaves."""
+
+    def __init__(self, problems):
+        self.problems = list(problems)  # (keeps them alive: the batch must go first)
+        self.ctx = self.problems[0].ctx if self.problems else default_context()
+        hs = (C.c_void_p * max(1, len(self.problems)))(*[p.h.value for p in self.problems])
+        self.h = C.c_void_p()
+        check(load().sga_batch_create(self.ctx.h, hs, len(self.problems), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            load().sga_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __len__(self):
+        return len(self.problems)
+
+    def linearize(self, factor_params, Ts, active=None, out=None):
+        """Reduction::linearize for every active pair: (H (B, 6, 6), b (B, 6), e (B,), num_inliers (B,)).  Entries of inactive pairs keep
+        what `out` (a tuple of such arrays) held, zeros without it."""
+        B = len(self.problems)
+        H, b, e, n = out if out is not None else (np.zeros((B, 6, 6)), np.zeros((B, 6)), np.zeros(B), np.zeros(B, np.uint64))
+        t = _T16s(Ts, B)
+        act = None if active is None else np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))
+        if act is not None and len(act) != B:
+            raise ValueError(f"{len(act)} flags for {B} pairs")
+        check(load().sga_batch_linearize(self.ctx.h, self.h, C.byref(factor_params), _dp(t), None if act is None else act.ctypes.data_as(C.POINTER(C.c_ubyte)), _dp(H), _dp(b), _dp(e), n.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return H, b, e, n
+
+    def align(self, setting, init_Ts=None):
+        """Registration<>::align for every pair in lock-step rounds -> [RegistrationResult] in the problems' order."""
+        B = len(self.problems)
+        res = (ResultC * max(1, B))()
+        t = _T16s(init_Ts, B)
+        check(load().sga_align_batch(self.ctx.h, self.h, _dp(t) if B else None, C.byref(setting), res))
+        return [RegistrationResult(res[k]) for k in range(B)]
+
+
+def align_batch(targets, sources, init_Ts=None, setting=None):
+    """Register sources[k] (a PointCloud, or a KdTree taken in its own order) against the kd-tree targets[k] for all k in one batch;
+    setting: make_setting(...) (default GICP, 1 m).  The problems live for the call only."""
+    if len(targets) != len(sources):
+        raise ValueError("as many targets as sources")
+    init = [None] * len(targets) if init_Ts is None else init_Ts
+    problems = [Problem(t, s, T) for t, s, T in zip(targets, sources, init)]
+    batch = BatchProblem(problems)
+    try:
+        return batch.align(setting if setting is not None else make_setting("GICP"), init_Ts)
+    finally:
+        batch.__del__()  # before its problems
+
+
+def optimize_batch(setting, init_Ts, linearize, error):
+    """sga_optimize_batch: the lock-step host LM / GN over python callbacks linearize(k, T) -> (H, b, e, num_inliers) and
+    error(k, T) -> e, each asked per active pair k in ascending order within a round.  -> [RegistrationResult]"""
+    B = len(init_Ts)
+    exc = []
+
+    def _lin(user, count, active, T, H, b, e, n):
+        try:
+            for k in range(count):
+                if not active[k]:
+                    continue
+                Tm = np.ctypeslib.as_array(T, shape=(count * 16,))[16 * k : 16 * k + 16].reshape(4, 4).T
+                h, bb, ee, nn = linearize(k, Tm.copy())
+                np.ctypeslib.as_array(H, shape=(count * 36,))[36 * k : 36 * k + 36] = np.asarray(h, dtype=np.float64).reshape(36)
+                np.ctypeslib.as_array(b, shape=(count * 6,))[6 * k : 6 * k + 6] = np.asarray(bb, dtype=np.float64).reshape(6)
+                e[k] = float(ee)
+                n[k] = int(nn)
+            return 0
+        except Exception as ex:  # noqa: BLE001
+            exc.append(ex)
+            return 1
+
+    def _err(user, count, active, T, e):
+        try:
+            for k in range(count):
+                if active[k]:
+                    Tm = np.ctypeslib.as_array(T, shape=(count * 16,))[16 * k : 16 * k + 16].reshape(4, 4).T
+                    e[k] = float(error(k, Tm.copy()))
+            return 0
+        except Exception as ex:  # noqa: BLE001
+            exc.append(ex)
+            return 1
+
+    res = (ResultC * max(1, B))()
+    t = _T16s(init_Ts, B)
+    rc = load().sga_optimize_batch(C.byref(setting), B, _dp(t) if B else None, _lib.BATCH_LINEARIZE_FN(_lin), _lib.BATCH_ERROR_FN(_err), None, res)
+    if exc:
+        raise exc[0]
+    check(rc)
+    return [RegistrationResult(res[k]) for k in range(B)]
+
+
 class MultiProblem:
     """sga_multi: one registration over several GPUs of this process (source sharded, target replicated; small_gicp_amd.h).  `devices`
     may name a device more than once (logical shards on one GPU).  Clouds are given as host arrays: points (n, 3), normals (n, 3) or

@@ -1,0 +1,39 @@
+// Batched registration (batch.hip): B independent (target kd-tree, source) problems of ONE context whose linearizations run as one
+// search + factor launch and one row reduction per round, with one hand-off to the host for all pairs.
+#pragma once
+#include "common.hpp"
+
+struct sga_batch {
+  sga_context* ctx = nullptr;
+  std::vector<sga_problem*> problems;  // borrowed: the caller destroys the batch first
+  std::vector<int> tiles;              // 64-point tiles per pair (0: empty source or empty target); the pair's rows are its own partials[0, tiles)
+  std::vector<long long> tile_prefix;  // tiles of the pairs before k (count + 1 entries): the whole batch must fit an int grid
+  int max_depth = 0;                   // deepest target tree: sizes the LDS traversal stack of the launch
+  // the round table (linearize.hip: BatchPair): filled by the host in pinned memory, copied to the device with one command per round
+  void* h_round = nullptr;
+  sga::DevBuf<unsigned char> d_round;
+  size_t round_bytes = 0;
+  // results: count x 96 doubles + the sequence word, pinned and device-mapped (the hand-off of reduce_rows_kernel, once for all pairs)
+  double* h_out = nullptr;
+  double* h_out_dev = nullptr;
+  sga::DevBuf<unsigned> ticket;  // arrival counter of batch_reduce_rows_kernel, zero between launches
+  unsigned long long seq = 0;
+};
+
+namespace sga {
+size_t batch_round_bytes(size_t count);  // linearize.hip: bytes of a round table for `count` pairs
+// One linearization round over the pairs with active[k] != 0 (null: all) at the caller-frame poses T (count x 16): enqueue, hand-off,
+// wait.  Afterwards h_out[k * 96 ..] holds pair k's reduced row (device frames) and every active member problem the state a lone cold
+// pass at that pose leaves (correspondences, certificates, error model).  seedless: the walks ignore the neighbours of earlier passes.
+// The arguments have been validated (batch.hip: batch_check).
+int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, const double* T, const unsigned char* active, bool seedless);
+// pair k's row of the last round as the caller's H (36, exactly symmetric), b (6), e, inliers (batch.hip)
+void batch_unpack(const sga_batch* bt, size_t k, double* H, double* b, double* e, uint64_t* num_inliers);
+// validation of a batch call, before any device work (batch.hip)
+int batch_check(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp);
+// device frames (linearize.hip)
+const double* problem_pose(const sga_problem* pb, const double T[16], double Td[16]);
+void problem_system_to_caller(const sga_problem* pb, double H[36], double b[6]);
+double error_model_value(const double* acc96, const double T_lin[16], const double T[16]);
+bool error_model_enabled();
+}  // namespace sga

@@ -290,6 +290,7 @@ struct sga_index {
 
 struct sga_problem {
   int device = 0;
+  const sga_context* owner = nullptr;  // the context the problem was created on (compared, never dereferenced: a batch takes problems of one context)
   const sga_index* target = nullptr;
   size_t n = 0;  // source points
   double src_origin[3] = {0, 0, 0};  // device frame of the source records (the target's is target->origin, which an insert into a voxel map may move)

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "batch.hpp"
 #include "common.hpp"
 #include "device_math.hpp"
 #include "cell_grid.hpp"
@@ -1293,6 +1294,85 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CHECK ? SGA_
 #endif
 }
 
+// ---- batched registration (batch.hip): the rounds of B independent problems ---------------------------------
+// One entry of a round's table per ACTIVE pair, largest pair first: what search_linearize_kernel receives as its two arguments, for
+// that pair at its pose of the round.  The table lives in device memory (it does not fit the kernel-argument segment for large B); a
+// wave reads its pair's entry with scalar loads (uniform_const).
+struct BatchPair {
+  NNParams<float> q;
+  LinParams<float> p;
+  int ntiles;    // 64-point tiles of the pair = its partial rows, p.partials[0, ntiles)
+  int seedless;  // the walks start without the neighbour of an earlier pass (first round of a registration)
+  int pair;      // position in the batch: the reduced row goes to host[pair * kRow]
+  int pad;
+};
+
+// A wave-uniform pointer into memory that nothing writes while the kernel runs, as the constant address space: the loads through it are
+// scalar loads, issued where their values are used (see kernarg_lin_params)
+template <typename T>
+__device__ __forceinline__ const T* uniform_const(const T* ptr) {
+  using C = const __attribute__((address_space(4))) T;
+  C* a = (C*)ptr;
+  asm volatile("" : "+s"(a));
+  return (const T*)a;
+}
+
+// search_linearize_kernel (cold) for the tiles of all active pairs in one grid.  Workgroup (= wave) b belongs to the pair k with
+// prefix[k] <= b < prefix[k + 1]; every pair's share of the grid is padded to a multiple of 8 so that — workgroup b runs on XCD b % 8 —
+// each XCD gets one contiguous eighth of the pair's (spatially sorted) tiles, as search_tile_of_block arranges for a lone pass; the
+// waves of the padding leave at once.  The row of a tile goes to the pair's own partials at the tile's LOCAL number: neither the
+// placement nor the company a pair keeps enters any sum.
+template <int FACTOR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SGA_SL_WAVES, SGA_SL_WAVES))) void batch_search_linearize_kernel(const int* __restrict__ prefix_g, const BatchPair* __restrict__ pairs_g, int nactive) {
+  extern __shared__ uint32_t kd_stack[];  // max(deepest tree of the batch, 3) x 64 words: the traversal stacks, then the wave's row of kRow doubles
+  const int lane = threadIdx.x;
+  const int* prefix = uniform_const(prefix_g);
+  const int b = blockIdx.x;
+  int lo = 0, hi = nactive;  // wave-uniform binary search
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid] <= b)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int first = prefix[lo], per_xcd = (prefix[lo + 1] - first) >> 3, slot = b - first;
+  const int tile = (slot & 7) * per_xcd + (slot >> 3);
+  const BatchPair& d = *uniform_const(pairs_g + lo);
+  if (tile >= d.ntiles) return;  // wave-uniform
+  const NNParams<float>& p = d.q;
+  const LinParams<float>& lp = d.p;
+  const int i = tile * 64 + lane;
+  const bool active = i < p.n;
+  const float4 ps = active ? p.src_pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float q[3] = {0.f, 0.f, 0.f};
+  int j = -1;
+  if (active) {
+    transform_point<float>(p.T, ps.x, ps.y, ps.z, q[0], q[1], q[2]);
+    const int seed = d.seedless ? -1 : p.nn[i];  // (the cold form of search_lane)
+    j = walk_lane<float, 64>(p, i, q[0], q[1], q[2], seed, 0.f, kd_stack, lane);
+  }
+  // ---- the factors of the wave's 64 points, exactly as in search_linearize_kernel
+  float P[1][3] = {{ps.x, ps.y, ps.z}}, G[1][3] = {{0.f, 0.f, 0.f}}, E[1] = {0.f};
+  Sym3<float> Mp[1] = {Sym3<float>{}};
+  Sym3<float> Mh{};
+  bool inl = false;
+  if (j >= 0) {
+    const float4 m = lp.tgt_pts[j];
+    const bool within = kd_dist2(m.x, m.y, m.z, q[0], q[1], q[2]) < lp.bound2;
+    inl = pair_moments<float, FACTOR>(lp, i, j, within, q[0], q[1], q[2], m.x, m.y, m.z, Mp[0], G[0], E[0], Mh);
+  }
+  if (active) lp.corr[i] = inl ? j : -1;  // (the mahalanobis matrices are recomputed if ever asked for: problem_ensure_maha)
+  const int inliers = __popcll(__ballot(inl));
+  __syncthreads();  // one wave: every lane is done with its stack
+  double* row = reinterpret_cast<double*>(kd_stack);
+  for (int c = lane; c < kRow; c += 64) row[c] = 0.0;
+  __syncthreads();
+  if (inliers > 0) accumulate_moments<float, 1>(P, Mp, G, E, inliers, row, lane);
+  __syncthreads();
+  for (int c = lane; c < kRow; c += 64) lp.partials[static_cast<size_t>(tile) * kRow + c] = row[c];
+}
+
 // Per-point export of the same factors (the reference's Python binding exposes Factor::linearize per source point,
 // src/python/factors.cpp:52-101): the 28 values of every pair instead of their sum.  Runs after a linearize pass at the same pose
 // (kd-tree: the neighbours come from hint[]; flat map, FLAT: the correspondences that pass kept in corr[], slot or -1); not on the hot path.
@@ -1467,6 +1547,54 @@ __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host + kSeqWord), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The sums of a round: workgroup k adds the rows of the k-th active pair in the fixed order of reduce_rows_kernel's single-workgroup form
+// (slice s: rows s, s + 8, ... in four chains; then the slices), derives the moment-form columns and stores the pair's kRow doubles
+// into the pinned, device-mapped result block.  The workgroup that arrives last publishes the round's sequence number: ONE hand-off
+// for all pairs (the release / acquire chain of box_reduce_publish, notes.hpp).
+__global__ __launch_bounds__(kReduceSlices * kCols) void batch_reduce_rows_kernel(const BatchPair* __restrict__ pairs, unsigned* __restrict__ ticket, double* __restrict__ host, double* __restrict__ seq_word, unsigned long long seq) {
+  __shared__ double sh[kReduceSlices][kCols];
+  __shared__ unsigned sh_ticket;
+  const BatchPair* d = uniform_const(pairs + blockIdx.x);
+  const double* __restrict__ partials = d->p.partials;
+  const int nrows = d->ntiles, out_row = d->pair;
+  const int c = threadIdx.x & (kCols - 1), s = threadIdx.x / kCols;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  if (c < kModelCols) {
+    constexpr int step = kReduceSlices;
+    int r = s;
+    for (; r + 3 * step < nrows; r += 4 * step) {
+      const double v0 = partials[static_cast<size_t>(r) * kRow + c], v1 = partials[static_cast<size_t>(r + step) * kRow + c];
+      const double v2 = partials[static_cast<size_t>(r + 2 * step) * kRow + c], v3 = partials[static_cast<size_t>(r + 3 * step) * kRow + c];
+      a0 += v0, a1 += v1, a2 += v2, a3 += v3;
+    }
+    for (; r < nrows; r += step) a0 += partials[static_cast<size_t>(r) * kRow + c];
+  }
+  sh[s][c] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (threadIdx.x < kCols) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < kReduceSlices; k++) t += sh[k][threadIdx.x];
+    sh[0][threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < kRow) {
+    const int cc = threadIdx.x;
+    const double t = is_derived_col(cc) ? derived_entry(cc, sh[0]) : sh[0][cc];
+    host[static_cast<size_t>(out_row) * kRow + cc] = cc < kModelCols ? t : 0.0;
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (sh_ticket != gridDim.x - 1) return;  // workgroup-uniform
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next round
+    __threadfence_system();
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(seq_word), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -2106,8 +2234,9 @@ __global__ void publish_kernel(const double* __restrict__ src, int count, double
   if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host + kSeqWord), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-static int wait_result(sga_context* ctx, unsigned long long seq) {
-  const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(ctx->h_accum + kSeqWord);
+// spin until the device has published `seq` in the pinned sequence word `word` (null: the context's own, behind h_accum)
+static int wait_result(sga_context* ctx, unsigned long long seq, const double* word = nullptr) {
+  const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(word != nullptr ? word : ctx->h_accum + kSeqWord);
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0;; spins++) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
@@ -2451,6 +2580,98 @@ int linearize_collect(sga_context* ctx, sga_problem* pb, const double T[16], uns
 }
 }  // namespace sga
 
+namespace sga {
+// ---- batched registration: one round (see BatchPair) --------------------------------------------------------------------------------
+// round table: [prefix: count + 1 ints, padded to 16 bytes][BatchPair x count]
+static size_t batch_pairs_offset(size_t count) { return ((count + 1) * sizeof(int) + 15) / 16 * 16; }
+size_t batch_round_bytes(size_t count) { return batch_pairs_offset(count) + count * sizeof(BatchPair); }
+
+int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, const double* T, const unsigned char* active, bool seedless) {
+  const size_t count = bt->problems.size();
+  // the active pairs, largest first: the long pair's waves start first and the short pairs fill in behind them
+  std::vector<int> order;
+  for (size_t k = 0; k < count; k++)
+    if (active == nullptr || active[k]) order.push_back(static_cast<int>(k));
+  if (order.empty()) return SGA_OK;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bt->tiles[a] > bt->tiles[b]; });
+  int* prefix = static_cast<int*>(bt->h_round);
+  BatchPair* pairs = reinterpret_cast<BatchPair*>(static_cast<unsigned char*>(bt->h_round) + batch_pairs_offset(count));
+  std::vector<double> Tdev(16 * order.size());
+  int blocks = 0;
+  for (size_t a = 0; a < order.size(); a++) {
+    const int k = order[a];
+    sga_problem* pb = bt->problems[k];
+    const sga_index* idx = pb->target;
+    double* Td = &Tdev[16 * a];
+    const double* Tp = problem_pose(pb, T + 16 * k, Td);  // each pair's pose between ITS two device frames (common.hpp)
+    if (Tp != Td) memcpy(Td, Tp, 16 * sizeof(double));
+    BatchPair d{};
+    d.p = factor_params<float>(pb, fp, Td, false);
+    d.p.kd = make_kd_view(idx);
+    d.p.partials = pb->partials.p;
+    d.q.src_pts = pb->src_pts();
+    d.q.n = d.p.n;
+    d.q.kd = d.p.kd;
+    d.q.T = d.p.T;
+    d.q.within2 = d.p.bound2;
+    d.q.bound2 = d.p.bound2 * (1.f + kSearchMargin) * (1.f + kSearchMargin);
+    d.q.nn = pb->hint.p, d.q.nn2 = pb->hint2.p, d.q.rex = pb->rex.p, d.q.walked = pb->walked.p;
+    d.q.fast = g_fast_scan;
+    d.ntiles = bt->tiles[k];
+    d.seedless = seedless ? 1 : 0;
+    d.pair = k;
+    prefix[a] = blocks;
+    blocks += (d.ntiles + 7) / 8 * 8;  // (bt->tile_prefix bounds the sum: batch.hip)
+    pairs[a] = d;
+  }
+  prefix[order.size()] = blocks;
+  const int nactive = static_cast<int>(order.size());
+  const unsigned long long seq = ++bt->seq;
+  SGA_HIP(hipMemcpyAsync(bt->d_round.p, bt->h_round, batch_round_bytes(count), hipMemcpyHostToDevice, ctx->stream));
+  const int* d_prefix = reinterpret_cast<const int*>(bt->d_round.p);
+  const BatchPair* d_pairs = reinterpret_cast<const BatchPair*>(bt->d_round.p + batch_pairs_offset(count));
+  for (int k : order) {  // as in linearize_dispatch: until the round is launched completely the certificates belong to no pose the host knows
+    sga_problem* pb = bt->problems[k];
+    pb->prev_valid = false;
+    pb->model_valid = false;
+    pb->state_fresh = false;
+    pb->order_tiles = 0;
+    if (bt->tiles[k] == 0 && pb->n > 0) SGA_HIP(hipMemsetAsync(pb->corr.p, 0xff, pb->n * sizeof(int), ctx->stream));  // an empty target: no correspondences
+  }
+  if (blocks > 0) {
+    const size_t lds = static_cast<size_t>(std::max(bt->max_depth, 3)) * 64 * sizeof(uint32_t);
+    with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((batch_search_linearize_kernel<decltype(f)::value>), dim3(blocks), dim3(64), lds, ctx->stream, d_prefix, d_pairs, nactive); });
+  }
+  hipLaunchKernelGGL(batch_reduce_rows_kernel, dim3(nactive), dim3(kReduceSlices * kCols), 0, ctx->stream, d_pairs, bt->ticket.p, bt->h_out_dev, bt->h_out_dev + count * kRow, seq);
+  SGA_HIP(hipGetLastError());
+  int rc = wait_result(ctx, seq, bt->h_out + count * kRow);
+  if (rc != SGA_OK) {
+    (void)hipMemsetAsync(bt->ticket.p, 0, sizeof(unsigned), ctx->stream);
+    return rc;
+  }
+  for (size_t a = 0; a < order.size(); a++) {  // what a lone cold pass at this pose leaves in the problem
+    const int k = order[a];
+    sga_problem* pb = bt->problems[k];
+    const double* Td = &Tdev[16 * a];
+    pb->last_math = SGA_MATH_FP32;
+    pb->lin_factor = fp->factor_kind;
+    memcpy(pb->lin_T, Td, sizeof(pb->lin_T));
+    pb->maha_valid = false;
+    memcpy(pb->T_prev, Td, sizeof(pb->T_prev));
+    pb->prev_valid = true;
+    pb->prev_math = SGA_MATH_FP32;
+    pb->cold_passes++;
+    pb->grid_stats_pending = false;
+    const int lp[8] = {static_cast<int>(Route::kFusedLane), 0, 0, 1, 0, 0, bt->tiles[k], 1};
+    std::copy(lp, lp + 8, pb->last_plan);
+    memcpy(pb->model, bt->h_out + static_cast<size_t>(k) * kRow, sizeof(pb->model));
+    memcpy(pb->model_T, Td, sizeof(pb->model_T));
+    pb->model_valid = true;
+  }
+  return SGA_OK;
+}
+}  // namespace sga
+
 extern "C" {
 
 int sga_linearize(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double H[36], double b[6], double* e, uint64_t* num_inliers) {
@@ -2625,13 +2846,15 @@ void preload_hot_kernels() {
   SGA_PRELOAD(nn_search_queue_kernel<float, true, F>);              \
   SGA_PRELOAD(certify_linearize_kernel<float, F, 1>);               \
   SGA_PRELOAD(linearize_kernel<float, F, 0, kLinPts>);              \
-  SGA_PRELOAD(linearize_kernel<float, F, 0, 1>)
+  SGA_PRELOAD(linearize_kernel<float, F, 0, 1>);                   \
+  SGA_PRELOAD(batch_search_linearize_kernel<F>)
   SGA_PRELOAD_FACTOR(SGA_GICP);
   SGA_PRELOAD_FACTOR(SGA_PLANE_ICP);
   SGA_PRELOAD_FACTOR(SGA_ICP);
   SGA_PRELOAD(linearize_kernel<float, SGA_GICP, 1, kLinPts>);
   SGA_PRELOAD(linearize_kernel<float, SGA_GICP, 1, 1>);
   SGA_PRELOAD(reduce_rows_kernel);
+  SGA_PRELOAD(batch_reduce_rows_kernel);
   SGA_PRELOAD(tile_order_kernel);
   SGA_PRELOAD(publish_kernel);
   SGA_PRELOAD(error_kernel<float, SGA_GICP>);

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 
+#include "batch.hpp"
 #include "common.hpp"
 
 namespace sga {
@@ -196,6 +197,165 @@ static int optimize_impl(const sga_registration_setting& s, const double init_T[
   return SGA_OK;
 }
 
+// ---- the same loop for `count` independent pairs in lock-step ROUNDS -----------------------------------------------------------------
+// Every pair runs optimize_impl's loop as a state machine: it waits for a linearization (kLinearize), then — LM — for the error of its
+// trial pose (kError), any number of times, and so on until it is done.  A round serves all pairs that wait for the same thing with ONE
+// batched callback; a pair that is done appears in no later request.  Per pair the sequence of requests, their poses and the result are
+// exactly those of optimize_impl over that pair alone (tests/test_batch_optimizer.py compares them bit for bit).
+struct PairState {
+  enum Phase { kLinearize, kError, kDone } phase = kDone;
+  M4 T, new_T;
+  double lambda = 0, delta[6] = {0};
+  int i = 0, j = 0;  // outer / inner iteration
+  double H[36] = {0}, b[6] = {0}, e = 0;  // the accumulators of optimize_impl: a callback that leaves one untouched leaves the previous value
+  uint64_t inliers = 0;
+};
+
+static int optimize_batch_impl(const sga_registration_setting& s, size_t count, const double* init_T, sga_batch_linearize_fn lin, sga_batch_error_fn err, void* user, sga_result* out) {
+  static const double I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const bool gn = s.optimizer == SGA_GAUSS_NEWTON;
+  std::vector<PairState> st(count);
+  std::vector<unsigned char> mask(count);
+  std::vector<double> Ts(16 * count), Hs(36 * count), bs(6 * count), es(count);
+  std::vector<uint64_t> inl(count);
+  for (size_t k = 0; k < count; k++) {
+    PairState& p = st[k];
+    sga_result& r = out[k];
+    memcpy(p.T.a, init_T ? init_T + 16 * k : I16, sizeof(p.T.a));
+    r.converged = 0;
+    r.iterations = 0;
+    r.num_inliers = 0;
+    for (int i = 0; i < 36; i++) r.H[i] = 0;
+    for (int i = 0; i < 6; i++) r.b[i] = 0;
+    r.error = 0;
+    p.lambda = s.init_lambda;
+    p.phase = s.max_iterations > 0 ? PairState::kLinearize : PairState::kDone;
+    if (s.verbose) std::printf("pair=%zu --- %s optimization ---\n", k, gn ? "GN" : "LM");
+  }
+  // the end of outer iteration p.i (optimizer.hpp: after the inner loop)
+  auto end_iteration = [&](PairState& p, sga_result& r, bool success) {
+    r.iterations = p.i;
+    memcpy(r.H, p.H, sizeof(p.H));
+    memcpy(r.b, p.b, sizeof(p.b));
+    r.error = p.e;
+    p.i++;
+    p.phase = (success && p.i < s.max_iterations && !r.converged) ? PairState::kLinearize : PairState::kDone;
+  };
+  // LM: the next trial of the inner loop, or its unsuccessful end
+  auto next_trial = [&](PairState& p, sga_result& r) {
+    if (p.j >= s.max_inner_iterations) return end_iteration(p, r, false);
+    solve_damped(p.H, p.b, p.lambda, p.delta);
+    p.new_T = mul(p.T, se3_exp(p.delta));
+    p.phase = PairState::kError;
+  };
+  auto gather = [&](PairState::Phase ph) {
+    bool any = false;
+    for (size_t k = 0; k < count; k++) {
+      mask[k] = st[k].phase == ph ? 1 : 0;
+      any = any || mask[k];
+    }
+    return any;
+  };
+  for (;;) {
+    if (!gather(PairState::kLinearize)) break;  // (no pair waits for an error between rounds)
+    for (size_t k = 0; k < count; k++) {
+      if (!mask[k]) continue;
+      const PairState& p = st[k];
+      memcpy(&Ts[16 * k], p.T.a, sizeof(p.T.a));
+      memcpy(&Hs[36 * k], p.H, sizeof(p.H));
+      memcpy(&bs[6 * k], p.b, sizeof(p.b));
+      es[k] = p.e;
+      inl[k] = p.inliers;
+    }
+    if (lin(user, count, mask.data(), Ts.data(), Hs.data(), bs.data(), es.data(), inl.data())) return fail(SGA_ERR_CALLBACK, "linearize callback failed");
+    for (size_t k = 0; k < count; k++) {
+      if (!mask[k]) continue;
+      PairState& p = st[k];
+      sga_result& r = out[k];
+      memcpy(p.H, &Hs[36 * k], sizeof(p.H));
+      memcpy(p.b, &bs[6 * k], sizeof(p.b));
+      p.e = es[k];
+      p.inliers = inl[k];
+      apply_general_factor(s, p.H);
+      if (gn) {
+        solve_damped(p.H, p.b, s.gn_lambda, p.delta);
+        const double* d = p.delta;
+        if (s.verbose) std::printf("pair=%zu iter=%d e=%g lambda=%g dt=%g dr=%g\n", k, p.i, p.e, s.gn_lambda, std::sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]), std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]));
+        r.converged = converged(s, p.delta);
+        p.T = mul(p.T, se3_exp(p.delta));
+        end_iteration(p, r, true);
+      } else {
+        p.j = 0;
+        next_trial(p, r);
+      }
+    }
+    while (gather(PairState::kError)) {  // the LM inner loops, trial by trial
+      for (size_t k = 0; k < count; k++)
+        if (mask[k]) {
+          memcpy(&Ts[16 * k], st[k].new_T.a, sizeof(st[k].new_T.a));
+          es[k] = 0;
+        }
+      if (err(user, count, mask.data(), Ts.data(), es.data())) return fail(SGA_ERR_CALLBACK, "error callback failed");
+      for (size_t k = 0; k < count; k++) {
+        if (!mask[k]) continue;
+        PairState& p = st[k];
+        sga_result& r = out[k];
+        const double new_e = es[k];
+        const double* d = p.delta;
+        if (s.verbose)
+          std::printf(
+            "pair=%zu iter=%d inner=%d e=%g new_e=%g lambda=%g dt=%g dr=%g\n", k, p.i, p.j, p.e, new_e, p.lambda, std::sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]), std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]));
+        if (new_e <= p.e) {
+          r.converged = converged(s, p.delta);
+          p.T = p.new_T;
+          p.lambda /= s.lambda_factor;
+          p.e = new_e;
+          end_iteration(p, r, true);
+        } else {
+          p.lambda *= s.lambda_factor;
+          p.j++;
+          next_trial(p, r);
+        }
+      }
+    }
+  }
+  for (size_t k = 0; k < count; k++) {
+    out[k].num_inliers = st[k].inliers;
+    memcpy(out[k].T_target_source, st[k].T.a, sizeof(st[k].T.a));
+  }
+  return SGA_OK;
+}
+
+// sga_align_batch's reductions: the batched round on the device, the error model of each pair's last linearization on the host
+struct GpuBatchReduction {
+  sga_context* ctx;
+  sga_batch* bt;
+  const sga_factor_params* fp;
+  bool first;  // the first round of a registration walks without the neighbours of earlier calls
+};
+
+static int gpu_batch_linearize(void* user, size_t count, const unsigned char* active, const double* T, double* H, double* b, double* e, uint64_t* inl) {
+  auto* g = static_cast<GpuBatchReduction*>(user);
+  const int rc = batch_round(g->ctx, g->bt, g->fp, T, active, g->first);
+  g->first = false;
+  if (rc != SGA_OK) return rc;
+  for (size_t k = 0; k < count; k++) {
+    if (!active[k]) continue;
+    batch_unpack(g->bt, k, H + 36 * k, b + 6 * k, e + k, inl + k);
+  }
+  return SGA_OK;
+}
+static int gpu_batch_error(void* user, size_t count, const unsigned char* active, const double* T, double* e) {
+  auto* g = static_cast<GpuBatchReduction*>(user);
+  for (size_t k = 0; k < count; k++) {
+    if (!active[k]) continue;
+    const sga_problem* pb = g->bt->problems[k];
+    double Tdev[16];
+    e[k] = error_model_value(pb->model, pb->model_T, problem_pose(pb, T + 16 * k, Tdev));  // what sga_error answers after sga_linearize
+  }
+  return SGA_OK;
+}
+
 struct GpuReduction {
   sga_context* ctx;
   sga_problem* pb;
@@ -261,6 +421,31 @@ int sga_align_problem(sga_context* ctx, sga_problem* problem, const double init_
   problem->prev_valid = false;
   GpuReduction g{ctx, problem, &setting->factor};
   return optimize_impl(*setting, init_T ? init_T : I16, gpu_linearize, gpu_error, &g, out);
+}
+
+int sga_optimize_batch(const sga_registration_setting* setting, size_t count, const double* init_T, sga_batch_linearize_fn linearize, sga_batch_error_fn error, void* user, sga_result* out) {
+  if (!setting || !linearize) return fail(SGA_ERR_INVALID, "null argument");
+  if (setting->optimizer == SGA_LEVENBERG_MARQUARDT && !error) return fail(SGA_ERR_INVALID, "LM needs an error callback");
+  if (count == 0) return SGA_OK;
+  if (!out) return fail(SGA_ERR_INVALID, "null argument");
+  return optimize_batch_impl(*setting, count, init_T, linearize, error, user, out);
+}
+
+int sga_align_batch(sga_context* ctx, sga_batch* batch, const double* init_T, const sga_registration_setting* setting, sga_result* out) {
+  if (!setting) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(batch_check(ctx, batch, &setting->factor));
+  const size_t count = batch->problems.size();
+  if (count == 0) return SGA_OK;
+  if (!out) return fail(SGA_ERR_INVALID, "null argument");
+  for (size_t k = 0; k < count; k++) {  // registration.hpp:34-39 warns (does not fail) on tiny clouds
+    const sga_problem* pb = batch->problems[k];
+    if (pb->target->n <= 10) std::fprintf(stderr, "warning: target point cloud is too small. |target|=%zu\n", pb->target->n);
+    if (pb->n <= 10) std::fprintf(stderr, "warning: source point cloud is too small. |source|=%zu\n", pb->n);
+  }
+  SGA_ENTER(ctx);
+  // like sga_align_problem, every pair starts without search state of earlier calls: the first round's walks take no seed (no fill per pair)
+  GpuBatchReduction g{ctx, batch, &setting->factor, true};
+  return optimize_batch_impl(*setting, count, init_T, gpu_batch_linearize, gpu_batch_error, &g, out);
 }
 
 int sga_align(sga_context* ctx, const sga_index* target, const sga_cloud* source, const double init_T[16], const sga_registration_setting* setting, sga_result* out) {

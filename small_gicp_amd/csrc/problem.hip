@@ -269,6 +269,7 @@ __global__ void problem_state_init_kernel(int* __restrict__ corr, int* __restric
 }
 
 static int problem_alloc_state(sga_context* ctx, sga_problem* pb, size_t n, bool has_covs, bool own_arrays = true) {
+  pb->owner = ctx;
   SGA_TRY(pb->partials.alloc(problem_partials_doubles(n)));
   SGA_TRY(pb->walked.alloc(n / 64 + 1));
   if (n > 0 && own_arrays) {

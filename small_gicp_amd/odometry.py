@@ -325,6 +325,49 @@ def run_synthetic(num_frames=20, pinned=False, **kw):
     }
 
 
+def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None):
+    """The flow protocol (every pair (i - 1, i) registered from the identity, the relative poses multiplied up in frame order:
+    odometry_benchmark_small_gicp_tbb_flow.cpp:73-110) with the registrations BATCHED: the scans are preprocessed as OnlineOdometry does,
+    then groups of `batch` consecutive pairs are registered by one BatchProblem.align each — one search + factor launch, one row
+    reduction and one hand-off per LM round for the whole group.  The last group may be smaller; batch = 1 works.  Returns the poses,
+    the relative poses and iteration counts per pair, and the wall time of the registration stage per scan."""
+    from . import synthetic
+
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    ctx = ctx or api.Context(0)
+    prev_mode = ctx.set_stream_ordered(True)
+    try:
+        setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
+        frames = []  # (cloud, tree) per scan
+        for f in range(num_frames):
+            pts, _ = synthetic.kitti_like_scan(f)
+            cloud = api.voxelgrid_sampling(api.PointCloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), ctx=ctx), downsampling_resolution)
+            tree = api.KdTree(cloud)
+            api.estimate_covariances(cloud, tree, num_neighbors)
+            frames.append((cloud, tree))
+        ctx.synchronize()
+        rel, iters = [], []
+        t0 = time.perf_counter()
+        for first in range(1, num_frames, batch):
+            group = range(first, min(first + batch, num_frames))
+            problems = [api.Problem(frames[i - 1][1], frames[i][1], np.eye(4), ctx=ctx) for i in group]  # the scan by its own index, as OnlineOdometry
+            bp = api.BatchProblem(problems)
+            for r in bp.align(setting):
+                rel.append(r.T_target_source)
+                iters.append(r.iterations + 1)
+            del bp  # before its problems
+        ctx.synchronize()
+        wall = time.perf_counter() - t0
+    finally:
+        ctx.set_stream_ordered(prev_mode)
+    est = [np.eye(4)]
+    for T in rel:
+        est.append(est[-1] @ T)
+    return {"frames": num_frames, "batch": batch, "registration_ms_per_scan": 1e3 * wall / max(1, num_frames - 1), "mean_iterations": float(np.mean(iters)) if iters else 0.0,
+            "relative_poses": rel, "iterations": iters, "estimated": est}
+
+
 def run_synthetic_pairs(num_frames, rank, world, device=0, **kw):
     """Frame-pair parallelism over ranks (the other way to spread C5 over GPUs): under the reference's protocol every pair (scan f-1, scan f)
     is registered from the identity (odometry_benchmark_small_gicp_omp.cpp:16-49), so the pairs are independent — rank r takes the
