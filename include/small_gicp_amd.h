@@ -112,12 +112,25 @@ int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf_si
 /* util/normal_estimation.hpp:65-92 estimate_local_features: kNN(k, incl. self) -> mean/cov -> eigvecs -> normal / covariance.
  * index: a kd-tree built over `cloud`, or NULL to build a temporary one.  flags: bit0 = normals, bit1 = covariances. */
 int sga_estimate_normals_covariances(sga_context* ctx, sga_cloud* cloud, const sga_index* index, int num_neighbors, int flags);
+/* sga_estimate_normals_covariances for `count` (cloud, kd-tree index built over that cloud) pairs on the context's device in one chain
+ * of launches on the context's stream (a member made by another context of that device is waited for, as in the lone call; a member on
+ * another device is SGA_ERR_INVALID); every cloud and index gets, bit for bit, what the lone call gives it.  indices[k] must not be NULL, no cloud or index may
+ * appear twice.  Members of more than sga_set_knn_wave_max points (default 81920), and calls with num_neighbors > 64, are estimated by
+ * the lone routine, one after the other, inside the call.  All arguments are checked before any device work.  count == 0 is SGA_OK. */
+int sga_estimate_normals_covariances_batch(sga_context* ctx, sga_cloud* const* clouds, sga_index* const* indices, size_t count, int num_neighbors, int flags);
 
 /* ---- search indices --------------------------------------------------------------------------------------------- */
 /* Replaces KdTree<PointCloud>(points) (ann/kdtree.hpp:80-126, :250-252): exact nearest neighbour / kNN over `target`.
  * An implicit, perfectly balanced kd-tree (median splits like the reference, no pointers) built on the GPU; the index keeps its
  * own kd-ordered copy of the target's points / normals / covariances. */
 int sga_index_build_kdtree(sga_context* ctx, const sga_cloud* target, sga_index** out);
+/* sga_index_build_kdtree for `count` clouds on the context's device in one chain of launches on the context's stream (a cloud made by
+ * another context of that device is waited for, as in the lone call; a cloud on another device is SGA_ERR_INVALID): out[k] is an ordinary kd-tree index over clouds[k],
+ * bit-identical to the lone call's, owning its buffers, destroyed with sga_index_destroy in any order.  Clouds of at most 32768 points
+ * (a LiDAR scan after the voxel grid) share the launches — B scans of similar size cost the launches of one; empty and larger clouds are
+ * built by the lone path, one after the other, inside the call.  The host waits once for the bounding boxes of all members; a member
+ * with non-finite coordinates fails the call (SGA_ERR_INVALID).  On any failure every out[k] is NULL.  count == 0 is SGA_OK. */
+int sga_index_build_kdtree_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, sga_index** out);
 /* Replaces create_gaussian_voxelmap (registration_helper.cpp:50-54; ann/incremental_voxelmap.hpp:55-92, gaussian_voxelmap.hpp:32-53):
  * one-shot insert of a cloud WITH covariances; voxel ids follow first-insertion order like the reference. */
 int sga_index_build_gaussian_voxelmap(sga_context* ctx, const sga_cloud* points_with_covs, double leaf_size, sga_index** out);

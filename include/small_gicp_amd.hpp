@@ -178,6 +178,8 @@ private:
 struct KdTree {
   using Ptr = std::shared_ptr<KdTree>;
   explicit KdTree(std::shared_ptr<const PointCloud> pts) : points(std::move(pts)) { check(sga_index_build_kdtree(points->ctx, points->h, &h), "sga_index_build_kdtree"); }
+  /// takes over an index built over `pts` (build_kdtrees)
+  KdTree(std::shared_ptr<const PointCloud> pts, sga_index* built) : points(std::move(pts)), h(built) {}
   KdTree(const KdTree&) = delete;
   KdTree& operator=(const KdTree&) = delete;
   ~KdTree() { sga_index_destroy(h); }
@@ -372,6 +374,26 @@ inline void estimate_covariances(PointCloud& cloud, KdTree& tree, int num_neighb
 inline void estimate_normals(PointCloud& cloud, KdTree& tree, int num_neighbors = 20) {
   check(sga_estimate_normals_covariances(cloud.ctx, cloud.h, tree.h, num_neighbors, 1), "estimate_normals");
   cloud.invalidate_host();
+}
+/// sga_index_build_kdtree_batch: the kd-trees of several clouds of one context in one chain of launches (each bit-identical to KdTree(cloud))
+inline std::vector<KdTree::Ptr> build_kdtrees(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds) {
+  std::vector<const sga_cloud*> hs;
+  for (const auto& c : clouds) hs.push_back(c->h);
+  std::vector<sga_index*> out(clouds.size(), nullptr);
+  check(sga_index_build_kdtree_batch(ctx, hs.data(), hs.size(), out.data()), "sga_index_build_kdtree_batch");
+  std::vector<KdTree::Ptr> trees;
+  for (size_t k = 0; k < clouds.size(); k++) trees.push_back(std::make_shared<KdTree>(clouds[k], out[k]));
+  return trees;
+}
+/// sga_estimate_normals_covariances_batch (covariances): trees[k] must have been built over clouds[k]
+inline void estimate_covariances(sga_context* ctx, const std::vector<std::shared_ptr<PointCloud>>& clouds, const std::vector<KdTree::Ptr>& trees, int num_neighbors = 20) {
+  std::vector<sga_cloud*> cs;
+  std::vector<sga_index*> ts;
+  for (const auto& c : clouds) cs.push_back(c->h);
+  for (const auto& t : trees) ts.push_back(t->h);
+  if (cs.size() != ts.size()) throw std::runtime_error("estimate_covariances: as many trees as clouds");
+  check(sga_estimate_normals_covariances_batch(ctx, cs.data(), ts.data(), cs.size(), num_neighbors, 2), "sga_estimate_normals_covariances_batch");
+  for (const auto& c : clouds) c->invalidate_host();
 }
 
 // ---- factors (factors/*.hpp): tag types, the per-point state lives on the device ----------------------------------------------------

@@ -46,6 +46,13 @@ int sga_index_spacing(const sga_index* index, double* spacing);
  * of depth d; entry 0 unused, never written); xyzw = the n points in kd order (device frame, w = original index as bits).  nodes / xyzw may be null
  * (depth only).  Other kinds of index are refused. */
 int sga_debug_kd_tree(sga_context* ctx, const sga_index* index, int* depth, float* nodes, float* xyzw);
+/* The bounding box of its points (device frame: the cloud's records) that the build of an index stored: a kd-tree's comes from the root
+ * level of its build; all zeros for an empty index. */
+int sga_debug_index_bbox(const sga_index* index, float lo[3], float hi[3]);
+/* Kernels enqueued so far, in this process, by the forest form of sga_index_build_kdtree_batch and
+ * sga_estimate_normals_covariances_batch (members that take the lone path inside those calls are not counted): a forest of B clouds of
+ * equal depth enqueues as many kernels as a forest of one. */
+int sga_debug_forest_launches(unsigned long long* launches);
 /* GPU time (HIP events) between two points of the context's stream: start() records an event, stop() records another, waits for it and
  * returns the milliseconds in between — the kernel times of bench.py's per-stage roofline lines (voxel grid, index build, covariances). */
 int sga_debug_timer_start(sga_context* ctx);

@@ -22,10 +22,15 @@ from .api import (  # noqa: F401
     RegistrationResult,
     align,
     align_batch,
+    build_kdtrees,
     default_context,
     estimate_covariances,
+    estimate_covariances_batch,
     estimate_normals,
+    estimate_normals_batch,
     estimate_normals_covariances,
+    estimate_normals_covariances_batch,
+    forest_launches,
     error_model_eval,
     get_warm_limit,
     set_error_model,
@@ -37,6 +42,7 @@ from .api import (  # noqa: F401
     optimize_batch,
     pinned_copy,
     pinned_empty,
+    preprocess_batch,
     preprocess_points,
     unpack_accumulator,
     voxelgrid_sampling,

@@ -295,11 +295,14 @@ class KdTree:
     """Exact nearest-neighbour index over a PointCloud (small_gicp.KdTree): an implicit balanced kd-tree built on the GPU
     (sga_index_build_kdtree)."""
 
-    def __init__(self, points, num_threads=1, **_ignored):
+    def __init__(self, points, num_threads=1, _handle=None, **_ignored):
         if not isinstance(points, PointCloud):
             points = PointCloud(points)
         self.cloud = points
         self.ctx = points.ctx
+        if _handle is not None:  # an index built over `points` already (build_kdtrees)
+            self.h = _handle
+            return
         self.h = C.c_void_p()
         check(load().sga_index_build_kdtree(self.ctx.h, points.h, C.byref(self.h)))
 
@@ -330,6 +333,12 @@ class KdTree:
         xyzw = np.zeros((self.size(), 4), np.float32)
         check(lib.sga_debug_kd_tree(self.ctx.h, self.h, C.byref(depth), nodes.ctypes.data_as(C.c_void_p), xyzw.ctypes.data_as(C.c_void_p)))
         return depth.value, nodes[:, 0].copy(), nodes[:, 1].view(np.int32).copy(), xyzw[:, :3].copy(), xyzw[:, 3].view(np.uint32).astype(np.int64)
+
+    def _bbox(self):
+        """Diagnostics (sga_debug_index_bbox): (lo (3,), hi (3,)) float32, the box of the points in the cloud's device frame as the build stored it."""
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(load().sga_debug_index_bbox(self.h, _fp(lo), _fp(hi)))
+        return lo, hi
 
     def refresh_attributes(self):
         """Pull the cloud's current normals / covariances into the index (needed when they were set after the index was built)."""
@@ -1149,6 +1158,71 @@ def estimate_covariances(points, tree=None, num_neighbors=20, num_threads=1):
 
 def estimate_normals_covariances(points, tree=None, num_neighbors=20, num_threads=1):
     _estimate(points, tree, num_neighbors, 3)
+
+
+def _one_context(clouds):
+    for c in clouds:
+        if not isinstance(c, PointCloud):
+            raise TypeError("a batch takes PointCloud objects")
+    ctx = clouds[0].ctx if clouds else default_context()
+    if any(c.ctx is not ctx for c in clouds):
+        raise ValueError("the clouds of a batch must belong to one context")
+    return ctx
+
+
+def build_kdtrees(clouds):
+    """sga_index_build_kdtree_batch: [KdTree(c) for c in clouds] in one chain of launches (clouds of one context).  Every tree is an
+    ordinary KdTree, bit-identical to the lone build's; clouds of at most 32768 points share the launches, others are built one by one."""
+    clouds = list(clouds)
+    ctx = _one_context(clouds)
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    out = (C.c_void_p * max(1, len(clouds)))()
+    check(load().sga_index_build_kdtree_batch(ctx.h, hs, len(clouds), out))
+    return [KdTree(c, _handle=C.c_void_p(out[k])) for k, c in enumerate(clouds)]
+
+
+def _estimate_batch(clouds, trees, num_neighbors, flags):
+    clouds, trees = list(clouds), list(trees)
+    if len(clouds) != len(trees):
+        raise ValueError("as many trees as clouds")
+    ctx = _one_context(clouds)
+    for t in trees:
+        if not isinstance(t, KdTree):
+            raise TypeError("a batched estimation takes the KdTree of every cloud")
+    cs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    ts = (C.c_void_p * max(1, len(trees)))(*[t.h.value for t in trees])
+    check(load().sga_estimate_normals_covariances_batch(ctx.h, cs, ts, len(clouds), int(num_neighbors), flags))
+
+
+def estimate_normals_batch(clouds, trees, num_neighbors=20):
+    """estimate_normals(clouds[k], trees[k], num_neighbors) for all k in one chain of launches (sga_estimate_normals_covariances_batch)."""
+    _estimate_batch(clouds, trees, num_neighbors, 1)
+
+
+def estimate_covariances_batch(clouds, trees, num_neighbors=20):
+    """estimate_covariances(clouds[k], trees[k], num_neighbors) for all k in one chain of launches."""
+    _estimate_batch(clouds, trees, num_neighbors, 2)
+
+
+def estimate_normals_covariances_batch(clouds, trees, num_neighbors=20):
+    """estimate_normals_covariances(clouds[k], trees[k], num_neighbors) for all k in one chain of launches."""
+    _estimate_batch(clouds, trees, num_neighbors, 3)
+
+
+def preprocess_batch(clouds, num_neighbors=20):
+    """The kd-trees and the covariances of several (downsampled) clouds of one context, each made by one batched call:
+    [(cloud, tree)] with what KdTree(cloud) and estimate_covariances(cloud, tree, num_neighbors) give every pair, bit for bit."""
+    clouds = list(clouds)
+    trees = build_kdtrees(clouds)
+    estimate_covariances_batch(clouds, trees, num_neighbors)
+    return list(zip(clouds, trees))
+
+
+def forest_launches():
+    """Diagnostics (sga_debug_forest_launches): kernels enqueued so far by the forest form of the two batched preprocessing calls."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_forest_launches(C.byref(v)))
+    return v.value
 
 
 def preprocess_points(points, downsampling_resolution=0.25, num_neighbors=10, num_threads=1):

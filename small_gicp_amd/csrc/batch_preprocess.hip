@@ -1,0 +1,266 @@
+// Batched preprocessing: sga_index_build_kdtree and sga_estimate_normals_covariances for B clouds of one context
+// in one chain of launches.  A scan after the voxel grid (11 - 12k points) leaves the chip idle in every step of its lone build — level d
+// of the tree is 2^d workgroups — and pays ~10 launches for ~100 us of kernels; B such scans fill the same launches B times over.
+// The results are ordinary sga_index objects, each owning its buffers, bit-identical to what the lone calls produce: the batched
+// kernels (index_build.hip, preprocess.hip) run the lone kernels' bodies with the arguments read from a per-call table (forest.hpp).
+#include <atomic>
+#include <chrono>
+#include <memory>
+#include <thread>
+#include <unordered_set>
+#include <vector>
+
+#include "common.hpp"
+#include "forest.hpp"
+#include "notes.hpp"
+
+namespace sga {
+int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
+
+namespace {
+std::atomic<unsigned long long> g_forest_launches{0};
+
+// the context's box block with room for `members` slots (grow-only; no call is in flight: every call waits for its boxes)
+int forest_box_block(sga_context* ctx, size_t members) {
+  const size_t need = 4 * members + 4;
+  if (ctx->forest_words >= need) return SGA_OK;
+  if (ctx->h_forest) (void)hipHostFree(ctx->h_forest);
+  ctx->h_forest = ctx->h_forest_dev = nullptr;
+  ctx->forest_words = 0;
+  size_t want = 1024;
+  while (want < need) want <<= 1;
+  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_forest), want * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+    ctx->h_forest = nullptr;
+    return fail(SGA_ERR_HIP, "hipHostMalloc(%zu bytes) failed", want * sizeof(unsigned long long));
+  }
+  std::memset(ctx->h_forest, 0, want * sizeof(unsigned long long));
+  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->h_forest_dev), ctx->h_forest, 0) != hipSuccess) return fail(SGA_ERR_HIP, "hipHostGetDevicePointer failed");
+  ctx->forest_words = want;
+  return SGA_OK;
+}
+
+// the ONE wait of a forest build: all boxes are there once the block shows the call's sequence number (note_wait's spin, context.hip)
+int forest_boxes_wait(sga_context* ctx, unsigned long long seq) {
+  const unsigned long long* word = ctx->h_forest;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned spins = 0;; spins++) {
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
+    __builtin_ia32_pause();
+    if (spins > 200000u) std::this_thread::yield();
+    if ((spins & 0xfffu) == 0xfffu) {
+      const hipError_t q = hipStreamQuery(ctx->stream);
+      if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+        (void)hipGetLastError();
+        SGA_HIP(hipStreamSynchronize(ctx->stream));
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
+        return fail(SGA_ERR_HIP, "the boxes of a batched kd-tree build were not published by the device");
+      }
+      (void)hipGetLastError();  // hipErrorNotReady is sticky in hipGetLastError
+    }
+  }
+}
+
+int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count, std::vector<std::unique_ptr<sga_index>>& made) {
+  made.resize(count);
+  std::vector<size_t> forest;  // positions of the members the forest builds: 1 <= n <= kForestMaxPoints
+  size_t forest_points = 0;
+  for (size_t k = 0; k < count; k++) {
+    const sga_cloud* cloud = clouds[k];
+    if (cloud->n == 0 || cloud->n > kForestMaxPoints) continue;  // the empty index below / the lone path
+    std::unique_ptr<sga_index> idx(new sga_index);  // as sga_index_build_kdtree sets it up
+    idx->kind = SGA_INDEX_KDTREE;
+    idx->device = ctx->device;
+    idx->n = cloud->n;
+    for (int a = 0; a < 3; a++) idx->origin[a] = cloud->origin[a];
+    idx->has_normals = cloud->has_normals;
+    idx->has_covs = cloud->has_covs;
+    SGA_TRY(wait_ready(ctx, cloud->ready));
+    made[k] = std::move(idx);
+    forest.push_back(k);
+    forest_points += cloud->n;
+  }
+  DevBuf<uint32_t> perms;                 // the two permutation buffers of every tree
+  DevBuf<unsigned long long> table;       // forest.hpp; both live until the end of the call (then: the stream's free list)
+  unsigned long long seq = 0;
+  if (!forest.empty()) {
+    // ---- every allocation of every member, then the launches
+    SGA_TRY(perms.alloc(2 * forest_points));
+    SGA_TRY(forest_box_block(ctx, forest.size()));
+    std::vector<ForestTree> trees(forest.size());
+    size_t at = 0;
+    for (size_t j = 0; j < forest.size(); j++) {
+      const sga_cloud* cloud = clouds[forest[j]];
+      sga_index* idx = made[forest[j]].get();
+      const size_t n = cloud->n;
+      int D = 0, dA = 0;
+      forest_tree_shape(n, &D, &dA);
+      idx->kd_depth = D;
+      SGA_TRY(idx->kd_nodes.alloc(1ull << D));
+      SGA_TRY(idx->kd_nodes4.alloc(kd_pair_count(D)));
+      SGA_TRY(idx->kd_pts.alloc(n + kKdLeafMax));
+      if (cloud->has_normals) SGA_TRY(idx->nrm.alloc(n));
+      if (cloud->has_covs) SGA_TRY(idx->cov.alloc(n));
+      SGA_TRY(idx->kd_boxes.alloc(4ull << D));
+      SGA_TRY(idx->kd_groups.alloc(8ull << (D - (D < 2 ? D : 2))));
+      SGA_TRY(idx->kd_leaf.alloc(8ull << D));
+      ForestTree& t = trees[j];
+      std::memset(&t, 0, sizeof(t));
+      t.pts = cloud->pts.p;
+      t.nrm = cloud->has_normals ? cloud->nrm.p : nullptr;
+      t.cov = cloud->has_covs ? cloud->cov.p : nullptr;
+      t.perm[0] = perms.p + at;
+      t.perm[1] = perms.p + at + n;
+      at += 2 * n;
+      t.nodes = idx->kd_nodes.p;
+      t.opts = idx->kd_pts.p;
+      t.onrm = idx->nrm.p;
+      t.ocov = idx->cov.p;
+      t.boxes = idx->kd_boxes.p;
+      t.groups = idx->kd_groups.p;
+      t.blocks = reinterpret_cast<float*>(idx->kd_leaf.p);
+      t.pairs = idx->kd_nodes4.p;
+      t.late_seq = late_note_begin(ctx->device, &t.late_slot);  // the length scale travels as a late note per index, as in the lone build
+      idx->spacing = 0.0;
+      idx->spacing_seq = t.late_seq;
+      t.box_slot = ctx->h_forest_dev + 4 + 4 * j;
+      t.n = static_cast<uint32_t>(n);
+      t.D = D;
+      t.dA = dA;
+    }
+    seq = ++ctx->forest_seq;
+    if (const int rc = forest_build(ctx, trees, ctx->h_forest_dev, seq, table); rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // root levels already enqueued write into the box block: nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    // ---- the one wait: the boxes of all members
+    SGA_TRY(forest_boxes_wait(ctx, seq));
+    for (size_t j = 0; j < forest.size(); j++) {
+      sga_index* idx = made[forest[j]].get();
+      box_note_decode(ctx->h_forest + 4 + 4 * j + 1, idx->bbox_lo, idx->bbox_hi);
+      for (int a = 0; a < 3; a++)
+        if (!std::isfinite(idx->bbox_lo[a]) || !std::isfinite(idx->bbox_hi[a])) return fail(SGA_ERR_INVALID, "target cloud %zu contains non-finite coordinates", forest[j]);
+    }
+    for (size_t k : forest) SGA_TRY(build_cell_grid(ctx, made[k].get()));  // (declines by its own rule for clouds this small)
+  }
+  // ---- the other members through the lone path, one after the other: empty clouds, clouds of more than kForestMaxPoints points
+  for (size_t k = 0; k < count; k++) {
+    if (made[k]) continue;
+    sga_index* lone = nullptr;
+    SGA_TRY(sga_index_build_kdtree(ctx, clouds[k], &lone));
+    made[k].reset(lone);
+  }
+  if (!forest.empty() && !ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k : forest) SGA_TRY(mark_ready(ctx, made[k]->ready));
+  return SGA_OK;
+}
+}  // namespace
+
+void forest_count_launch() { g_forest_launches.fetch_add(1, std::memory_order_relaxed); }
+}  // namespace sga
+
+using namespace sga;
+
+extern "C" {
+
+int sga_debug_forest_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_index_build_kdtree_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, sga_index** out) {
+  if (count == 0) return SGA_OK;
+  if (out)
+    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
+  for (size_t k = 0; k < count; k++) {
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "clouds[%zu] is NULL", k);
+    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
+  }
+  SGA_ENTER(ctx);
+  std::vector<std::unique_ptr<sga_index>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
+  SGA_TRY(build_kdtrees(ctx, clouds, count, made));
+  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
+  return SGA_OK;
+}
+
+int sga_estimate_normals_covariances_batch(sga_context* ctx, sga_cloud* const* clouds, sga_index* const* indices, size_t count, int k, int flags) {
+  if (count == 0) return SGA_OK;
+  SGA_TRY(features_check_k(k));
+  if (!ctx || !clouds || !indices) return fail(SGA_ERR_INVALID, "null argument");
+  std::unordered_set<const void*> seen;
+  for (size_t m = 0; m < count; m++) {
+    const sga_cloud* cloud = clouds[m];
+    const sga_index* index = indices[m];
+    if (!cloud) return fail(SGA_ERR_INVALID, "clouds[%zu] is NULL", m);
+    if (!index) return fail(SGA_ERR_INVALID, "indices[%zu] is NULL (a batched estimation needs the index of every cloud)", m);
+    if (cloud->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", m);
+    if (index->device != ctx->device) return fail(SGA_ERR_INVALID, "index %zu lives on another device", m);
+    if (index->kind == SGA_INDEX_PROJECTIVE) return fail(SGA_ERR_UNSUPPORTED, "normal / covariance estimation needs a kd-tree index, not a projective search (member %zu)", m);
+    if (index->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_INVALID, "a kd-tree index is required (member %zu)", m);
+    if (index->n != cloud->n) return fail(SGA_ERR_INVALID, "index %zu was built over a cloud of %zu points, got %zu", m, index->n, cloud->n);
+    for (int a = 0; a < 3; a++)
+      if (index->origin[a] != cloud->origin[a]) return fail(SGA_ERR_INVALID, "index %zu was not built over its cloud (their device frames differ)", m);
+    if (!seen.insert(cloud).second) return fail(SGA_ERR_INVALID, "cloud %zu appears twice in the batch", m);
+    if (!seen.insert(index).second) return fail(SGA_ERR_INVALID, "index %zu appears twice in the batch", m);
+  }
+  if ((flags & 3) == 0) return SGA_OK;
+  SGA_ENTER(ctx);
+  // the forest form is knn_wave_kernel + features_from_list_kernel: the members the lone routine gives those two kernels
+  const long long wave_max = knn_wave_max_points();
+  std::vector<size_t> forest;
+  unsigned long long blocks = 0;
+  for (size_t m = 0; m < count; m++) {
+    const size_t n = clouds[m]->n;
+    if (n == 0 || static_cast<long long>(n) > wave_max || k > 64 || blocks + n > 0x7fffffffull) continue;
+    forest.push_back(m);
+    blocks += n;
+  }
+  DevBuf<int> nbr;
+  DevBuf<unsigned long long> table;
+  if (!forest.empty()) {
+    std::vector<ForestFeat> members(forest.size());
+    SGA_TRY(nbr.alloc(blocks * static_cast<size_t>(k)));
+    size_t at = 0;
+    for (size_t j = 0; j < forest.size(); j++) {
+      sga_cloud* cloud = clouds[forest[j]];
+      sga_index* index = indices[forest[j]];
+      const size_t n = cloud->n;
+      SGA_TRY(wait_ready(ctx, index->ready));
+      SGA_TRY(wait_ready(ctx, cloud->ready));
+      if ((flags & 1) && cloud->nrm.n < n) SGA_TRY(cloud->nrm.alloc(n));
+      if ((flags & 2) && cloud->cov.n < n) SGA_TRY(cloud->cov.alloc(n));
+      if ((flags & 1) && index->nrm.n < n) SGA_TRY(index->nrm.alloc(n));
+      if ((flags & 2) && index->cov.n < n) SGA_TRY(index->cov.alloc(n));
+      ForestFeat& f = members[j];
+      f.g = make_kd_view(index);
+      f.nbr = nbr.p + at;
+      at += n * static_cast<size_t>(k);
+      f.idx_nrm = index->nrm.p;
+      f.idx_cov = index->cov.p;
+      f.cloud_nrm = cloud->nrm.p;
+      f.cloud_cov = cloud->cov.p;
+      f.ox = cloud->origin[0], f.oy = cloud->origin[1], f.oz = cloud->origin[2];
+    }
+    SGA_TRY(forest_features(ctx, members, k, flags, table));
+  }
+  // the other members through the lone routine: empty clouds, clouds above the one-wave-per-query limit, k > 64
+  for (size_t m = 0, j = 0; m < count; m++) {
+    if (j < forest.size() && forest[j] == m) {
+      j++;
+      continue;
+    }
+    SGA_TRY(sga_estimate_normals_covariances(ctx, clouds[m], indices[m], k, flags));
+  }
+  if (!forest.empty() && !ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t m : forest) {
+    if (flags & 1) clouds[m]->has_normals = indices[m]->has_normals = true;
+    if (flags & 2) clouds[m]->has_covs = indices[m]->has_covs = true;
+    SGA_TRY(mark_ready(ctx, indices[m]->ready));
+    SGA_TRY(mark_ready(ctx, clouds[m]->ready));
+  }
+  return SGA_OK;
+}
+
+}  // extern "C"

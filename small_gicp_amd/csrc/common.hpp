@@ -128,6 +128,12 @@ struct sga_context {
   unsigned long long* h_notes = nullptr;      // kNoteSlots x kNoteWords words behind h_accum
   unsigned long long* h_notes_dev = nullptr;
   unsigned long long note_seq = 0;
+  // batched preprocessing (batch_preprocess.hip): the pinned, device-mapped block the root levels of a forest write their clouds' boxes
+  // into (grow-only).  Word 0 = the sequence number of the last call whose boxes have all arrived, words 4 k + 4 .. 4 k + 7 = member k's slot
+  unsigned long long* h_forest = nullptr;
+  unsigned long long* h_forest_dev = nullptr;
+  size_t forest_words = 0;
+  unsigned long long forest_seq = 0;
   // voxel grid (preprocess.hip: ds_segments_kernel): look-back status words, {arrival counter, runs, valid points}, launch epoch
   sga::DevBuf<unsigned long long> vg_status;
   sga::DevBuf<uint32_t> vg_scratch;
@@ -167,6 +173,11 @@ struct sga_context {
   void* comm_user = nullptr;
   bool sharded() const { return comm != nullptr || comm_fn != nullptr; }
 };
+
+// context.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
+// the event that stage_release records behind its reader has completed.
+int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot** out);
+int stage_release(sga_context* ctx, sga_context::StageSlot* slot);
 
 // Producer / consumer ordering across streams.  In stream-ordered mode (sga_context_set_stream_ordered) an index build or an attribute
 // estimation returns while its kernels are still in flight on the producing context's stream.  The object remembers that stream and an

@@ -586,6 +586,7 @@ int sga_context_destroy(sga_context* ctx) {
   if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
   if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
   if (ctx->h_accum) (void)hipHostFree(ctx->h_accum);
+  if (ctx->h_forest) (void)hipHostFree(ctx->h_forest);
   for (auto& slot : ctx->stage) {
     if (slot.host) (void)hipHostFree(slot.host);
     if (slot.done) (void)hipEventDestroy(slot.done);
@@ -800,7 +801,7 @@ int late_note_peek(unsigned long long seq, unsigned long long payload[kLateWords
 // ---- uploads ------------------------------------------------------------------------------------------------------------------
 // A slot of the context's pinned staging ring with room for `bytes` (grow-only).  A slot handed out before is reused only after the
 // event recorded behind its reader (stage_release) has completed.
-static int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot** out) {
+int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot** out) {
   sga_context::StageSlot& slot = ctx->stage[ctx->stage_next++ % sga_context::kStageSlots];
   if (slot.busy) {
     SGA_HIP(hipEventSynchronize(slot.done));
@@ -820,7 +821,7 @@ static int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot*
   return SGA_OK;
 }
 // behind the launch that reads the slot
-static int stage_release(sga_context* ctx, sga_context::StageSlot* slot) {
+int stage_release(sga_context* ctx, sga_context::StageSlot* slot) {
   if (!slot->done) SGA_HIP(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
   SGA_HIP(hipEventRecord(slot->done, ctx->stream));
   slot->busy = true;

@@ -1,0 +1,80 @@
+// Batched preprocessing (batch_preprocess.hip): the kd-trees and the covariances of B small clouds in one chain
+// of launches.  A call writes ONE table into pinned memory and copies it to the device with one command; the batched kernels
+// (index_build.hip, preprocess.hip: beside the lone kernels whose bodies they share) read what the lone kernel receives as its arguments
+// from the table entry of their tree, with scalar loads (uniform_const).
+#pragma once
+#include <vector>
+
+#include "common.hpp"
+#include "kd_search.hpp"
+#include "uniform.hpp"
+
+namespace sga {
+
+// One tree of a forest build: the arguments of kd_split_level_kernel / kd_finish_kernel / kd_tail_kernel / kd_boxes_kernel for it.
+// Level d of the build reads perm[(d + 1) & 1] (level 0: the identity) and writes perm[d & 1]; the finish kernel is level dA.
+struct ForestTree {
+  const float4* pts;   // the cloud
+  const float4* nrm;   // its attributes, or null
+  const Cov8* cov;
+  uint32_t* perm[2];
+  float2* nodes;
+  float4* opts;        // the index's arrays (kd_tail_kernel)
+  float4* onrm;
+  Cov8* ocov;
+  float4* boxes;
+  float4* groups;
+  float* blocks;
+  float4* pairs;
+  unsigned long long* spacing_acc;  // {sum, leaves counted, arrival counter, 0} of this tree's tail launch; zero between launches
+  unsigned long long* late_slot;    // the late note that carries the tree's length scale (notes.hpp), or null
+  unsigned long long late_seq;
+  unsigned long long* box_slot;     // words 1..3 receive the cloud's bounding box (pinned, device-mapped: the call's box block)
+  uint32_t n;
+  int D, dA;  // depth; first level finished in LDS (index_build.hip: build_kdtree)
+};
+
+// The hand-off of the boxes: every tree's root level writes its box, the last to arrive publishes the call's sequence number
+struct ForestBoxes {
+  unsigned* ticket;               // arrivals of the trees' root levels (device memory, zero when the call starts)
+  unsigned total;                 // trees of the forest
+  unsigned long long* seq_word;   // in the box block
+  unsigned long long seq;
+};
+
+// One member of a batched covariance / normal estimation: the arguments of knn_wave_kernel / features_from_list_kernel for it
+struct ForestFeat {
+  KdView g;
+  int* nbr;
+  float4* idx_nrm;
+  Cov8* idx_cov;
+  float4* cloud_nrm;
+  Cov8* cloud_cov;
+  double ox, oy, oz;
+};
+
+// the member that owns workgroup b: prefix[k] <= b < prefix[k + 1] (wave-uniform binary search, as batch_search_linearize_kernel's)
+__device__ __forceinline__ int forest_member_of(const uint32_t* prefix, int count, uint32_t b) {
+  int lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid] <= b)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// index_build.hip: the build of all `trees` (every field but spacing_acc filled in by the caller) enqueued on the context's stream;
+// `table` (device memory: the trees, the launches' member lists, the accumulators) must live until the kernels have run
+int forest_build(sga_context* ctx, std::vector<ForestTree>& trees, unsigned long long* box_seq_word, unsigned long long box_seq, DevBuf<unsigned long long>& table);
+// preprocess.hip: knn_wave_kernel + features_from_list_kernel for all members
+int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, int k, int flags, DevBuf<unsigned long long>& table);
+void forest_tree_shape(size_t n, int* D, int* dA);  // index_build.hip: depth and first LDS level of a cloud of 1 <= n <= kForestMaxPoints points
+int features_check_k(int k);     // preprocess.hip: SGA_OK, or the lone estimation's error for a num_neighbors outside its range
+long long knn_wave_max_points();  // preprocess.hip: g_knn_wave_max
+void forest_count_launch();       // batch_preprocess.hip: every kernel the two entry points enqueue (sga_debug_forest_launches)
+constexpr uint32_t kForestMaxPoints = 1024 * 32;  // = kSplitMaxPoints (index_build.hip): the clouds the split kernel holds whole
+
+}  // namespace sga

@@ -6,10 +6,12 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "forest.hpp"
 #include "notes.hpp"
 #include "sort_util.hpp"
 
 #include <memory>
+#include <vector>
 #include <rocprim/rocprim.hpp>
 #include "kd_search.hpp"
 #include "voxel_hash.hpp"
@@ -117,15 +119,15 @@ constexpr int kFinishMaxSub = 256;  // sub-segments at the last level; 32 would 
 __device__ __forceinline__ uint32_t ordered_u32(float c) { return static_cast<uint32_t>(ordered_from_float(c)) ^ 0x80000000u; }
 
 // CAP: points per workgroup; THREADS: workgroup size (built as <kSplitFinish, kSplitFinish>: one thread per point)
+// (the body of kd_finish_kernel and of its batched form, kd_forest_finish_kernel; seg: the segment of depth dA this workgroup finishes)
 template <int CAP, int THREADS>
-__global__ __launch_bounds__(THREADS) void kd_finish_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in, uint32_t* __restrict__ perm_out, uint32_t n, int dA, int D, float2* __restrict__ nodes) {
+__device__ __forceinline__ void kd_finish_body(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in, uint32_t* __restrict__ perm_out, uint32_t n, int dA, int D, float2* __restrict__ nodes, const uint32_t seg) {
   __shared__ float cx[CAP], cy[CAP], cz[CAP];
   __shared__ uint32_t gidx[CAP];
   __shared__ unsigned long long key[CAP];
   __shared__ unsigned short ord[CAP], ord2[CAP];
   __shared__ int box[kFinishMaxSub][6];
   __shared__ int axis_of[kFinishMaxSub];
-  const uint32_t seg = blockIdx.x;
   const uint32_t B0 = kd_bound(n, dA, seg), B1 = kd_bound(n, dA, seg + 1);
   const uint32_t m = B1 - B0;
   const int tid = threadIdx.x;
@@ -218,6 +220,10 @@ __global__ __launch_bounds__(THREADS) void kd_finish_kernel(const float4* __rest
   }
   for (uint32_t pos = tid; pos < m; pos += THREADS) perm_out[B0 + pos] = gidx[ord[pos]];
 }
+template <int CAP, int THREADS>
+__global__ __launch_bounds__(THREADS) void kd_finish_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in, uint32_t* __restrict__ perm_out, uint32_t n, int dA, int D, float2* __restrict__ nodes) {
+  kd_finish_body<CAP, THREADS>(pts, perm_in, perm_out, n, dA, D, nodes, blockIdx.x);
+}
 
 // ---- top levels of SMALL clouds: one launch per level, one workgroup per segment --------------------------------------------------
 // A 15k-point scan (the odometry workload) is launch-bound: a sort-based level (a box kernel, a key kernel, a rocPRIM sort of 3 - 6
@@ -248,15 +254,17 @@ __device__ __forceinline__ uint32_t split_scan_exclusive(uint32_t v, uint32_t* _
   return base + inc - v;
 }
 
-template <int THREADS, int kSplitKeys>  // kSplitKeys: keys per thread; the launcher picks the smallest THREADS x kSplitKeys that holds a segment
-__global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in /* null: the identity (level 0) */, uint32_t* __restrict__ perm_out, uint32_t n, int d, float2* __restrict__ nodes,
-                                                                 unsigned long long* __restrict__ note_slot /* level 0: the cloud's bounding box goes to the host as a note (notes.hpp), or null */, unsigned long long note_seq) {
+// (the body of kd_split_level_kernel and of its batched form, kd_forest_split_kernel; seg: the segment of depth d this workgroup splits.
+// FOREST: the box words are written but not published — the batched kernel hands all boxes of a call over at once)
+template <int THREADS, int kSplitKeys, bool FOREST>  // kSplitKeys: keys per thread; the launcher picks the smallest THREADS x kSplitKeys that holds a segment
+__device__ __forceinline__ void kd_split_level_body(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in /* null: the identity (level 0) */, uint32_t* __restrict__ perm_out, uint32_t n, int d, float2* __restrict__ nodes,
+                                                    unsigned long long* __restrict__ note_slot /* level 0: the cloud's bounding box goes to the host as a note (notes.hpp), or null */, unsigned long long note_seq, const uint32_t seg) {
   constexpr int kWaves = THREADS / 64, kBinsPerThread = kSplitBins / THREADS;
   __shared__ uint32_t hist[3][kSplitBins];
   __shared__ uint32_t sh_wave[4][kWaves];
   __shared__ float sh_lo[kWaves][3], sh_hi[kWaves][3];
   __shared__ uint32_t sh_sel[3][3];  // per round: bucket, keys below it, keys in it
-  const uint32_t seg = blockIdx.x, tid = threadIdx.x;
+  const uint32_t tid = threadIdx.x;
   const uint32_t first = kd_bound(n, d, seg), end = kd_bound(n, d, seg + 1), mid = kd_bound(n, d + 1, 2 * seg + 1);
   const uint32_t len = end - first, m = mid - first;  // the left half gets m elements
   if (len == 0) {  // cannot happen for the clouds this path is used for (segments of more than kSplitFinish points); workgroup-uniform
@@ -313,7 +321,7 @@ __global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* _
     ext[a] = h - l;
     if (note_slot != nullptr && tid == 0) note_slot[1 + a] = static_cast<unsigned long long>(static_cast<unsigned>(box_enc(l))) | (static_cast<unsigned long long>(static_cast<unsigned>(box_enc(h))) << 32);
   }
-  if (note_slot != nullptr && tid == 0) note_publish(note_slot, note_seq);  // (one workgroup at level 0)
+  if (!FOREST && note_slot != nullptr && tid == 0) note_publish(note_slot, note_seq);  // (one workgroup at level 0)
   const int axis = ext[0] >= ext[1] ? (ext[0] >= ext[2] ? 0 : 2) : (ext[1] >= ext[2] ? 1 : 2);  // same rule as kd_longest_axis
   uint32_t key[kSplitKeys];  // the coordinate along the split axis (read again, one word: the lines are in the cache), order-preserving encoding
   const float* __restrict__ coord = reinterpret_cast<const float*>(pts) + axis;
@@ -384,6 +392,11 @@ __global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* _
     }
   }
   if (tid == 0) nodes[(1u << d) + seg] = make_float2(float_from_ordered(static_cast<int>(median ^ 0x80000000u)), __int_as_float(axis));
+}
+template <int THREADS, int kSplitKeys>
+__global__ __launch_bounds__(THREADS) void kd_split_level_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm_in, uint32_t* __restrict__ perm_out, uint32_t n, int d, float2* __restrict__ nodes,
+                                                                 unsigned long long* __restrict__ note_slot, unsigned long long note_seq) {
+  kd_split_level_body<THREADS, kSplitKeys, false>(pts, perm_in, perm_out, n, d, nodes, note_slot, note_seq, blockIdx.x);
 }
 
 // ---- top levels of LARGE clouds: the same select + partition, a segment spread over many workgroups (round 6) -------------------------
@@ -650,9 +663,10 @@ __global__ __launch_bounds__(kTopThreads) void kd_top_scatter_kernel(const float
 // Tight bounding boxes of all nodes, bottom-up (kd_search.hpp: a pending far side is opened only if its box can hold a closer point).
 // One launch covers up to 8 levels: every workgroup takes 256 adjacent nodes of depth `base` — their boxes come from the points
 // (base = D, leaves) or from the previous launch — and merges them pairwise in LDS up to depth base - 8.
-__global__ __launch_bounds__(256) void kd_boxes_kernel(const float4* __restrict__ pts, uint32_t n, int D, int base, float4* __restrict__ boxes) {
+// (the body of kd_boxes_kernel and of kd_forest_boxes_kernel; block: the workgroup's number among those of its tree)
+__device__ __forceinline__ void kd_boxes_body(const float4* __restrict__ pts, uint32_t n, int D, int base, float4* __restrict__ boxes, const uint32_t block) {
   __shared__ float slo[3][256], shi[3][256];
-  const uint32_t t = threadIdx.x, k = blockIdx.x * 256u + t;
+  const uint32_t t = threadIdx.x, k = block * 256u + t;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   if (k < (1u << base)) {
     const uint32_t node = (1u << base) + k;
@@ -698,7 +712,7 @@ __global__ __launch_bounds__(256) void kd_boxes_kernel(const float4* __restrict_
         slo[a][t] = lo[a];
         shi[a][t] = hi[a];
       }
-      const uint32_t kk = (blockIdx.x * 256u >> l) + t;
+      const uint32_t kk = (block * 256u >> l) + t;
       if (kk < (1u << (base - l))) {
         const uint32_t node = (1u << (base - l)) + kk;
         boxes[2 * node] = make_float4(lo[0], lo[1], lo[2], 0.f);
@@ -708,6 +722,7 @@ __global__ __launch_bounds__(256) void kd_boxes_kernel(const float4* __restrict_
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(256) void kd_boxes_kernel(const float4* __restrict__ pts, uint32_t n, int D, int base, float4* __restrict__ boxes) { kd_boxes_body(pts, n, D, base, boxes, blockIdx.x); }
 
 // The tail of a build in ONE launch (round 6: a 11.5k-point scan paid six launches for it — gather, leaf boxes, group headers, leaf blocks,
 // pair records, upper boxes).  Thread g of the grid owns leaf g and heap node g:
@@ -722,14 +737,17 @@ __global__ __launch_bounds__(256) void kd_boxes_kernel(const float4* __restrict_
 //   * node g's PAIR RECORD for the 1-NN walk (kd_search.hpp): a node of even depth + its two children in one 16-byte record, stored at
 //     the node's heap number.
 // Trees deeper than 8 levels finish their upper boxes with kd_boxes_kernel(base = D - 8) as before.
-__global__ __launch_bounds__(256) void kd_tail_kernel(const uint32_t* __restrict__ order, uint32_t n, int D, const float4* __restrict__ pts, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, const float2* __restrict__ nodes,
-                                                      float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov, float4* __restrict__ boxes, float4* __restrict__ groups, float* __restrict__ blocks,
-                                                      float4* __restrict__ pairs, uint32_t npairs, unsigned long long* __restrict__ d_spacing, unsigned long long* __restrict__ late_slot, unsigned long long late_seq) {
+// (the body of kd_tail_kernel and of kd_forest_tail_kernel; block / nblocks: the workgroup's number among the nblocks of its tree, whose
+// arrivals d_spacing[2] counts)
+__device__ __forceinline__ void kd_tail_body(const uint32_t* __restrict__ order, uint32_t n, int D, const float4* __restrict__ pts, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, const float2* __restrict__ nodes,
+                                             float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov, float4* __restrict__ boxes, float4* __restrict__ groups, float* __restrict__ blocks,
+                                             float4* __restrict__ pairs, uint32_t npairs, unsigned long long* __restrict__ d_spacing, unsigned long long* __restrict__ late_slot, unsigned long long late_seq, const uint32_t block,
+                                             const uint32_t nblocks) {
   __shared__ float slo[3][256], shi[3][256];
   __shared__ long long sh_sum[4];
   __shared__ unsigned sh_cnt[4];
   __shared__ bool sh_last;
-  const uint32_t t = threadIdx.x, k = blockIdx.x * 256u + t;
+  const uint32_t t = threadIdx.x, k = block * 256u + t;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   if (k < (1u << D)) {
     const uint32_t first = kd_bound(n, D, k), end = kd_bound(n, D, k + 1);
@@ -787,7 +805,7 @@ __global__ __launch_bounds__(256) void kd_tail_kernel(const uint32_t* __restrict
       atomicAdd(&d_spacing[0], static_cast<unsigned long long>(bs));
       atomicAdd(&d_spacing[1], static_cast<unsigned long long>(bc));
       __threadfence();
-      sh_last = __hip_atomic_fetch_add(&d_spacing[2], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+      sh_last = __hip_atomic_fetch_add(&d_spacing[2], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1;
       if (sh_last) {
         late_slot[0] = __hip_atomic_load(&d_spacing[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         late_slot[1] = __hip_atomic_load(&d_spacing[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -845,7 +863,7 @@ __global__ __launch_bounds__(256) void kd_tail_kernel(const uint32_t* __restrict
         slo[a][t] = lo[a];
         shi[a][t] = hi[a];
       }
-      const uint32_t kk = (blockIdx.x * 256u >> l) + t;
+      const uint32_t kk = (block * 256u >> l) + t;
       if (kk < (1u << (D - l))) {
         const uint32_t node = (1u << (D - l)) + kk;
         boxes[2 * node] = make_float4(lo[0], lo[1], lo[2], 0.f);
@@ -854,6 +872,11 @@ __global__ __launch_bounds__(256) void kd_tail_kernel(const uint32_t* __restrict
     }
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void kd_tail_kernel(const uint32_t* __restrict__ order, uint32_t n, int D, const float4* __restrict__ pts, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, const float2* __restrict__ nodes,
+                                                      float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov, float4* __restrict__ boxes, float4* __restrict__ groups, float* __restrict__ blocks,
+                                                      float4* __restrict__ pairs, uint32_t npairs, unsigned long long* __restrict__ d_spacing, unsigned long long* __restrict__ late_slot, unsigned long long late_seq) {
+  kd_tail_body(order, n, D, pts, nrm, cov, nodes, opts, onrm, ocov, boxes, groups, blocks, pairs, npairs, d_spacing, late_slot, late_seq, blockIdx.x, gridDim.x);
 }
 
 __global__ void compose_perm_kernel(const uint32_t* __restrict__ inner, const uint32_t* __restrict__ outer, uint32_t* __restrict__ out, size_t n) {
@@ -872,6 +895,15 @@ __global__ void gather_attr_kernel(const float4* __restrict__ sorted_pts, size_t
   const uint32_t s = __float_as_uint(sorted_pts[i].w);
   if (nrm) onrm[i] = nrm[s];
   if (cov) ocov[i] = cov[s];
+}
+
+// the THREADS x kSplitKeys instantiation of kd_split_level_kernel for a level whose largest segment holds seg_max points: 0 .. 6 =
+// 256 x 2, 256 x 4, 256 x 8, 1024 x 4, 1024 x 8, 1024 x 16, 1024 x 32 (the smallest that holds the segment)
+static int split_class(size_t seg_max) {
+  const size_t reach[6] = {256 * 2, 256 * 4, 256 * 8, 1024 * 4, 1024 * 8, 1024 * 16};
+  int c = 0;
+  while (c < 6 && seg_max > reach[c]) c++;
+  return c;
 }
 
 // box_seq: the note (notes.hpp) that carries the cloud's bounding box to the host — from the first split level when there is one (it takes
@@ -966,13 +998,15 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
     }
     const uint32_t* level_in = (d == 0 || (top_levels && d == dS)) ? nullptr : cur;
 #define SGA_SPLIT(THREADS, KEYS) hipLaunchKernelGGL((kd_split_level_kernel<THREADS, KEYS>), dim3(1u << d), dim3(THREADS), 0, ctx->stream, base_pts, level_in, nxt, static_cast<uint32_t>(n), d, idx->kd_nodes.p, note_slot, *box_seq)
-    if (seg_max <= 256 * 2) SGA_SPLIT(256, 2);
-    else if (seg_max <= 256 * 4) SGA_SPLIT(256, 4);
-    else if (seg_max <= 256 * 8) SGA_SPLIT(256, 8);
-    else if (seg_max <= 1024 * 4) SGA_SPLIT(1024, 4);
-    else if (seg_max <= 1024 * 8) SGA_SPLIT(1024, 8);
-    else if (seg_max <= 1024 * 16) SGA_SPLIT(1024, 16);
-    else SGA_SPLIT(1024, 32);
+    switch (split_class(seg_max)) {
+      case 0: SGA_SPLIT(256, 2); break;
+      case 1: SGA_SPLIT(256, 4); break;
+      case 2: SGA_SPLIT(256, 8); break;
+      case 3: SGA_SPLIT(1024, 4); break;
+      case 4: SGA_SPLIT(1024, 8); break;
+      case 5: SGA_SPLIT(1024, 16); break;
+      default: SGA_SPLIT(1024, 32); break;
+    }
 #undef SGA_SPLIT
     std::swap(cur, nxt);
   }
@@ -1002,6 +1036,167 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
   for (int base = D - 8; base > 0; base -= 8) hipLaunchKernelGGL(kd_boxes_kernel, dim3(((1u << base) + 255) / 256), block, 0, ctx->stream, idx->kd_pts.p, static_cast<uint32_t>(n), D, base, idx->kd_boxes.p);
   SGA_HIP(hipGetLastError());
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  return SGA_OK;
+}
+
+// ---- a forest: the trees of B small clouds (n <= kSplitMaxPoints: no kd_top_* levels) in one chain of launches ---------------------------
+// Every launch is a grid (workgroups of ONE tree at this step, trees of this step): blockIdx.y picks the tree from the launch's member
+// list, and the tree's table entry (forest.hpp: ForestTree) holds what the lone kernel receives as arguments.  The steps are the lone
+// build's, and a tree takes part in exactly the launches the lone launcher would give it:
+//   * a split level d runs one grid PER INSTANTIATION, over the trees whose level d the lone launcher gives that instantiation
+//     (split_class of the tree's own largest segment): the partition order inside a half is thread-major, so it depends on THREADS —
+//     sharing an instantiation between trees of different size would change the permutation (not the tree's validity);
+//   * the finish kernel runs one grid per dA (2^dA workgroups per tree), the tail and the upper boxes one grid per depth D.
+// Scans of similar size share every grid: 16 trees of equal depth cost the launches of one.  Nothing in a workgroup depends on the other
+// trees of its grid, so a tree comes out bit-identical to the lone build's (tests/test_batch_preprocess_gpu.py).
+static_assert(sizeof(ForestTree) % 8 == 0, "table entries are copied as 8-byte words");
+static_assert(kForestMaxPoints == kSplitMaxPoints, "the forest takes the clouds the split kernel holds whole");
+
+// by ONE thread of a tree's root level, after it wrote the tree's box words: the last tree to arrive publishes the call's sequence
+// number (agent-scope ticket, system-scope release: batch_reduce_rows_kernel's hand-off, linearize.hip)
+__device__ __forceinline__ void forest_box_arrive(const ForestBoxes& h) {
+  __threadfence_system();
+  if (__hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == h.total - 1u) {
+    __threadfence_system();
+    __hip_atomic_store(h.seq_word, h.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+template <int THREADS, int KEYS>
+__global__ __launch_bounds__(THREADS) void kd_forest_split_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members, int d, const ForestBoxes hand) {
+  const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.y]);
+  kd_split_level_body<THREADS, KEYS, true>(t.pts, d == 0 ? nullptr : t.perm[(d + 1) & 1], t.perm[d & 1], t.n, d, t.nodes, d == 0 ? t.box_slot : nullptr, 0ull, blockIdx.x);
+  if (d == 0 && threadIdx.x == 0) forest_box_arrive(hand);  // (thread 0 wrote the box words)
+}
+
+// Trees of at most kSplitFinish points have no split level (dA = 0): what the lone build does for them with bbox_note_kernel and
+// iota_kernel — the box (a non-finite coordinate counts as +inf) and the identity permutation the finish / tail kernel reads.  One
+// workgroup per tree, one point per thread.
+__global__ __launch_bounds__(kSplitFinish) void kd_forest_root_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members, const ForestBoxes hand) {
+  __shared__ float sh_lo[kSplitFinish / 64][3], sh_hi[kSplitFinish / 64][3];
+  const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.x]);
+  const uint32_t tid = threadIdx.x;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  if (tid < t.n) {
+    float4 p = t.pts[tid];
+    t.perm[1][tid] = tid;
+    p.x = fabsf(p.x) <= 3.4028234e38f ? p.x : INFINITY;
+    p.y = fabsf(p.y) <= 3.4028234e38f ? p.y : INFINITY;
+    p.z = fabsf(p.z) <= 3.4028234e38f ? p.z : INFINITY;
+    lo[0] = hi[0] = p.x, lo[1] = hi[1] = p.y, lo[2] = hi[2] = p.z;
+  }
+  for (int a = 0; a < 3; a++)
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off));
+      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off));
+    }
+  if ((tid & 63u) == 0u)
+    for (int a = 0; a < 3; a++) sh_lo[tid >> 6][a] = lo[a], sh_hi[tid >> 6][a] = hi[a];
+  __syncthreads();
+  if (tid == 0) {
+    for (int a = 0; a < 3; a++) {
+      float l = INFINITY, h = -INFINITY;
+      for (int w = 0; w < kSplitFinish / 64; w++) l = fminf(l, sh_lo[w][a]), h = fmaxf(h, sh_hi[w][a]);
+      t.box_slot[1 + a] = static_cast<unsigned long long>(static_cast<unsigned>(box_enc(l))) | (static_cast<unsigned long long>(static_cast<unsigned>(box_enc(h))) << 32);
+    }
+    forest_box_arrive(hand);
+  }
+}
+
+__global__ __launch_bounds__(kSplitFinish) void kd_forest_finish_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members) {
+  const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.y]);
+  kd_finish_body<kSplitFinish, kSplitFinish>(t.pts, t.perm[(t.dA + 1) & 1], t.perm[t.dA & 1], t.n, t.dA, t.D, t.nodes, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void kd_forest_tail_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members) {
+  const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.y]);
+  const uint32_t* order = t.dA < t.D ? t.perm[t.dA & 1] : t.perm[(t.dA + 1) & 1];  // what the last level (or the root kernel) wrote
+  kd_tail_body(order, t.n, t.D, t.pts, t.nrm, t.cov, t.nodes, t.opts, t.onrm, t.ocov, t.boxes, t.groups, t.blocks, t.pairs, kd_pair_count(t.D), t.spacing_acc, t.late_slot, t.late_seq, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void kd_forest_boxes_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members, int base) {
+  const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.y]);
+  kd_boxes_body(t.opts, t.n, t.D, base, t.boxes, blockIdx.x);
+}
+
+// depth and first level finished in LDS of a cloud of n points, 1 <= n <= kSplitMaxPoints: build_kdtree's D and dA (dS = 0)
+void forest_tree_shape(size_t n, int* D_out, int* dA_out) {
+  int D = 0;
+  while (((n + (1ull << D) - 1) >> D) > static_cast<size_t>(kKdLeafMax)) D++;
+  int dA = 0;
+  while (dA < D && ((n + (1ull << dA) - 1) >> dA) > static_cast<size_t>(kSplitFinish)) dA++;
+  *D_out = D;
+  *dA_out = dA;
+}
+
+int forest_build(sga_context* ctx, std::vector<ForestTree>& trees, unsigned long long* box_seq_word, unsigned long long box_seq, DevBuf<unsigned long long>& table) {
+  const size_t count = trees.size();
+  if (count == 0) return SGA_OK;
+  // ---- the launches and their member lists
+  struct Step {
+    int kind, arg, cls;  // kind 0 root, 1 split (arg = d, cls = instantiation), 2 finish (arg = dA), 3 tail (arg = D), 4 upper boxes (arg = D)
+    uint32_t first, num;
+  };
+  std::vector<Step> steps;
+  std::vector<uint32_t> members;
+  auto add_step = [&](int kind, int arg, int cls, auto&& takes) {
+    const uint32_t first = static_cast<uint32_t>(members.size());
+    for (size_t k = 0; k < count; k++)
+      if (takes(trees[k])) members.push_back(static_cast<uint32_t>(k));
+    if (members.size() > first) steps.push_back(Step{kind, arg, cls, first, static_cast<uint32_t>(members.size()) - first});
+  };
+  int max_dA = 0, max_D = 0;
+  for (const ForestTree& t : trees) max_dA = std::max(max_dA, t.dA), max_D = std::max(max_D, t.D);
+  add_step(0, 0, 0, [](const ForestTree& t) { return t.dA == 0; });
+  for (int d = 0; d < max_dA; d++)
+    for (int c = 0; c < 7; c++) add_step(1, d, c, [&](const ForestTree& t) { return d < t.dA && split_class((t.n + (1ull << d) - 1) >> d) == c; });
+  for (int a = 0; a <= max_dA; a++) add_step(2, a, 0, [&](const ForestTree& t) { return t.dA == a && t.dA < t.D; });
+  for (int D = 0; D <= max_D; D++) add_step(3, D, 0, [&](const ForestTree& t) { return t.D == D; });
+  for (int D = 9; D <= max_D; D++) add_step(4, D, 0, [&](const ForestTree& t) { return t.D == D; });
+  // ---- one table: [trees][accumulators of the tails: 4 words per tree][ticket][member lists], written in pinned memory, one copy command
+  const size_t tree_words = count * (sizeof(ForestTree) / 8), acc_words = 4 * count, list_words = (members.size() + 1) / 2;
+  const size_t words = tree_words + acc_words + 1 + list_words;
+  SGA_TRY(table.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  for (size_t k = 0; k < count; k++) trees[k].spacing_acc = table.p + tree_words + 4 * k;
+  std::memcpy(host, trees.data(), tree_words * 8);
+  std::memset(host + tree_words, 0, (acc_words + 1 + list_words) * 8);
+  std::memcpy(host + tree_words + acc_words + 1, members.data(), members.size() * sizeof(uint32_t));
+  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  const ForestTree* d_trees = reinterpret_cast<const ForestTree*>(table.p);
+  const uint32_t* d_members = reinterpret_cast<const uint32_t*>(table.p + tree_words + acc_words + 1);
+  const ForestBoxes hand{reinterpret_cast<unsigned*>(table.p + tree_words + acc_words), static_cast<unsigned>(count), box_seq_word, box_seq};
+  constexpr uint32_t kMaxGridY = 65535;  // the trees of a step are blockIdx.y: longer member lists go out in pieces
+  for (const Step& whole : steps)
+    for (uint32_t off = 0; off < whole.num; off += kMaxGridY) {
+    const Step s{whole.kind, whole.arg, whole.cls, whole.first + off, std::min(kMaxGridY, whole.num - off)};
+    const uint32_t* list = d_members + s.first;
+    forest_count_launch();
+    switch (s.kind) {
+      case 0: hipLaunchKernelGGL(kd_forest_root_kernel, dim3(s.num), dim3(kSplitFinish), 0, ctx->stream, d_trees, list, hand); break;
+      case 1: {
+#define SGA_FOREST_SPLIT(THREADS, KEYS) hipLaunchKernelGGL((kd_forest_split_kernel<THREADS, KEYS>), dim3(1u << s.arg, s.num), dim3(THREADS), 0, ctx->stream, d_trees, list, s.arg, hand)
+        switch (s.cls) {
+          case 0: SGA_FOREST_SPLIT(256, 2); break;
+          case 1: SGA_FOREST_SPLIT(256, 4); break;
+          case 2: SGA_FOREST_SPLIT(256, 8); break;
+          case 3: SGA_FOREST_SPLIT(1024, 4); break;
+          case 4: SGA_FOREST_SPLIT(1024, 8); break;
+          case 5: SGA_FOREST_SPLIT(1024, 16); break;
+          default: SGA_FOREST_SPLIT(1024, 32); break;
+        }
+#undef SGA_FOREST_SPLIT
+        break;
+      }
+      case 2: hipLaunchKernelGGL(kd_forest_finish_kernel, dim3(1u << s.arg, s.num), dim3(kSplitFinish), 0, ctx->stream, d_trees, list); break;
+      case 3: hipLaunchKernelGGL(kd_forest_tail_kernel, dim3(((1u << s.arg) + 255) / 256, s.num), dim3(256), 0, ctx->stream, d_trees, list); break;
+      default: hipLaunchKernelGGL(kd_forest_boxes_kernel, dim3(1, s.num), dim3(256), 0, ctx->stream, d_trees, list, s.arg - 8); break;  // (D <= 12: one launch, 2^(D - 8) <= 16 nodes)
+    }
+    SGA_HIP(hipGetLastError());
+  }
   return SGA_OK;
 }
 
@@ -1306,6 +1501,13 @@ int sga_index_clone(sga_context* ctx, const sga_index* src, sga_index** out) {
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
   SGA_TRY(mark_ready(ctx, idx->ready));
   *out = idx.release();
+  return SGA_OK;
+}
+
+// diagnostics: the bounding box the build recorded (device frame)
+int sga_debug_index_bbox(const sga_index* index, float lo[3], float hi[3]) {
+  if (!index || !lo || !hi) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 3; k++) lo[k] = index->bbox_lo[k], hi[k] = index->bbox_hi[k];
   return SGA_OK;
 }
 

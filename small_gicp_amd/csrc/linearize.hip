@@ -25,6 +25,7 @@
 #include "batch.hpp"
 #include "common.hpp"
 #include "device_math.hpp"
+#include "uniform.hpp"
 #include "cell_grid.hpp"
 #include "kd_search.hpp"
 #include "projective.hpp"
@@ -1307,15 +1308,7 @@ struct BatchPair {
   int pad;
 };
 
-// A wave-uniform pointer into memory that nothing writes while the kernel runs, as the constant address space: the loads through it are
-// scalar loads, issued where their values are used (see kernarg_lin_params)
-template <typename T>
-__device__ __forceinline__ const T* uniform_const(const T* ptr) {
-  using C = const __attribute__((address_space(4))) T;
-  C* a = (C*)ptr;
-  asm volatile("" : "+s"(a));
-  return (const T*)a;
-}
+// (uniform_const: uniform.hpp — a wave-uniform pointer into memory that nothing writes while the kernel runs, read with scalar loads)
 
 // search_linearize_kernel (cold) for the tiles of all active pairs in one grid.  Workgroup (= wave) b belongs to the pair k with
 // prefix[k] <= b < prefix[k + 1]; every pair's share of the grid is padded to a multiple of 8 so that — workgroup b runs on XCD b % 8 —

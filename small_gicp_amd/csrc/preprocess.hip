@@ -8,6 +8,7 @@
 #include <memory>
 #include <rocprim/rocprim.hpp>
 
+#include "forest.hpp"
 #include "kd_search.hpp"
 #include "knn_wave.hpp"
 #include "notes.hpp"
@@ -306,6 +307,7 @@ __device__ __forceinline__ Eig3 eigen_sym3(const double a[3][3] /* lower triangl
 // ---- normals / covariances -----------------------------------------------------------------------------------------------------
 constexpr int kFeatBlock = 64;
 constexpr int kFeatWindow = 128;
+constexpr int kFeatMaxK = ((64 * 1024 - kFeatWindow * 16) / 64 - kKdMaxDepth * 4) / 8 / 4 * 4;  // the largest num_neighbors (sga_estimate_normals_covariances)
 
 // mean / covariance of the neighbourhood -> normal, regularised covariance (normal_estimation.hpp:65-92, :13-63), written to the index's
 // kd-ordered arrays and, through the original index in p.w, to the caller's cloud.  id_at(j): kd position of the j-th neighbour, < 0 = no more.
@@ -441,22 +443,42 @@ __global__ __launch_bounds__(kFeatBlock) __attribute__((amdgpu_waves_per_eu(SGA_
 }
 
 // ---- small clouds: one wave per query (knn_wave.hpp), then one lane per point for the eigen-decompositions ------------------------
-__global__ __launch_bounds__(64) void knn_wave_kernel(const KdView g, uint32_t n, int k, int* __restrict__ nbr /* n x k kd positions, nearest first, -1 = none */) {
+// (the bodies of knn_wave_kernel / features_from_list_kernel and of their batched forms; i: the query / the point among its cloud's own)
+__device__ __forceinline__ void knn_wave_body(const KdView& g, uint32_t n, int k, int* __restrict__ nbr /* n x k kd positions, nearest first, -1 = none */, const uint32_t i) {
   __shared__ uint32_t stack[2 * kKdMaxDepth + 2];
   const int lane = threadIdx.x;
-  const uint32_t i = blockIdx.x;
   float bd;
   int bid;
   knn_wave_query(g, i, k, lane, stack, bd, bid);
   if (lane < k) nbr[static_cast<size_t>(i) * k + lane] = bd < INFINITY ? bid : -1;
 }
+__global__ __launch_bounds__(64) void knn_wave_kernel(const KdView g, uint32_t n, int k, int* __restrict__ nbr) { knn_wave_body(g, n, k, nbr, blockIdx.x); }
 
-__global__ __launch_bounds__(64) void features_from_list_kernel(const KdView g, size_t n, int k, const int* __restrict__ nbr, int flags, float4* __restrict__ idx_nrm, Cov8* __restrict__ idx_cov, float4* __restrict__ cloud_nrm,
-                                                                Cov8* __restrict__ cloud_cov, double ox, double oy, double oz) {
-  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+__device__ __forceinline__ void features_from_list_body(const KdView& g, size_t n, int k, const int* __restrict__ nbr, int flags, float4* __restrict__ idx_nrm, Cov8* __restrict__ idx_cov, float4* __restrict__ cloud_nrm,
+                                                        Cov8* __restrict__ cloud_cov, double ox, double oy, double oz, const size_t i) {
   if (i >= n) return;
   const int* __restrict__ mine = nbr + i * k;
   features_from_neighbours(g, i, g.pts[i], [&](int j) { return mine[j]; }, k, flags, idx_nrm, idx_cov, cloud_nrm, cloud_cov, ox, oy, oz);
+}
+__global__ __launch_bounds__(64) void features_from_list_kernel(const KdView g, size_t n, int k, const int* __restrict__ nbr, int flags, float4* __restrict__ idx_nrm, Cov8* __restrict__ idx_cov, float4* __restrict__ cloud_nrm,
+                                                                Cov8* __restrict__ cloud_cov, double ox, double oy, double oz) {
+  features_from_list_body(g, n, k, nbr, flags, idx_nrm, idx_cov, cloud_nrm, cloud_cov, ox, oy, oz, blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x);
+}
+
+// The batched forms (forest.hpp): workgroup b belongs to the member k with prefix[k] <= b < prefix[k + 1] (one workgroup per query /
+// per 64 points of every member, members in the call's order), whose table entry holds the lone kernel's arguments.
+__global__ __launch_bounds__(64) void knn_wave_forest_kernel(const ForestFeat* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, int k) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const ForestFeat& f = *uniform_const(members + m);
+  knn_wave_body(f.g, f.g.n, k, f.nbr, blockIdx.x - prefix[m]);
+}
+
+__global__ __launch_bounds__(64) void features_from_list_forest_kernel(const ForestFeat* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, int k, int flags) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const ForestFeat& f = *uniform_const(members + m);
+  features_from_list_body(f.g, f.g.n, k, f.nbr, flags, f.idx_nrm, f.idx_cov, f.cloud_nrm, f.cloud_cov, f.ox, f.oy, f.oz, (blockIdx.x - prefix[m]) * static_cast<size_t>(64) + threadIdx.x);
 }
 
 __global__ void refresh_attributes_kernel(const float4* __restrict__ idx_pts, size_t n, const float4* __restrict__ cloud_nrm, const Cov8* __restrict__ cloud_cov, float4* __restrict__ idx_nrm, Cov8* __restrict__ idx_cov) {
@@ -481,6 +503,46 @@ extern "C" {
 void sga_set_knn_wave_max(long long max_points) { g_knn_wave_max = max_points; }
 
 }  // extern "C"
+
+namespace sga {
+long long knn_wave_max_points() { return g_knn_wave_max; }
+// LDS per workgroup: the k-best list (kpad * 8 bytes per lane, kpad = k rounded up to 4) + the traversal stack (kKdMaxDepth words per
+// lane) + the static candidate window (kFeatWindow float4) must fit the 64 KB a workgroup may allocate: kFeatMaxK = 112
+int features_check_k(int k) {
+  if (k < 1 || k > kFeatMaxK) return fail(SGA_ERR_INVALID, "num_neighbors must be in [1,%d] (k-best list + traversal stack + candidate window must fit 64 KB of LDS per workgroup)", kFeatMaxK);
+  return SGA_OK;
+}
+
+// knn_wave_kernel + features_from_list_kernel for all members (every one of 1 <= n <= g_knn_wave_max points, k <= 64) in two launches;
+// `table`: [members][prefix of the search grid: count + 1][prefix of the feature grid: count + 1], written in pinned memory, one copy command
+static_assert(sizeof(ForestFeat) % 8 == 0, "table entries are copied as 8-byte words");
+int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, int k, int flags, DevBuf<unsigned long long>& table) {
+  const size_t count = members.size();
+  if (count == 0) return SGA_OK;
+  std::vector<uint32_t> prefix(2 * (count + 1), 0u);
+  for (size_t m = 0; m < count; m++) {
+    prefix[m + 1] = prefix[m] + members[m].g.n;
+    prefix[count + 1 + m + 1] = prefix[count + 1 + m] + (members[m].g.n + kFeatBlock - 1) / kFeatBlock;
+  }
+  const size_t member_words = count * (sizeof(ForestFeat) / 8), words = member_words + (count + 1);
+  SGA_TRY(table.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  const ForestFeat* d_members = reinterpret_cast<const ForestFeat*>(table.p);
+  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(table.p + member_words);
+  forest_count_launch();
+  hipLaunchKernelGGL(knn_wave_forest_kernel, dim3(prefix[count]), dim3(64), 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), k);
+  forest_count_launch();
+  hipLaunchKernelGGL(features_from_list_forest_kernel, dim3(prefix[2 * count + 1]), dim3(kFeatBlock), 0, ctx->stream, d_members, d_prefix + count + 1, static_cast<int>(count), k, flags);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+}  // namespace sga
 
 namespace {
 // bits needed for the values 0 .. range - 1
@@ -630,10 +692,7 @@ int sga_index_refresh_attributes(sga_context* ctx, sga_index* index, const sga_c
 
 int sga_estimate_normals_covariances(sga_context* ctx, sga_cloud* cloud, const sga_index* index_in, int k, int flags) {
   if (!ctx || !cloud) return fail(SGA_ERR_INVALID, "null argument");
-  // LDS per workgroup: the k-best list (kpad * 8 bytes per lane, kpad = k rounded up to 4) + the traversal stack (kKdMaxDepth words per
-  // lane) + the static candidate window (kFeatWindow float4) must fit the 64 KB a workgroup may allocate
-  constexpr int kMaxK = ((64 * 1024 - kFeatWindow * 16) / 64 - kKdMaxDepth * 4) / 8 / 4 * 4;  // 112
-  if (k < 1 || k > kMaxK) return fail(SGA_ERR_INVALID, "num_neighbors must be in [1,%d] (k-best list + traversal stack + candidate window must fit 64 KB of LDS per workgroup)", kMaxK);
+  SGA_TRY(features_check_k(k));
   if ((flags & 3) == 0) return SGA_OK;
   if (cloud->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
   SGA_ENTER(ctx);
