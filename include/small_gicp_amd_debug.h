@@ -53,6 +53,16 @@ int sga_debug_index_bbox(const sga_index* index, float lo[3], float hi[3]);
  * sga_estimate_normals_covariances_batch (members that take the lone path inside those calls are not counted): a forest of B clouds of
  * equal depth enqueues as many kernels as a forest of one. */
 int sga_debug_forest_launches(unsigned long long* launches);
+/* What sga_voxelgrid_sampling(cloud, leaf) would do, decided by the very code the call itself runs (csrc/preprocess.hip: voxelgrid_plan):
+ * out[0] = bytes of a sort key (4 or 8), out[1..3] = key bits of x, y, z, out[4] = their sum (the dropped-point key is 1 << total),
+ * out[5] = the layout comes from the cloud's box (0: the reference's 21 / 21 / 21), out[6] = the sort's branch (csrc/sort_util.hpp:
+ * sort_path, 0 up to 2048 keys, 1 up to 200 000, 2 above), out[7] = tiles (workgroups) of ds_segments_kernel, out[8] = the centroid kernel
+ * is launched for n voxels before the host knows their number.  All 0 for an empty cloud (no kernel runs).  No device work. */
+int sga_debug_voxelgrid_plan(const sga_cloud* cloud, double leaf, int out[9]);
+/* Sets the launch epoch of the context's voxel-grid calls (the tag of ds_segments_kernel's status words; the next call uses epoch + 1, and
+ * a call that finds 2^30 - 1 clears the words and starts again at 1) so that a test reaches the wrap-around a service meets after 2^30
+ * calls.  Forwards only: an epoch below the current one, or above 2^30 - 1, is refused (words of earlier launches would read as current). */
+int sga_debug_set_voxelgrid_epoch(sga_context* ctx, unsigned epoch);
 /* GPU time (HIP events) between two points of the context's stream: start() records an event, stop() records another, waits for it and
  * returns the milliseconds in between — the kernel times of bench.py's per-stage roofline lines (voxel grid, index build, covariances). */
 int sga_debug_timer_start(sga_context* ctx);

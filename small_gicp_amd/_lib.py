@@ -159,6 +159,8 @@ SYMBOLS = [
     ("sga_index_spacing", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("sga_set_knn_wave_max", None, [C.c_longlong]),
     ("sga_debug_kd_tree", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    ("sga_debug_voxelgrid_plan", C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int)]),
+    ("sga_debug_set_voxelgrid_epoch", C.c_int, [C.c_void_p, C.c_uint]),
     ("sga_debug_timer_start", C.c_int, [C.c_void_p]),
     ("sga_debug_timer_stop", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("sga_debug_shard_frame_pack", None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -88,6 +88,10 @@ class Context:
         self.stream_ordered = bool(enabled)
         return prev
 
+    def _set_voxelgrid_epoch(self, epoch):
+        """Diagnostics (sga_debug_set_voxelgrid_epoch): the launch epoch of this context's voxel-grid calls; forwards only."""
+        check(load().sga_debug_set_voxelgrid_epoch(self.h, int(epoch)))
+
     def gpu_time_ms(self, fn):
         """GPU time (HIP events on the context's stream) of whatever fn() enqueues; returns (milliseconds, fn's result)."""
         check(load().sga_debug_timer_start(self.h))
@@ -247,6 +251,14 @@ class PointCloud:
 
     def empty(self):
         return self.size() == 0
+
+    def _voxelgrid_plan(self, leaf):
+        """Diagnostics (sga_debug_voxelgrid_plan): what voxelgrid_sampling(self, leaf) would do — key_bytes (4 / 8), bits (x, y, z), total,
+        box (the key layout comes from the cloud's box), sort (0 / 1 / 2: csrc/sort_util.hpp sort_path), tiles of ds_segments_kernel,
+        speculative (the centroid kernel is launched before the voxel count is known).  All 0 for an empty cloud."""
+        out = (C.c_int * 9)()
+        check(load().sga_debug_voxelgrid_plan(self.h, float(leaf), out))
+        return {"key_bytes": out[0], "bits": (out[1], out[2], out[3]), "total": out[4], "box": bool(out[5]), "sort": out[6], "tiles": out[7], "speculative": bool(out[8])}
 
     def _has(self):
         a, b = C.c_int(), C.c_int()

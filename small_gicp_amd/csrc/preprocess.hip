@@ -552,8 +552,54 @@ int bits_for(long long range) {
   return b;
 }
 
+// Everything the host decides about a voxel-grid call before it launches anything: sga_voxelgrid_sampling acts on it,
+// sga_debug_voxelgrid_plan reports it (so a test can assert the regime its input reached).
+constexpr size_t kSpeculativeMax = 262144;
+struct VoxelPlan {
+  VoxelKeyLayout L;   // the reference's key layout, or - when the box of the records is known - as many bits per axis as the cloud's voxel range needs
+  bool box;           // L comes from the cloud's box
+  int key_bytes;      // 4: downsample_keys_kernel<uint32_t> (total <= 31: the dropped-point key 1 << total fits), 8: <unsigned long long>
+  int sort;           // sort_util.hpp: sort_path
+  uint32_t tiles;     // workgroups of ds_segments_kernel
+  bool speculative;   // the centroid kernel is launched for n voxels before the host knows how many there are
+};
+
+VoxelPlan voxelgrid_plan(const sga_cloud* in, double leaf) {
+  VoxelPlan P{{{0, 0, 0}, {21, 21, 21}, 63}, false, 8, 0, 0u, false};
+  VoxelKeyLayout& L = P.L;
+  if (in->has_box) {
+    long long lo[3], hi[3];
+    bool ok = true;
+    for (int k = 0; k < 3; k++) {
+      const double a = std::floor((static_cast<double>(in->box_lo[k]) + in->origin[k]) / leaf), b = std::floor((static_cast<double>(in->box_hi[k]) + in->origin[k]) / leaf);
+      ok = ok && std::isfinite(a) && std::isfinite(b) && std::fabs(a) < 1e15 && std::fabs(b) < 1e15;
+      // one voxel of slack on either side: p * (1 / leaf) in the kernel and p / leaf here may round to different sides of an integer
+      const long long top = (1 << 21) - 1;
+      lo[k] = std::min(std::max<long long>(ok ? static_cast<long long>(a) - 1 + (1 << 20) : 0, 0), top);
+      hi[k] = std::max(std::min<long long>(ok ? static_cast<long long>(b) + 1 + (1 << 20) : top, top), lo[k]);  // (a box outside the grid: its points are dropped by the range test)
+    }
+    if (ok) {
+      P.box = true;
+      L.total = 0;
+      for (int k = 0; k < 3; k++) {
+        L.cmin[k] = static_cast<int>(lo[k]);
+        L.bits[k] = std::max(1, bits_for(hi[k] - lo[k] + 1));
+        L.total += L.bits[k];
+      }
+    }
+  }
+  P.key_bytes = L.total <= 31 ? 4 : 8;
+  P.sort = sort_path(in->n);
+  P.tiles = static_cast<uint32_t>((in->n + kSegTile - 1) / kSegTile);
+  // Small clouds (a LiDAR scan): the centroid kernel is launched for n voxels before the host knows how many there are, so the device
+  // never waits for the host; the output then keeps room for n points.  Large clouds wait for the count and allocate what they need.
+  P.speculative = in->n <= kSpeculativeMax;
+  return P;
+}
+
 template <typename Key>
-int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const VoxelKeyLayout& L, sga_cloud* res) {
+int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const VoxelPlan& P, sga_cloud* res) {
+  const VoxelKeyLayout& L = P.L;
   const size_t n = in->n;
   const uint32_t n32 = static_cast<uint32_t>(n);
   DevBuf<Key> keys, keys_sorted;
@@ -563,7 +609,7 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
   SGA_TRY(vals.alloc(n));
   SGA_TRY(order.alloc(n));
   SGA_TRY(seg_start.alloc(n + 1));
-  const uint32_t tiles = (n32 + kSegTile - 1) / kSegTile;
+  const uint32_t tiles = P.tiles;
   if (ctx->vg_status.n < tiles || ctx->vg_scratch.n < 4 || ctx->vg_epoch >= (1u << 30) - 1u) {  // grow-only; a fresh array reads "nothing yet" for every epoch > 0
     if (ctx->vg_status.n < tiles) SGA_TRY(ctx->vg_status.alloc(std::max<size_t>(2 * tiles, 1024)));
     SGA_HIP(hipMemsetAsync(ctx->vg_status.p, 0, ctx->vg_status.n * sizeof(unsigned long long), ctx->stream));
@@ -584,12 +630,9 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
   const unsigned long long seq = note_begin(ctx, &slot);
   hipLaunchKernelGGL((ds_segments_kernel<Key>), dim3(tiles), dim3(kSegThreads), 0, ctx->stream, keys_sorted.p, n32, static_cast<Key>(1) << L.total, ctx->vg_status.p, epoch, ctx->vg_scratch.p, seg_start.p, slot, seq);
   SGA_HIP(hipGetLastError());
-  // Small clouds (a LiDAR scan): the centroid kernel is launched for n voxels before the host knows how many there are, so the device
-  // never waits for the host; the output then keeps room for n points.  Large clouds wait for the count and allocate what they need.
-  constexpr size_t kSpeculativeMax = 262144;
   unsigned long long payload[kNoteWords - 1];
   uint32_t nseg = 0;
-  if (n <= kSpeculativeMax) {
+  if (P.speculative) {
     SGA_TRY(res->pts.alloc(n));
     hipLaunchKernelGGL(ds_mean_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, ctx->stream, seg_start.p, ctx->vg_scratch.p, order.p, in->pts.p, res->pts.p);
     SGA_HIP(hipGetLastError());
@@ -615,6 +658,7 @@ int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf, s
   if (!ctx || !in || !out) return fail(SGA_ERR_INVALID, "null argument");
   if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
   if (in->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
+  if (in->n >= (1ull << 31)) return fail(SGA_ERR_INVALID, "cloud too large (%zu points; limit 2^31-1)", in->n);  // the kernels index points with 32 bits
   *out = nullptr;
   SGA_ENTER(ctx);
   const size_t n = in->n;
@@ -626,32 +670,35 @@ int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf, s
     *out = res.release();
     return SGA_OK;
   }
-  // the reference's key layout, or — when the box of the records is known — as many bits per axis as the cloud's voxel range needs
-  VoxelKeyLayout L{{0, 0, 0}, {21, 21, 21}, 63};
-  if (in->has_box) {
-    long long lo[3], hi[3];
-    bool ok = true;
-    for (int k = 0; k < 3; k++) {
-      const double a = std::floor((static_cast<double>(in->box_lo[k]) + in->origin[k]) / leaf), b = std::floor((static_cast<double>(in->box_hi[k]) + in->origin[k]) / leaf);
-      ok = ok && std::isfinite(a) && std::isfinite(b) && std::fabs(a) < 1e15 && std::fabs(b) < 1e15;
-      // one voxel of slack on either side: p * (1 / leaf) in the kernel and p / leaf here may round to different sides of an integer
-      const long long top = (1 << 21) - 1;
-      lo[k] = std::min(std::max<long long>(ok ? static_cast<long long>(a) - 1 + (1 << 20) : 0, 0), top);
-      hi[k] = std::max(std::min<long long>(ok ? static_cast<long long>(b) + 1 + (1 << 20) : top, top), lo[k]);  // (a box outside the grid: its points are dropped by the range test)
-    }
-    if (ok) {
-      L.total = 0;
-      for (int k = 0; k < 3; k++) {
-        L.cmin[k] = static_cast<int>(lo[k]);
-        L.bits[k] = std::max(1, bits_for(hi[k] - lo[k] + 1));
-        L.total += L.bits[k];
-      }
-    }
-  }
-  SGA_TRY(L.total <= 31 ? voxelgrid_run<uint32_t>(ctx, in, leaf, L, res.get()) : voxelgrid_run<unsigned long long>(ctx, in, leaf, L, res.get()));
+  const VoxelPlan P = voxelgrid_plan(in, leaf);
+  SGA_TRY(P.key_bytes == 4 ? voxelgrid_run<uint32_t>(ctx, in, leaf, P, res.get()) : voxelgrid_run<unsigned long long>(ctx, in, leaf, P, res.get()));
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
   SGA_TRY(mark_ready(ctx, res->ready));
   *out = res.release();
+  return SGA_OK;
+}
+
+int sga_debug_voxelgrid_plan(const sga_cloud* cloud, double leaf, int out[9]) {
+  if (!cloud || !out) return fail(SGA_ERR_INVALID, "null argument");
+  if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
+  for (int k = 0; k < 9; k++) out[k] = 0;
+  if (cloud->n == 0 || cloud->n >= (1ull << 31)) return SGA_OK;  // no kernel runs
+  const VoxelPlan P = voxelgrid_plan(cloud, leaf);
+  out[0] = P.key_bytes;
+  for (int k = 0; k < 3; k++) out[1 + k] = P.L.bits[k];
+  out[4] = P.L.total;
+  out[5] = P.box ? 1 : 0;
+  out[6] = P.sort;
+  out[7] = static_cast<int>(P.tiles);
+  out[8] = P.speculative ? 1 : 0;
+  return SGA_OK;
+}
+
+int sga_debug_set_voxelgrid_epoch(sga_context* ctx, unsigned epoch) {
+  if (!ctx) return fail(SGA_ERR_INVALID, "null argument");
+  // forwards only: the status words of earlier launches carry epochs <= the current one and must keep reading as "nothing yet"
+  if (epoch < ctx->vg_epoch || epoch > (1u << 30) - 1u) return fail(SGA_ERR_INVALID, "epoch must lie in [%u, 2^30 - 1]", ctx->vg_epoch);
+  ctx->vg_epoch = epoch;
   return SGA_OK;
 }
 

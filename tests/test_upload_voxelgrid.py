@@ -1,7 +1,8 @@
 """Round 6: the upload and the voxel grid of a preprocessing chain (registration_helper.cpp:22-34; util/downsampling.hpp:23-78) without
 copy commands or stream synchronisations (csrc/notes.hpp), with the bounding box taken in the upload's one pass, short sort keys when
 the box is known, and pinned host arrays read in place (sga_host_alloc).  Every form must give the records and the voxel partition of
-the plain one — bit for bit — and the partition must be the oracle's."""
+the plain one — bit for bit — and the partition must be the oracle's.
+(The voxel grid against its float64 definition, in every regime of its kernels: tests/test_voxelgrid_matrix.py.)"""
 import ctypes as C
 
 import numpy as np
