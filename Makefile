@@ -22,12 +22,18 @@ trips:
 	@mkdir -p build/obj_trips
 	for f in $(SRCS); do $(HIPCC) $(HIPFLAGS) -DSGA_KD_TRIPS $(TRIPS_FLAGS) -c $$f -o build/obj_trips/$$(basename $$f .hip).o || exit 1; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(TRIPS_LIB) build/obj_trips/*.o
+# diagnostics build: clock stamps inside reduce_rows_kernel (scripts/diag_reduce_split.py); not part of the product
+STAMPS_LIB := small_gicp_amd/lib/libsmall_gicp_amd_stamps.so
+stamps:
+	@mkdir -p build/obj_stamps
+	for f in $(SRCS); do $(HIPCC) $(HIPFLAGS) -DSGA_REDUCE_STAMPS -c $$f -o build/obj_stamps/$$(basename $$f .hip).o || exit 1; done
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(STAMPS_LIB) build/obj_stamps/*.o
 oracle:
 	$(MAKE) -C oracle
 clean:
 	rm -rf build $(LIB)
 	$(MAKE) -C oracle clean
-.PHONY: all lib oracle clean trips
+.PHONY: all lib oracle clean trips stamps
 # experiment builds: the library with other compile-time settings, e.g.  make variant V=w6 VFLAGS=-DSGA_SEARCH_WAVES=6
 variant:
 	@mkdir -p build/obj_$(V) small_gicp_amd/lib

@@ -73,6 +73,15 @@ int sga_debug_timer_stop(sga_context* ctx, double* ms);
 #define SGA_FRAME_CHECK_DOUBLES 32
 void sga_debug_shard_frame_pack(const double origin[3], double out[SGA_FRAME_CHECK_DOUBLES]);
 int sga_debug_shard_frame_agree(const double sum[SGA_FRAME_CHECK_DOUBLES]);
+/* The row sum that ends a linearization pass, on rows given by the caller: uploads `nrows` rows of 96 doubles and adds them exactly as a
+ * pass does (csrc/linearize.hip: launch_reduce over the 95 columns of a row, reduce_groups(nrows) workgroups, fixed summation order, the
+ * result handed to the host through the pinned block); derive != 0 fills the derived columns in from the totals as a pass does.
+ * out = 96 doubles (column 95 is 0).  For tests of the summation order and for the clock stamps below. */
+int sga_debug_reduce_rows(sga_context* ctx, const double* rows, int nrows, int derive, double* out);
+/* Diagnostics build only (make stamps): the 100 MHz clock at six points of the last reduce_rows_kernel (entry, end of stage 1, after the
+ * ticket, end of stage 2, after the host stores, after the system fence) from the first workgroup (out[0..5]), the last (out[8..13]) and
+ * the one that finished the sum (out[16..21]; out[22] its index, out[23] the number of workgroups). */
+int sga_debug_reduce_stamps(unsigned long long* out24);
 /* Diagnostics build only (make trips): loop-trip counters of the kd walk and the start / end clock of every search wave. */
 int sga_debug_kd_trips(unsigned long long* out16);
 int sga_debug_kd_wave_times(unsigned long long* out, int waves);

@@ -165,6 +165,8 @@ SYMBOLS = [
     ("sga_debug_timer_stop", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("sga_debug_shard_frame_pack", None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("sga_debug_shard_frame_agree", C.c_int, [C.POINTER(C.c_double)]),
+    ("sga_debug_reduce_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("sga_debug_reduce_stamps", C.c_int, [C.c_void_p]),
     ("sga_debug_kd_trips", C.c_int, [C.c_void_p]),
     ("sga_debug_kd_wave_times", C.c_int, [C.c_void_p, C.c_int]),
     ("sga_set_search_mode", None, [C.c_int, C.c_int, C.c_int]),

@@ -644,9 +644,11 @@ __device__ __forceinline__ bool pair_factor(const LinParams<Real>& p, int i, int
 // Row layout: [0, 21) H, [21, 27) b, 27 e, 28 inliers, [32, 41) sum p_a g_j, [41, 59) sum p_a M'_c, [59, 95) sum p_a p_b M'_c
 // (c = xx, xy, xz, yy, yz, zz; pairs ab = 00, 01, 02, 11, 12, 22); columns [0, 15) and [21, 24) are derived.
 __host__ __device__ inline double derived_entry(int col, const double* m) {
-  const int S[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-  auto A = [&](int a, int j, int k) { return m[kModelOff + 9 + 6 * a + S[j][k]]; };                   // sum p_a M'_jk
-  auto B = [&](int a, int b, int j, int k) { return m[kModelOff + 27 + 6 * S[a][b] + S[j][k]]; };     // sum p_a p_b M'_jk
+  // position of (j, k) in a packed symmetric 3x3 {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, four bits each in one immediate: a table indexed at run
+  // time would live in constant memory, and its loads, cold in every launch, would stand between the last fold and the hand-off
+  auto S = [](int j, int k) { return static_cast<int>((0x542431210ull >> (4 * (3 * j + k))) & 15ull); };
+  auto A = [&](int a, int j, int k) { return m[kModelOff + 9 + 6 * a + S(j, k)]; };                   // sum p_a M'_jk
+  auto B = [&](int a, int b, int j, int k) { return m[kModelOff + 27 + 6 * S(a, b) + S(j, k)]; };     // sum p_a p_b M'_jk
   auto G = [&](int a, int j) { return m[kModelOff + 3 * a + j]; };                                    // sum p_a g_j
   // K = skew(p) M': K_ik = p_i1 M'_i2,k - p_i2 M'_i1,k  (i1 = i + 1, i2 = i + 2 mod 3)
   auto PK = [&](int l, int i, int k) { const int i1 = (i + 1) % 3, i2 = (i + 2) % 3; return B(l, i1, i2, k) - B(l, i2, i1, k); };  // sum p_l K_ik
@@ -1471,6 +1473,24 @@ __global__ __launch_bounds__(kTile) void error_kernel(const ErrParams<Real> p) {
 // hipStreamSynchronize, whose fixed cost is paid twice per optimizer iteration.
 constexpr int kReduceGroups = 64;
 
+#ifdef SGA_REDUCE_STAMPS
+// diagnostics build (make stamps): 100 MHz wall clock at six points of reduce_rows_kernel — 0 entry, 1 end of stage 1, 2 after the
+// ticket, 3 end of stage 2, 4 after the host stores, 5 after the system fence — taken by thread 0 of the first workgroup ([0, 6)), of
+// the last one ([8, 14)) and of the one that arrived last and finished the sum ([16, 22); [22] its index, [23] the workgroups)
+static __device__ unsigned long long g_reduce_stamps[24];
+#define SGA_STAMP(k)                                                                         \
+  do {                                                                                       \
+    if (threadIdx.x == 0) {                                                                  \
+      const unsigned long long stamp_now = wall_clock64();                                   \
+      stamp_local[k] = stamp_now;                                                            \
+      if (blockIdx.x == 0) g_reduce_stamps[k] = stamp_now;                                   \
+      if (blockIdx.x == gridDim.x - 1) g_reduce_stamps[8 + (k)] = stamp_now;                 \
+    }                                                                                        \
+  } while (0)
+#else
+#define SGA_STAMP(k) ((void)0)
+#endif
+
 constexpr int kReduceSlices = 8;  // 1024 threads = 8 slices of 128 columns
 __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
   const double* __restrict__ partials, int nrows, int ncols, int row_stride, double* __restrict__ stage, unsigned* __restrict__ ticket, double* __restrict__ out, int out_n, double* __restrict__ host,
@@ -1479,6 +1499,10 @@ __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
   __shared__ unsigned sh_ticket;
   const int c = threadIdx.x & (kCols - 1), s = threadIdx.x / kCols;
   const int G = gridDim.x;
+#ifdef SGA_REDUCE_STAMPS
+  unsigned long long stamp_local[6] = {0, 0, 0, 0, 0, 0};
+#endif
+  SGA_STAMP(0);
   // stage 1: (workgroup g, slice s) adds rows g + G * s, g + G * (s + 8), ...: four independent chains, the loads of a chain in flight together
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   if (c < ncols) {
@@ -1503,12 +1527,14 @@ __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
     __syncthreads();
   };
   fold();
+  SGA_STAMP(1);
   if (G > 1) {
     if (threadIdx.x < kCols) __hip_atomic_store(&stage[blockIdx.x * kCols + threadIdx.x], sh[0][threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);  // release this workgroup's stage row, acquire the earlier ones
     __syncthreads();
+    SGA_STAMP(2);
     if (sh_ticket != static_cast<unsigned>(G - 1)) return;  // workgroup-uniform
     // the last workgroup adds the G <= 64 stage rows: slice s takes rows s, s + 8, ...: at most 8 loads per thread, all in flight
     double v[kReduceGroups / kReduceSlices];
@@ -1525,6 +1551,7 @@ __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
     __syncthreads();
     fold();
   }
+  SGA_STAMP(3);
   if (threadIdx.x < kCols) {
     const int cc = threadIdx.x;
     const double t = (derive && is_derived_col(cc)) ? derived_entry(cc, sh[0]) : sh[0][cc];  // moment form: H_rr, H_rt, b_r from the totals
@@ -1537,10 +1564,21 @@ __global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
   }
   if (G > 1 && threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
   if (host != nullptr) {
-    __threadfence_system();
+    SGA_STAMP(4);
+    // only the two waves that stored the result fence it; all sixteen meet at the barrier.  (A system-scope fence writes the L2 back and
+    // invalidates it, ~0.15 us per wave, one wave after the other: sixteen of them stood 2.6 us in front of the sequence word, two 0.7:
+    // profiles/reduce_chain_split.txt, blocks 2 and 3.)
+    if (threadIdx.x < kCols) __threadfence_system();
     __syncthreads();
+    SGA_STAMP(5);
     if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host + kSeqWord), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+#ifdef SGA_REDUCE_STAMPS
+  if (threadIdx.x == 0) {  // the workgroup that finished the sum
+    for (int k = 0; k < 6; k++) g_reduce_stamps[16 + k] = stamp_local[k];
+    g_reduce_stamps[22] = blockIdx.x, g_reduce_stamps[23] = gridDim.x;
+  }
+#endif
 }
 
 // The sums of a round: workgroup k adds the rows of the k-th active pair in the fixed order of reduce_rows_kernel's single-workgroup form
@@ -2804,6 +2842,34 @@ int sga_problem_get_search_stats(sga_context* ctx, const sga_problem* pb, int* l
   SGA_HIP(hipStreamSynchronize(ctx->stream));
   return SGA_OK;
 }
+
+// diagnostics / tests: the fixed-order sum of `nrows` host rows of kRow doubles, exactly as a linearization pass runs it (launch_reduce over
+// kModelCols columns, stage rows behind the partial rows, result handed over through the pinned block); out = kRow doubles
+int sga_debug_reduce_rows(sga_context* ctx, const double* rows, int nrows, int derive, double* out) {
+  if (!ctx || !out || nrows < 0 || (nrows > 0 && !rows)) return fail(SGA_ERR_INVALID, "null argument or negative row count");
+  SGA_ENTER(ctx);
+  const size_t stage_off = sga::partial_rows(static_cast<size_t>(nrows) * 64) * sga::kRow;  // (one row per 64 points: where a pass over that many rows keeps its stage rows)
+  sga::DevBuf<double> buf;
+  SGA_TRY(buf.alloc(stage_off + static_cast<size_t>(sga::kReduceGroups) * sga::kCols));
+  if (nrows > 0) SGA_HIP(hipMemcpyAsync(buf.p, rows, static_cast<size_t>(nrows) * sga::kRow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const unsigned long long seq = ++ctx->publish_seq;
+  sga::launch_reduce(ctx, buf.p, nrows, sga::kModelCols, sga::kRow, buf.p + stage_off, ctx->d_accum.p, sga::kRow, ctx->h_accum_dev, seq, derive != 0);
+  SGA_HIP(hipGetLastError());
+  SGA_TRY(sga::wait_result(ctx, seq));
+  memcpy(out, ctx->h_accum, sga::kRow * sizeof(double));
+  return SGA_OK;
+}
+
+#ifdef SGA_REDUCE_STAMPS
+// diagnostics build (make stamps): the clock stamps of the last reduce_rows_kernel (layout: g_reduce_stamps)
+int sga_debug_reduce_stamps(unsigned long long* out24) {
+  if (hipDeviceSynchronize() != hipSuccess) return SGA_ERR_HIP;  // the finishing workgroup writes its stamps after it has released the result to the host
+  if (hipMemcpyFromSymbol(out24, HIP_SYMBOL(sga::g_reduce_stamps), sizeof(unsigned long long) * 24) != hipSuccess) return SGA_ERR_HIP;
+  return SGA_OK;
+}
+#else
+int sga_debug_reduce_stamps(unsigned long long*) { return fail(SGA_ERR_UNSUPPORTED, "clock stamps of the row sum exist in the diagnostics build only (make stamps)"); }
+#endif
 
 #ifdef SGA_KD_TRIPS
 // diagnostics build (make trips): loop-body executions of the walk since the last call, [0, 6) per lane, [8, 14) per wave
