@@ -109,6 +109,16 @@ int sga_cloud_download_f64(sga_context* ctx, const sga_cloud* cloud, double* xyz
 /* ---- preprocessing (registration_helper.cpp:22-34 preprocess_points) ----------------------------------------------- */
 /* util/downsampling.hpp:23-78 voxelgrid_sampling: centroid per occupied voxel, output in ascending packed-key order. */
 int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf_size, sga_cloud** out);
+/* sga_voxelgrid_sampling(ctx, clouds[k], leaf_size, &out[k]) for `count` clouds on the context's device in one chain of launches on the
+ * context's stream — keys, ONE sort over the concatenation under the key (member << W) | the member's own short key, runs, centroids —
+ * whose length does not grow with count.  out[k] is an ordinary cloud, owning its buffers, in the input's device frame, its records
+ * bit-identical to the lone call's.  The chain takes the members that have a bounding box (uploads), 1 .. 262144 points, and whose
+ * composite key fits 64 bits (2^24 points in all); the others — clouds made on the device, larger ones — go through the lone routine, one
+ * after the other, inside the call; an empty member gives an empty cloud.  The same cloud may appear twice (inputs are only read); a member
+ * made by another context of the device is waited for.  The host waits once, for the voxel counts of all members of the chain.  All
+ * arguments are checked before any device work (status and message as the lone call's, naming the member); on any failure every out[k]
+ * is NULL.  count == 0 is SGA_OK. */
+int sga_voxelgrid_sampling_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf_size, sga_cloud** out);
 /* util/normal_estimation.hpp:65-92 estimate_local_features: kNN(k, incl. self) -> mean/cov -> eigvecs -> normal / covariance.
  * index: a kd-tree built over `cloud`, or NULL to build a temporary one.  flags: bit0 = normals, bit1 = covariances. */
 int sga_estimate_normals_covariances(sga_context* ctx, sga_cloud* cloud, const sga_index* index, int num_neighbors, int flags);

@@ -375,6 +375,16 @@ inline void estimate_normals(PointCloud& cloud, KdTree& tree, int num_neighbors 
   check(sga_estimate_normals_covariances(cloud.ctx, cloud.h, tree.h, num_neighbors, 1), "estimate_normals");
   cloud.invalidate_host();
 }
+/// sga_voxelgrid_sampling_batch: the voxel grids of several clouds of one context in one chain of launches (each bit-identical to voxelgrid_sampling(cloud))
+inline std::vector<PointCloud::Ptr> voxelgrid_sampling_batch(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds, double leaf_size) {
+  std::vector<const sga_cloud*> hs;
+  for (const auto& c : clouds) hs.push_back(c->h);
+  std::vector<sga_cloud*> out(clouds.size(), nullptr);
+  check(sga_voxelgrid_sampling_batch(ctx, hs.data(), hs.size(), leaf_size, out.data()), "sga_voxelgrid_sampling_batch");
+  std::vector<PointCloud::Ptr> down;
+  for (size_t k = 0; k < clouds.size(); k++) down.push_back(std::make_shared<PointCloud>(out[k], ctx));
+  return down;
+}
 /// sga_index_build_kdtree_batch: the kd-trees of several clouds of one context in one chain of launches (each bit-identical to KdTree(cloud))
 inline std::vector<KdTree::Ptr> build_kdtrees(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds) {
   std::vector<const sga_cloud*> hs;

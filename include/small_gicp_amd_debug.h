@@ -59,6 +59,14 @@ int sga_debug_forest_launches(unsigned long long* launches);
  * sort_path, 0 up to 2048 keys, 1 up to 200 000, 2 above), out[7] = tiles (workgroups) of ds_segments_kernel, out[8] = the centroid kernel
  * is launched for n voxels before the host knows their number.  All 0 for an empty cloud (no kernel runs).  No device work. */
 int sga_debug_voxelgrid_plan(const sga_cloud* cloud, double leaf, int out[9]);
+/* What sga_voxelgrid_sampling_batch(clouds, count, leaf) would do, decided by the very code the call itself runs (csrc/preprocess.hip:
+ * grid_forest_plan): out[0] = bytes of a composite sort key (4 or 8; 0: no member shares the chain), out[1] = W, the bits below the member
+ * number (the widest member layout's total + 1), out[2] = the bits of the member number, out[3] = members of the shared chain, out[4] =
+ * members that go through the lone routine (empty members are in neither), out[5] = tiles (workgroups) of the runs kernel.  No device work. */
+int sga_debug_voxelgrid_batch_plan(const sga_cloud* const* clouds, size_t count, double leaf, int out[6]);
+/* Launches enqueued so far, in this process, by the shared chain of sga_voxelgrid_sampling_batch: its own kernels plus one per sort call
+ * (members that take the lone path inside the call are not counted): a chain of B clouds counts as many as a chain of one. */
+int sga_debug_voxelgrid_batch_launches(unsigned long long* launches);
 /* Sets the launch epoch of the context's voxel-grid calls (the tag of ds_segments_kernel's status words; the next call uses epoch + 1, and
  * a call that finds 2^30 - 1 clears the words and starts again at 1) so that a test reaches the wrap-around a service meets after 2^30
  * calls.  Forwards only: an epoch below the current one, or above 2^30 - 1, is refused (words of earlier launches would read as current). */

@@ -44,8 +44,11 @@ from .api import (  # noqa: F401
     pinned_empty,
     preprocess_batch,
     preprocess_points,
+    preprocess_points_batch,
     unpack_accumulator,
     voxelgrid_sampling,
+    voxelgrid_sampling_batch,
+    voxelgrid_batch_launches,
 )
 
 __version__ = "0.1.0"

@@ -1230,6 +1230,43 @@ def preprocess_batch(clouds, num_neighbors=20):
     return list(zip(clouds, trees))
 
 
+def voxelgrid_sampling_batch(clouds, resolution):
+    """sga_voxelgrid_sampling_batch: [voxelgrid_sampling(c, resolution) for c in clouds] in one chain of launches (PointCloud objects of one
+    context).  Every output is an ordinary PointCloud, bit-identical to the lone call's; uploaded clouds of at most 262144 points share
+    the launches, others (clouds made on the device, larger ones) are downsampled one by one inside the call."""
+    clouds = list(clouds)
+    ctx = _one_context(clouds)
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    out = (C.c_void_p * max(1, len(clouds)))()
+    check(load().sga_voxelgrid_sampling_batch(ctx.h, hs, len(clouds), float(resolution), out))
+    return [PointCloud(ctx=ctx, _handle=C.c_void_p(out[k])) for k in range(len(clouds))]
+
+
+def preprocess_points_batch(clouds, downsampling_resolution=0.25, num_neighbors=10):
+    """preprocess_points for several raw clouds of one context, every stage batched: voxelgrid_sampling_batch, then preprocess_batch.
+    [(downsampled cloud, tree)], each pair what the lone calls give, bit for bit."""
+    return preprocess_batch(voxelgrid_sampling_batch(clouds, downsampling_resolution), num_neighbors)
+
+
+def _voxelgrid_batch_plan(clouds, resolution):
+    """Diagnostics (sga_debug_voxelgrid_batch_plan): what voxelgrid_sampling_batch(clouds, resolution) would do — key_bytes (4 / 8; 0: no
+    shared chain), W (bits below the member number), member_bits, forest (members of the shared chain), lone (members through the lone
+    routine; empty members are in neither), tiles of the runs kernel."""
+    clouds = list(clouds)
+    _one_context(clouds)
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    out = (C.c_int * 6)()
+    check(load().sga_debug_voxelgrid_batch_plan(hs, len(clouds), float(resolution), out))
+    return {"key_bytes": out[0], "W": out[1], "member_bits": out[2], "forest": out[3], "lone": out[4], "tiles": out[5]}
+
+
+def voxelgrid_batch_launches():
+    """Diagnostics (sga_debug_voxelgrid_batch_launches): kernels and sorts enqueued so far by the shared chain of voxelgrid_sampling_batch."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_voxelgrid_batch_launches(C.byref(v)))
+    return v.value
+
+
 def forest_launches():
     """Diagnostics (sga_debug_forest_launches): kernels enqueued so far by the forest form of the two batched preprocessing calls."""
     v = C.c_ulonglong()

@@ -3,6 +3,8 @@
 // of the tree is 2^d workgroups — and pays ~10 launches for ~100 us of kernels; B such scans fill the same launches B times over.
 // The results are ordinary sga_index objects, each owning its buffers, bit-identical to what the lone calls produce: the batched
 // kernels (index_build.hip, preprocess.hip) run the lone kernels' bodies with the arguments read from a per-call table (forest.hpp).
+// sga_voxelgrid_sampling_batch does the same for the stage before them: B raw scans downsampled by one chain —
+// keys, ONE sort over the concatenation under the key (member, the member's own short key), runs, centroids — and one host wait.
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -18,7 +20,8 @@ namespace sga {
 int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
 
 namespace {
-std::atomic<unsigned long long> g_forest_launches{0};
+std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0};
+}  // namespace
 
 // the context's box block with room for `members` slots (grow-only; no call is in flight: every call waits for its boxes)
 int forest_box_block(sga_context* ctx, size_t members) {
@@ -39,8 +42,8 @@ int forest_box_block(sga_context* ctx, size_t members) {
   return SGA_OK;
 }
 
-// the ONE wait of a forest build: all boxes are there once the block shows the call's sequence number (note_wait's spin, context.hip)
-int forest_boxes_wait(sga_context* ctx, unsigned long long seq) {
+// the ONE wait of a forest call: all boxes (run counts) are there once the block shows the call's sequence number (note_wait's spin, context.hip)
+int forest_boxes_wait(sga_context* ctx, unsigned long long seq, const char* what) {
   const unsigned long long* word = ctx->h_forest;
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0;; spins++) {
@@ -53,13 +56,14 @@ int forest_boxes_wait(sga_context* ctx, unsigned long long seq) {
         (void)hipGetLastError();
         SGA_HIP(hipStreamSynchronize(ctx->stream));
         if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
-        return fail(SGA_ERR_HIP, "the boxes of a batched kd-tree build were not published by the device");
+        return fail(SGA_ERR_HIP, "the %s were not published by the device", what);
       }
       (void)hipGetLastError();  // hipErrorNotReady is sticky in hipGetLastError
     }
   }
 }
 
+namespace {
 int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count, std::vector<std::unique_ptr<sga_index>>& made) {
   made.resize(count);
   std::vector<size_t> forest;  // positions of the members the forest builds: 1 <= n <= kForestMaxPoints
@@ -134,7 +138,7 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
       return rc;
     }
     // ---- the one wait: the boxes of all members
-    SGA_TRY(forest_boxes_wait(ctx, seq));
+    SGA_TRY(forest_boxes_wait(ctx, seq, "boxes of a batched kd-tree build"));
     for (size_t j = 0; j < forest.size(); j++) {
       sga_index* idx = made[forest[j]].get();
       box_note_decode(ctx->h_forest + 4 + 4 * j + 1, idx->bbox_lo, idx->bbox_hi);
@@ -154,9 +158,61 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
   for (size_t k : forest) SGA_TRY(mark_ready(ctx, made[k]->ready));
   return SGA_OK;
 }
+
+// sga_voxelgrid_sampling for every member.  The members of the plan's forest share one chain of launches
+// (preprocess.hip: grid_forest_enqueue) and ONE host wait, for their voxel counts; the others go through the lone routine afterwards.
+int voxelgrid_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, std::vector<std::unique_ptr<sga_cloud>>& made) {
+  made.resize(count);
+  for (size_t k = 0; k < count; k++) {
+    std::unique_ptr<sga_cloud> res(new sga_cloud);  // as sga_voxelgrid_sampling sets it up
+    res->device = ctx->device;
+    for (int a = 0; a < 3; a++) res->origin[a] = clouds[k]->origin[a];  // the centroids stay in the input's device frame
+    SGA_TRY(wait_ready(ctx, clouds[k]->ready));
+    made[k] = std::move(res);
+  }
+  const GridForestPlan plan = grid_forest_plan(clouds, count, leaf);
+  if (!plan.forest.empty()) {
+    std::vector<float4*> out(plan.forest.size());
+    for (size_t j = 0; j < plan.forest.size(); j++) {
+      sga_cloud* res = made[plan.forest[j]].get();
+      SGA_TRY(res->pts.alloc(clouds[plan.forest[j]]->n));  // room for one voxel per point: the centroid kernel runs before the host knows the count
+      out[j] = res->pts.p;
+    }
+    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
+    const unsigned long long seq = ++ctx->forest_seq;
+    if (const int rc = grid_forest_enqueue(ctx, clouds, leaf, plan, out.data(), seq); rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block and the outputs: nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    // ---- the one wait: the voxel counts of all forest members
+    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel grid"));
+    for (size_t j = 0; j < plan.forest.size(); j++) made[plan.forest[j]]->n = static_cast<size_t>(ctx->h_forest[4 + 4 * j + 1]);
+  }
+  // ---- the other members through the lone routine, one after the other: no box, more than 262144 points, past the forest's caps
+  for (size_t k : plan.lone) {
+    sga_cloud* lone = nullptr;
+    SGA_TRY(sga_voxelgrid_sampling(ctx, clouds[k], leaf, &lone));
+    made[k].reset(lone);
+  }
+  if (!plan.forest.empty() && !ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k : plan.forest) SGA_TRY(mark_ready(ctx, made[k]->ready));
+  return SGA_OK;
+}
+
+// the argument checks of sga_voxelgrid_sampling_batch and of its plan (status and message as the lone call's, naming the member)
+int voxelgrid_batch_check(const sga_cloud* const* clouds, size_t count, double leaf) {
+  if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
+  for (size_t k = 0; k < count; k++) {
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "clouds[%zu] is NULL", k);
+    if (clouds[k]->n >= (1ull << 31)) return fail(SGA_ERR_INVALID, "cloud %zu too large (%zu points; limit 2^31-1)", k, clouds[k]->n);
+  }
+  return SGA_OK;
+}
 }  // namespace
 
 void forest_count_launch() { g_forest_launches.fetch_add(1, std::memory_order_relaxed); }
+void grid_forest_count_launch() { g_grid_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 }  // namespace sga
 
 using namespace sga;
@@ -166,6 +222,41 @@ extern "C" {
 int sga_debug_forest_launches(unsigned long long* launches) {
   if (!launches) return fail(SGA_ERR_INVALID, "null argument");
   *launches = g_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_voxelgrid_batch_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_grid_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_voxelgrid_batch_plan(const sga_cloud* const* clouds, size_t count, double leaf, int out[6]) {
+  if (!out || (count > 0 && !clouds)) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  SGA_TRY(voxelgrid_batch_check(clouds, count, leaf));
+  const GridForestPlan P = grid_forest_plan(clouds, count, leaf);
+  out[0] = P.key_bytes;
+  out[1] = P.W;
+  out[2] = P.member_bits;
+  out[3] = static_cast<int>(P.forest.size());
+  out[4] = static_cast<int>(P.lone.size());
+  out[5] = static_cast<int>(P.tiles);
+  return SGA_OK;
+}
+
+int sga_voxelgrid_sampling_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, sga_cloud** out) {
+  if (count == 0) return SGA_OK;
+  if (out)
+    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(voxelgrid_batch_check(clouds, count, leaf));
+  for (size_t k = 0; k < count; k++)
+    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
+  SGA_ENTER(ctx);
+  std::vector<std::unique_ptr<sga_cloud>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
+  SGA_TRY(voxelgrid_batch(ctx, clouds, count, leaf, made));
+  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
   return SGA_OK;
 }
 

@@ -42,6 +42,16 @@ struct ForestBoxes {
   unsigned long long seq;
 };
 
+// by ONE thread of a member (a tree's root level, a grid's last tile), after it wrote the member's words of the box block: the last member
+// to arrive publishes the call's sequence number (agent-scope ticket, system-scope release: batch_reduce_rows_kernel's hand-off, linearize.hip)
+__device__ __forceinline__ void forest_box_arrive(const ForestBoxes& h) {
+  __threadfence_system();
+  if (__hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == h.total - 1u) {
+    __threadfence_system();
+    __hip_atomic_store(h.seq_word, h.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // One member of a batched covariance / normal estimation: the arguments of knn_wave_kernel / features_from_list_kernel for it
 struct ForestFeat {
   KdView g;
@@ -75,6 +85,29 @@ void forest_tree_shape(size_t n, int* D, int* dA);  // index_build.hip: depth an
 int features_check_k(int k);     // preprocess.hip: SGA_OK, or the lone estimation's error for a num_neighbors outside its range
 long long knn_wave_max_points();  // preprocess.hip: g_knn_wave_max
 void forest_count_launch();       // batch_preprocess.hip: every kernel the two entry points enqueue (sga_debug_forest_launches)
+int forest_box_block(sga_context* ctx, size_t members);  // batch_preprocess.hip: the context's box block with room for `members` slots
+int forest_boxes_wait(sga_context* ctx, unsigned long long seq, const char* what);  // the ONE wait of a forest call: the block shows `seq`
+
+// ---- the grid forest: sga_voxelgrid_sampling for B clouds in one chain of launches --------------------------
+// What the host decides about a batched voxel-grid call before it launches anything (preprocess.hip: grid_forest_plan);
+// sga_voxelgrid_sampling_batch acts on it, sga_debug_voxelgrid_batch_plan reports it.  A member joins the shared chain when it has a box
+// (a short-key layout of its own), 1 .. 262144 points, and — members taken in the call's order — the composite key
+// (member << W) | short key still fits 64 bits and the concatenation kGridForestMaxPoints points with it; every other non-empty member
+// goes through the lone routine.
+constexpr size_t kGridForestMaxPoints = 1ull << 24;  // cap of the concatenation (28 bytes of scratch per point: 448 MB)
+struct GridForestPlan {
+  int key_bytes = 0;    // 4: the composite key fits 32 bits, 8 otherwise; 0: no member in the chain
+  int W = 0;            // bits below the member number: the widest short key of a member (its `total`) + 1, for the dropped points' key
+  int member_bits = 0;  // bits_for(members of the chain)
+  uint32_t tiles = 0;   // workgroups of the runs kernel: tiles of 2048 keys counted from every member's own start
+  size_t points = 0;    // the concatenation
+  std::vector<size_t> forest, lone;  // positions of the members in the chain / through the lone routine (empty members are in neither)
+};
+GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, double leaf);
+// preprocess.hip: keys, sort, runs, centroids of the plan's forest members enqueued on the context's stream; out[j]: the records of forest
+// member j (room for the member's point count); member j's run count arrives in word 4 j + 5 of the context's box block, then `seq` in word 0
+int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq);
+void grid_forest_count_launch();  // batch_preprocess.hip: every kernel and sort of grid_forest_enqueue (sga_debug_voxelgrid_batch_launches)
 constexpr uint32_t kForestMaxPoints = 1024 * 32;  // = kSplitMaxPoints (index_build.hip): the clouds the split kernel holds whole
 
 }  // namespace sga

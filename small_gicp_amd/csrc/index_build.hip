@@ -1052,16 +1052,6 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
 static_assert(sizeof(ForestTree) % 8 == 0, "table entries are copied as 8-byte words");
 static_assert(kForestMaxPoints == kSplitMaxPoints, "the forest takes the clouds the split kernel holds whole");
 
-// by ONE thread of a tree's root level, after it wrote the tree's box words: the last tree to arrive publishes the call's sequence
-// number (agent-scope ticket, system-scope release: batch_reduce_rows_kernel's hand-off, linearize.hip)
-__device__ __forceinline__ void forest_box_arrive(const ForestBoxes& h) {
-  __threadfence_system();
-  if (__hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == h.total - 1u) {
-    __threadfence_system();
-    __hip_atomic_store(h.seq_word, h.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
 template <int THREADS, int KEYS>
 __global__ __launch_bounds__(THREADS) void kd_forest_split_kernel(const ForestTree* __restrict__ trees, const uint32_t* __restrict__ members, int d, const ForestBoxes hand) {
   const ForestTree& t = *uniform_const(trees + uniform_const(members)[blockIdx.y]);

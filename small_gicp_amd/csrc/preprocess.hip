@@ -71,13 +71,15 @@ __global__ void downsample_keys_kernel(const float4* __restrict__ pts, uint32_t 
 // and looks back over its predecessors' published counts / prefixes 64 at a time (decoupled look-back).  status[]: one word per tile,
 // {epoch : 30, state : 2, value : 32}; words of earlier launches carry an older epoch and read as "nothing yet", so nothing is cleared.
 constexpr int kSegThreads = 256, kSegItems = 8, kSegTile = kSegThreads * kSegItems;
-template <typename Key>
-__global__ __launch_bounds__(kSegThreads) void ds_segments_kernel(const Key* __restrict__ keys, uint32_t n, Key bad, unsigned long long* __restrict__ status, unsigned epoch, uint32_t* __restrict__ scratch, uint32_t* __restrict__ seg_start,
-                                                                   unsigned long long* __restrict__ note_slot, unsigned long long seq) {
+// (the body of ds_segments_kernel and of its batched form; num_tiles: the workgroups that share scratch[0] and status[]; done(runs) is
+// called by one thread of the last tile to be taken)
+template <typename Key, typename Done>
+__device__ __forceinline__ void ds_segments_body(const Key* __restrict__ keys, uint32_t n, Key bad, unsigned long long* __restrict__ status, unsigned epoch, uint32_t* __restrict__ scratch, uint32_t* __restrict__ seg_start,
+                                                 const uint32_t num_tiles, Done done) {
   __shared__ uint32_t sh_tile, sh_wave[kSegThreads / 64], sh_excl;
   if (threadIdx.x == 0) sh_tile = atomicAdd(&scratch[0], 1u);
   __syncthreads();
-  const uint32_t tile = sh_tile, num_tiles = gridDim.x;
+  const uint32_t tile = sh_tile;
   const uint32_t first = tile * kSegTile + threadIdx.x * kSegItems;
   Key k[kSegItems + 1];
   k[0] = (first > 0 && first - 1 < n) ? keys[first - 1] : bad;
@@ -144,20 +146,29 @@ __global__ __launch_bounds__(kSegThreads) void ds_segments_kernel(const Key* __r
     const uint32_t nseg = sh_excl + total;
     scratch[1] = nseg;
     __hip_atomic_store(&scratch[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    done(nseg);
+  }
+}
+template <typename Key>
+__global__ __launch_bounds__(kSegThreads) void ds_segments_kernel(const Key* __restrict__ keys, uint32_t n, Key bad, unsigned long long* __restrict__ status, unsigned epoch, uint32_t* __restrict__ scratch, uint32_t* __restrict__ seg_start,
+                                                                   unsigned long long* __restrict__ note_slot, unsigned long long seq) {
+  ds_segments_body<Key>(keys, n, bad, status, epoch, scratch, seg_start, gridDim.x, [&](uint32_t nseg) {
     note_slot[1] = nseg;
     note_publish(note_slot, seq);
-  }
+  });
 }
 
 // Eight lanes per voxel: a LiDAR scan has a few voxels with hundreds of points next to the sensor, and one lane walking such a
 // segment alone was the tail of the whole kernel.  Lane g sums the points g, g+8, ... of the segment in fp64, then the eight partial
 // sums are added in a fixed order (bit-reproducible; the grouping differs from a serial sum by rounding of the last bit at most).
 // Launched for `capacity` voxels; the number there are (scratch[1]) and the end of the last run (scratch[2]) are read here.
-__global__ void ds_mean_kernel(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ scratch, const uint32_t* __restrict__ order, const float4* __restrict__ pts, float4* __restrict__ out) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+// (the body of ds_mean_kernel and of its batched form; block_first: the first lane of this workgroup among the lanes of its cloud)
+__device__ __forceinline__ void ds_mean_body(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ scratch, const uint32_t* __restrict__ order, const float4* __restrict__ pts, float4* __restrict__ out,
+                                             const uint32_t block_first) {
+  const uint32_t t = block_first + threadIdx.x;
   const uint32_t v = t >> 3, g = t & 7u;
   const uint32_t nseg = scratch[1];
-  if ((blockIdx.x * blockDim.x) >> 3 >= nseg) return;  // workgroup-uniform
+  if (block_first >> 3 >= nseg) return;  // workgroup-uniform
   const bool valid = v < nseg;
   double sx = 0, sy = 0, sz = 0;
   uint32_t cnt = 0;
@@ -190,6 +201,79 @@ __global__ void ds_mean_kernel(const uint32_t* __restrict__ seg_start, const uin
     const double inv = 1.0 / cnt;
     out[v] = make_float4(static_cast<float>(sx * inv), static_cast<float>(sy * inv), static_cast<float>(sz * inv), __uint_as_float(v));
   }
+}
+__global__ void ds_mean_kernel(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ scratch, const uint32_t* __restrict__ order, const float4* __restrict__ pts, float4* __restrict__ out) {
+  ds_mean_body(seg_start, scratch, order, pts, out, blockIdx.x * blockDim.x);
+}
+
+// ---- the grid forest: the voxel grids of B clouds in one chain of launches (forest.hpp) ----------------------
+// The members' points are concatenated (member m at [off, off + n)) and sorted ONCE under the composite key (m << W) | short key, the short
+// key being what downsample_keys_kernel computes under the member's own layout: sorted position p belongs to member m exactly when
+// off <= p < off + n, the sort is stable, so a member's stretch holds what the lone call's sort gives — the same runs, the points of a run
+// in original order — and the runs and centroid bodies above, handed the member's stretch, write the lone call's bits.
+// One table entry per member (read with scalar loads): what the lone kernels receive as arguments.
+struct GridMember {
+  const float4* pts;
+  float4* out;
+  uint32_t* scratch;               // {arrival counter, runs, valid points, 0} of this member: in the call's table, set up with it
+  unsigned long long* count_slot;  // word 1 receives the member's run count (pinned, device-mapped: the context's box block)
+  double ox, oy, oz;
+  unsigned long long tag, bad;     // m << W; tag | 1 << L.total: the key of the member's dropped points
+  VoxelKeyLayout L;
+  uint32_t n, off, pad;
+};
+static_assert(sizeof(GridMember) % 8 == 0, "table entries are copied as 8-byte words");
+
+// downsample_keys_kernel's key of one record under the layout L, statement for statement.  (A body of its own: sharing one with the lone
+// kernel changed that kernel's register row, profiles/batch_voxelgrid_kernel_resources.txt.)
+template <typename Key>
+__device__ __forceinline__ Key voxel_short_key(const float4 p, double inv_leaf, double ox, double oy, double oz, const VoxelKeyLayout& L) {
+  const int cx = fast_floor_dd((static_cast<double>(p.x) + ox) * inv_leaf) + (1 << 20);
+  const int cy = fast_floor_dd((static_cast<double>(p.y) + oy) * inv_leaf) + (1 << 20);
+  const int cz = fast_floor_dd((static_cast<double>(p.z) + oz) * inv_leaf) + (1 << 20);
+  const int mask = (1 << 21) - 1;
+  bool bad = cx < 0 || cy < 0 || cz < 0 || cx > mask || cy > mask || cz > mask;
+  bad = bad || !(fabsf(p.x) <= 3.4028234e38f) || !(fabsf(p.y) <= 3.4028234e38f) || !(fabsf(p.z) <= 3.4028234e38f);
+  const unsigned ux = static_cast<unsigned>(cx - L.cmin[0]), uy = static_cast<unsigned>(cy - L.cmin[1]), uz = static_cast<unsigned>(cz - L.cmin[2]);
+  bad = bad || (ux >> L.bits[0]) != 0u || (uy >> L.bits[1]) != 0u || (uz >> L.bits[2]) != 0u;
+  const Key key = static_cast<Key>(ux) | (static_cast<Key>(uy) << L.bits[0]) | (static_cast<Key>(uz) << (L.bits[0] + L.bits[1]));
+  return bad ? (static_cast<Key>(1) << L.total) : key;
+}
+
+// workgroup b: 256 points of the member k with prefix[k] <= b < prefix[k + 1]
+template <typename Key>
+__global__ __launch_bounds__(256) void downsample_keys_forest_kernel(const GridMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, double inv_leaf, Key* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const GridMember& g = *uniform_const(members + m);
+  const uint32_t i = (blockIdx.x - prefix[m]) * 256u + threadIdx.x;
+  if (i >= g.n) return;
+  keys[g.off + i] = static_cast<Key>(g.tag) | voxel_short_key<Key>(g.pts[i], inv_leaf, g.ox, g.oy, g.oz, g.L);
+  vals[g.off + i] = i;  // the index within the member
+}
+
+// workgroup b: one tile of the member that owns it — WHICH tile the member's own arrival counter says, so the look-back of a workgroup
+// only ever waits for workgroups of its member that have taken their tiles: ds_segments_kernel's argument, per member.  Status words
+// [prefix[m], prefix[m + 1]) are the member's, under the call's one epoch.  The member's last tile hands its run count to the host.
+template <typename Key>
+__global__ __launch_bounds__(kSegThreads) void ds_segments_forest_kernel(const GridMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, const Key* __restrict__ keys, unsigned long long* __restrict__ status, unsigned epoch,
+                                                                          uint32_t* __restrict__ seg_start, const ForestBoxes hand) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const GridMember& g = *uniform_const(members + m);
+  unsigned long long* slot = g.count_slot;
+  ds_segments_body<Key>(keys + g.off, g.n, static_cast<Key>(g.bad), status + prefix[m], epoch, g.scratch, seg_start + g.off, prefix[m + 1] - prefix[m], [&](uint32_t nseg) {
+    slot[1] = nseg;
+    forest_box_arrive(hand);
+  });
+}
+
+// workgroup b: 32 voxels (x 8 lanes) of the member that owns it, launched for the member's point count like the lone kernel
+__global__ __launch_bounds__(256) void ds_mean_forest_kernel(const GridMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ order) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const GridMember& g = *uniform_const(members + m);
+  ds_mean_body(seg_start + g.off, g.scratch, order + g.off, g.pts, g.out, (blockIdx.x - prefix[m]) * 256u);
 }
 
 // ---- 3x3 symmetric eigen-decomposition (Eigen 3.4.0 computeDirect, restated), fp64 -------------------------------------------------
@@ -650,7 +734,123 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
   res->n = nseg;
   return SGA_OK;
 }
+
+// the status words of ds_segments_kernel for a launch of `tiles` workgroups, and the launch's epoch (voxelgrid_run's rule: grow-only; a
+// fresh or zeroed array reads "nothing yet" for every epoch > 0; the epochs end at 2^30 - 1)
+int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch) {
+  if (ctx->vg_status.n < tiles || ctx->vg_epoch >= (1u << 30) - 1u) {
+    if (ctx->vg_status.n < tiles) SGA_TRY(ctx->vg_status.alloc(std::max<size_t>(2 * static_cast<size_t>(tiles), 1024)));
+    SGA_HIP(hipMemsetAsync(ctx->vg_status.p, 0, ctx->vg_status.n * sizeof(unsigned long long), ctx->stream));
+    ctx->vg_epoch = 0;
+  }
+  *epoch = ++ctx->vg_epoch;
+  return SGA_OK;
+}
+
+template <typename Key>
+int grid_forest_launch(sga_context* ctx, const GridMember* d_members, const uint32_t* d_prefix, const std::vector<uint32_t>& prefix, size_t count, size_t points, double leaf, unsigned end_bit, unsigned epoch, const ForestBoxes& hand) {
+  DevBuf<Key> keys, keys_sorted;
+  DevBuf<uint32_t> vals, order, seg_start;
+  SGA_TRY(keys.alloc(points));
+  SGA_TRY(keys_sorted.alloc(points));
+  SGA_TRY(vals.alloc(points));
+  SGA_TRY(order.alloc(points));
+  SGA_TRY(seg_start.alloc(points));
+  const int B = static_cast<int>(count);
+  const uint32_t *key_blocks = prefix.data(), *tiles = key_blocks + count + 1, *mean_blocks = tiles + count + 1;
+  grid_forest_count_launch();
+  hipLaunchKernelGGL((downsample_keys_forest_kernel<Key>), dim3(key_blocks[count]), dim3(256), 0, ctx->stream, d_members, d_prefix, B, 1.0 / leaf, keys.p, vals.p);
+  SGA_HIP(hipGetLastError());
+  grid_forest_count_launch();
+  SGA_TRY(sort_pairs(ctx, keys.p, keys_sorted.p, vals.p, order.p, points, 0, std::min<unsigned>(end_bit, 8 * sizeof(Key))));
+  grid_forest_count_launch();
+  hipLaunchKernelGGL((ds_segments_forest_kernel<Key>), dim3(tiles[count]), dim3(kSegThreads), 0, ctx->stream, d_members, d_prefix + count + 1, B, keys_sorted.p, ctx->vg_status.p, epoch, seg_start.p, hand);
+  SGA_HIP(hipGetLastError());
+  grid_forest_count_launch();
+  hipLaunchKernelGGL(ds_mean_forest_kernel, dim3(mean_blocks[count]), dim3(256), 0, ctx->stream, d_members, d_prefix + 2 * (count + 1), B, seg_start.p, order.p);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;  // (the buffers go to the stream's free list: reused only behind these kernels)
+}
 }  // namespace
+
+namespace sga {
+GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, double leaf) {
+  GridForestPlan P;
+  for (size_t k = 0; k < count; k++) {
+    const sga_cloud* c = clouds[k];
+    if (c->n == 0) continue;  // an empty cloud for an empty cloud: no kernel runs
+    bool joins = c->n <= kSpeculativeMax && P.points + c->n <= kGridForestMaxPoints;
+    if (joins) {
+      const VoxelPlan vp = voxelgrid_plan(c, leaf);
+      const int W = std::max(P.W, vp.L.total + 1), member_bits = bits_for(static_cast<long long>(P.forest.size()) + 1);
+      joins = vp.box && W + member_bits <= 64;
+      if (joins) {
+        P.W = W;
+        P.member_bits = member_bits;
+        P.forest.push_back(k);
+        P.points += c->n;
+        P.tiles += vp.tiles;
+      }
+    }
+    if (!joins) P.lone.push_back(k);
+  }
+  if (!P.forest.empty()) P.key_bytes = P.W + P.member_bits <= 32 ? 4 : 8;
+  return P;
+}
+
+// `table`: [members][scratch: 4 x uint32 per member][ticket][prefix of the key grid, of the tiles, of the centroid grid: count + 1 each],
+// written in pinned memory, one copy command
+int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq) {
+  const size_t count = plan.forest.size();
+  if (count == 0) return SGA_OK;
+  std::vector<GridMember> members(count);
+  std::vector<uint32_t> prefix(3 * (count + 1), 0u);
+  const size_t member_words = count * (sizeof(GridMember) / 8), scratch_words = 2 * count, prefix_words = (prefix.size() + 1) / 2;
+  const size_t words = member_words + scratch_words + 1 + prefix_words;
+  DevBuf<unsigned long long> table;
+  SGA_TRY(table.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
+  uint32_t* host_scratch = reinterpret_cast<uint32_t*>(host + member_words);
+  uint32_t off = 0;
+  for (size_t j = 0; j < count; j++) {
+    const sga_cloud* c = clouds[plan.forest[j]];
+    const VoxelPlan vp = voxelgrid_plan(c, leaf);
+    const uint32_t n = static_cast<uint32_t>(c->n);
+    GridMember& g = members[j];
+    std::memset(&g, 0, sizeof(g));
+    g.pts = c->pts.p;
+    g.out = out[j];
+    g.scratch = reinterpret_cast<uint32_t*>(table.p + member_words) + 4 * j;
+    g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
+    g.ox = c->origin[0], g.oy = c->origin[1], g.oz = c->origin[2];
+    g.tag = plan.W < 64 ? static_cast<unsigned long long>(j) << plan.W : 0ull;  // (W = 64: one member, number 0)
+    g.bad = g.tag | (1ull << vp.L.total);
+    g.L = vp.L;
+    g.n = n;
+    g.off = off;
+    off += n;
+    host_scratch[4 * j + 2] = n;  // valid points: lowered by the first dropped point the runs kernel meets
+    prefix[j + 1] = prefix[j] + (n + 255u) / 256u;
+    prefix[count + 1 + j + 1] = prefix[count + 1 + j] + vp.tiles;
+    prefix[2 * (count + 1) + j + 1] = prefix[2 * (count + 1) + j] + (n * 8u + 255u) / 256u;
+  }
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words + scratch_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
+  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  unsigned epoch = 0;
+  SGA_TRY(voxelgrid_status(ctx, prefix[2 * count + 1], &epoch));
+  const GridMember* d_members = reinterpret_cast<const GridMember*>(table.p);
+  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(table.p + member_words + scratch_words + 1);
+  const ForestBoxes hand{reinterpret_cast<unsigned*>(table.p + member_words + scratch_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  const unsigned end_bit = static_cast<unsigned>(plan.W + plan.member_bits);
+  return plan.key_bytes == 4 ? grid_forest_launch<uint32_t>(ctx, d_members, d_prefix, prefix, count, plan.points, leaf, end_bit, epoch, hand)
+                             : grid_forest_launch<unsigned long long>(ctx, d_members, d_prefix, prefix, count, plan.points, leaf, end_bit, epoch, hand);
+}
+}  // namespace sga
 
 extern "C" {
 

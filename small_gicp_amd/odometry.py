@@ -325,14 +325,16 @@ def run_synthetic(num_frames=20, pinned=False, **kw):
     }
 
 
-def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, batched_preprocessing=False):
+def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, batched_preprocessing=False, batched_downsampling=False):
     """The flow protocol (every pair (i - 1, i) registered from the identity, the relative poses multiplied up in frame order:
     odometry_benchmark_small_gicp_tbb_flow.cpp:73-110) with the registrations BATCHED: the scans are preprocessed as OnlineOdometry does,
     then groups of `batch` consecutive pairs are registered by one BatchProblem.align each — one search + factor launch, one row
     reduction and one hand-off per LM round for the whole group.  The last group may be smaller; batch = 1 works.  Returns the poses,
     the relative poses and iteration counts per pair, and the wall time of the registration stage per scan.
-    batched_preprocessing: the scans are still downsampled one by one, but the kd-trees and covariances of every `batch` scans are made
-    by one api.preprocess_batch (the same trees and covariances, bit for bit: the results do not change)."""
+    batched_preprocessing: the kd-trees and covariances of every `batch` scans are made by one api.preprocess_batch (the same trees and
+    covariances, bit for bit: the results do not change).
+    batched_downsampling: the raw scans of every `batch` frames are uploaded and downsampled by one api.voxelgrid_sampling_batch (the
+    same clouds, bit for bit); without it the scans are downsampled one by one."""
     from . import synthetic
 
     if batch < 1:
@@ -343,18 +345,28 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
         setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
         frames = []  # (cloud, tree) per scan
         pending = []  # downsampled scans waiting for their batched trees and covariances
+        raw = []  # uploaded scans waiting for their batched voxel grid
         for f in range(num_frames):
             pts, _ = synthetic.kitti_like_scan(f)
-            cloud = api.voxelgrid_sampling(api.PointCloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), ctx=ctx), downsampling_resolution)
-            if batched_preprocessing:
-                pending.append(cloud)
-                if len(pending) == batch or f == num_frames - 1:
-                    frames.extend(api.preprocess_batch(pending, num_neighbors))
-                    pending = []
-                continue
-            tree = api.KdTree(cloud)
-            api.estimate_covariances(cloud, tree, num_neighbors)
-            frames.append((cloud, tree))
+            scan = api.PointCloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), ctx=ctx)
+            if batched_downsampling:
+                raw.append(scan)
+                if len(raw) < batch and f < num_frames - 1:
+                    continue
+                clouds = api.voxelgrid_sampling_batch(raw, downsampling_resolution)
+                raw = []
+            else:
+                clouds = [api.voxelgrid_sampling(scan, downsampling_resolution)]
+            for cloud in clouds:
+                if batched_preprocessing:
+                    pending.append(cloud)
+                    continue
+                tree = api.KdTree(cloud)
+                api.estimate_covariances(cloud, tree, num_neighbors)
+                frames.append((cloud, tree))
+            if pending and (len(pending) >= batch or f == num_frames - 1):
+                frames.extend(api.preprocess_batch(pending, num_neighbors))
+                pending = []
         ctx.synchronize()
         rel, iters = [], []
         t0 = time.perf_counter()
