@@ -34,8 +34,9 @@ clean:
 	rm -rf build $(LIB)
 	$(MAKE) -C oracle clean
 .PHONY: all lib oracle clean trips stamps
-# experiment builds: the library with other compile-time settings, e.g.  make variant V=w6 VFLAGS=-DSGA_SEARCH_WAVES=6
+# experiment builds: the library with other compile-time settings, e.g.  make variant V=w6 VFLAGS=-DSGA_SL_WAVES=6
+# (the settings are read by linearize.hip and by pass_layout.hpp: whatever includes that header is compiled again)
 variant:
 	@mkdir -p build/obj_$(V) small_gicp_amd/lib
-	for f in $(SRCS); do o=build/obj_$(V)/$$(basename $$f .hip).o; if [ $$(basename $$f) = linearize.hip ] || [ ! -f $$o ]; then $(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $$f -o $$o || exit 1; fi; done
+	for f in $(SRCS); do o=build/obj_$(V)/$$(basename $$f .hip).o; if [ $$(basename $$f) = linearize.hip ] || grep -q pass_layout.hpp $$f || [ ! -f $$o ]; then $(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $$f -o $$o || exit 1; fi; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o small_gicp_amd/lib/libsmall_gicp_amd_$(V).so build/obj_$(V)/*.o

@@ -75,14 +75,14 @@ int sga_debug_set_voxelgrid_epoch(sga_context* ctx, unsigned epoch);
  * returns the milliseconds in between — the kernel times of bench.py's per-stage roofline lines (voxel grid, index build, covariances). */
 int sga_debug_timer_start(sga_context* ctx);
 int sga_debug_timer_stop(sga_context* ctx, double* ms);
-/* The host arithmetic of the frame check of sharded registrations (linearize.hip: problem_check_shard_frames), exposed so that it can be
+/* The host arithmetic of the frame check of sharded registrations (csrc/frames.hip: problem_check_shard_frames), exposed so that it can be
  * tested without a device: pack() turns a source origin into the SGA_FRAME_CHECK_DOUBLES values a rank contributes to the all-reduce,
  * agree() says whether the ranks whose contributions were summed all named the same origin (exact for any origin, up to 1024 ranks). */
 #define SGA_FRAME_CHECK_DOUBLES 32
 void sga_debug_shard_frame_pack(const double origin[3], double out[SGA_FRAME_CHECK_DOUBLES]);
 int sga_debug_shard_frame_agree(const double sum[SGA_FRAME_CHECK_DOUBLES]);
 /* The row sum that ends a linearization pass, on rows given by the caller: uploads `nrows` rows of 96 doubles and adds them exactly as a
- * pass does (csrc/linearize.hip: launch_reduce over the 95 columns of a row, reduce_groups(nrows) workgroups, fixed summation order, the
+ * pass does (csrc/reduce_rows.hpp: launch_reduce over the 95 columns of a row, reduce_groups(nrows) workgroups, fixed summation order, the
  * result handed to the host through the pinned block); derive != 0 fills the derived columns in from the totals as a pass does.
  * out = 96 doubles (column 95 is 0).  For tests of the summation order and for the clock stamps below. */
 int sga_debug_reduce_rows(sga_context* ctx, const double* rows, int nrows, int derive, double* out);

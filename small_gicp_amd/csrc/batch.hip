@@ -1,7 +1,7 @@
 // Batched registration: B independent (target kd-tree, source) problems of one context, linearized by ONE search + factor launch and
 // ONE row reduction per round, with one hand-off to the host for all pairs.  The kernels and the round itself
-// sit beside the lone kernels whose device functions they share (linearize.hip: batch_search_linearize_kernel,
-// batch_reduce_rows_kernel, batch_round); the lock-step LM / GN loop over the pairs is optimizer.hip's (sga_align_batch).  This file:
+// sit beside the lone kernels whose device functions they share (linearize.hip: batch_search_linearize_kernel, batch_round;
+// reduce_rows.hpp: batch_reduce_rows_kernel); the lock-step LM / GN loop over the pairs is optimizer.hip's (sga_align_batch).  This file:
 // the batch object and sga_batch_linearize.
 //
 // Scope: kd-tree targets; ICP, PLANE_ICP, GICP; distance or null rejector; fp32 pair arithmetic, no robust kernel, no host rejector,

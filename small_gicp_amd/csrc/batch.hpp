@@ -9,7 +9,7 @@ struct sga_batch {
   std::vector<int> tiles;              // 64-point tiles per pair (0: empty source or empty target); the pair's rows are its own partials[0, tiles)
   std::vector<long long> tile_prefix;  // tiles of the pairs before k (count + 1 entries): the whole batch must fit an int grid
   int max_depth = 0;                   // deepest target tree: sizes the LDS traversal stack of the launch
-  // the round table (linearize.hip: BatchPair): filled by the host in pinned memory, copied to the device with one command per round
+  // the round table (pass_layout.hpp: BatchPair): filled by the host in pinned memory, copied to the device with one command per round
   void* h_round = nullptr;
   sga::DevBuf<unsigned char> d_round;
   size_t round_bytes = 0;
@@ -31,9 +31,11 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
 void batch_unpack(const sga_batch* bt, size_t k, double* H, double* b, double* e, uint64_t* num_inliers);
 // validation of a batch call, before any device work (batch.hip)
 int batch_check(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp);
-// device frames (linearize.hip)
+// device frames (frames.hip)
 const double* problem_pose(const sga_problem* pb, const double T[16], double Td[16]);
 void problem_system_to_caller(const sga_problem* pb, double H[36], double b[6]);
-double error_model_value(const double* acc96, const double T_lin[16], const double T[16]);
-bool error_model_enabled();
+int problem_accumulator_to_caller(sga_context* ctx, const sga_problem* pb, double* d_out30);  // the same on the device, in place (asynchronous entry points)
+int problem_check_shard_frames(sga_context* ctx, sga_problem* pb);
+double error_model_value(const double* acc96, const double T_lin[16], const double T[16]);  // error_model.hip
+bool error_model_enabled();  // linearize.hip
 }  // namespace sga

@@ -6,9 +6,7 @@
 // sga_voxelgrid_sampling_batch does the same for the stage before them: B raw scans downsampled by one chain —
 // keys, ONE sort over the concatenation under the key (member, the member's own short key), runs, centroids — and one host wait.
 #include <atomic>
-#include <chrono>
 #include <memory>
-#include <thread>
 #include <unordered_set>
 #include <vector>
 
@@ -42,25 +40,10 @@ int forest_box_block(sga_context* ctx, size_t members) {
   return SGA_OK;
 }
 
-// the ONE wait of a forest call: all boxes (run counts) are there once the block shows the call's sequence number (note_wait's spin, context.hip)
+// the ONE wait of a forest call: all boxes (run counts) are there once the block shows the call's sequence number (wait_published, context.hip)
 int forest_boxes_wait(sga_context* ctx, unsigned long long seq, const char* what) {
-  const unsigned long long* word = ctx->h_forest;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; spins++) {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
-    __builtin_ia32_pause();
-    if (spins > 200000u) std::this_thread::yield();
-    if ((spins & 0xfffu) == 0xfffu) {
-      const hipError_t q = hipStreamQuery(ctx->stream);
-      if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-        (void)hipGetLastError();
-        SGA_HIP(hipStreamSynchronize(ctx->stream));
-        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
-        return fail(SGA_ERR_HIP, "the %s were not published by the device", what);
-      }
-      (void)hipGetLastError();  // hipErrorNotReady is sticky in hipGetLastError
-    }
-  }
+  const int rc = wait_published(ctx, ctx->h_forest, seq);
+  return rc == kNotPublished ? fail(SGA_ERR_HIP, "the %s were not published by the device", what) : rc;
 }
 
 namespace {

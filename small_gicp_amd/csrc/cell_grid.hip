@@ -193,7 +193,7 @@ struct GridParams {
   uint32_t* __restrict__ stats;
 };
 
-__device__ __forceinline__ int grid_tile_of_block() {  // XCD-aware tile order (linearize.hip: search_tile_of_block)
+__device__ __forceinline__ int grid_tile_of_block() {  // XCD-aware tile order (search_stage.hpp: search_tile_of_block)
   const int nblk = gridDim.x, per_xcd = nblk >> 3, b = blockIdx.x;
   return b < 8 * per_xcd ? (b & 7) * per_xcd + (b >> 3) : b;
 }

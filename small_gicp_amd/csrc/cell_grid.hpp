@@ -114,7 +114,7 @@ __device__ __forceinline__ float grid_rho2(const GridView& g, float qx, float qy
   return safe > 0.f ? safe * safe : 0.f;
 }
 
-__device__ __forceinline__ float grid_rex_from_r2(float r2) { return sqrtf(r2) * 0.9999995f; }  // as linearize.hip: sqrt of the bound, rounded down
+__device__ __forceinline__ float grid_rex_from_r2(float r2) { return sqrtf(r2) * 0.9999995f; }  // as search_stage.hpp (rex_from_r2): sqrt of the bound, rounded down
 
 // nn / nn2 / rex of a query whose block has been scanned.  Returns false if the block does not settle it.  by_face (optional): the
 // exclusion radius ends at the block's FACE, not at a third target point — a radius a tree walk could widen.

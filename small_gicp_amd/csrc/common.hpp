@@ -109,7 +109,7 @@ struct sga_context {
   bool registered = false;  // known to the allocator (context.hip)
   // scratch
   sga::DevBuf<double> d_accum;    // 128 doubles: a linearization result (30, or 96 with the error model)
-  sga::DevBuf<unsigned> d_ticket; // arrival counter of the reduction kernel (linearize.hip), zero between launches
+  sga::DevBuf<unsigned> d_ticket; // arrival counter of the reduction kernel (reduce_rows.hpp), zero between launches
   double* h_accum = nullptr;      // pinned + device-mapped: [0, 128) a result, word 128 = sequence number of the last published result
   double* h_accum_dev = nullptr;  // device address of h_accum
   // pinned, device-mapped staging ring for uploads from pageable memory (context.hip): the pack kernel reads a slot over PCIe while
@@ -349,7 +349,7 @@ struct sga_problem {
   void* rejector_user = nullptr;
   const double* caller_T = nullptr;  // the pose as the caller passed it to the linearization being dispatched (what a host rejector is shown)
   sga::DevBuf<unsigned char> reject;
-  // the quadratic error model of the last linearization (linearize.hip): valid for trial poses until the next linearization
+  // the quadratic error model of the last linearization (error_model.hip): valid for trial poses until the next linearization
   bool model_valid = false;
   double model[96] = {0};        // the reduced row: system + model sums
   double model_T[16] = {0};      // its pose

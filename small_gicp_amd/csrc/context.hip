@@ -720,25 +720,32 @@ unsigned long long note_begin(sga_context* ctx, unsigned long long** dev_slot) {
   *dev_slot = ctx->h_notes_dev + (seq % kNoteSlots) * kNoteWords;
   return seq;
 }
-int note_wait(sga_context* ctx, unsigned long long seq, unsigned long long payload[kNoteWords - 1]) {
-  const unsigned long long* slot = ctx->h_notes + (seq % kNoteSlots) * kNoteWords;
+int wait_published(sga_context* ctx, const unsigned long long* word, unsigned long long seq) {
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0;; spins++) {
-    if (__atomic_load_n(slot, __ATOMIC_ACQUIRE) == seq) break;
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
+#if defined(__x86_64__)
     __builtin_ia32_pause();
-    if (spins > 200000u) std::this_thread::yield();
+#else
+    std::this_thread::yield();
+#endif
+    if (spins > 200000u) std::this_thread::yield();  // a word normally arrives within tens of microseconds; past ~1 ms stop hogging the core
     if ((spins & 0xfffu) == 0xfffu) {
       // the stream has drained without publishing (a fault), or this is taking implausibly long: let the runtime report it
       const hipError_t q = hipStreamQuery(ctx->stream);
-      if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-        (void)hipGetLastError();
-        SGA_HIP(hipStreamSynchronize(ctx->stream));
-        if (__atomic_load_n(slot, __ATOMIC_ACQUIRE) == seq) break;
-        return fail(SGA_ERR_HIP, "a note was not published by the device");
-      }
       (void)hipGetLastError();  // hipErrorNotReady is sticky in hipGetLastError
+      if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+        SGA_HIP(hipStreamSynchronize(ctx->stream));
+        return __atomic_load_n(word, __ATOMIC_ACQUIRE) == seq ? SGA_OK : kNotPublished;
+      }
     }
   }
+}
+int note_wait(sga_context* ctx, unsigned long long seq, unsigned long long payload[kNoteWords - 1]) {
+  const unsigned long long* slot = ctx->h_notes + (seq % kNoteSlots) * kNoteWords;
+  const int rc = wait_published(ctx, slot, seq);
+  if (rc == kNotPublished) return fail(SGA_ERR_HIP, "a note was not published by the device");
+  SGA_TRY(rc);
   for (int k = 0; k < kNoteWords - 1; k++) payload[k] = slot[1 + k];
   return SGA_OK;
 }

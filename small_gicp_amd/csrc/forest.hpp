@@ -43,7 +43,7 @@ struct ForestBoxes {
 };
 
 // by ONE thread of a member (a tree's root level, a grid's last tile), after it wrote the member's words of the box block: the last member
-// to arrive publishes the call's sequence number (agent-scope ticket, system-scope release: batch_reduce_rows_kernel's hand-off, linearize.hip)
+// to arrive publishes the call's sequence number (agent-scope ticket, system-scope release: batch_reduce_rows_kernel's hand-off, reduce_rows.hpp)
 __device__ __forceinline__ void forest_box_arrive(const ForestBoxes& h) {
   __threadfence_system();
   if (__hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == h.total - 1u) {

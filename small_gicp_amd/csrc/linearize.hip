@@ -16,11 +16,23 @@
 // coefficients of the quadratic error model sga_error answers from without a pass over the cloud; error_kernel (K2) only for robust
 // factors, the async API and tests.  Sums: DPP inside a wave (fp32), fp64 across waves, one row of 96 doubles per tile / chunk /
 // workgroup, added in fixed order by reduce_rows_kernel (no floating-point atomics: bit-reproducible).
+//
+// Where things live.  THIS translation unit compiles every kernel of the pass — the device code of the four headers exists here only,
+// and so does every compile-time knob (SGA_SL_WAVES, SGA_SL_WAVES_WARM, SGA_CERT_WAVES, SGA_MAX_BLOCKS, SGA_SPACING_REF):
+//   pass_layout.hpp    the partial row (constants, the comment that documents its columns) and the parameter structs LinParams, NNParams,
+//                      ErrParams, FusedTail, BatchPair
+//   search_stage.hpp   device functions of the search: tile_schedule, certify, walk_lane, search_lane, search_tile_of_block
+//   factor_stage.hpp   device functions of the factors: pair_factor, pair_moments, accumulate_moments, kernarg_lin_params, linearize_group
+//   reduce_rows.hpp    derived_entry, fused_tail, reduce_rows_kernel, batch_reduce_rows_kernel, launch_reduce
+//   linearize.hip      the __global__ pass kernels, the tuning table, the routing (Route, PassPlan, plan_pass, linearize_dispatch,
+//                      error_dispatch), the two halves of the entry points (enqueue / collect), batch_round, the C entry points that launch
+//                      a kernel of this file, preload_hot_kernels
+// and beside it, in translation units of their own (they launch no template of this file):
+//   frames.hip         device frames at the C-ABI boundary (problem_pose, problem_system_to_caller, frame_accumulator_kernel) and the shard frame check
+//   error_model.hip    the quadratic error model on the host (error_model_value, sga_error_model_eval) and sga_unpack_accumulator
+//   context.hip        wait_published (notes.hpp): the one host wait for a sequence word the device publishes
 #include <algorithm>
-#include <chrono>
-#include <thread>
 #include <type_traits>
-#include <utility>
 
 #include "batch.hpp"
 #include "common.hpp"
@@ -30,6 +42,11 @@
 #include "kd_search.hpp"
 #include "projective.hpp"
 #include "voxel_hash.hpp"
+#include "notes.hpp"
+#include "pass_layout.hpp"
+#include "search_stage.hpp"
+#include "factor_stage.hpp"
+#include "reduce_rows.hpp"
 
 void sga_profile_collect_pending(sga_context* ctx);
 
@@ -43,297 +60,6 @@ int grid_rings_for(const sga_index* idx, double reach);
 
 #ifndef SGA_SPACING_REF
 #define SGA_SPACING_REF 0.5486  // length scale (geometric mean leaf diagonal) of the C3 target (scripts/spacing_probe.py), the scene the routing thresholds were tuned on
-#endif
-constexpr int kTile = 256;           // threads per workgroup = source points per tile
-constexpr int kRow = 96;             // doubles per partial row: [0, 29) the system (21 H, 6 b, e, inliers), [32, 95) the quadratic error model
-constexpr int kCols = 128;           // columns the reduction kernels handle (>= kRow)
-constexpr int kModelOff = 32;        // error model: [32, 41) sum p_a g_j, [41, 59) sum p_a M'_c, [59, 95) sum p_a p_b M'_c
-constexpr int kModelCols = 95;
-constexpr int kStatsCol = 30;        // spare columns 30, 31: search statistics of a grid pass (cell_grid.hip), not sums over points
-constexpr int kSearchBlock = 64;      // search kernels: one wave per workgroup
-#ifndef SGA_MAX_BLOCKS
-#define SGA_MAX_BLOCKS 2048
-#endif
-constexpr int kMaxBlocks = SGA_MAX_BLOCKS;  // linearize_kernel / error_kernel / certify_linearize_kernel: 8 workgroups per CU
-
-// Small grids (a 15k-point scan is 60 workgroups) fold the final reduction into the producer kernel: every workgroup publishes its
-// partial row (agent-scope write-through stores), takes a ticket, and the workgroup that arrives last adds the rows in fixed order
-// and hands the result over — one launch and one dependent-launch gap less per pass.  (With the 2048 workgroups of a 1M-point pass
-// the ticket contention costs more than the launch: those keep the separate reduce_rows_kernel.)  Where the gain ends, measured late in
-// round 6 on VGICP iterations of 3k ... 400k points (the workgroups of a streaming kernel finish together and take the ticket one after
-// the other, an agent-scope acquire / release each): 12 workgroups -1.6 us per pass, 24 -0.6, 40 +1.1, 63 +3.4, 120 (30k points) +10,
-// 235 (60k) +25, 245 (250k points at four per lane) +30 us — the limit was 256 since round 3.
-constexpr int kFuseMaxBlocks = 32;
-constexpr int kSeqWord = 128;  // h_accum: [0, 128) a result, word 128 the sequence number of the last published one
-struct FusedTail {
-  int enabled;
-  unsigned* ticket;
-  double* out;        // device result (out_n doubles)
-  int out_n;
-  double* host;       // pinned, device-mapped host result or null
-  unsigned long long seq;
-};
-
-__host__ __device__ inline double derived_entry(int col, const double* m);
-__host__ __device__ inline bool is_derived_col(int c);
-
-// derive: the row holds a linearization in moment form — its derived columns are filled in from the totals (derived_entry)
-__device__ __forceinline__ void fused_tail(const FusedTail& f, const double* __restrict__ partials, int nrows, int ncols, int row_stride, bool derive = false) {
-  __shared__ unsigned sh_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this workgroup's row has left the CU
-  __syncthreads();
-  // agent-scope release (this workgroup's row, ordered before by the barrier) / acquire (the rows of the workgroups that arrived earlier)
-  if (threadIdx.x == 0) sh_last = __hip_atomic_fetch_add(f.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == static_cast<unsigned>(nrows - 1) ? 1u : 0u;
-  __syncthreads();
-  if (!sh_last) return;  // workgroup-uniform
-  // 2 slices of 128 columns: slice s adds rows s, s + 2, ... (independent loads), then the slices are added in fixed order
-  __shared__ double sh_slice[2][kCols];
-  {
-    const int c = threadIdx.x & (kCols - 1), sl = threadIdx.x / kCols;
-    double t = 0.0;
-    if (c < ncols && sl < 2)
-      for (int r = sl; r < nrows; r += 2) t += __hip_atomic_load(&partials[static_cast<size_t>(r) * row_stride + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (sl < 2) sh_slice[sl][c] = t;
-  }
-  __syncthreads();
-  if (derive) {  // workgroup-uniform
-    if (threadIdx.x < kCols) sh_slice[0][threadIdx.x] += sh_slice[1][threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x < kCols) sh_slice[1][threadIdx.x] = 0.0;
-    __syncthreads();
-  }
-  if (threadIdx.x < kCols) {
-    const int c = threadIdx.x;
-    const double t = (derive && is_derived_col(c)) ? derived_entry(c, sh_slice[0]) : sh_slice[0][c] + sh_slice[1][c];
-    if (c < f.out_n) {
-      const double v = c < ncols ? t : 0.0;
-      f.out[c] = v;
-      if (f.host != nullptr) f.host[c] = v;
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
-  if (f.host != nullptr) {
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(f.host + kSeqWord), f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-template <typename Real>
-struct LinParams {
-  const float4* __restrict__ src_pts;
-  const Cov8* __restrict__ src_cov;
-  int n;
-  int num_tiles;
-  const float4* __restrict__ tgt_pts;
-  const float4* __restrict__ tgt_nrm;
-  const Cov8* __restrict__ tgt_cov;
-  KdView kd;
-  VoxelView vox;
-  FlatView flat;
-  int* __restrict__ corr;
-  const int* __restrict__ hint;  // exact nearest neighbour per source point at this pose (kd position) or -1, from nn_search_kernel
-  const unsigned char* __restrict__ reject;  // optional: verdict of a host rejector per source point in the CALLER's order (1 = reject)
-  Real* __restrict__ maha;  // n*6
-  int store_maha;  // cache the mahalanobis matrices for the error kernel (robust factors); otherwise they are recomputed if ever asked for
-  Rigid<Real> T;
-  Real max_sq;   // INFINITY = no rejector; in the pair arithmetic's type: fp64 passes compare double distances with the double threshold (rejector.hpp)
-  float bound2;  // a neighbour counts only if kd_dist2 < bound2 (max_sq nudged up by an ulp, or INFINITY); the walks reach a little farther
-  int robust_kind;
-  Real robust_c;
-  double* __restrict__ partials;
-  FusedTail tail;
-  // warm pass with the certificate check inside the factor kernel (certify_linearize_kernel): the certificate of the previous
-  // linearization pose T_prev is checked per point on the way through; a point whose certificate fails contributes nothing to the
-  // streaming part, is flagged (rex[i] = -(exploration slack) < 0) and walks at the end of its workgroup's step
-  int* __restrict__ cert_nn;
-  int* __restrict__ cert_nn2;
-  float* __restrict__ cert_rex;
-  uint32_t* __restrict__ cert_walked;
-  Rigid<Real> T_prev;
-  float cert_within2, cert_slack_min, cert_slack_max;
-  float cert_pad;  // headroom of the certificate check (see certify)
-};
-
-// XCD-aware tile schedule: workgroup b runs on XCD b % 8 (observed placement; used for L2 affinity only).  Each XCD
-// gets one contiguous 1/8th of the (spatially sorted) tiles so that neighbouring tiles share an L2.
-__device__ __forceinline__ void tile_schedule(int num_tiles, int& first, int& stride, int& end, int nblocks = 0) {
-  if (nblocks == 0) nblocks = gridDim.x;
-  if (nblocks % 8 == 0 && num_tiles >= nblocks) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd_blocks = nblocks >> 3;
-    const int t0 = static_cast<int>((static_cast<long long>(num_tiles) * xcd) >> 3);
-    const int t1 = static_cast<int>((static_cast<long long>(num_tiles) * (xcd + 1)) >> 3);
-    first = t0 + slot;
-    stride = per_xcd_blocks;
-    end = t1;
-  } else {
-    first = blockIdx.x;
-    stride = nblocks;
-    end = num_tiles;
-  }
-}
-
-template <typename Real>
-__device__ __forceinline__ Sym3<Real> load_sym(const Cov8* __restrict__ c, int i) {
-  const float4 a = reinterpret_cast<const float4*>(c)[2 * i];
-  const float4 b = reinterpret_cast<const float4*>(c)[2 * i + 1];
-  return {Real(a.x), Real(a.y), Real(a.z), Real(a.w), Real(b.x), Real(b.y)};
-}
-
-// exclusion radius stored per point: sqrt of the walk's exclusion bound, rounded down
-__device__ __forceinline__ float rex_from_r2(float r2) { return sqrtf(r2) * 0.9999995f; }
-
-// The walks search a little farther than the rejector reaches: a source point without a neighbour inside max_dist then carries the
-// certificate "nothing within max_dist * (1 + margin)" and stays settled while it moves by less than the margin — without it those
-// points (isolated clutter: the longest walks there are) would be searched again in every pass.
-constexpr float kSearchMargin = 0.05f;
-
-// The search: exact nearest neighbour of every transformed source point: nn[i] = its kd position (or -1 when nothing lies within the
-// search bound), rex[i] = the exclusion radius the walk certifies (kd_search.hpp: every OTHER target point is farther than rex[i]).
-//
-// COLD pass (check = 0): the full walk for every point, seeded with the previous neighbour.
-// WARM pass (check = 1): nn[] / rex[] describe the previous linearization pose T_prev.  The query has moved by
-// delta = |T p - T_prev p| since; if the old neighbour is now closer than rex[i] - delta, no other point can be closer (triangle
-// inequality): it is still the exact nearest neighbour, the lane shrinks the radius by delta and is done — no tree access at all.
-// Only the lanes whose certificate fails walk (seeded with the old neighbour, which usually is the answer).  A small relative margin
-// covers the rounding of the fp32 distances; it only ever sends a lane into the walk, never changes a result.  Late LM iterations
-// move the points by micrometres: their passes are a stream over 40 bytes per point.
-//
-// One wave per workgroup (a finished wave frees its slot and its 4 KB of stack at once; the hardware dispatcher balances the uneven
-// walks) at 7 - 8 waves per SIMD (72 / 64 VGPRs), which the walk needs.  The factor stage either follows inside the same wave
-// (search_linearize_kernel: the moment form needs 42 VGPRs at one point per lane) or runs as linearize_kernel over nn[].
-template <typename Real>
-struct NNParams {
-  const float4* __restrict__ src_pts;
-  int n;
-  KdView kd;
-  Rigid<Real> T;
-  float bound2;      // the walks find neighbours with kd_dist2 < bound2 (the rejector's reach + kSearchMargin)
-  float within2;     // a neighbour counts for the rejector only if kd_dist2 < within2
-  float slack_min, slack_max;  // exploration slack of a re-walk = clamp(motion, slack_min, slack_max) (kSlackMin / kSlackMax)
-  float cert_pad;    // headroom of the certificate check as a share of the point's motion (see certify; SGA_CERT_PAD)
-  int* __restrict__ nn;
-  int* __restrict__ nn2;   // the runner-up of every walk: second candidate of the certificate
-  float* __restrict__ rex;
-  int check;         // warm pass
-  Rigid<Real> T_prev;
-  uint32_t* __restrict__ walked;  // statistics, one counter per wave tile: lanes of warm passes that had to walk
-  const uint32_t* __restrict__ tile_order;  // launch slot -> tile (longest tile first), or null: slot = tile
-  uint32_t* __restrict__ tile_cost;         // out, or null: duration of the tile's wave (100 MHz ticks)
-  int* __restrict__ leaves;  // diagnostics (sga_problem_set_search_stats): leaves scanned per source point in this pass, or null
-  double inv_leaf;   // 2^depth / n (kd_leaf_rank)
-  int chunk_tiles;   // queue-fed kernel: tiles of 64 queries per wave
-  int fast;          // one-query-per-lane kernels: walk with the fast leaf scan (exact repeat where it cannot decide)
-  GridView grid;     // the target's cell grid (cell_grid.hpp), if grid_walk
-  int grid_walk;     // the walkers of certify_linearize_kernel try ring 1 of the grid before they walk the tree
-};
-
-// Returns the shrunken radius (relative to the new pose) or a negative value if the certificate fails.
-// Headroom (round 5): the DECISION asks for pad * moved metres more than the certificate needs, the radius handed on is the true one.
-// A point that is sent into the walk although its certificate holds is found again exactly, so nothing but the number of walkers
-// depends on it.  Why: the steps of an LM run shrink geometrically, and a certificate that survives this pass by less than the motion
-// still to come fails in one of the LATE passes — where the streaming kernel pays for the tail of a single walk —
-// whereas this pass walks thousands of points anyway and the re-walk (exploration slack = this pass's motion) buys a certificate that
-// lasts.  Measured on C3 (profiles/r05_cert_pad.txt): walkers of the passes after 1.7 / 0.29 / 0.05 mm 14 021 / 2 625 / 413 -> 2 091 /
-// 89 / 6 at pad 0.6, those passes 128 / 96 / 68 -> 92 / 78 / 62 us.  pad = 0: the plain check, bit for bit.
-__device__ __forceinline__ float certify(float rex, float moved, bool has_neighbour, float d2_new, float within2, float pad) {
-  const float lim = rex - moved * 1.000001f;
-  const float lim_d = lim - moved * pad;
-  const float lim2 = lim_d > 0.f ? lim_d * lim_d * 0.999995f : -1.f;
-  const bool ok = has_neighbour ? d2_new < lim2 : lim2 > within2;  // no neighbour within reach before: still none
-  return ok ? lim * 0.9999995f : -1.f;
-}
-
-// The walk of ONE source point, top-down and seeded, with the fast leaf scan (kd_search.hpp); the rare query it cannot decide (two
-// candidates within 1e-6 of each other, or of the search bound) is searched again with the exact keys.  Stores nn / nn2 / rex.
-// `tid` = the lane's column of kd_stack ([level][BLOCK] words): threadIdx.x in the kernels whose workgroup is BLOCK wide; a kernel that gives
-// every wave of a wider workgroup its own stack passes the lane number (with threadIdx.x there, wave w's rows were shifted by w
-// and a full stack of wave 3 reached past the allocation).
-template <typename Real, int BLOCK>
-__device__ __forceinline__ int walk_lane(const NNParams<Real>& p, int i, float fx, float fy, float fz, int seed, float slack, uint32_t* __restrict__ kd_stack, int tid) {
-  KdBest nb{};
-  bool exact = p.fast == 0;
-  if (!exact) {
-    const KdBestFast f = kd_nearest_fast<BLOCK>(p.kd, fx, fy, fz, p.bound2, seed, kd_stack, tid, slack);
-    nb = f.best;
-    exact = f.ambiguous;
-  }
-  if (exact) nb = kd_nearest<BLOCK>(p.kd, fx, fy, fz, p.bound2, seed, kd_stack, tid, slack);
-  p.nn[i] = nb.idx;
-  p.nn2[i] = nb.idx2;
-  p.rex[i] = rex_from_r2(nb.r2);
-  if (p.leaves != nullptr) p.leaves[i] = nb.leaves;
-  return nb.idx;
-}
-
-// The search of ONE source point (a lane of a one-query-per-lane kernel): certificate check (warm) or walk, results stored to nn[] /
-// nn2[] / rex[]; returns the neighbour's kd position or -1.  Called by every lane of the wave that holds a point (`i < n`), also
-// under divergence: the wave-level steps inside kd_nearest only involve the lanes that walk.
-template <typename Real, int BLOCK, bool CHECK>  // CHECK: warm pass (two instantiations: the cold one carries no certificate / margin state in registers)
-__device__ __forceinline__ int search_lane(const NNParams<Real>& p, int tile, int i, const float4& ps, float fx, float fy, float fz, uint32_t* __restrict__ kd_stack) {
-  int seed = p.nn[i];
-  float slack = 0.f;
-  if constexpr (CHECK) {
-    Real ox, oy, oz;
-    transform_point<Real>(p.T_prev, ps.x, ps.y, ps.z, ox, oy, oz);
-    const float moved = sqrtf(kd_dist2(static_cast<float>(ox), static_cast<float>(oy), static_cast<float>(oz), fx, fy, fz));
-    const int cand2 = p.nn2[i];
-    float d1 = INFINITY, d2 = INFINITY;
-    if (seed >= 0) {
-      const float4 c = p.kd.pts[seed];
-      d1 = kd_dist2(c.x, c.y, c.z, fx, fy, fz);
-    }
-    if (cand2 >= 0) {
-      const float4 c = p.kd.pts[cand2];
-      d2 = kd_dist2(c.x, c.y, c.z, fx, fy, fz);
-    }
-    // the nearer of the two candidates (the canonical rule again: equidistant -> lower position)
-    const bool swap = cand2 >= 0 && (d2 < d1 || (d2 == d1 && cand2 < seed));
-    const int best = swap ? cand2 : seed;
-    const float r = certify(p.rex[i], moved, best >= 0, swap ? d2 : d1, p.within2, p.cert_pad);
-    if (r >= 0.f) {
-      p.rex[i] = r;
-      if (swap) {
-        p.nn[i] = cand2;
-        p.nn2[i] = seed;
-      }
-      return best;
-    }
-    seed = best;
-    // this point's certificate did not survive: walk again, and explore a margin around the new neighbour proportional to the motion,
-    // so that the certificate survives the following (smaller) steps
-    slack = fminf(fmaxf(moved, p.slack_min), p.slack_max);
-    const unsigned long long walking = __ballot(true);
-    if (threadIdx.x == __ffsll(static_cast<long long>(walking)) - 1) p.walked[tile] += static_cast<uint32_t>(__popcll(walking));  // the tile belongs to this wave: no atomic
-    // A point whose certificate failed sits next to a surface (isolated points carry wide certificates and rarely fail): ring 1 of the
-    // cell grid (cell_grid.hpp) settles it exactly with two dependent loads and gives the new certificate the tightest radius there is
-    // (the third-nearest distance); the walk — with its exploration margin — only for what the ring does not settle.
-    if (p.grid_walk & 2) {
-      int g_nn, g_nn2;
-      float g_rex, g_seen;
-      bool g_face = false;
-      // (a radius that ends at the ring's face with less than the re-walk's slack to spare is left to the walk: see certify_linearize_kernel)
-      if (grid_ring1_lane(p.grid, fx, fy, fz, p.bound2, g_nn, g_nn2, g_rex, g_seen, &g_face) && !(g_face && g_nn >= 0 && (p.grid_walk & 32) && g_rex - g_seen < slack)) {
-        p.nn[i] = g_nn;
-        p.nn2[i] = g_nn2;
-        p.rex[i] = g_rex;
-        return g_nn;
-      }
-    }
-  }
-  return walk_lane<Real, BLOCK>(p, i, fx, fy, fz, seed, CHECK ? slack : 0.f, kd_stack, threadIdx.x);
-}
-
-// XCD-aware tile order: workgroup b runs on XCD b % 8 (observed placement; only speed depends on it), and the source is sorted by
-// target leaf, so giving each XCD one contiguous eighth of the tiles makes its L2 hold one eighth of the target instead of all of it
-__device__ __forceinline__ int search_tile_of_block(int nblk = 0) {
-  if (nblk == 0) nblk = gridDim.x;
-  const int per_xcd = nblk >> 3, b = blockIdx.x;
-  return b < 8 * per_xcd ? (b & 7) * per_xcd + (b >> 3) : b;
-}
-
-#ifdef SGA_KD_TRIPS
-static __device__ unsigned long long g_kd_wave_times[2 * 32768];  // diagnostics build: start / end (100 MHz wall clock) of every search wave
 #endif
 
 template <typename Real, int BLOCK, bool CHECK>
@@ -375,15 +101,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 // one-query-per-lane kernel's (both are valid bounds).
 constexpr int kQueueCap = 128;        // entries; a tile is staged while at most kQueueCap - 64 are waiting
 constexpr int kPathRecords = 10;      // pair records fetched at once by kd_push_path: covers depth 20 (8 M points); deeper trees take a second batch
-
-template <typename Real, int FACTOR, int TARGET, int PTS, bool FRESH_NN = false, bool CERT = false, bool STAGED = false>
-__device__ __forceinline__ void linearize_group(const LinParams<Real>& p, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks = nullptr,
-                                                const ProjView* __restrict__ proj = nullptr);
-template <typename Real, int FACTOR, bool OWN_D2 = true>
-__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
-                                             const float4* nn_pre = nullptr);
-template <typename Real, int PTS>
-__device__ __forceinline__ void accumulate_moments(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3], const Real (&E)[PTS], int inliers, double* __restrict__ acc_row, int lane);
 
 // FACTOR >= 0: when the chunk's searches are done the wave also evaluates the factors of its chunk (four tiles at a time, like
 // linearize_kernel) and writes ONE partial row per chunk — in the warm passes this kernel runs, the memory system and the VALUs are
@@ -588,443 +305,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 6))) void
     }
   }
 #endif
-}
-
-// One correspondence (source point i at q = T p, target candidate j at t): rejector, fused mahalanobis, robust weight, the 28
-// values of the pair's system.  Returns whether the pair is an inlier; caches the mahalanobis (GICP).
-template <typename Real, int FACTOR>
-__device__ __forceinline__ bool pair_factor(const LinParams<Real>& p, int i, int j, bool within_bound, Real px, Real py, Real pz, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Real* vals, Sym3<Real>* Mp_out = nullptr,
-                                            Real* g_out = nullptr) {
-  const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
-  const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && !(d2 > p.max_sq);
-  if (inlier) {
-    Sym3<Real> M;
-    if constexpr (FACTOR == SGA_GICP) {
-      const Sym3<Real> Cs = load_sym<Real>(p.src_cov, i);
-      const Sym3<Real> Ct = load_sym<Real>(p.tgt_cov, j);
-      const Sym3<Real> RCR = rotate_sym(p.T.r, Cs);
-      M = inverse_sym<Real>({Ct.xx + RCR.xx, Ct.xy + RCR.xy, Ct.xz + RCR.xz, Ct.yy + RCR.yy, Ct.yz + RCR.yz, Ct.zz + RCR.zz});
-      Real* m = p.maha + static_cast<size_t>(i) * 6;
-      m[0] = M.xx;
-      m[1] = M.xy;
-      m[2] = M.xz;
-      m[3] = M.yy;
-      m[4] = M.yz;
-      m[5] = M.zz;
-    } else if constexpr (FACTOR == SGA_PLANE_ICP) {
-      const float4 nn = p.tgt_nrm[j];
-      M = {Real(nn.x) * Real(nn.x), Real(0), Real(0), Real(nn.y) * Real(nn.y), Real(0), Real(nn.z) * Real(nn.z)};
-    } else {
-      M = {Real(1), Real(0), Real(0), Real(1), Real(0), Real(1)};
-    }
-    Real w = Real(1);
-    if (p.robust_kind != SGA_ROBUST_NONE) {
-      const Real vx = M.xx * rx + M.xy * ry + M.xz * rz, vy = M.xy * rx + M.yy * ry + M.yz * rz, vz = M.xz * rx + M.yz * ry + M.zz * rz;
-      w = robust_weight<Real>(p.robust_kind, p.robust_c, Real(0.5) * (rx * vx + ry * vy + rz * vz));
-    }
-    pair_system<Real>(p.T.r, px, py, pz, rx, ry, rz, M, w, vals, Mp_out, g_out);
-  }
-  return inlier;
-}
-
-// The sums of one linearization, in MOMENT form.  With M' = R^T M R and g = R^T M r of a pair (source frame, device_math.hpp) and
-// p = the source point, everything the optimizer needs is linear in
-//   sum M'            sum g            sum p_a M'          sum p_a g          sum p_a p_b M'          sum e, #inliers
-//   (6 = H_tt)        (3 = -b_t)       (18)                (9)                (36)
-// because H_rt = sum skew(p) M', H_rr = sum skew(p) M' skew(p)^T and b_r = -sum skew(p) g only recombine those (derived_entry,
-// evaluated once per pass by the reducing workgroup).  The same sums ARE the coefficients of the quadratic ERROR MODEL:
-// Reduction::error (reduction_omp.hpp:61-70) evaluates sum_i 1/2 r_i^T M_i r_i at a trial pose with the correspondences and
-// mahalanobis matrices CACHED by the last linearization (gicp_factor.hpp:80-89); with those frozen it is a quadratic polynomial in
-// Y = [R^T R_n - I | R^T (tau_n - tau)] (trial pose (R_n, tau_n) relative to the linearization pose (R, tau)):
-//   e(T_n) = e0 - sum_a Y[:,a] . S1[a] + 1/2 sum_ab Y[:,a]^T S2[a][b] Y[:,b],   S1[a] = sum p~_a g,  S2[a][b] = sum p~_a p~_b M'
-// with p~ = (p, 1).  sga_error evaluates it on the host: no pass over the cloud, no device round trip.
-// 74 sums instead of the 29 of the direct form, but a lane adds up PTS points before a value goes through the wave reduction (the
-// DPP chain is what a sum costs): 74 * (PTS + 6) / PTS instructions per point instead of 29 * 7 + the skew products.
-// Row layout: [0, 21) H, [21, 27) b, 27 e, 28 inliers, [32, 41) sum p_a g_j, [41, 59) sum p_a M'_c, [59, 95) sum p_a p_b M'_c
-// (c = xx, xy, xz, yy, yz, zz; pairs ab = 00, 01, 02, 11, 12, 22); columns [0, 15) and [21, 24) are derived.
-__host__ __device__ inline double derived_entry(int col, const double* m) {
-  // position of (j, k) in a packed symmetric 3x3 {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, four bits each in one immediate: a table indexed at run
-  // time would live in constant memory, and its loads, cold in every launch, would stand between the last fold and the hand-off
-  auto S = [](int j, int k) { return static_cast<int>((0x542431210ull >> (4 * (3 * j + k))) & 15ull); };
-  auto A = [&](int a, int j, int k) { return m[kModelOff + 9 + 6 * a + S(j, k)]; };                   // sum p_a M'_jk
-  auto B = [&](int a, int b, int j, int k) { return m[kModelOff + 27 + 6 * S(a, b) + S(j, k)]; };     // sum p_a p_b M'_jk
-  auto G = [&](int a, int j) { return m[kModelOff + 3 * a + j]; };                                    // sum p_a g_j
-  // K = skew(p) M': K_ik = p_i1 M'_i2,k - p_i2 M'_i1,k  (i1 = i + 1, i2 = i + 2 mod 3)
-  auto PK = [&](int l, int i, int k) { const int i1 = (i + 1) % 3, i2 = (i + 2) % 3; return B(l, i1, i2, k) - B(l, i2, i1, k); };  // sum p_l K_ik
-  if (col >= 21) {  // b_r = -sum p x g
-    const int i = col - 21, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-    return G(i2, i1) - G(i1, i2);
-  }
-  // upper triangle of H, row-wise: row i starts at 6 i - i (i - 1) / 2
-  const int i = col < 6 ? 0 : (col < 11 ? 1 : 2);
-  const int j = col - (6 * i - i * (i - 1) / 2) + i;  // column in the 6x6
-  if (j >= 3) {  // H_rt = sum K
-    const int k = j - 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-    return A(i1, i2, k) - A(i2, i1, k);
-  }
-  // H_rr = sum K skew(p)^T: [i][j] = p_j1 K_i,j2 - p_j2 K_i,j1
-  const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-  return PK(j1, i, j2) - PK(j2, i, j1);
-}
-__host__ __device__ inline bool is_derived_col(int c) { return c < 15 || (c >= 21 && c < 24); }
-
-// M' and g of one correspondence (weighted by the robust kernel), its error, and whether it is an inlier; caches the mahalanobis
-// matrix for the error pass.  (The direct form — the 28 values of pair_system — is pair_factor below; the per-point export uses it.)
-// nn_pre (PLANE_ICP): the target normal when the caller has fetched it already (linearize_group over a flat map), else it is read here.
-// OWN_D2 = false: the caller's within_bound already is the rejector's verdict on the search's own distance (a projective target)
-template <typename Real, int FACTOR, bool OWN_D2>
-__device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, int j, bool within_bound, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Sym3<Real>& Mp, Real* g, Real& e, Sym3<Real>& M_out,
-                                             const float4* nn_pre) {
-  const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
-  const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && (!OWN_D2 || !(d2 > p.max_sq));
-  Mp = Sym3<Real>{};
-  g[0] = g[1] = g[2] = Real(0);
-  e = Real(0);
-  if (inlier) {
-    Sym3<Real> M;
-    if constexpr (FACTOR == SGA_GICP) {
-      const Sym3<Real> Cs = load_sym<Real>(p.src_cov, i);
-      const Sym3<Real> Ct = load_sym<Real>(p.tgt_cov, j);
-      const Sym3<Real> RCR = rotate_sym(p.T.r, Cs);
-      M = inverse_sym<Real>({Ct.xx + RCR.xx, Ct.xy + RCR.xy, Ct.xz + RCR.xz, Ct.yy + RCR.yy, Ct.yz + RCR.yz, Ct.zz + RCR.zz});
-      M_out = M;  // the caller caches it for the error pass (gicp_factor.hpp:80-89)
-    } else if constexpr (FACTOR == SGA_PLANE_ICP) {
-      const float4 nn = nn_pre != nullptr ? *nn_pre : p.tgt_nrm[j];
-      M = {Real(nn.x) * Real(nn.x), Real(0), Real(0), Real(nn.y) * Real(nn.y), Real(0), Real(nn.z) * Real(nn.z)};
-    } else {
-      M = {Real(1), Real(0), Real(0), Real(1), Real(0), Real(1)};
-    }
-    const Real vx = M.xx * rx + M.xy * ry + M.xz * rz, vy = M.xy * rx + M.yy * ry + M.yz * rz, vz = M.xz * rx + M.yz * ry + M.zz * rz;
-    const Real e0 = Real(0.5) * (rx * vx + ry * vy + rz * vz);
-    const Real w = p.robust_kind != SGA_ROBUST_NONE ? robust_weight<Real>(p.robust_kind, p.robust_c, e0) : Real(1);
-    const Real* R = p.T.r;
-    g[0] = w * (R[0] * vx + R[3] * vy + R[6] * vz);
-    g[1] = w * (R[1] * vx + R[4] * vy + R[7] * vz);
-    g[2] = w * (R[2] * vx + R[5] * vy + R[8] * vz);
-    Mp = rotate_sym_t(R, M);
-    Mp = {w * Mp.xx, w * Mp.xy, w * Mp.xz, w * Mp.yy, w * Mp.yz, w * Mp.zz};
-    e = w * e0;
-  }
-  return inlier;
-}
-
-// Adds the moments of PTS points per lane (zero M' / g / e for the points that are no inliers) to the wave's fp64 row in LDS.  The
-// lane adds its points up in registers; the 72 fp32 sums then go through ONE transposing wave reduction (device_math.hpp:
-// wave_transpose_sum, ~3 instructions per sum instead of a 6-step DPP chain each) that leaves the totals spread over the lanes —
-// lane l holds the sums number `slot` and 64 + slot — and every lane adds its own two to the row.  e is summed in fp64.
-// Must be called by all 64 lanes of the wave (cross-lane operations).
-// Sum number s -> row column: s < 6: H_tt (15 + s); s < 9: b_t (24 + s - 6); else the error-model block (kModelOff + s - 9).
-constexpr int kMomentSums = 72;
-__host__ __device__ constexpr int moment_column(int s) { return s < 6 ? 15 + s : (s < 9 ? 18 + s : kModelOff - 9 + s); }
-
-// the S-th sum of one lane's PTS points (S is a template parameter: every index below is a compile-time constant, so the 72 values
-// live in registers — a run-time-indexed array of them would be placed in scratch memory)
-template <typename Real, int PTS, int S>
-__device__ __forceinline__ Real moment_sum(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3]) {
-  auto m6 = [&](int u, int c) -> Real { return c == 0 ? Mp[u].xx : (c == 1 ? Mp[u].xy : (c == 2 ? Mp[u].xz : (c == 3 ? Mp[u].yy : (c == 4 ? Mp[u].yz : Mp[u].zz)))); };
-  Real v = Real(0);
-  if constexpr (S < 6) {
-#pragma unroll
-    for (int u = 0; u < PTS; u++) v += m6(u, S);
-  } else if constexpr (S < 9) {
-#pragma unroll
-    for (int u = 0; u < PTS; u++) v -= G[u][S - 6];
-  } else if constexpr (S < 18) {
-    constexpr int a = (S - 9) / 3, j = (S - 9) % 3;
-#pragma unroll
-    for (int u = 0; u < PTS; u++) v += P[u][a] * G[u][j];
-  } else if constexpr (S < 36) {
-    constexpr int a = (S - 18) / 6, c = (S - 18) % 6;
-#pragma unroll
-    for (int u = 0; u < PTS; u++) v += P[u][a] * m6(u, c);
-  } else {
-    constexpr int pair = (S - 36) / 6, c = (S - 36) % 6;
-    constexpr int a = pair < 3 ? 0 : (pair < 5 ? 1 : 2), b = pair < 3 ? pair : (pair < 5 ? pair - 2 : 2);
-#pragma unroll
-    for (int u = 0; u < PTS; u++) v += (P[u][a] * P[u][b]) * m6(u, c);
-  }
-  return v;
-}
-template <typename Real, int PTS, int BASE, int... S>  // v[S] = sum number BASE + S
-__device__ __forceinline__ void moment_sums(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3], Real (&v)[sizeof...(S)], std::integer_sequence<int, S...>) {
-  ((v[S] = moment_sum<Real, PTS, BASE + S>(P, Mp, G)), ...);
-}
-
-template <typename Real, int PTS>
-__device__ __forceinline__ void accumulate_moments(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3], const Real (&E)[PTS], int inliers, double* __restrict__ acc_row, int lane) {
-  double es = 0.0;
-#pragma unroll
-  for (int u = 0; u < PTS; u++) es += static_cast<double>(E[u]);
-  const double et = wave_sum_f64(es);
-  if (lane == 0) {
-    acc_row[27] += et;
-    acc_row[28] += static_cast<double>(inliers);
-  }
-  if constexpr (sizeof(Real) == 4 && PTS == 1) {
-    // inside the one-query-per-lane search kernels (64 VGPRs): two reductions of 36 sums each — all 72 at once do not fit the register
-    // budget there, and the spills (60 bytes per lane through scratch memory) showed up as 60 MB of HBM traffic per pass
-    constexpr int kHalf = kMomentSums / 2;
-#pragma unroll
-    for (int part = 0; part < 2; part++) {
-      float v[kHalf];
-      if (part == 0)
-        moment_sums<float, PTS, 0>(P, Mp, G, v, std::make_integer_sequence<int, kHalf>{});
-      else
-        moment_sums<float, PTS, kHalf>(P, Mp, G, v, std::make_integer_sequence<int, kHalf>{});
-      float lo, hi;
-      int slot;
-      wave_transpose_sum<kHalf>(v, lane, lo, hi, slot);
-      if (slot < kHalf) acc_row[moment_column(part * kHalf + slot)] += static_cast<double>(lo);
-    }
-    return;
-  }
-  Real v[kMomentSums];
-  moment_sums<Real, PTS, 0>(P, Mp, G, v, std::make_integer_sequence<int, kMomentSums>{});
-  if constexpr (sizeof(Real) == 4) {
-    float lo, hi;
-    int slot;
-    wave_transpose_sum<kMomentSums>(v, lane, lo, hi, slot);
-    acc_row[moment_column(slot)] += static_cast<double>(lo);
-    if (slot + 64 < kMomentSums) acc_row[moment_column(slot + 64)] += static_cast<double>(hi);
-  } else {
-#pragma unroll
-    for (int s = 0; s < kMomentSums; s++) {
-      const double t = wave_sum_f64(v[s]);
-      if (lane == 0) acc_row[moment_column(s)] += t;
-    }
-  }
-}
-
-// The kernel's FIRST argument (a LinParams) read again from the kernel-argument segment through a pointer the compiler cannot see through:
-// the scalar loads of the fields a stage uses are issued in that stage and their registers die with it.  Without this the compiler loads
-// every field at the kernel's start and keeps all of them for its whole length — more than the 100 scalar registers a wave has, so it
-// parks them in the lanes of vector registers and fetches them back one v_readlane at a time (certify_linearize_kernel: 448 of its ~3 200
-// vector instructions per wave).  Only valid inside a kernel whose first parameter is the LinParams<Real> passed by value.
-template <typename Real>
-__device__ __forceinline__ const LinParams<Real>& kernarg_lin_params() {
-  using Args = const __attribute__((address_space(4))) LinParams<Real>;
-  Args* a = (Args*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(a));
-  return *(const LinParams<Real>*)a;
-}
-
-// The factor stage as a kernel of its own.  TARGET: 0 kd-tree (the neighbours come from the search kernel), 1 Gaussian voxel map, 2 flat voxel map, 3 projective
-// search (`proj`: ann/projective_search.hpp; the lookup of these targets happens right here).  Streaming + two gathers; a lane handles PTS points (PTS x kTile consecutive points per
-// workgroup step), their products are added up in registers, reduced with DPP inside the wave, in fp64 across waves.
-// The factors of PTS points per lane — points first, first + stride, ... below `limit` — added to the wave's row.
-// FRESH_NN: hint[] was written earlier in this very kernel (by any lane of this wave): read it past the vector L1.
-// STAGED (the caller is a kernel whose first argument is `p0` itself): every stage reads the parameters it uses afresh (kernarg_lin_params).
-template <typename Real, int FACTOR, int TARGET, int PTS, bool FRESH_NN, bool CERT, bool STAGED>
-__device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int first, int stride, int limit, double* __restrict__ acc_row, int lane, unsigned long long* __restrict__ failed_masks,
-                                                const ProjView* __restrict__ proj) {
-#define SGA_STAGE_PARAMS(name) const LinParams<Real>& name = STAGED ? kernarg_lin_params<Real>() : p0
-  SGA_STAGE_PARAMS(p);
-  Real P[PTS][3], G[PTS][3], E[PTS];
-  Sym3<Real> Mp[PTS];
-  int inliers = 0;
-  // The PTS points of a lane go through the stages TOGETHER — source point + neighbour index, neighbour point, covariances — so
-  // that the loads of a stage are in flight at once (one latency per stage, not per point); the stores (mahalanobis cache,
-  // correspondence) come after the last load, or they would pin the loads of the next point behind them.
-  float4 ps4[PTS];
-  int jn[PTS];
-  bool act[PTS];
-#pragma unroll
-  for (int u = 0; u < PTS; u++) {
-    const int i = first + u * stride;
-    act[u] = i < limit;
-    ps4[u] = act[u] ? p.src_pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    jn[u] = -1;
-    if constexpr (TARGET == 0 && CERT)
-      jn[u] = act[u] ? p.cert_nn[i] : -1;  // (the same array as hint[]: read through the pointer it is written through)
-    else if constexpr (TARGET == 0)
-      jn[u] = act[u] ? (FRESH_NN ? __hip_atomic_load(&p.hint[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : p.hint[i]) : -1;
-  }
-  Real Q[PTS][3], Tg[PTS][3];
-  bool within[PTS];
-  {
-  SGA_STAGE_PARAMS(p);
-#pragma unroll
-  for (int u = 0; u < PTS; u++) {
-    P[u][0] = ps4[u].x, P[u][1] = ps4[u].y, P[u][2] = ps4[u].z;  // multiplied by zero M' / g when the point is no inlier
-    Q[u][0] = Q[u][1] = Q[u][2] = Real(0);
-    if (act[u]) transform_point(p.T, P[u][0], P[u][1], P[u][2], Q[u][0], Q[u][1], Q[u][2]);
-    Tg[u][0] = Tg[u][1] = Tg[u][2] = Real(0);
-    within[u] = true;
-    if constexpr (TARGET == 2) {
-      if (act[u]) {
-        float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
-        jn[u] = flat_nearest<Real>(p.flat, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2], m);
-        Tg[u][0] = m.x, Tg[u][1] = m.y, Tg[u][2] = m.z;
-      }
-    } else if constexpr (TARGET == 3) {
-      // the windowed scan of projective_search.hpp:107-140 (projective.hpp); the rejector (rejector.hpp:19-28) judges the scan's own
-      // distance, in Real, so pair_moments does not measure the pair again
-      if (act[u]) {
-        Real d2 = Real(0);
-        jn[u] = projective_nearest<Real>(*proj, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2], d2);
-        within[u] = jn[u] >= 0 && !(d2 > p.max_sq);
-        const float4 m = jn[u] >= 0 ? p.tgt_pts[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-        Tg[u][0] = m.x, Tg[u][1] = m.y, Tg[u][2] = m.z;
-      }
-    } else if constexpr (TARGET == 1) {
-      if (act[u]) {
-        if (p.vox.offsets == 1)  // (wave-uniform) the default: the query's own voxel, no distance to compare
-          jn[u] = voxel_lookup(p.vox, static_cast<float>(Q[u][0]), static_cast<float>(Q[u][1]), static_cast<float>(Q[u][2]));
-        else
-          jn[u] = voxel_nearest<Real>(p.vox, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2]);
-      }
-    }
-  }
-  }
-  if constexpr (TARGET != 2 && TARGET != 3) {
-    float4 m4[PTS];
-    if constexpr (CERT && TARGET == 0) {
-      // The certificate check of the warm pass (search_lane / nn_search_queue_kernel: the same arithmetic, bit for bit) on the way through:
-      // both candidates of the previous pass are fetched, the nearer one (canonical rule) is the neighbour if its new distance is
-      // below the exclusion radius minus the point's motion; otherwise the point is flagged for the walkers' kernel and skipped here.
-      int c2[PTS];
-      float rx[PTS];
-      float4 m4b[PTS];
-      {
-        SGA_STAGE_PARAMS(p);
-#pragma unroll
-        for (int u = 0; u < PTS; u++) {
-          const int i = first + u * stride;
-          c2[u] = act[u] ? p.cert_nn2[i] : -1;
-          rx[u] = act[u] ? p.cert_rex[i] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < PTS; u++) {
-          m4[u] = jn[u] >= 0 ? p.tgt_pts[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-          m4b[u] = c2[u] >= 0 ? p.tgt_pts[c2[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
-      SGA_STAGE_PARAMS(p);
-#pragma unroll
-      for (int u = 0; u < PTS; u++) {
-        const int i = first + u * stride;
-        bool failed = false;
-        if (act[u]) {
-          const float fx = static_cast<float>(Q[u][0]), fy = static_cast<float>(Q[u][1]), fz = static_cast<float>(Q[u][2]);
-          Real ox, oy, oz;
-          transform_point<Real>(p.T_prev, P[u][0], P[u][1], P[u][2], ox, oy, oz);
-          const float moved = sqrtf(kd_dist2(static_cast<float>(ox), static_cast<float>(oy), static_cast<float>(oz), fx, fy, fz));
-          const float d1 = jn[u] >= 0 ? kd_dist2(m4[u].x, m4[u].y, m4[u].z, fx, fy, fz) : INFINITY;
-          const float d2 = c2[u] >= 0 ? kd_dist2(m4b[u].x, m4b[u].y, m4b[u].z, fx, fy, fz) : INFINITY;
-          const bool swap = c2[u] >= 0 && (d2 < d1 || (d2 == d1 && c2[u] < jn[u]));  // the canonical rule: equidistant -> lower position
-          const int best = swap ? c2[u] : jn[u];
-          const float r = certify(rx[u], moved, best >= 0, swap ? d2 : d1, p.cert_within2, p.cert_pad);
-          failed = !(r >= 0.f);
-          // settled: the shrunken radius; failed: the flag of the walkers' kernel, which is also the exploration slack of the re-walk
-          p.cert_rex[i] = failed ? -fminf(fmaxf(moved, p.cert_slack_min), p.cert_slack_max) : r;
-          if (swap) {  // (for a walker: its seed is the nearer candidate)
-            p.cert_nn[i] = c2[u];
-            p.cert_nn2[i] = jn[u];
-            m4[u] = m4b[u];
-          }
-          jn[u] = failed ? -1 : best;
-        }
-        const unsigned long long fm = __ballot(failed);
-        if (lane == 0) {
-          failed_masks[u] = fm;  // (LDS) which of this wave's 64 points of sub-step u walk
-          if (fm != 0ull) p.cert_walked[i >> 6] += static_cast<uint32_t>(__popcll(fm));  // the 64 points belong to this wave: no atomic
-        }
-        if (failed) act[u] = false;  // the walk phase writes its correspondence
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < PTS; u++) m4[u] = jn[u] >= 0 ? p.tgt_pts[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    bool decided64[PTS];
-#pragma unroll
-    for (int u = 0; u < PTS; u++) decided64[u] = false;
-    if constexpr (TARGET == 0 && !CERT && sizeof(Real) == 8) {
-      // fp64 per-pair arithmetic: the reference compares DOUBLE distances (ann/knn_result.hpp:80-100, double queries against the stored
-      // points).  The walk compared fp32 distances of the fp32-rounded query; it also kept its runner-up — the only other point that can
-      // be the nearest in double when the two agree to fp32 rounding.  Both candidates are measured again here, in double, against the
-      // double query: the nearer one is the correspondence (equidistant: the lower kd position, the canonical rule), and the rejector's
-      // test (rejector.hpp:19-28: reject iff sq_dist > max_dist_sq) runs on that double distance.  hint[] / hint2[] / rex[] — the state of
-      // the SEARCH — stay what the walk wrote.
-      if (p.cert_nn2 != nullptr) {
-#pragma unroll
-        for (int u = 0; u < PTS; u++) {
-          const int i = first + u * stride;
-          if (!act[u] || jn[u] < 0) continue;
-          const int j2 = p.cert_nn2[i];
-          const double ax = static_cast<double>(m4[u].x) - Q[u][0], ay = static_cast<double>(m4[u].y) - Q[u][1], az = static_cast<double>(m4[u].z) - Q[u][2];
-          double d1 = ax * ax + ay * ay + az * az;
-          if (j2 >= 0) {
-            const float4 c = p.tgt_pts[j2];
-            const double bx = static_cast<double>(c.x) - Q[u][0], by = static_cast<double>(c.y) - Q[u][1], bz = static_cast<double>(c.z) - Q[u][2];
-            const double d2 = bx * bx + by * by + bz * bz;
-            if (d2 < d1 || (d2 == d1 && j2 < jn[u])) {
-              d1 = d2;
-              jn[u] = j2;
-              m4[u] = c;
-            }
-          }
-          within[u] = d1 <= p.max_sq;
-          if (p.reject != nullptr) within[u] = within[u] && p.reject[__float_as_uint(ps4[u].w)] == 0;
-          decided64[u] = true;
-        }
-      }
-    }
-    SGA_STAGE_PARAMS(p);
-#pragma unroll
-    for (int u = 0; u < PTS; u++) {
-      Tg[u][0] = m4[u].x, Tg[u][1] = m4[u].y, Tg[u][2] = m4[u].z;
-      if constexpr (TARGET == 0) {
-        if (jn[u] >= 0 && !decided64[u]) {
-          // the search reaches a little beyond the rejector (kSearchMargin) and a certified neighbour may have drifted out of
-          // reach: a neighbour counts only inside the reach of a plain search, whichever way it was found
-          within[u] = kd_dist2(m4[u].x, m4[u].y, m4[u].z, static_cast<float>(Q[u][0]), static_cast<float>(Q[u][1]), static_cast<float>(Q[u][2])) < p.bound2;
-          if (p.reject != nullptr) within[u] = within[u] && p.reject[__float_as_uint(ps4[u].w)] == 0;
-        }
-      }
-    }
-  }
-  Sym3<Real> Mh[PTS];  // the mahalanobis matrices, stored after the last load
-  bool inl[PTS];
-  // point-to-plane over a flat map: the normals of the PTS slots the search has just found, one 16-byte gather each, in flight together
-  constexpr bool kFlatNormals = TARGET == 2 && FACTOR == SGA_PLANE_ICP;
-  float4 nn4[kFlatNormals ? PTS : 1];
-  if constexpr (kFlatNormals) {
-    SGA_STAGE_PARAMS(p);
-#pragma unroll
-    for (int u = 0; u < PTS; u++) nn4[u] = act[u] && jn[u] >= 0 ? p.tgt_nrm[jn[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  {
-  SGA_STAGE_PARAMS(p);
-#pragma unroll
-  for (int u = 0; u < PTS; u++) {
-    const int i = first + u * stride;
-    inl[u] = false;
-    Mp[u] = Sym3<Real>{};
-    Mh[u] = Sym3<Real>{};
-    G[u][0] = G[u][1] = G[u][2] = E[u] = Real(0);
-    if (act[u]) inl[u] = pair_moments<Real, FACTOR, TARGET != 3>(p, i, jn[u], within[u], Q[u][0], Q[u][1], Q[u][2], Tg[u][0], Tg[u][1], Tg[u][2], Mp[u], G[u], E[u], Mh[u], kFlatNormals ? &nn4[u] : nullptr);
-    inliers += __popcll(__ballot(inl[u]));
-  }
-  }
-  SGA_STAGE_PARAMS(pw);
-#pragma unroll
-  for (int u = 0; u < PTS; u++) {
-    const int i = first + u * stride;
-    if (act[u]) {
-      pw.corr[i] = inl[u] ? jn[u] : -1;
-      if constexpr (FACTOR == SGA_GICP) {
-        if (inl[u] && pw.store_maha) {  // only robust factors read it back (error kernel); otherwise it is recomputed on demand
-          Real* m = pw.maha + static_cast<size_t>(i) * 6;
-          m[0] = Mh[u].xx, m[1] = Mh[u].xy, m[2] = Mh[u].xz, m[3] = Mh[u].yy, m[4] = Mh[u].yz, m[5] = Mh[u].zz;
-        }
-      }
-    }
-  }
-  if (inliers == 0) return;  // wave-uniform
-  accumulate_moments<Real, PTS>(P, Mp, G, E, inliers, acc_row, lane);
-#undef SGA_STAGE_PARAMS
 }
 
 template <typename Real, int FACTOR, int TARGET, int PTS>
@@ -1297,19 +577,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CHECK ? SGA_
 #endif
 }
 
-// ---- batched registration (batch.hip): the rounds of B independent problems ---------------------------------
-// One entry of a round's table per ACTIVE pair, largest pair first: what search_linearize_kernel receives as its two arguments, for
-// that pair at its pose of the round.  The table lives in device memory (it does not fit the kernel-argument segment for large B); a
-// wave reads its pair's entry with scalar loads (uniform_const).
-struct BatchPair {
-  NNParams<float> q;
-  LinParams<float> p;
-  int ntiles;    // 64-point tiles of the pair = its partial rows, p.partials[0, ntiles)
-  int seedless;  // the walks start without the neighbour of an earlier pass (first round of a registration)
-  int pair;      // position in the batch: the reduced row goes to host[pair * kRow]
-  int pad;
-};
-
 // (uniform_const: uniform.hpp — a wave-uniform pointer into memory that nothing writes while the kernel runs, read with scalar loads)
 
 // search_linearize_kernel (cold) for the tiles of all active pairs in one grid.  Workgroup (= wave) b belongs to the pair k with
@@ -1399,22 +666,6 @@ __global__ __launch_bounds__(256) void per_point_kernel(const LinParams<Real> p,
   for (int k = 0; k < 28; k++) out28[static_cast<size_t>(orig) * 28 + k] = static_cast<double>(vals[k]);
 }
 
-template <typename Real>
-struct ErrParams {
-  const float4* __restrict__ src_pts;
-  int n;
-  int num_tiles;
-  const float4* __restrict__ tgt_pts;
-  const float4* __restrict__ tgt_nrm;
-  const int* __restrict__ corr;
-  const Real* __restrict__ maha;
-  Rigid<Real> T;
-  int robust_kind;
-  Real robust_c;
-  double* __restrict__ partials;
-  FusedTail tail;
-};
-
 template <typename Real, int FACTOR>
 __global__ __launch_bounds__(kTile) void error_kernel(const ErrParams<Real> p) {
   __shared__ double sh_e[kTile / 64];
@@ -1462,173 +713,6 @@ __global__ __launch_bounds__(kTile) void error_kernel(const ErrParams<Real> p) {
   if (p.tail.enabled) fused_tail(p.tail, p.partials, gridDim.x, 1, 1);
 }
 
-// Deterministic fp64 sum of `nrows` partial rows of `ncols` (<= 32) doubles in ONE launch of G = 32 workgroups: workgroup g sums
-// rows g, g+G, g+2G, ... into row g of `stage`; the workgroup that finishes LAST (a ticket counter) adds the G stage rows in fixed
-// order — which workgroup that is changes nothing in the arithmetic — and writes out[ncols] (+ zero padding up to out_n).
-// Hand-off between workgroups (per-CU L1s and per-XCD L2s are not coherent): a workgroup writes its stage row, a barrier orders the
-// row before lane 0's ticket increment, which is an agent-scope release / acquire (the row accesses themselves are agent-scope
-// relaxed atomics, i.e. write-through stores and cache-bypassing loads); only these <= 64 workgroups touch the ticket.  (Putting the ticket into the 2048 workgroups of the producer kernel was measured: +20 us.)
-// When `host` is given the result is handed to the host right here: copied into pinned, device-mapped host memory, then a
-// sequence number is published (system-scope release) on which the host spins.  This replaces hipMemcpyAsync +
-// hipStreamSynchronize, whose fixed cost is paid twice per optimizer iteration.
-constexpr int kReduceGroups = 64;
-
-#ifdef SGA_REDUCE_STAMPS
-// diagnostics build (make stamps): 100 MHz wall clock at six points of reduce_rows_kernel — 0 entry, 1 end of stage 1, 2 after the
-// ticket, 3 end of stage 2, 4 after the host stores, 5 after the system fence — taken by thread 0 of the first workgroup ([0, 6)), of
-// the last one ([8, 14)) and of the one that arrived last and finished the sum ([16, 22); [22] its index, [23] the workgroups)
-static __device__ unsigned long long g_reduce_stamps[24];
-#define SGA_STAMP(k)                                                                         \
-  do {                                                                                       \
-    if (threadIdx.x == 0) {                                                                  \
-      const unsigned long long stamp_now = wall_clock64();                                   \
-      stamp_local[k] = stamp_now;                                                            \
-      if (blockIdx.x == 0) g_reduce_stamps[k] = stamp_now;                                   \
-      if (blockIdx.x == gridDim.x - 1) g_reduce_stamps[8 + (k)] = stamp_now;                 \
-    }                                                                                        \
-  } while (0)
-#else
-#define SGA_STAMP(k) ((void)0)
-#endif
-
-constexpr int kReduceSlices = 8;  // 1024 threads = 8 slices of 128 columns
-__global__ __launch_bounds__(kReduceSlices * kCols) void reduce_rows_kernel(
-  const double* __restrict__ partials, int nrows, int ncols, int row_stride, double* __restrict__ stage, unsigned* __restrict__ ticket, double* __restrict__ out, int out_n, double* __restrict__ host,
-  unsigned long long seq, int derive, const uint32_t* __restrict__ stats) {
-  __shared__ double sh[kReduceSlices][kCols];
-  __shared__ unsigned sh_ticket;
-  const int c = threadIdx.x & (kCols - 1), s = threadIdx.x / kCols;
-  const int G = gridDim.x;
-#ifdef SGA_REDUCE_STAMPS
-  unsigned long long stamp_local[6] = {0, 0, 0, 0, 0, 0};
-#endif
-  SGA_STAMP(0);
-  // stage 1: (workgroup g, slice s) adds rows g + G * s, g + G * (s + 8), ...: four independent chains, the loads of a chain in flight together
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  if (c < ncols) {
-    const int step = G * kReduceSlices;
-    int r = blockIdx.x + G * s;
-    for (; r + 3 * step < nrows; r += 4 * step) {
-      const double v0 = partials[static_cast<size_t>(r) * row_stride + c], v1 = partials[static_cast<size_t>(r + step) * row_stride + c];
-      const double v2 = partials[static_cast<size_t>(r + 2 * step) * row_stride + c], v3 = partials[static_cast<size_t>(r + 3 * step) * row_stride + c];
-      a0 += v0, a1 += v1, a2 += v2, a3 += v3;
-    }
-    for (; r < nrows; r += step) a0 += partials[static_cast<size_t>(r) * row_stride + c];
-  }
-  sh[s][c] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  auto fold = [&]() {  // sh[0][c] = sum over the slices, fixed order
-    if (threadIdx.x < kCols) {
-      double t = 0.0;
-#pragma unroll
-      for (int k = 0; k < kReduceSlices; k++) t += sh[k][threadIdx.x];
-      sh[0][threadIdx.x] = t;
-    }
-    __syncthreads();
-  };
-  fold();
-  SGA_STAMP(1);
-  if (G > 1) {
-    if (threadIdx.x < kCols) __hip_atomic_store(&stage[blockIdx.x * kCols + threadIdx.x], sh[0][threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);  // release this workgroup's stage row, acquire the earlier ones
-    __syncthreads();
-    SGA_STAMP(2);
-    if (sh_ticket != static_cast<unsigned>(G - 1)) return;  // workgroup-uniform
-    // the last workgroup adds the G <= 64 stage rows: slice s takes rows s, s + 8, ...: at most 8 loads per thread, all in flight
-    double v[kReduceGroups / kReduceSlices];
-#pragma unroll
-    for (int k = 0; k < kReduceGroups / kReduceSlices; k++) {
-      const int g = s + k * kReduceSlices;
-      v[k] = g < G ? __hip_atomic_load(&stage[g * kCols + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    }
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < kReduceGroups / kReduceSlices; k++) t += v[k];
-    __syncthreads();
-    sh[s][c] = t;
-    __syncthreads();
-    fold();
-  }
-  SGA_STAMP(3);
-  if (threadIdx.x < kCols) {
-    const int cc = threadIdx.x;
-    const double t = (derive && is_derived_col(cc)) ? derived_entry(cc, sh[0]) : sh[0][cc];  // moment form: H_rr, H_rt, b_r from the totals
-    if (cc < out_n) {
-      double r = cc < ncols ? t : 0.0;
-      if (stats != nullptr && (cc == kStatsCol || cc == kStatsCol + 1)) r = static_cast<double>(stats[cc - kStatsCol]);  // a grid pass's search statistics ride along in two spare columns
-      out[cc] = r;
-      if (host != nullptr) host[cc] = r;
-    }
-  }
-  if (G > 1 && threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
-  if (host != nullptr) {
-    SGA_STAMP(4);
-    // only the two waves that stored the result fence it; all sixteen meet at the barrier.  (A system-scope fence writes the L2 back and
-    // invalidates it, ~0.15 us per wave, one wave after the other: sixteen of them stood 2.6 us in front of the sequence word, two 0.7:
-    // profiles/reduce_chain_split.txt, blocks 2 and 3.)
-    if (threadIdx.x < kCols) __threadfence_system();
-    __syncthreads();
-    SGA_STAMP(5);
-    if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host + kSeqWord), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-#ifdef SGA_REDUCE_STAMPS
-  if (threadIdx.x == 0) {  // the workgroup that finished the sum
-    for (int k = 0; k < 6; k++) g_reduce_stamps[16 + k] = stamp_local[k];
-    g_reduce_stamps[22] = blockIdx.x, g_reduce_stamps[23] = gridDim.x;
-  }
-#endif
-}
-
-// The sums of a round: workgroup k adds the rows of the k-th active pair in the fixed order of reduce_rows_kernel's single-workgroup form
-// (slice s: rows s, s + 8, ... in four chains; then the slices), derives the moment-form columns and stores the pair's kRow doubles
-// into the pinned, device-mapped result block.  The workgroup that arrives last publishes the round's sequence number: ONE hand-off
-// for all pairs (the release / acquire chain of box_reduce_publish, notes.hpp).
-__global__ __launch_bounds__(kReduceSlices * kCols) void batch_reduce_rows_kernel(const BatchPair* __restrict__ pairs, unsigned* __restrict__ ticket, double* __restrict__ host, double* __restrict__ seq_word, unsigned long long seq) {
-  __shared__ double sh[kReduceSlices][kCols];
-  __shared__ unsigned sh_ticket;
-  const BatchPair* d = uniform_const(pairs + blockIdx.x);
-  const double* __restrict__ partials = d->p.partials;
-  const int nrows = d->ntiles, out_row = d->pair;
-  const int c = threadIdx.x & (kCols - 1), s = threadIdx.x / kCols;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  if (c < kModelCols) {
-    constexpr int step = kReduceSlices;
-    int r = s;
-    for (; r + 3 * step < nrows; r += 4 * step) {
-      const double v0 = partials[static_cast<size_t>(r) * kRow + c], v1 = partials[static_cast<size_t>(r + step) * kRow + c];
-      const double v2 = partials[static_cast<size_t>(r + 2 * step) * kRow + c], v3 = partials[static_cast<size_t>(r + 3 * step) * kRow + c];
-      a0 += v0, a1 += v1, a2 += v2, a3 += v3;
-    }
-    for (; r < nrows; r += step) a0 += partials[static_cast<size_t>(r) * kRow + c];
-  }
-  sh[s][c] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (threadIdx.x < kCols) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < kReduceSlices; k++) t += sh[k][threadIdx.x];
-    sh[0][threadIdx.x] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kRow) {
-    const int cc = threadIdx.x;
-    const double t = is_derived_col(cc) ? derived_entry(cc, sh[0]) : sh[0][cc];
-    host[static_cast<size_t>(out_row) * kRow + cc] = cc < kModelCols ? t : 0.0;
-  }
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (sh_ticket != gridDim.x - 1) return;  // workgroup-uniform
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next round
-    __threadfence_system();
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(seq_word), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
 // Longest tile first.  A pass of the one-query-per-lane kernel is 1.9 rounds of waves, and 35 - 40 % of it is the drain of the waves
 // that happened to start last and run long.  Which tiles run long is only known afterwards — but after a small
 // motion the next pass's costs resemble this one's (correlation 0.9 at <= 0.1 m, scripts/diag_lpt.py).  This kernel sorts the tiles of
@@ -1657,17 +741,6 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __rest
   }
   if (x == 0)
     for (int t = 8 * per_xcd + threadIdx.x; t < num_tiles; t += blockDim.x) order[t] = static_cast<uint32_t>(t);  // the (< 8) tiles beyond the XCD shares
-}
-
-// partial rows (one per workgroup of linearize_kernel / error_kernel, or one per 64 source points when the search kernel does the factor algebra itself);
-// the stage-1 rows of the reduction follow them
-static size_t partial_rows(size_t n) { return std::max<size_t>(kMaxBlocks, (n + 63) / 64); }
-
-static int reduce_groups(int nrows) { return nrows > 256 ? std::min(kReduceGroups, std::max(8, nrows / 128)) : 1; }  // <= 256 rows: one workgroup, no hand-off between workgroups
-
-static void launch_reduce(sga_context* ctx, const double* partials, int nrows, int ncols, int row_stride, double* stage, double* out, int out_n, double* host, unsigned long long seq, bool derive = false, const uint32_t* stats = nullptr) {
-  const int groups = reduce_groups(nrows);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(groups), dim3(kReduceSlices * kCols), 0, ctx->stream, partials, nrows, ncols, row_stride, stage, ctx->d_ticket.p, out, out_n, host, seq, derive ? 1 : 0, stats);
 }
 
 // ---- the tuning table of the pass routing ------------------------------------------------------------------------------------------
@@ -2265,27 +1338,14 @@ __global__ void publish_kernel(const double* __restrict__ src, int count, double
   if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host + kSeqWord), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// spin until the device has published `seq` in the pinned sequence word `word` (null: the context's own, behind h_accum)
+// wait until the device has published `seq` in the pinned sequence word `word` (null: the context's own, behind h_accum)
 static int wait_result(sga_context* ctx, unsigned long long seq, const double* word = nullptr) {
-  const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(word != nullptr ? word : ctx->h_accum + kSeqWord);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; spins++) {
-    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
-    __builtin_ia32_pause();
-    if (spins > 200000u) std::this_thread::yield();  // a result normally arrives within tens of microseconds; past ~1 ms stop hogging the core
-    if ((spins & 0xfffu) == 0xfffu) {
-      // the stream has drained without publishing (a fault), or this is taking implausibly long: let the runtime report it
-      const hipError_t q = hipStreamQuery(ctx->stream);
-      if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-        SGA_HIP(hipStreamSynchronize(ctx->stream));
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return SGA_OK;
-        // a faulted or aborted launch may have left the arrival counter of reduce_rows_kernel non-zero: the next result on this
-        // context would never be published
-        (void)hipMemsetAsync(ctx->d_ticket.p, 0, ctx->d_ticket.n * sizeof(unsigned), ctx->stream);
-        return fail(SGA_ERR_HIP, "result was not published by the device");
-      }
-    }
-  }
+  const int rc = wait_published(ctx, reinterpret_cast<const unsigned long long*>(word != nullptr ? word : ctx->h_accum + kSeqWord), seq);
+  if (rc != kNotPublished) return rc;
+  // a faulted or aborted launch may have left the arrival counter of reduce_rows_kernel non-zero: the next result on this
+  // context would never be published
+  (void)hipMemsetAsync(ctx->d_ticket.p, 0, ctx->d_ticket.n * sizeof(unsigned), ctx->stream);
+  return fail(SGA_ERR_HIP, "result was not published by the device");
 }
 
 // single GPU: the final reduction kernel publishes; with a communicator the all-reduce comes first
@@ -2342,122 +1402,10 @@ void sga_profile_collect_pending(sga_context* ctx) {
   }
   ctx->pending = 0;
 }
-namespace sga {
-
-}  // namespace sga
-
-namespace sga {
-// ---- device frames (common.hpp): what crosses the boundary is converted HERE, everything below works between the two device frames ----
-bool problem_framed(const sga_problem* pb) { return !origin_is_zero(pb->src_origin) || !origin_is_zero(pb->target->origin); }
-// the caller's pose -> the same rigid motion between the source's and the target's device frames; returns Td (or T itself when both origins are 0)
-const double* problem_pose(const sga_problem* pb, const double T[16], double Td[16]) {
-  if (!problem_framed(pb)) return T;
-  pose_to_device(T, pb->src_origin, pb->target->origin, Td);
-  return Td;
-}
-void problem_system_to_caller(const sga_problem* pb, double H[36], double b[6]) {
-  if (!origin_is_zero(pb->src_origin)) system_to_caller(pb->src_origin, H, b);
-}
-// the 30-double accumulator of the asynchronous entry points, in place on the device (one thread: a 6x6 congruence)
-__global__ void frame_accumulator_kernel(double* __restrict__ acc, double ox, double oy, double oz) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double H[36], b[6];
-  int k = 0;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++) {
-      H[6 * i + j] = H[6 * j + i] = acc[k];
-      k++;
-    }
-  for (int i = 0; i < 6; i++) b[i] = acc[21 + i];
-  const double X[3][3] = {{0, oz, -oy}, {-oz, 0, ox}, {oy, -ox, 0}};  // -skew(o), see system_to_caller (context.hip)
-  double HA[6][6];
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j < 6; j++) {
-      double v = H[6 * i + j];
-      if (j < 3)
-        for (int c = 0; c < 3; c++) v += H[6 * i + 3 + c] * X[c][j];
-      HA[i][j] = v;
-    }
-  k = 0;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++) {
-      double v = HA[i][j];
-      if (i < 3)
-        for (int c = 0; c < 3; c++) v += X[c][i] * HA[3 + c][j];
-      acc[k++] = v;
-    }
-  for (int i = 0; i < 3; i++) {
-    double v = b[i];
-    for (int c = 0; c < 3; c++) v += X[c][i] * b[3 + c];
-    acc[21 + i] = v;
-  }
-}
-// Sharded contexts add the ranks' accumulators: their moments are sums over source points in the SOURCE's device frame, so every rank's
-// shard must live in the same one (slices of one uploaded cloud do: sga_cloud_slice; separately uploaded shards name a common origin:
-// sga_cloud_create_*_origin).  Checked once per problem with one small sum over the ranks: all equal <=> n sum(o^2) == (sum o)^2.
-// The ranks of a sharded registration must share ONE source frame (their accumulators are added).  Compared with one all-reduce of sums
-// that are EXACT for any number of ranks and any origin (n * sum(o^2) == (sum o)^2 on the doubles themselves rounds differently
-// on both sides for 3+ ranks and non-round origins): every origin coordinate is cut into four 16-bit pieces of its bit pattern, each an
-// integer < 2^16, and the ranks add the pieces p and their squares p^2.  All of those sums are integers below 2^53 for up to 2^10 ranks, so
-// they do not depend on the order of the additions, every rank reads the same numbers and takes the same decision, and by the equality case
-// of Cauchy-Schwarz  n * sum(p^2) == (sum p)^2  holds iff all ranks hold the same piece.
-constexpr int kFrameCheckDoubles = SGA_FRAME_CHECK_DOUBLES;
-void shard_frame_pack(const double origin[3], double out[kFrameCheckDoubles]) {
-  for (int k = 0; k < 3; k++) {
-    const double o = origin[k] + 0.0;  // -0.0 and +0.0 are one origin
-    unsigned long long bits;
-    memcpy(&bits, &o, sizeof(bits));
-    for (int j = 0; j < 4; j++) {
-      const double piece = static_cast<double>((bits >> (16 * j)) & 0xffffull);
-      out[4 * k + j] = piece;
-      out[12 + 4 * k + j] = piece * piece;
-    }
-  }
-  out[24] = 1.0;  // the number of ranks
-  for (int i = 25; i < kFrameCheckDoubles; i++) out[i] = 0.0;
-}
-bool shard_frame_agree(const double sum[kFrameCheckDoubles]) {
-  for (int i = 0; i < 12; i++)
-    if (sum[24] * sum[12 + i] != sum[i] * sum[i]) return false;
-  return true;
-}
-int problem_check_shard_frames(sga_context* ctx, sga_problem* pb) {
-  if (pb->frame_checked || !ctx->sharded()) return SGA_OK;
-  double h[kFrameCheckDoubles];
-  shard_frame_pack(pb->src_origin, h);
-  DevBuf<double> d;
-  SGA_TRY(d.alloc(kFrameCheckDoubles));
-  SGA_HIP(hipMemcpyAsync(d.p, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  SGA_HIP(hipStreamSynchronize(ctx->stream));
-  SGA_TRY(comm_allreduce_sum(ctx, d.p, kFrameCheckDoubles));
-  SGA_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-  SGA_HIP(hipStreamSynchronize(ctx->stream));
-  if (!shard_frame_agree(h))
-    return fail(SGA_ERR_INVALID, "the source shards of the ranks live in different device frames (origins differ): slice ONE uploaded cloud (sga_cloud_slice) or upload the shards with a common origin (sga_cloud_create_f64_origin)");
-  pb->frame_checked = true;
-  return SGA_OK;
-}
-}  // namespace sga
 
 using namespace sga;
 
 extern "C" {
-
-void sga_debug_shard_frame_pack(const double origin[3], double out[SGA_FRAME_CHECK_DOUBLES]) { shard_frame_pack(origin, out); }
-int sga_debug_shard_frame_agree(const double sum[SGA_FRAME_CHECK_DOUBLES]) { return shard_frame_agree(sum) ? 1 : 0; }
-
-void sga_unpack_accumulator(const double acc[SGA_ACCUM_DOUBLES], double H[36], double b[6], double* e, uint64_t* num_inliers) {
-  int k = 0;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++) {
-      H[6 * i + j] = acc[k];
-      H[6 * j + i] = acc[k];
-      k++;
-    }
-  for (int i = 0; i < 6; i++) b[i] = acc[21 + i];
-  if (e) *e = acc[27];
-  if (num_inliers) *num_inliers = static_cast<uint64_t>(acc[28] + 0.5);
-}
 
 int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double* values28, unsigned char* inlier) {
   SGA_TRY(check_args(ctx, pb, fp, T));
@@ -2527,10 +1475,7 @@ int sga_linearize_async(sga_context* ctx, sga_problem* pb, const sga_factor_para
   const int rc_dispatch = fp->math_mode == SGA_MATH_FP64 ? linearize_dispatch<double>(ctx, pb, fp, Td, d_out30, nullptr, 0) : linearize_dispatch<float>(ctx, pb, fp, Td, d_out30, nullptr, 0);
   pb->caller_T = nullptr;  // (valid for this dispatch only)
   SGA_TRY(rc_dispatch);
-  if (!origin_is_zero(pb->src_origin)) {  // the caller reads H / b in its own twist convention (common.hpp: device frames)
-    hipLaunchKernelGGL(frame_accumulator_kernel, dim3(1), dim3(64), 0, ctx->stream, d_out30, pb->src_origin[0], pb->src_origin[1], pb->src_origin[2]);
-    SGA_HIP(hipGetLastError());
-  }
+  SGA_TRY(problem_accumulator_to_caller(ctx, pb, d_out30));  // frames.hip
   return SGA_OK;
 }
 
@@ -2718,49 +1663,9 @@ int sga_linearize(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp
   return SGA_OK;
 }
 
-// e(T_n) from the quadratic error model of the last linearization (accumulate_model): a few hundred flops on the host
-static double evaluate_error_model(const double* acc, const double T[16], const double Tn[16]) {
-  // Y = [R^T R_n - I | R^T (tau_n - tau)], column-major 4x4 inputs
-  double Y[3][4];
-  for (int r = 0; r < 3; r++) {
-    for (int a = 0; a < 3; a++) {
-      double v = 0.0;
-      for (int k = 0; k < 3; k++) v += T[4 * r + k] * Tn[4 * a + k];  // (R^T R_n)[r][a] = sum_k R[k][r] R_n[k][a]
-      Y[r][a] = v - (r == a ? 1.0 : 0.0);
-    }
-    double v = 0.0;
-    for (int k = 0; k < 3; k++) v += T[4 * r + k] * (Tn[12 + k] - T[12 + k]);
-    Y[r][3] = v;
-  }
-  // S1[a][j] = sum p_h,a g_j; a = 3: sum g = -b_t
-  double S1[4][3];
-  for (int a = 0; a < 3; a++)
-    for (int j = 0; j < 3; j++) S1[a][j] = acc[kModelOff + 3 * a + j];
-  for (int j = 0; j < 3; j++) S1[3][j] = -acc[24 + j];
-  // S2[a][b] = sum p_h,a p_h,b M' as symmetric 3x3 (xx, xy, xz, yy, yz, zz)
-  auto S2 = [&](int a, int b) -> const double* {
-    if (a > b) std::swap(a, b);
-    if (b == 3) return a == 3 ? acc + 15 : acc + kModelOff + 9 + 6 * a;
-    static const int pair_of[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-    return acc + kModelOff + 27 + 6 * pair_of[a][b];
-  };
-  double lin = 0.0, quad = 0.0;
-  for (int a = 0; a < 4; a++) {
-    for (int j = 0; j < 3; j++) lin += Y[j][a] * S1[a][j];
-    for (int b2 = 0; b2 < 4; b2++) {
-      const double* m = S2(a, b2);
-      const double ya[3] = {Y[0][a], Y[1][a], Y[2][a]}, yb[3] = {Y[0][b2], Y[1][b2], Y[2][b2]};
-      const double mv[3] = {m[0] * yb[0] + m[1] * yb[1] + m[2] * yb[2], m[1] * yb[0] + m[3] * yb[1] + m[4] * yb[2], m[2] * yb[0] + m[4] * yb[1] + m[5] * yb[2]};
-      quad += ya[0] * mv[0] + ya[1] * mv[1] + ya[2] * mv[2];
-    }
-  }
-  return acc[27] - lin + 0.5 * quad;
-}
-
 }  // extern "C"
 
 namespace sga {
-double error_model_value(const double* acc96, const double T_lin[16], const double T[16]) { return evaluate_error_model(acc96, T_lin, T); }
 bool error_model_enabled() { return g_error_model; }
 // sga_error's device pass in two halves (see linearize_enqueue)
 int error_enqueue(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T_caller[16], unsigned long long* seq_out) {
@@ -2792,19 +1697,13 @@ int sga_error(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, co
   if (!e) return fail(SGA_ERR_INVALID, "null output");
   if (pb->model_valid && fp->robust_kind == SGA_ROBUST_NONE && g_error_model) {  // no pass over the cloud: the model of the last linearization
     double Tdev[16];
-    *e = evaluate_error_model(pb->model, pb->model_T, problem_pose(pb, T, Tdev));
+    *e = error_model_value(pb->model, pb->model_T, problem_pose(pb, T, Tdev));
     return SGA_OK;
   }
   SGA_ENTER(ctx);
   unsigned long long seq = 0;
   SGA_TRY(error_enqueue(ctx, pb, fp, T, &seq));
   return error_collect(ctx, seq, e);
-}
-
-int sga_error_model_eval(const double acc96[SGA_MODEL_DOUBLES], const double T_lin[16], const double T[16], double* e) {
-  if (!acc96 || !T_lin || !T || !e) return fail(SGA_ERR_INVALID, "null argument");
-  *e = evaluate_error_model(acc96, T_lin, T);
-  return SGA_OK;
 }
 
 // experiments / tests: 0 = every error pass runs the error kernel (the reference's literal procedure)

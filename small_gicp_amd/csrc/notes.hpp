@@ -5,8 +5,8 @@
 // occupied voxels, the bounding box of the downsampled cloud.  Fetched with hipMemcpyAsync + hipStreamSynchronize each of them costs two
 // commands and a blocking wait (measured on a C5 scan: the voxel-grid stage took 240 us of wall time for 120 us of kernels).  Here the
 // kernel that produces the fact stores it into the context's pinned, device-mapped note block and then publishes a sequence number with
-// a system-scope release — the hand-off the linearization results already use (linearize.hip: reduce_rows_kernel / wait_result) — and
-// the host spins on that word: its wait ends a microsecond or two after the kernel's last store.
+// a system-scope release — the hand-off the linearization results already use (reduce_rows.hpp: reduce_rows_kernel; linearize.hip:
+// wait_result) — and the host spins on that word: its wait ends a microsecond or two after the kernel's last store.
 #pragma once
 #include "common.hpp"
 
@@ -16,6 +16,12 @@ constexpr int kNoteSlots = 4;  // notes in flight per context (slot = seq % kNot
 constexpr int kNoteWords = 8;  // per slot: word 0 = the sequence number, words 1..7 = payload
 
 // host side (context.hip)
+// The ONE host wait for a word the device publishes with a system-scope release (notes, linearization results, the boxes of a forest
+// call): acquire loads of the pinned `word` until it shows `seq`, a pause between them and a yield once a wait is long; every 4096
+// spins the stream is asked, and when it has drained without publishing (a fault) or 20 s have passed it is synchronised — a HIP error
+// is reported as such — and the word read once more.  SGA_OK, SGA_ERR_HIP (reported), or kNotPublished: the caller says what is missing.
+constexpr int kNotPublished = -1;
+int wait_published(sga_context* ctx, const unsigned long long* word, unsigned long long seq);
 unsigned long long note_begin(sga_context* ctx, unsigned long long** dev_slot);             // next sequence number + the device address of its slot
 int note_wait(sga_context* ctx, unsigned long long seq, unsigned long long payload[kNoteWords - 1]);  // spin (bounded; then the runtime reports what happened)
 

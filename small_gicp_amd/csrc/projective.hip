@@ -1,6 +1,6 @@
 // ProjectiveSearch (ann/projective_search.hpp) as a target index: the build of the equirectangular index image, the standalone kNN, the
 // source order of a problem over it, and the C entry points.  The factor kernel's search is projective_nearest (projective.hpp) inside
-// linearize_group<..., TARGET = 3> (linearize.hip).
+// linearize_group<..., TARGET = 3> (factor_stage.hpp).
 #include "common.hpp"
 
 #include <algorithm>

@@ -1,6 +1,6 @@
 // A wave-uniform pointer into memory that nothing writes while the kernel runs, as the constant address space: the loads through it are
-// scalar loads, issued where their values are used (see kernarg_lin_params, linearize.hip).  How the batched kernels read their
-// per-call tables (linearize.hip: BatchPair; forest.hpp: ForestTree, ForestFeat).
+// scalar loads, issued where their values are used (see kernarg_lin_params, factor_stage.hpp).  How the batched kernels read their
+// per-call tables (pass_layout.hpp: BatchPair; forest.hpp: ForestTree, ForestFeat).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-"""Test helper: the 96-double accumulator of the engine (csrc/linearize.hip: row layout) assembled on the CPU from the oracle's factor
+"""Test helper: the 96-double accumulator of the engine (csrc/pass_layout.hpp: row layout) assembled on the CPU from the oracle's factor
 state — [0, 29) the system, [32, 41) sum p_a g_j, [41, 59) sum p_a M'_c, [59, 95) sum p_a p_b M'_c with M' = R^T M R and g = R^T M r
 (r = target - T source) over the accepted pairs; c = xx, xy, xz, yy, yz, zz, pairs ab = 00, 01, 02, 11, 12, 22."""
 import numpy as np

@@ -215,7 +215,7 @@ def test_small_gicp_module_name_exports_the_reference_surface():
 
 def test_shard_frame_check_is_exact_for_any_rank_count():
     """the ranks of a sharded registration compare their source origins through ONE sum over the ranks
-    (linearize.hip: problem_check_shard_frames).  The sums must be exact whatever the origin and the number of ranks: identical
+    (frames.hip: problem_check_shard_frames).  The sums must be exact whatever the origin and the number of ranks: identical
     origins are accepted (n = 1 .. 9, origins up to 1e6 m with fractional parts), a single deviating rank — by one ulp — is refused,
     and every rank takes the same decision (the decision is a function of the summed values alone).  The sums are integers below 2^53:
     their value does not depend on the order in which a transport adds them (checked by summing in shuffled orders)."""

@@ -1,4 +1,4 @@
-"""Batched registration on the device (csrc/batch.hip, linearize.hip: batch_search_linearize_kernel / batch_reduce_rows_kernel,
+"""Batched registration on the device (csrc/batch.hip, linearize.hip: batch_search_linearize_kernel, reduce_rows.hpp: batch_reduce_rows_kernel,
 optimizer.hip: sga_align_batch): several independent pairs linearized by one search + factor launch and one row reduction per round.
 
   * every batched linearization against a float64 sum over its own pairs: checks 1 - 5 of tests/test_route_matrix.py's header

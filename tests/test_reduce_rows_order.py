@@ -1,4 +1,4 @@
-"""The row sum that ends every linearization pass (csrc/linearize.hip: reduce_rows_kernel through launch_reduce) adds its rows in ONE
+"""The row sum that ends every linearization pass (csrc/reduce_rows.hpp: reduce_rows_kernel through launch_reduce) adds its rows in ONE
 documented, fixed order — the results of a registration are bit-reproducible because of it.  This file states that order in numpy and
 compares the kernel with it BITWISE, on rows of mixed magnitude (any other order of the additions changes bits):
 
@@ -133,7 +133,7 @@ def test_derived_columns_leave_the_summed_ones_alone(ctx):
     assert_bits_equal(got[keep], want[keep], "derive")
 
 
-# The derived columns of a row in moment form (csrc/linearize.hip: derived_entry), restated from the layout of a row: with SYM the position
+# The derived columns of a row in moment form (csrc/reduce_rows.hpp: derived_entry), restated from the layout of a row: with SYM the position
 # of (j, k) in a packed symmetric 3x3, G(a, j) = m[32 + 3 a + j] (sum p_a g_j), A(a, j, k) = m[41 + 6 a + SYM[j][k]] (sum p_a M'_jk) and
 # B(a, b, j, k) = m[59 + 6 SYM[a][b] + SYM[j][k]] (sum p_a p_b M'_jk):  b_r[i] = G(i2, i1) - G(i1, i2) (columns 21 .. 23),
 # H_rt[i][k] = A(i1, i2, k) - A(i2, i1, k), H_rr[i][j] = PK(j1, i, j2) - PK(j2, i, j1) with PK(l, i, k) = B(l, i1, i2, k) - B(l, i2, i1, k),

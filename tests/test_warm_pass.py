@@ -280,7 +280,7 @@ print("RESULT " + json.dumps({"hash": h.hexdigest(), "sums": sums, "warm": s["wa
 
 
 def test_certificate_headroom_changes_nothing_but_the_walkers():
-    """SGA_CERT_PAD (linearize.hip: certify) only decides which points of a warm pass search again — every one of them is found again exactly —
+    """SGA_CERT_PAD (search_stage.hpp: certify) only decides which points of a warm pass search again — every one of them is found again exactly —
     so a pose chain shaped like an LM run gives the same correspondences on every pass whatever the value: the plain check (0), the default,
     and a value that sends nearly every point into the walk.  The switch is read when the library loads, hence one process per value."""
     import json
