@@ -372,8 +372,12 @@ int sga_align_problem(sga_context* ctx, sga_problem* problem, const double init_
  * One linearization of the batch is ONE search + factor launch over the tiles of all its active pairs, ONE row reduction and ONE
  * hand-off to the host, whatever `count` is: the throughput form for many small clouds (a 11k-point scan fills 2 % of an MI355X).
  * Every pair has its own pose and its own device frames; its sums do not depend on the company it keeps, bit for bit.
- * Scope: kd-tree targets (voxel maps, flat maps, projective indexes: SGA_ERR_UNSUPPORTED at creation); one factor kind per call (ICP,
- * PLANE_ICP, GICP), distance or null rejector; SGA_MATH_FP32, SGA_ROBUST_NONE, the error model on (sga_set_error_model) and no host
+ * Scope: the members' targets are ALL kd-trees, ALL Gaussian voxel maps (VGICP) or ALL flat maps — one-shot, incremental or created from
+ * host voxels, any mix of leaf sizes, search offsets and flat contents, and one map may be the target of several members; a batch that
+ * mixes the kinds, or holds a projective index, is SGA_ERR_UNSUPPORTED at creation.  A map batch runs one factor launch (the lookup
+ * inside it) instead of the search + factor launch.  One factor kind per call (ICP, PLANE_ICP, GICP; against maps as the lone path takes
+ * them: PLANE_ICP needs a flat map with normals, GICP covariances on both sides — refused with the lone path's status), distance or null
+ * rejector; SGA_MATH_FP32, SGA_ROBUST_NONE, the error model on (sga_set_error_model) and no host
  * rejector on any member — otherwise SGA_ERR_UNSUPPORTED before any device work.  count == 0 is SGA_OK and does nothing.  A problem
  * is in one batch at a time and is not used through the lone entry points while a batch call runs; after a batch call it holds what a
  * lone pass at the same pose leaves (sga_problem_get_factors, sga_linearize_per_point, sga_error keep working on it). */

@@ -908,8 +908,10 @@ def _T16s(Ts, count):
 
 class BatchProblem:
     """sga_batch: several independent Problems of ONE context linearized by one search + factor launch, one row reduction and one
-    hand-off to the host per round, each pair at its own pose (small_gicp_amd.h).  kd-tree targets; ICP, PLANE_ICP or GICP in fp32
-    arithmetic, no robust kernel, no host rejector.  The problems are borrowed: after a call each holds what a lone pass leaves."""
+    hand-off to the host per round, each pair at its own pose (small_gicp_amd.h).  The targets are all KdTrees, all GaussianVoxelMaps
+    (VGICP) or all flat maps (IncrementalVoxelMap*; any leaf sizes, search offsets and contents, a map may serve several problems) — a
+    mix of kinds is refused; ICP, PLANE_ICP or GICP (against maps as Problem takes them) in fp32 arithmetic, no robust kernel, no host
+    rejector.  The problems are borrowed: after a call each holds what a lone pass leaves."""
 
     def __init__(self, problems):
         self.problems = list(problems)  # (keeps them alive: the batch must go first)
@@ -948,8 +950,13 @@ class BatchProblem:
 
 
 def align_batch(targets, sources, init_Ts=None, setting=None):
-    """Register sources[k] (a PointCloud, or a KdTree taken in its own order) against the kd-tree targets[k] for all k in one batch;
-    setting: make_setting(...) (default GICP, 1 m).  The problems live for the call only."""
+    """Register sources[k] (a PointCloud, or a KdTree taken in its own order) against targets[k] for all k in one batch; the targets are
+    all KdTrees, all GaussianVoxelMaps or all flat maps (IncrementalVoxelMap*), and one target may appear several times.
+    setting: make_setting(...) (default GICP, 1 m).  The problems live for the call only.
+
+    VGICP, four scans against one model map:
+        model = GaussianVoxelMap(1.0); model.insert(map_cloud)
+        results = align_batch([model] * 4, scans, init_Ts=guesses)"""
     if len(targets) != len(sources):
         raise ValueError("as many targets as sources")
     init = [None] * len(targets) if init_Ts is None else init_Ts

@@ -1,12 +1,14 @@
-// Batched registration: B independent (target kd-tree, source) problems of one context, linearized by ONE search + factor launch and
-// ONE row reduction per round, with one hand-off to the host for all pairs (DESIGN.md section 3.8).  The kernels and the round itself
-// sit beside the lone kernels whose device functions they share (linearize.hip: batch_search_linearize_kernel, batch_round;
-// reduce_rows.hpp: batch_reduce_rows_kernel); the lock-step LM / GN loop over the pairs is optimizer.hip's (sga_align_batch).  This file:
-// the batch object and sga_batch_linearize.
+// Batched registration: B independent (target, source) problems of one context, linearized by ONE search + factor launch and
+// ONE row reduction per round, with one hand-off to the host for all pairs (DESIGN.md section 3.11).  The kernels and the round itself
+// sit beside the lone kernels whose device functions they share (linearize.hip: batch_search_linearize_kernel for kd-tree targets,
+// batch_map_linearize_kernel for voxel maps, batch_round; reduce_rows.hpp: batch_reduce_rows_kernel); the lock-step LM / GN loop over
+// the pairs is optimizer.hip's (sga_align_batch).  This file: the batch object and sga_batch_linearize.
 //
-// Scope: kd-tree targets; ICP, PLANE_ICP, GICP; distance or null rejector; fp32 pair arithmetic, no robust kernel, no host rejector,
-// error model on — the conditions under which a lone pass fuses search and factors (plan_pass) and answers trial errors from the
-// quadratic model.  Everything else is refused before any device work.
+// Scope: the members' targets are ALL kd-trees, ALL Gaussian voxel maps or ALL flat maps (one-shot, incremental or created from host
+// voxels; any mix of leaf sizes, search offsets and flat contents; one map may serve several members) — a mix of kinds and projective
+// indexes are refused at creation; ICP, PLANE_ICP (kd-trees and flat maps with normals), GICP; distance or null rejector; fp32 pair
+// arithmetic, no robust kernel, no host rejector, error model on — the conditions under which a lone kd pass fuses search and factors
+// (plan_pass) and every lone pass answers trial errors from the quadratic model.  Everything else is refused before any device work.
 #include <climits>
 #include <memory>
 
@@ -24,11 +26,14 @@ int batch_check(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp) {
   if (!ctx || !bt) return fail(SGA_ERR_INVALID, "null argument");
   if (bt->ctx != ctx) return fail(SGA_ERR_INVALID, "the batch belongs to another context");
   if (ctx->sharded()) return fail(SGA_ERR_UNSUPPORTED, "a batch does not run on a sharded context");
-  for (const sga_problem* pb : bt->problems) {
+  for (size_t k = 0; k < bt->problems.size(); k++) {  // the factor against each member's target: linearize_dispatch's conditions, status and wording
+    const sga_problem* pb = bt->problems[k];
     const sga_index* idx = pb->target;
+    const bool flat = idx->kind == SGA_INDEX_FLATMAP, gaussian = idx->kind == SGA_INDEX_VOXELMAP;
     if (pb->rejector_fn != nullptr) return fail(SGA_ERR_UNSUPPORTED, "a member problem has a host rejector");
-    if (fp->factor_kind == SGA_GICP && ((pb->n > 0 && !pb->has_covs) || (idx->n > 0 && !idx->has_covs))) return fail(SGA_ERR_INVALID, "GICP needs covariances on both source and target");
-    if (fp->factor_kind == SGA_PLANE_ICP && idx->n > 0 && !idx->has_normals) return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals");
+    if (fp->factor_kind == SGA_GICP && ((pb->n > 0 && !pb->has_covs) || (idx->n > 0 && !idx->has_covs))) return fail(SGA_ERR_INVALID, "GICP needs covariances on both source and target (problem %zu)", k);
+    if (fp->factor_kind == SGA_PLANE_ICP && (gaussian || ((flat || idx->n > 0) && !idx->has_normals)))
+      return fail(SGA_ERR_UNSUPPORTED, "PLANE_ICP needs a kd-tree index over a target with normals (problem %zu)", k);
   }
   return SGA_OK;
 }
@@ -63,13 +68,17 @@ int sga_batch_create(sga_context* ctx, sga_problem* const* problems, size_t coun
     if (pb->owner != ctx || pb->device != ctx->device) return fail(SGA_ERR_INVALID, "problem %zu belongs to another context", k);
     for (size_t j = 0; j < k; j++)
       if (problems[j] == pb) return fail(SGA_ERR_INVALID, "problem %zu is in the batch twice", k);
-    if (pb->target->kind != SGA_INDEX_KDTREE) return fail(SGA_ERR_UNSUPPORTED, "a batch takes kd-tree targets only (problem %zu)", k);
+    const int kind = pb->target->kind;
+    if (kind != SGA_INDEX_KDTREE && kind != SGA_INDEX_VOXELMAP && kind != SGA_INDEX_FLATMAP) return fail(SGA_ERR_UNSUPPORTED, "a batch takes kd-tree, Gaussian voxel-map or flat-map targets (problem %zu)", k);
+    if (k == 0) bt->kind = kind;
+    if (kind != bt->kind) return fail(SGA_ERR_UNSUPPORTED, "the targets of a batch are all kd-trees, all Gaussian voxel maps or all flat maps (problem %zu)", k);
     if (pb->n > static_cast<size_t>(INT_MAX) - 64) return fail(SGA_ERR_INVALID, "problem %zu is too large", k);
-    const int tiles = (pb->n > 0 && pb->target->n > 0) ? static_cast<int>((pb->n + 63) / 64) : 0;
+    // a map may be filled after the batch was created: its pairs are counted with the tiles of their source, the most a round launches
+    const int tiles = kind == SGA_INDEX_KDTREE ? batch_pair_tiles(pb) : static_cast<int>((pb->n + 63) / 64);
     bt->problems.push_back(pb);
     bt->tiles.push_back(tiles);
     bt->tile_prefix.push_back(bt->tile_prefix.back() + (tiles + 7) / 8 * 8);  // as launched: every pair's share padded to a multiple of 8
-    bt->max_depth = std::max(bt->max_depth, pb->target->kd_depth);
+    if (kind == SGA_INDEX_KDTREE) bt->max_depth = std::max(bt->max_depth, pb->target->kd_depth);
   }
   if (bt->tile_prefix.back() > static_cast<long long>(INT_MAX)) return fail(SGA_ERR_INVALID, "the batch has more tiles than one grid holds");
   if (count > 0) {

@@ -635,6 +635,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SGA_SL_WAVES
   for (int c = lane; c < kRow; c += 64) lp.partials[static_cast<size_t>(tile) * kRow + c] = row[c];
 }
 
+// linearize_kernel<float, FACTOR, TARGET, 1> (TARGET 1: Gaussian voxel map, 2: flat map; the lookup happens inside linearize_group) for
+// the tiles of all active pairs in one grid: the round table, the padding of every pair's share to a multiple of 8, the XCD-striped tile
+// numbering and the row at the tile's LOCAL number in the pair's own partials are batch_search_linearize_kernel's, so the reduction is
+// shared.  (The pair lookup is a second copy on purpose: as a shared device function it would be free to move the kd kernel's registers.)
+// The pair's LinParams — the map's hash, leaf size, origin and search offsets among them — are read per wave with scalar loads: maps of
+// different leaf size and offsets share a launch, and `offsets` stays wave-uniform.  No walk, no traversal stack: the LDS is the row.
+// Occupancy: a round of 32 C5-shaped pairs is ~5 600 waves on 1 024 SIMDs and a wave lasts a few microseconds, so more than 5 - 6 waves
+// are never resident on a SIMD; 4 (the lone factor kernel's floor, <= 128 VGPRs) leaves the allocator twice the ~70 registers the
+// one-point-per-lane factor stage needs, and the 768 bytes of LDS per wave limit nothing.
+template <int FACTOR, int TARGET>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void batch_map_linearize_kernel(const int* __restrict__ prefix_g, const BatchPair* __restrict__ pairs_g, int nactive) {
+  static_assert(TARGET == 1 || TARGET == 2, "voxel-map targets");
+  __shared__ double row[kRow];
+  const int lane = threadIdx.x;
+  const int* prefix = uniform_const(prefix_g);
+  const int b = blockIdx.x;
+  int lo = 0, hi = nactive;  // wave-uniform binary search
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid] <= b)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int first = prefix[lo], per_xcd = (prefix[lo + 1] - first) >> 3, slot = b - first;
+  const int tile = (slot & 7) * per_xcd + (slot >> 3);
+  const BatchPair& d = *uniform_const(pairs_g + lo);
+  if (tile >= d.ntiles) return;  // wave-uniform
+  const LinParams<float>& lp = d.p;
+  for (int c = lane; c < kRow; c += 64) row[c] = 0.0;
+  __syncthreads();
+  linearize_group<float, FACTOR, TARGET, 1>(lp, tile * 64 + lane, 64, lp.n, row, lane);
+  __syncthreads();
+  for (int c = lane; c < kRow; c += 64) lp.partials[static_cast<size_t>(tile) * kRow + c] = row[c];
+}
+
 // Per-point export of the same factors (the reference's Python binding exposes Factor::linearize per source point,
 // src/python/factors.cpp:52-101): the 28 values of every pair instead of their sum.  Runs after a linearize pass at the same pose
 // (kd-tree: the neighbours come from hint[]; flat map, FLAT: the correspondences that pass kept in corr[], slot or -1); not on the hot path.
@@ -1019,6 +1055,30 @@ static LinParams<Real> factor_params(const sga_problem* pb, const sga_factor_par
   return p;
 }
 
+// the factor stage's view of the target's search structure: the hash of a voxel map (Gaussian or flat: the lookup happens inside the
+// factor kernel), the kd-tree otherwise; a projective index travels as a kernel argument of its own (projective_linearize_kernel)
+template <typename Real>
+static void target_view(LinParams<Real>& p, const sga_index* idx) {
+  if (idx->kind == SGA_INDEX_FLATMAP) {
+    p.flat.hkeys = idx->hkeys.p;
+    p.flat.hvals = idx->hvals.p;
+    p.flat.hmask = idx->hmask;
+    p.flat.inv_leaf = 1.0 / idx->leaf;
+    p.flat.vnum = idx->vcounts.p;
+    p.flat.offsets = idx->search_offsets;
+    for (int k = 0; k < 3; k++) p.flat.org[k] = idx->origin[k];
+  } else if (idx->kind == SGA_INDEX_VOXELMAP) {
+    p.vox.hkeys = idx->hkeys.p;
+    p.vox.hvals = idx->hvals.p;
+    p.vox.hmask = idx->hmask;
+    p.vox.inv_leaf = 1.0 / idx->leaf;
+    for (int k = 0; k < 3; k++) p.vox.org[k] = idx->origin[k];
+    p.vox.offsets = idx->search_offsets;
+  } else if (idx->kind == SGA_INDEX_KDTREE) {
+    p.kd = make_kd_view(idx);
+  }
+}
+
 template <typename Real>
 static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_factor_params* fp, const double T[16], double* d_out30, double* host, unsigned long long seq, bool with_model = false) {
   const sga_index* idx = pb->target;
@@ -1039,26 +1099,7 @@ static int linearize_dispatch(sga_context* ctx, sga_problem* pb, const sga_facto
     if (pb->maha64.n < pb->n * 6) SGA_TRY(pb->maha64.alloc(pb->n * 6));
   const bool host_rejector = pb->rejector_fn != nullptr && !voxel;
   LinParams<Real> p = factor_params<Real>(pb, fp, T, host_rejector);
-  if (flat) {
-    p.flat.hkeys = idx->hkeys.p;
-    p.flat.hvals = idx->hvals.p;
-    p.flat.hmask = idx->hmask;
-    p.flat.inv_leaf = 1.0 / idx->leaf;
-    p.flat.vnum = idx->vcounts.p;
-    p.flat.offsets = idx->search_offsets;
-    for (int k = 0; k < 3; k++) p.flat.org[k] = idx->origin[k];
-  } else if (proj) {
-    // (the view is an argument of projective_linearize_kernel of its own)
-  } else if (voxel) {
-    p.vox.hkeys = idx->hkeys.p;
-    p.vox.hvals = idx->hvals.p;
-    p.vox.hmask = idx->hmask;
-    p.vox.inv_leaf = 1.0 / idx->leaf;
-    for (int k = 0; k < 3; k++) p.vox.org[k] = idx->origin[k];
-    p.vox.offsets = idx->search_offsets;
-  } else {
-    p.kd = make_kd_view(idx);
-  }
+  target_view(p, idx);
   p.cert_nn2 = (!voxel && sizeof(Real) == 8) ? pb->hint2.p : nullptr;  // fp64 arithmetic: the factor kernel measures the walk's two candidates again, in double
   p.store_maha = fp->robust_kind != SGA_ROBUST_NONE ? 1 : 0;  // the error passes of a robust factor run the error kernel
   p.partials = pb->partials.p;
@@ -1569,7 +1610,12 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
   for (size_t k = 0; k < count; k++)
     if (active == nullptr || active[k]) order.push_back(static_cast<int>(k));
   if (order.empty()) return SGA_OK;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bt->tiles[a] > bt->tiles[b]; });
+  // a voxel map may have grown (or been filled) since the batch was created: its pairs' tiles are counted per round
+  const bool map = bt->kind != SGA_INDEX_KDTREE;
+  std::vector<int> tiles(bt->tiles);
+  if (map)
+    for (int k : order) tiles[k] = batch_pair_tiles(bt->problems[k]);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tiles[a] > tiles[b]; });
   int* prefix = static_cast<int*>(bt->h_round);
   BatchPair* pairs = reinterpret_cast<BatchPair*>(static_cast<unsigned char*>(bt->h_round) + batch_pairs_offset(count));
   std::vector<double> Tdev(16 * order.size());
@@ -1583,18 +1629,20 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
     if (Tp != Td) memcpy(Td, Tp, 16 * sizeof(double));
     BatchPair d{};
     d.p = factor_params<float>(pb, fp, Td, false);
-    d.p.kd = make_kd_view(idx);
+    target_view(d.p, idx);  // (as linearize_dispatch fills it: the kd-tree, or the map's hash, leaf size, origin and search offsets)
     d.p.partials = pb->partials.p;
-    d.q.src_pts = pb->src_pts();
-    d.q.n = d.p.n;
-    d.q.kd = d.p.kd;
-    d.q.T = d.p.T;
-    d.q.within2 = d.p.bound2;
-    d.q.bound2 = d.p.bound2 * (1.f + kSearchMargin) * (1.f + kSearchMargin);
-    d.q.nn = pb->hint.p, d.q.nn2 = pb->hint2.p, d.q.rex = pb->rex.p, d.q.walked = pb->walked.p;
-    d.q.fast = g_fast_scan;
-    d.ntiles = bt->tiles[k];
-    d.seedless = seedless ? 1 : 0;
+    if (!map) {  // the search half: kd batches only
+      d.q.src_pts = pb->src_pts();
+      d.q.n = d.p.n;
+      d.q.kd = d.p.kd;
+      d.q.T = d.p.T;
+      d.q.within2 = d.p.bound2;
+      d.q.bound2 = d.p.bound2 * (1.f + kSearchMargin) * (1.f + kSearchMargin);
+      d.q.nn = pb->hint.p, d.q.nn2 = pb->hint2.p, d.q.rex = pb->rex.p, d.q.walked = pb->walked.p;
+      d.q.fast = g_fast_scan;
+      d.seedless = seedless ? 1 : 0;
+    }
+    d.ntiles = tiles[k];
     d.pair = k;
     prefix[a] = blocks;
     blocks += (d.ntiles + 7) / 8 * 8;  // (bt->tile_prefix bounds the sum: batch.hip)
@@ -1608,15 +1656,25 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
   const BatchPair* d_pairs = reinterpret_cast<const BatchPair*>(bt->d_round.p + batch_pairs_offset(count));
   for (int k : order) {  // as in linearize_dispatch: until the round is launched completely the certificates belong to no pose the host knows
     sga_problem* pb = bt->problems[k];
-    pb->prev_valid = false;
+    if (!map) {  // (a map pass is linearize_dispatch's Route::kFactors: it neither reads nor writes the state of the kd search)
+      pb->prev_valid = false;
+      pb->order_tiles = 0;
+    }
     pb->model_valid = false;
     pb->state_fresh = false;
-    pb->order_tiles = 0;
-    if (bt->tiles[k] == 0 && pb->n > 0) SGA_HIP(hipMemsetAsync(pb->corr.p, 0xff, pb->n * sizeof(int), ctx->stream));  // an empty target: no correspondences
+    if (tiles[k] == 0 && pb->n > 0) SGA_HIP(hipMemsetAsync(pb->corr.p, 0xff, pb->n * sizeof(int), ctx->stream));  // an empty target: no correspondences
   }
-  if (blocks > 0) {
+  if (blocks > 0 && !map) {
     const size_t lds = static_cast<size_t>(std::max(bt->max_depth, 3)) * 64 * sizeof(uint32_t);
     with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((batch_search_linearize_kernel<decltype(f)::value>), dim3(blocks), dim3(64), lds, ctx->stream, d_prefix, d_pairs, nactive); });
+  } else if (blocks > 0) {
+    with_factor(fp->factor_kind, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      if (bt->kind == SGA_INDEX_FLATMAP)
+        hipLaunchKernelGGL((batch_map_linearize_kernel<F, 2>), dim3(blocks), dim3(64), 0, ctx->stream, d_prefix, d_pairs, nactive);
+      else if constexpr (F != SGA_PLANE_ICP)  // (batch_check refuses PLANE_ICP on a Gaussian map)
+        hipLaunchKernelGGL((batch_map_linearize_kernel<F, 1>), dim3(blocks), dim3(64), 0, ctx->stream, d_prefix, d_pairs, nactive);
+    });
   }
   hipLaunchKernelGGL(batch_reduce_rows_kernel, dim3(nactive), dim3(kReduceSlices * kCols), 0, ctx->stream, d_pairs, bt->ticket.p, bt->h_out_dev, bt->h_out_dev + count * kRow, seq);
   SGA_HIP(hipGetLastError());
@@ -1625,7 +1683,7 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
     (void)hipMemsetAsync(bt->ticket.p, 0, sizeof(unsigned), ctx->stream);
     return rc;
   }
-  for (size_t a = 0; a < order.size(); a++) {  // what a lone cold pass at this pose leaves in the problem
+  for (size_t a = 0; a < order.size(); a++) {  // what a lone pass at this pose leaves in the problem: a cold kd pass, or a map pass (Route::kFactors)
     const int k = order[a];
     sga_problem* pb = bt->problems[k];
     const double* Td = &Tdev[16 * a];
@@ -1633,12 +1691,14 @@ int batch_round(sga_context* ctx, sga_batch* bt, const sga_factor_params* fp, co
     pb->lin_factor = fp->factor_kind;
     memcpy(pb->lin_T, Td, sizeof(pb->lin_T));
     pb->maha_valid = false;
-    memcpy(pb->T_prev, Td, sizeof(pb->T_prev));
-    pb->prev_valid = true;
-    pb->prev_math = SGA_MATH_FP32;
-    pb->cold_passes++;
+    if (!map) {  // certificates and pass statistics belong to kd targets
+      memcpy(pb->T_prev, Td, sizeof(pb->T_prev));
+      pb->prev_valid = true;
+      pb->prev_math = SGA_MATH_FP32;
+      pb->cold_passes++;
+    }
     pb->grid_stats_pending = false;
-    const int lp[8] = {static_cast<int>(Route::kFusedLane), 0, 0, 1, 0, 0, bt->tiles[k], 1};
+    const int lp[8] = {static_cast<int>(map ? Route::kFactors : Route::kFusedLane), 0, 0, 1, 0, 0, tiles[k], 1};
     std::copy(lp, lp + 8, pb->last_plan);
     memcpy(pb->model, bt->h_out + static_cast<size_t>(k) * kRow, sizeof(pb->model));
     memcpy(pb->model_T, Td, sizeof(pb->model_T));
@@ -1811,6 +1871,7 @@ void preload_hot_kernels() {
   SGA_PRELOAD_FACTOR(SGA_ICP);
   SGA_PRELOAD(linearize_kernel<float, SGA_GICP, 1, kLinPts>);
   SGA_PRELOAD(linearize_kernel<float, SGA_GICP, 1, 1>);
+  SGA_PRELOAD(batch_map_linearize_kernel<SGA_GICP, 1>);
   SGA_PRELOAD(reduce_rows_kernel);
   SGA_PRELOAD(batch_reduce_rows_kernel);
   SGA_PRELOAD(tile_order_kernel);

@@ -136,10 +136,11 @@ struct ErrParams {
   FusedTail tail;
 };
 
-// ---- batched registration (batch.hip, DESIGN.md section 3.8): the rounds of B independent problems ---------------------------------
+// ---- batched registration (batch.hip, DESIGN.md section 3.11): the rounds of B independent problems ---------------------------------
 // One entry of a round's table per ACTIVE pair, largest pair first: what search_linearize_kernel receives as its two arguments, for
 // that pair at its pose of the round.  The table lives in device memory (it does not fit the kernel-argument segment for large B); a
-// wave reads its pair's entry with scalar loads (uniform_const).
+// wave reads its pair's entry with scalar loads (uniform_const).  A batch over voxel maps (batch_map_linearize_kernel) fills and reads
+// `p` alone — p.vox / p.flat are the pair's own map: hash, leaf size, origin, search offsets — and leaves `q` and `seedless` zero.
 struct BatchPair {
   NNParams<float> q;
   LinParams<float> p;
