@@ -144,6 +144,20 @@ int sga_index_build_kdtree_batch(sga_context* ctx, const sga_cloud* const* cloud
 /* Replaces create_gaussian_voxelmap (registration_helper.cpp:50-54; ann/incremental_voxelmap.hpp:55-92, gaussian_voxelmap.hpp:32-53):
  * one-shot insert of a cloud WITH covariances; voxel ids follow first-insertion order like the reference. */
 int sga_index_build_gaussian_voxelmap(sga_context* ctx, const sga_cloud* points_with_covs, double leaf_size, sga_index** out);
+/* sga_index_build_gaussian_voxelmap(ctx, clouds_with_covs[k], leaf_size, &out[k]) for `count` clouds on the context's device in one chain
+ * of launches on the context's stream — keys, ONE stable sort over the concatenation under the key (member << 49) | 16 bits per axis,
+ * runs, one sort of all runs for the voxel ids, one launch that clears every hash table, one finalize launch — whose length does not grow
+ * with count.  out[k] is an ordinary one-shot voxel-map index: it owns its buffers, is destroyed with sga_index_destroy in any order, is a
+ * search target (not insertable) in its cloud's device frame with the default search offsets, and its contents (coordinates, counts,
+ * means, covariances, voxel ids) are bit-identical to the lone call's; only the layout of its hash table may differ.  The chain takes, in
+ * the call's order, the members of 1 .. 262144 points while their concatenation stays within 2^24 points; larger members, and members
+ * that span 65536 or more voxels along an axis (the device finds out, the host hears of it at its wait), go through the lone routine, one
+ * after the other, inside the call; an empty member gives an empty map.  The same cloud may appear twice (inputs are only read); a member
+ * made by another context of the device is waited for.  The host waits ONCE, for the voxel counts of all members of the chain, then
+ * allocates every index at its exact size and enqueues the rest: a stream-ordered context returns without a second wait, other contexts
+ * synchronise once at the end.  All arguments are checked before any device work (status and message as the lone call's, naming the
+ * member); on any failure every out[k] is NULL.  count == 0 is SGA_OK. */
+int sga_index_build_gaussian_voxelmap_batch(sga_context* ctx, const sga_cloud* const* clouds_with_covs, size_t count, double leaf_size, sga_index** out);
 /* The same kind of index from voxels that already exist on the host — the reference's GaussianVoxelMap object as it is (flat order:
  * coords n*3 int32, means n*3 doubles, cov6 n*6 doubles xx,xy,xz,yy,yz,zz; ann/incremental_voxelmap.hpp:39-92): the voxel ids are the
  * caller's.  What lets Registration<GICPFactor, ParallelReductionHIP>::align(voxelmap, source, voxelmap) (registration_helper.cpp:125-137) work. */

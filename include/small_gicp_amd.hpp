@@ -644,6 +644,22 @@ inline GaussianVoxelMap::Ptr create_gaussian_voxelmap(const PointCloud& points, 
   vm->insert(points);
   return vm;
 }
+/// sga_index_build_gaussian_voxelmap_batch: the one-shot Gaussian voxel maps of several clouds (with covariances) of one context in one
+/// chain of launches and one host wait; every map is a search target whose voxels equal create_gaussian_voxelmap(cloud, voxel_resolution)'s
+inline std::vector<GaussianVoxelMap::Ptr> create_gaussian_voxelmaps(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds, double voxel_resolution) {
+  std::vector<const sga_cloud*> hs;
+  for (const auto& c : clouds) hs.push_back(c->h);
+  std::vector<sga_index*> out(clouds.size(), nullptr);
+  check(sga_index_build_gaussian_voxelmap_batch(ctx, hs.data(), hs.size(), voxel_resolution, out.data()), "sga_index_build_gaussian_voxelmap_batch");
+  std::vector<GaussianVoxelMap::Ptr> maps;
+  for (size_t k = 0; k < clouds.size(); k++) {
+    auto vm = std::make_shared<GaussianVoxelMap>(voxel_resolution);
+    vm->ctx = ctx;
+    vm->h = out[k];
+    maps.push_back(vm);
+  }
+  return maps;
+}
 
 template <typename Reg>
 void copy_setting(Reg& reg, const RegistrationSetting& setting) {

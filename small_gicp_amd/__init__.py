@@ -22,6 +22,7 @@ from .api import (  # noqa: F401
     RegistrationResult,
     align,
     align_batch,
+    build_gaussian_voxelmaps,
     build_kdtrees,
     default_context,
     estimate_covariances,
@@ -49,6 +50,7 @@ from .api import (  # noqa: F401
     voxelgrid_sampling,
     voxelgrid_sampling_batch,
     voxelgrid_batch_launches,
+    voxelmap_batch_launches,
 )
 
 __version__ = "0.1.0"

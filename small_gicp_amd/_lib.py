@@ -99,6 +99,9 @@ SYMBOLS = [
     ("sga_voxelgrid_sampling_batch", C.c_int, [_vp, _pvp, C.c_size_t, C.c_double, _pvp]),
     ("sga_debug_voxelgrid_batch_plan", C.c_int, [_pvp, C.c_size_t, C.c_double, C.POINTER(C.c_int)]),
     ("sga_debug_voxelgrid_batch_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_index_build_gaussian_voxelmap_batch", C.c_int, [_vp, _pvp, C.c_size_t, C.c_double, _pvp]),
+    ("sga_debug_voxelmap_batch_plan", C.c_int, [_pvp, C.c_size_t, C.c_double, C.POINTER(C.c_int)]),
+    ("sga_debug_voxelmap_batch_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_index_bbox", C.c_int, [_vp, _fp, _fp]),
     ("sga_index_build_gaussian_voxelmap", C.c_int, [_vp, _vp, C.c_double, _pvp]),
     ("sga_index_create_voxelmap_from_voxels", C.c_int, [_vp, C.c_double, C.c_void_p, _dp, _dp, C.c_size_t, _pvp]),

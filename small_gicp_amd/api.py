@@ -487,6 +487,24 @@ class GaussianVoxelMap:
         check(load().sga_index_create_voxelmap_from_voxels(self.ctx.h, self.leaf, coords.ctypes.data_as(C.c_void_p), _dp(means), _dp(cov6), len(coords), C.byref(self.h)))
         return self
 
+    @classmethod
+    def _adopt(cls, leaf_size, ctx, handle):
+        self = cls.__new__(cls)
+        self.leaf = float(leaf_size)
+        self.ctx = ctx
+        self.h = handle
+        return self
+
+    @classmethod
+    def from_cloud(cls, cloud, leaf_size):
+        """The one-shot map of a cloud with covariances (sga_index_build_gaussian_voxelmap: create_gaussian_voxelmap's target, voxel ids
+        in first-insertion order), on the cloud's context.  A search target only: insert() reports the library's refusal."""
+        if not isinstance(cloud, PointCloud):
+            raise TypeError("from_cloud takes a PointCloud")
+        h = C.c_void_p()
+        check(load().sga_index_build_gaussian_voxelmap(cloud.ctx.h, cloud.h, float(leaf_size), C.byref(h)))
+        return cls._adopt(leaf_size, cloud.ctx, h)
+
     def insert(self, cloud, T=None):
         t16 = None if T is None else _T16(T)
         check(load().sga_voxelmap_insert(self.ctx.h, self.h, cloud.h, None if t16 is None else _dp(t16)))
@@ -1253,6 +1271,38 @@ def preprocess_points_batch(clouds, downsampling_resolution=0.25, num_neighbors=
     """preprocess_points for several raw clouds of one context, every stage batched: voxelgrid_sampling_batch, then preprocess_batch.
     [(downsampled cloud, tree)], each pair what the lone calls give, bit for bit."""
     return preprocess_batch(voxelgrid_sampling_batch(clouds, downsampling_resolution), num_neighbors)
+
+
+def build_gaussian_voxelmaps(clouds, leaf_size):
+    """sga_index_build_gaussian_voxelmap_batch: [GaussianVoxelMap.from_cloud(c, leaf_size) for c in clouds] in one chain of launches and
+    one host wait (PointCloud objects with covariances, of one context).  Every map is an ordinary one-shot GaussianVoxelMap, its contents
+    bit-identical to the lone build's; clouds of at most 262144 points share the launches, others — and clouds that span 65536 or more
+    voxels along an axis — are built one by one inside the call."""
+    clouds = list(clouds)
+    ctx = _one_context(clouds)
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    out = (C.c_void_p * max(1, len(clouds)))()
+    check(load().sga_index_build_gaussian_voxelmap_batch(ctx.h, hs, len(clouds), float(leaf_size), out))
+    return [GaussianVoxelMap._adopt(leaf_size, ctx, C.c_void_p(out[k])) for k in range(len(clouds))]
+
+
+def _voxelmap_batch_plan(clouds, leaf_size):
+    """Diagnostics (sga_debug_voxelmap_batch_plan): what build_gaussian_voxelmaps(clouds, leaf_size) would do — forest (members of the
+    shared chain), lone (members through the lone routine), empty, member_bits, end_bit of the chain's sort, points of the concatenation."""
+    clouds = list(clouds)
+    _one_context(clouds)
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    out = (C.c_int * 6)()
+    check(load().sga_debug_voxelmap_batch_plan(hs, len(clouds), float(leaf_size), out))
+    return {"forest": out[0], "lone": out[1], "empty": out[2], "member_bits": out[3], "end_bit": out[4], "points": out[5]}
+
+
+def voxelmap_batch_launches():
+    """Diagnostics (sga_debug_voxelmap_batch_launches): kernels, sorts, scans and copy commands enqueued so far by the shared chain of
+    build_gaussian_voxelmaps."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_voxelmap_batch_launches(C.byref(v)))
+    return v.value
 
 
 def _voxelgrid_batch_plan(clouds, resolution):

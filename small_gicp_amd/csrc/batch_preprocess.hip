@@ -18,7 +18,7 @@ namespace sga {
 int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
 
 namespace {
-std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0};
+std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0}, g_vox_forest_launches{0};
 }  // namespace
 
 // the context's box block with room for `members` slots (grow-only; no call is in flight: every call waits for its boxes)
@@ -192,10 +192,111 @@ int voxelgrid_batch_check(const sga_cloud* const* clouds, size_t count, double l
   }
   return SGA_OK;
 }
+// the argument checks of sga_index_build_gaussian_voxelmap_batch and of its plan (status and message as the lone call's, naming the member)
+int voxelmaps_batch_check(const sga_cloud* const* clouds, size_t count, double leaf) {
+  if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
+  for (size_t k = 0; k < count; k++) {
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "clouds[%zu] is NULL", k);
+    if (!clouds[k]->has_covs) return fail(SGA_ERR_INVALID, "GaussianVoxelMap needs point covariances (cloud %zu)", k);
+  }
+  return SGA_OK;
+}
+
+// sga_index_build_gaussian_voxelmap for every member.  The members of the plan's chain share the launches
+// (index_build.hip: vox_forest_enqueue_runs, vox_forest_enqueue_finalize) and ONE host wait, for their voxel counts and overflow words;
+// behind it every index is allocated at its exact size.  Members the plan leaves out, and members whose key overflowed, go through the
+// lone routine afterwards.
+int voxelmaps_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, std::vector<std::unique_ptr<sga_index>>& made) {
+  made.resize(count);
+  for (size_t k = 0; k < count; k++) SGA_TRY(wait_ready(ctx, clouds[k]->ready));
+  const VoxForestPlan plan = vox_forest_plan(clouds, count);
+  VoxForestChain ch;
+  std::vector<size_t> lone = plan.lone;
+  std::vector<VoxMember> members;  // of the stage behind the wait
+  std::vector<size_t> built;       // their positions in the call
+  auto add_member = [&](size_t k, uint32_t nvox, uint32_t off, uint32_t run0) -> int {
+    const sga_cloud* cloud = clouds[k];
+    std::unique_ptr<sga_index> idx(new sga_index);  // as sga_index_build_gaussian_voxelmap sets it up
+    idx->kind = SGA_INDEX_VOXELMAP;
+    idx->device = ctx->device;
+    idx->leaf = leaf;
+    idx->has_covs = true;
+    idx->has_normals = false;
+    for (int a = 0; a < 3; a++) idx->origin[a] = cloud->origin[a];
+    idx->n = nvox;
+    uint32_t hsize = 16;
+    while (hsize < 2 * static_cast<uint64_t>(nvox)) hsize <<= 1;
+    idx->hmask = hsize - 1;
+    SGA_TRY(idx->hkeys.alloc(hsize));
+    SGA_TRY(idx->hvals.alloc(hsize));
+    if (nvox > 0) {
+      SGA_TRY(idx->pts.alloc(nvox));
+      SGA_TRY(idx->cov.alloc(nvox));
+      SGA_TRY(idx->vcoords.alloc(static_cast<size_t>(nvox) * 3));
+      SGA_TRY(idx->vcounts.alloc(nvox));
+    }
+    VoxMember g;
+    std::memset(&g, 0, sizeof(g));
+    g.pts = cloud->pts.p;
+    g.cov = cloud->cov.p;
+    g.ox = cloud->origin[0], g.oy = cloud->origin[1], g.oz = cloud->origin[2];
+    g.n = static_cast<uint32_t>(cloud->n);
+    g.off = off;
+    g.means = idx->pts.p;
+    g.mcov = idx->cov.p;
+    g.coords = idx->vcoords.p;
+    g.counts = idx->vcounts.p;
+    g.hkeys = idx->hkeys.p;
+    g.hvals = idx->hvals.p;
+    g.hmask = idx->hmask;
+    g.nvox = nvox;
+    g.run0 = run0;
+    members.push_back(g);
+    built.push_back(k);
+    made[k] = std::move(idx);
+    return SGA_OK;
+  };
+  size_t runs = 0;
+  if (!plan.forest.empty()) {
+    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
+    const unsigned long long seq = ++ctx->forest_seq;
+    if (const int rc = vox_forest_enqueue_runs(ctx, clouds, leaf, plan, seq, ch); rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block: nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    // ---- the one wait: the voxel counts and overflow words of all members of the chain
+    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel-map build"));
+    uint32_t off = 0;
+    for (size_t j = 0; j < plan.forest.size(); j++) {
+      const size_t k = plan.forest[j];
+      const unsigned long long nvox = ctx->h_forest[4 + 4 * j + 1], overflow = ctx->h_forest[4 + 4 * j + 2];
+      if (nvox > clouds[k]->n) return fail(SGA_ERR_HIP, "the device reported %llu voxels for the %zu points of cloud %zu", nvox, clouds[k]->n, k);
+      if (overflow)
+        lone.push_back(k);  // two voxels of the member may have shared a key: what the chain made of it is dropped
+      else
+        SGA_TRY(add_member(k, static_cast<uint32_t>(nvox), off, static_cast<uint32_t>(runs)));
+      off += static_cast<uint32_t>(clouds[k]->n);
+      runs += nvox;  // (the runs are numbered over the whole chain, an overflowed member's included)
+    }
+  }
+  for (size_t k : plan.empty) SGA_TRY(add_member(k, 0u, 0u, 0u));  // an empty map: its 16-slot table is cleared with the others
+  SGA_TRY(vox_forest_enqueue_finalize(ctx, members, runs, leaf, ch));
+  // ---- the other members through the lone routine, one after the other
+  for (size_t k : lone) {
+    sga_index* one = nullptr;
+    SGA_TRY(sga_index_build_gaussian_voxelmap(ctx, clouds[k], leaf, &one));
+    made[k].reset(one);
+  }
+  if (!built.empty() && !ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k : built) SGA_TRY(mark_ready(ctx, made[k]->ready));
+  return SGA_OK;
+}
 }  // namespace
 
 void forest_count_launch() { g_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 void grid_forest_count_launch() { g_grid_forest_launches.fetch_add(1, std::memory_order_relaxed); }
+void vox_forest_count_launch() { g_vox_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 }  // namespace sga
 
 using namespace sga;
@@ -239,6 +340,41 @@ int sga_voxelgrid_sampling_batch(sga_context* ctx, const sga_cloud* const* cloud
   SGA_ENTER(ctx);
   std::vector<std::unique_ptr<sga_cloud>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
   SGA_TRY(voxelgrid_batch(ctx, clouds, count, leaf, made));
+  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
+  return SGA_OK;
+}
+
+int sga_debug_voxelmap_batch_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_vox_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_voxelmap_batch_plan(const sga_cloud* const* clouds, size_t count, double leaf, int out[6]) {
+  if (!out || (count > 0 && !clouds)) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  SGA_TRY(voxelmaps_batch_check(clouds, count, leaf));
+  const VoxForestPlan P = vox_forest_plan(clouds, count);
+  out[0] = static_cast<int>(P.forest.size());
+  out[1] = static_cast<int>(P.lone.size());
+  out[2] = static_cast<int>(P.empty.size());
+  out[3] = P.member_bits;
+  out[4] = P.end_bit;
+  out[5] = static_cast<int>(P.points);
+  return SGA_OK;
+}
+
+int sga_index_build_gaussian_voxelmap_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, sga_index** out) {
+  if (count == 0) return SGA_OK;
+  if (out)
+    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(voxelmaps_batch_check(clouds, count, leaf));
+  for (size_t k = 0; k < count; k++)
+    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
+  SGA_ENTER(ctx);
+  std::vector<std::unique_ptr<sga_index>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
+  SGA_TRY(voxelmaps_batch(ctx, clouds, count, leaf, made));
   for (size_t k = 0; k < count; k++) out[k] = made[k].release();
   return SGA_OK;
 }

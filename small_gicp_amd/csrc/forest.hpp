@@ -108,6 +108,74 @@ GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, do
 // member j (room for the member's point count); member j's run count arrives in word 4 j + 5 of the context's box block, then `seq` in word 0
 int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq);
 void grid_forest_count_launch();  // batch_preprocess.hip: every kernel and sort of grid_forest_enqueue (sga_debug_voxelgrid_batch_launches)
+// ---- the voxel-map forest: sga_index_build_gaussian_voxelmap for B clouds in one chain of launches -----------
+// The members' points are concatenated (member m at [off, off + n)) and sorted ONCE, stably, under the key
+//   (m << 49) | (cz & 0xffff) << 32 | (cy & 0xffff) << 16 | (cx & 0xffff);   a dropped point: (m << 49) | (2^49 - 1), last of its member
+// — the voxel coordinates being voxel_keys_kernel's.  The key separates the voxels of a member exactly when every axis of the member spans
+// fewer than 65536 voxels; the keys launch reduces the range, the runs stage raises the member's overflow word beside its voxel count,
+// and the host rebuilds such a member by the lone routine.
+constexpr size_t kVoxForestMaxMember = 262144;    // points of a member of the chain (2^18: a run's first point takes 18 bits of the rank key)
+constexpr size_t kVoxForestMaxMembers = 1u << 15;  // the member number's bits above bit 49
+constexpr int kVoxKeyMemberShift = 49, kVoxRankMemberShift = 18;
+struct VoxForestPlan {
+  int member_bits = 0;  // bits_for(members of the chain)
+  int end_bit = 0;      // the sort's: 49 + member_bits; 0: no member in the chain
+  size_t points = 0;    // the concatenation
+  std::vector<size_t> forest, lone, empty;  // positions of the members in the chain / through the lone routine / without points
+};
+// What the host decides about a batched voxel-map call before it launches anything: a member joins the chain — members taken in the
+// call's order — with 1 .. kVoxForestMaxMember points while the concatenation stays within kGridForestMaxPoints and the chain within
+// kVoxForestMaxMembers members; every other non-empty member goes through the lone routine.
+inline VoxForestPlan vox_forest_plan(const sga_cloud* const* clouds, size_t count) {
+  VoxForestPlan P;
+  for (size_t k = 0; k < count; k++) {
+    const size_t n = clouds[k]->n;
+    if (n == 0)
+      P.empty.push_back(k);
+    else if (n <= kVoxForestMaxMember && P.points + n <= kGridForestMaxPoints && P.forest.size() < kVoxForestMaxMembers)
+      P.forest.push_back(k), P.points += n;
+    else
+      P.lone.push_back(k);
+  }
+  if (!P.forest.empty()) {
+    while ((1ull << P.member_bits) < P.forest.size()) P.member_bits++;
+    P.end_bit = kVoxKeyMemberShift + P.member_bits;
+  }
+  return P;
+}
+
+// One member of the chain (read with scalar loads).  The first block is what voxel_keys_kernel receives, used by the stage before the
+// host's wait; the second is what voxel_finalize_kernel receives, known once the host has the voxel counts and filled in for the stage
+// behind the wait (a second table: the members that did not overflow, and the empty members, whose tables are cleared with the others').
+struct VoxMember {
+  const float4* pts;
+  const Cov8* cov;
+  double ox, oy, oz;
+  int* range;                      // {min x, y, z, max x, y, z} of the voxel coordinates: in the call's table, set up with it
+  unsigned long long* count_slot;  // word 1 receives the member's voxel count, word 2 its overflow word (pinned, device-mapped: the box block)
+  uint32_t n, off;                 // the member's stretch of the concatenation
+  float4* means;
+  Cov8* mcov;
+  int* coords;
+  uint32_t* counts;
+  unsigned long long* hkeys;
+  uint32_t* hvals;
+  uint32_t hmask, nvox;
+  uint32_t run0, pad;              // the member's first run among the runs of the whole chain
+};
+// the chain's scratch: lives from the first stage to the end of the call (then: the stream's free list)
+struct VoxForestChain {
+  DevBuf<unsigned long long> keys, keys_sorted, rank_keys, rank_keys_sorted, table1, table2;
+  DevBuf<uint32_t> vals, order, flags, seg_id, seg_start, seg_ids, seg_by_rank;
+  size_t points = 0;
+  int member_bits = 0;
+};
+// index_build.hip: keys, sort, runs of the plan's chain enqueued on the context's stream; member j's voxel count arrives in word 4 j + 5 of
+// the context's box block, its overflow word in word 4 j + 6, then `seq` in word 0
+int vox_forest_enqueue_runs(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const VoxForestPlan& plan, unsigned long long seq, VoxForestChain& ch);
+// the ranks' sort over `runs` runs, the clearing of every member's hash table and the finalize launch (members: second block filled in)
+int vox_forest_enqueue_finalize(sga_context* ctx, const std::vector<VoxMember>& members, size_t runs, double leaf, VoxForestChain& ch);
+void vox_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the two (sga_debug_voxelmap_batch_launches)
 constexpr uint32_t kForestMaxPoints = 1024 * 32;  // = kSplitMaxPoints (index_build.hip): the clouds the split kernel holds whole
 
 }  // namespace sga

@@ -325,7 +325,8 @@ def run_synthetic(num_frames=20, pinned=False, **kw):
     }
 
 
-def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, batched_preprocessing=False, batched_downsampling=False):
+def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, batched_preprocessing=False, batched_downsampling=False,
+                          registration_type="GICP", voxel_resolution=1.0, batched_voxelmaps=False):
     """The flow protocol (every pair (i - 1, i) registered from the identity, the relative poses multiplied up in frame order:
     odometry_benchmark_small_gicp_tbb_flow.cpp:73-110) with the registrations BATCHED: the scans are preprocessed as OnlineOdometry does,
     then groups of `batch` consecutive pairs are registered by one BatchProblem.align each — one search + factor launch, one row
@@ -334,15 +335,20 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
     batched_preprocessing: the kd-trees and covariances of every `batch` scans are made by one api.preprocess_batch (the same trees and
     covariances, bit for bit: the results do not change).
     batched_downsampling: the raw scans of every `batch` frames are uploaded and downsampled by one api.voxelgrid_sampling_batch (the
-    same clouds, bit for bit); without it the scans are downsampled one by one."""
+    same clouds, bit for bit); without it the scans are downsampled one by one.
+    registration_type: "GICP" (every pair against the kd-tree of scan i - 1) or "VGICP" (against the Gaussian voxel map of scan i - 1 at
+    voxel_resolution).  batched_voxelmaps: the maps of every `batch` scans are made by one api.build_gaussian_voxelmaps (the same maps,
+    bit for bit: the results do not change); without it by GaussianVoxelMap.from_cloud one by one."""
     from . import synthetic
 
     if batch < 1:
         raise ValueError("batch must be at least 1")
+    if registration_type not in ("GICP", "VGICP"):
+        raise ValueError("registration_type must be GICP or VGICP")
     ctx = ctx or api.Context(0)
     prev_mode = ctx.set_stream_ordered(True)
     try:
-        setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
+        setting = api.make_setting(registration_type, max_correspondence_distance=max_correspondence_distance)
         frames = []  # (cloud, tree) per scan
         pending = []  # downsampled scans waiting for their batched trees and covariances
         raw = []  # uploaded scans waiting for their batched voxel grid
@@ -367,12 +373,19 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
             if pending and (len(pending) >= batch or f == num_frames - 1):
                 frames.extend(api.preprocess_batch(pending, num_neighbors))
                 pending = []
+        targets = [tree for _, tree in frames]
+        if registration_type == "VGICP":  # the target of pair (i - 1, i): the map of scan i - 1 (the last scan is nobody's target)
+            targets = []
+            for first in range(0, num_frames - 1, batch):
+                clouds = [frames[i][0] for i in range(first, min(first + batch, num_frames - 1))]
+                targets.extend(api.build_gaussian_voxelmaps(clouds, voxel_resolution) if batched_voxelmaps else [api.GaussianVoxelMap.from_cloud(c, voxel_resolution) for c in clouds])
         ctx.synchronize()
         rel, iters = [], []
         t0 = time.perf_counter()
         for first in range(1, num_frames, batch):
             group = range(first, min(first + batch, num_frames))
-            problems = [api.Problem(frames[i - 1][1], frames[i][1], np.eye(4), ctx=ctx) for i in group]  # the scan by its own index, as OnlineOdometry
+            src = 0 if registration_type == "VGICP" else 1  # kd-tree targets: the scan by its own index, as OnlineOdometry; map targets: the scan's cloud
+            problems = [api.Problem(targets[i - 1], frames[i][src], np.eye(4), ctx=ctx) for i in group]
             bp = api.BatchProblem(problems)
             for r in bp.align(setting):
                 rel.append(r.T_target_source)
