@@ -184,6 +184,20 @@ int sga_index_voxelmap_download(sga_context* ctx, const sga_index* index, int32_
  * sga_problem_create / sga_align like a one-shot map; problems created before an insert must be re-created. */
 int sga_voxelmap_create(sga_context* ctx, double leaf_size, sga_index** out);
 int sga_voxelmap_insert(sga_context* ctx, sga_index* voxelmap, const sga_cloud* points_with_covs, const double T[16]);
+/* sga_voxelmap_insert(ctx, maps[k], clouds_with_covs[k], T + 16 k) for k = 0 .. count - 1 (T: count column-major 4x4 matrices, NULL =
+ * identities): B scans into the B maps of B scan-to-model streams.  Afterwards every map holds exactly what the lone call leaves — voxel
+ * ids in creation order, coordinates, counts, the fp64 means and covariances and the exported fp32 records, the origin of the export, the
+ * LRU stamps and counter, the LRU sweep when it falls due — bit for bit; only the layout of a hash table may differ.  Incremental GAUSSIAN
+ * maps with clouds of 1 .. 262144 points share one chain of launches on the context's stream (while their concatenation stays within
+ * 2^24 points) and ONE host wait, for the members' voxel counts; behind it every map grows under the lone call's conditions, LRU sweeps
+ * that fall due run one map at a time, and one launch exports the records of all maps.  A member whose scan spans 65536 or more voxels
+ * along an axis (the device finds out), a larger cloud and a FLAT map of any contents go through the lone routine inside the call, one
+ * after the other: a batched flat-map update is not built.  An empty cloud advances its map's insert counter (and sweeps, and exports)
+ * as the lone call does.  A map may appear ONCE per call (two inserts into one map are ordered: SGA_ERR_INVALID); a cloud may appear
+ * several times; members made by another context of the device are waited for.  Every member is checked before any device work, with
+ * the lone call's status and message plus the member's number; on such a failure no map is touched.  count == 0 is SGA_OK.  Blocking
+ * contexts synchronise once at the end; stream-ordered contexts return after the one wait. */
+int sga_voxelmap_insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds_with_covs, const double* T, size_t count);
 int sga_voxelmap_set_lru(sga_index* voxelmap, uint32_t horizon, uint32_t clear_cycle);
 /* IncrementalVoxelMap<FlatContainerCov> (ann/flat_container.hpp:15-100): voxels that keep up to max_num_points_in_cell (default 10,
  * at most 16) of the inserted points, at least sqrt(min_sq_dist_in_cell) (default 0.1 m) apart, with their covariances — the

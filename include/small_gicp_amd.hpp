@@ -660,6 +660,27 @@ inline std::vector<GaussianVoxelMap::Ptr> create_gaussian_voxelmaps(sga_context*
   }
   return maps;
 }
+/// sga_voxelmap_insert_batch: maps[k]->insert(*clouds[k], Ts[k]) for all k (Ts empty: identities) — the incremental Gaussian maps of several
+/// scan-to-model streams of one context updated by one chain of launches and one host wait; every map holds what the lone insert leaves,
+/// bit for bit.  A map may appear once per call; a map that has not been inserted into yet is created here, as insert() creates it.
+inline void insert_batch(sga_context* ctx, const std::vector<GaussianVoxelMap::Ptr>& maps, const std::vector<std::shared_ptr<const PointCloud>>& clouds, const std::vector<Isometry3d>& Ts = {}) {
+  if (maps.size() != clouds.size() || (!Ts.empty() && Ts.size() != maps.size())) throw std::runtime_error("insert_batch: as many maps as clouds (and poses)");
+  std::vector<sga_index*> ms;
+  std::vector<const sga_cloud*> cs;
+  std::vector<double> T16;
+  for (size_t k = 0; k < maps.size(); k++) {
+    GaussianVoxelMap& vm = *maps[k];
+    if (!vm.h) {
+      vm.ctx = ctx;
+      check(sga_voxelmap_create(ctx, vm.leaf, &vm.h), "sga_voxelmap_create");
+      check(sga_voxelmap_set_lru(vm.h, static_cast<uint32_t>(vm.lru_horizon), static_cast<uint32_t>(vm.lru_clear_cycle)), "sga_voxelmap_set_lru");
+    }
+    ms.push_back(vm.h);
+    cs.push_back(clouds[k]->h);
+    if (!Ts.empty()) T16.insert(T16.end(), Ts[k].data(), Ts[k].data() + 16);
+  }
+  check(sga_voxelmap_insert_batch(ctx, ms.data(), cs.data(), Ts.empty() ? nullptr : T16.data(), ms.size()), "sga_voxelmap_insert_batch");
+}
 
 template <typename Reg>
 void copy_setting(Reg& reg, const RegistrationSetting& setting) {

@@ -77,6 +77,16 @@ int sga_debug_voxelmap_batch_plan(const sga_cloud* const* clouds, size_t count, 
  * and scan call, and its copy commands (members that take the lone path inside the call are not counted): a chain of B clouds counts as
  * many as a chain of one. */
 int sga_debug_voxelmap_batch_launches(unsigned long long* launches);
+/* What sga_voxelmap_insert_batch(maps, clouds, count) would do, decided by the very code the call itself runs (csrc/forest.hpp:
+ * ivm_forest_plan): out[0] = members of the shared chain, out[1] = members that go through the lone routine (flat maps, more than 262144
+ * points, past the chain's caps), out[2] = Gaussian maps with an empty cloud, out[3] = the bits of the member number, out[4] = the end bit
+ * of the chain's sort (49 + out[3]; 0: no chain), out[5] = points of the concatenation.  A member whose scan spans 65536 or more voxels
+ * per axis is counted in out[0]: the device finds that out.  The members are checked as the call checks them.  No device work. */
+int sga_debug_voxelmap_insert_batch_plan(sga_index* const* maps, const sga_cloud* const* clouds, size_t count, int out[6]);
+/* Launches enqueued so far, in this process, by the shared chain of sga_voxelmap_insert_batch: its kernels, one per sort and scan call,
+ * and its table copies (growth, LRU sweeps and members that take the lone path inside the call are not counted): a round of B members
+ * without growth counts as many as a round of one. */
+int sga_debug_voxelmap_insert_batch_launches(unsigned long long* launches);
 /* Sets the launch epoch of the context's voxel-grid calls (the tag of ds_segments_kernel's status words; the next call uses epoch + 1, and
  * a call that finds 2^30 - 1 clears the words and starts again at 1) so that a test reaches the wrap-around a service meets after 2^30
  * calls.  Forwards only: an epoch below the current one, or above 2^30 - 1, is refused (words of earlier launches would read as current). */

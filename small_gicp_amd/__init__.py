@@ -34,6 +34,7 @@ from .api import (  # noqa: F401
     forest_launches,
     error_model_eval,
     get_warm_limit,
+    insert_batch,
     set_error_model,
     set_grid_mode,
     set_search_mode,
@@ -51,6 +52,7 @@ from .api import (  # noqa: F401
     voxelgrid_sampling_batch,
     voxelgrid_batch_launches,
     voxelmap_batch_launches,
+    voxelmap_insert_batch_launches,
 )
 
 __version__ = "0.1.0"

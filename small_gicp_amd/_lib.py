@@ -113,6 +113,9 @@ SYMBOLS = [
     ("sga_index_voxelmap_download", C.c_int, [_vp, _vp, C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint32)]),
     ("sga_voxelmap_create", C.c_int, [_vp, C.c_double, _pvp]),
     ("sga_voxelmap_insert", C.c_int, [_vp, _vp, _vp, _dp]),
+    ("sga_voxelmap_insert_batch", C.c_int, [_vp, _pvp, _pvp, _dp, C.c_size_t]),
+    ("sga_debug_voxelmap_insert_batch_plan", C.c_int, [_pvp, _pvp, C.c_size_t, C.POINTER(C.c_int)]),
+    ("sga_debug_voxelmap_insert_batch_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_voxelmap_set_lru", C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     ("sga_flatmap_create", C.c_int, [_vp, C.c_double, _pvp]),
     ("sga_flatmap_set_setting", C.c_int, [_vp, C.c_double, C.c_uint32]),

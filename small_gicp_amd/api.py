@@ -1305,6 +1305,49 @@ def voxelmap_batch_launches():
     return v.value
 
 
+def _insert_members(maps, clouds):
+    maps, clouds = list(maps), list(clouds)
+    if len(maps) != len(clouds):
+        raise ValueError(f"{len(maps)} maps for {len(clouds)} clouds")
+    for m in maps:
+        if not isinstance(m, (GaussianVoxelMap, _FlatVoxelMap)):
+            raise TypeError("insert_batch takes GaussianVoxelMap / IncrementalVoxelMap* objects")
+    ctx = _one_context(clouds)
+    if maps and any(m.ctx is not maps[0].ctx for m in maps):
+        raise ValueError("the maps of a batch must belong to one context")
+    ms = (C.c_void_p * max(1, len(maps)))(*[m.h.value for m in maps])
+    cs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    return maps, clouds, (maps[0].ctx if maps else ctx), ms, cs
+
+
+def insert_batch(maps, clouds, Ts=None):
+    """sga_voxelmap_insert_batch: maps[k].insert(clouds[k], Ts[k]) for all k (Ts None: identities) — the maps of several scan-to-model
+    streams updated by one chain of launches and one host wait.  Every map holds what the lone insert leaves, bit for bit.  Incremental
+    GaussianVoxelMaps with clouds of at most 262144 points share the launches; flat maps, larger clouds and scans that span 65536 or more
+    voxels along an axis are inserted one by one inside the call.  A map may appear once per call, a cloud several times."""
+    maps, clouds, ctx, ms, cs = _insert_members(maps, clouds)
+    t16 = None if Ts is None else _T16s(Ts, len(maps))
+    check(load().sga_voxelmap_insert_batch(ctx.h, ms, cs, None if t16 is None else _dp(t16), len(maps)))
+
+
+def _voxelmap_insert_batch_plan(maps, clouds):
+    """Diagnostics (sga_debug_voxelmap_insert_batch_plan): what insert_batch(maps, clouds) would do — forest (members of the shared chain),
+    lone (members through the lone routine), empty (Gaussian maps given an empty cloud), member_bits, end_bit of the chain's sort, points
+    of the concatenation."""
+    maps, clouds, _, ms, cs = _insert_members(maps, clouds)
+    out = (C.c_int * 6)()
+    check(load().sga_debug_voxelmap_insert_batch_plan(ms, cs, len(maps), out))
+    return {"forest": out[0], "lone": out[1], "empty": out[2], "member_bits": out[3], "end_bit": out[4], "points": out[5]}
+
+
+def voxelmap_insert_batch_launches():
+    """Diagnostics (sga_debug_voxelmap_insert_batch_launches): kernels, sorts, scans and table copies enqueued so far by the shared chain
+    of insert_batch."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_voxelmap_insert_batch_launches(C.byref(v)))
+    return v.value
+
+
 def _voxelgrid_batch_plan(clouds, resolution):
     """Diagnostics (sga_debug_voxelgrid_batch_plan): what voxelgrid_sampling_batch(clouds, resolution) would do — key_bytes (4 / 8; 0: no
     shared chain), W (bits below the member number), member_bits, forest (members of the shared chain), lone (members through the lone

@@ -5,6 +5,7 @@
 // kernels (index_build.hip, preprocess.hip) run the lone kernels' bodies with the arguments read from a per-call table (forest.hpp).
 // sga_voxelgrid_sampling_batch does the same for the stage before them: B raw scans downsampled by one chain —
 // keys, ONE sort over the concatenation under the key (member, the member's own short key), runs, centroids — and one host wait.
+// sga_voxelmap_insert_batch: B scans into B incremental Gaussian maps by one chain and one host wait.
 #include <atomic>
 #include <memory>
 #include <unordered_set>
@@ -18,7 +19,7 @@ namespace sga {
 int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
 
 namespace {
-std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0}, g_vox_forest_launches{0};
+std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0}, g_vox_forest_launches{0}, g_ivm_forest_launches{0};
 }  // namespace
 
 // the context's box block with room for `members` slots (grow-only; no call is in flight: every call waits for its boxes)
@@ -292,11 +293,149 @@ int voxelmaps_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t cou
   for (size_t k : built) SGA_TRY(mark_ready(ctx, made[k]->ready));
   return SGA_OK;
 }
+// the argument checks of sga_voxelmap_insert_batch and of its plan that need no context (status and message as the lone call's, naming the member)
+int insert_batch_check(sga_index* const* maps, const sga_cloud* const* clouds, size_t count) {
+  std::unordered_set<const void*> seen;
+  for (size_t k = 0; k < count; k++) {
+    if (!maps[k]) return fail(SGA_ERR_INVALID, "null argument: maps[%zu] is NULL", k);
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "null argument: clouds[%zu] is NULL", k);
+    const sga_index* idx = maps[k];
+    const sga_cloud* cloud = clouds[k];
+    if (!idx->incremental) return fail(SGA_ERR_INVALID, "not an incremental voxel map (create it with sga_voxelmap_create) (member %zu)", k);
+    if ((idx->kind != SGA_INDEX_FLATMAP || idx->has_covs) && cloud->n > 0 && !cloud->has_covs) return fail(SGA_ERR_INVALID, "GaussianVoxelMap needs point covariances (member %zu)", k);
+    if (idx->kind == SGA_INDEX_FLATMAP && idx->has_normals && cloud->n > 0 && !cloud->has_normals) return fail(SGA_ERR_INVALID, "a flat voxel map with normals needs point normals (member %zu)", k);
+    if (!seen.insert(idx).second) return fail(SGA_ERR_INVALID, "map %zu appears twice in the batch (two inserts into one map are ordered: make two calls)", k);
+  }
+  return SGA_OK;
+}
+
+// sga_voxelmap_insert for every member.  The members of the plan's chain share the launches (voxelmap.hip:
+// ivm_forest_enqueue_runs / _update / _export) and ONE host wait, for their run counts, new-voxel counts and overflow words; behind it
+// every map grows under the lone call's conditions.  Sweeps run one map at a time; the fp32 records of all maps are exported by one
+// launch.  Flat maps, larger clouds and members whose key overflowed go through the lone routine afterwards.
+int insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, size_t count) {
+  for (size_t k = 0; k < count; k++) {
+    SGA_TRY(wait_ready(ctx, clouds[k]->ready));
+    SGA_TRY(wait_ready(ctx, maps[k]->ready));
+  }
+  const IvmForestPlan plan = ivm_forest_plan(maps, clouds, count);
+  IvmForestChain ch;
+  std::vector<size_t> lone = plan.lone;
+  std::vector<size_t> own;  // the maps whose counter, sweep and export are this call's: the chain's members that did not overflow, and the empty ones
+  if (!plan.forest.empty()) {
+    const size_t B = plan.forest.size();
+    SGA_TRY(forest_box_block(ctx, B));
+    const unsigned long long seq = ++ctx->forest_seq;
+    if (const int rc = ivm_forest_enqueue_runs(ctx, maps, clouds, T, plan, seq, ch); rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block: nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    // ---- the one wait: run counts, overflow words and new-voxel counts of all members of the chain
+    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel-map insert"));
+    std::vector<uint32_t> nseg(B), n_new(B);
+    std::vector<bool> overflow(B);
+    size_t runs = 0, total_new = 0;
+    for (size_t j = 0; j < B; j++) {
+      const size_t k = plan.forest[j];
+      const unsigned long long s = ctx->h_forest[4 + 4 * j + 1], w = ctx->h_forest[4 + 4 * j + 3];
+      if (s > clouds[k]->n || w > s) return fail(SGA_ERR_HIP, "the device reported %llu voxels (%llu new) for the %zu points of cloud %zu", s, w, clouds[k]->n, k);
+      nseg[j] = static_cast<uint32_t>(s);
+      n_new[j] = static_cast<uint32_t>(w);
+      overflow[j] = ctx->h_forest[4 + 4 * j + 2] != 0;
+      runs += s;
+      total_new += w;
+      if (!overflow[j] && maps[k]->n + w >= (1ull << 31)) return fail(SGA_ERR_INVALID, "voxel map too large (member %zu)", k);
+    }
+    // ---- capacity, then the second table: the pointers after growth, each member's place in the ranks' order
+    std::vector<IvmUpdate> members;
+    uint32_t off = 0, new0 = 0, old0 = 0;
+    for (size_t j = 0; j < B; j++) {
+      const size_t k = plan.forest[j];
+      sga_index* idx = maps[k];
+      const sga_cloud* cloud = clouds[k];
+      if (overflow[j]) {
+        lone.push_back(k);  // two voxels of the member may have shared a key: the chain writes nothing of it
+      } else {
+        own.push_back(k);
+        if (nseg[j] > 0) {
+          SGA_TRY(ivm_reserve(ctx, idx, idx->n + n_new[j]));
+          IvmUpdate g;
+          std::memset(&g, 0, sizeof(g));
+          g.pts = cloud->pts.p;
+          g.cov = cloud->cov.p;
+          g.T = insert_pose(T ? T + 16 * k : nullptr, cloud->origin);
+          g.inv_leaf = 1.0 / idx->leaf;
+          g.mean64 = idx->vmean64.p;
+          g.cov64 = idx->vcov64.p;
+          g.counts = idx->vcounts.p;
+          g.lru = idx->vlru.p;
+          g.coords = idx->vcoords.p;
+          g.hkeys = idx->hkeys.p;
+          g.hvals = idx->hvals.p;
+          g.hmask = idx->hmask;
+          g.n_old = static_cast<uint32_t>(idx->n);
+          g.lru_counter = idx->lru_counter;
+          g.nseg = nseg[j];
+          g.n_new = n_new[j];
+          g.new0 = new0;
+          g.old0 = old0;
+          g.end = off + static_cast<uint32_t>(cloud->n);
+          members.push_back(g);
+        }
+      }
+      off += static_cast<uint32_t>(cloud->n);
+      new0 += n_new[j];  // (the runs of an overflowed member stay in the ranks' order)
+      old0 += nseg[j] - n_new[j];
+    }
+    SGA_TRY(ivm_forest_enqueue_update(ctx, members, runs, static_cast<uint32_t>(total_new), B, ch));
+    for (size_t j = 0; j < B; j++)
+      if (!overflow[j]) maps[plan.forest[j]]->n += n_new[j];
+  }
+  own.insert(own.end(), plan.empty.begin(), plan.empty.end());
+  // ---- LRU sweeps (rare: one map at a time), then the fp32 records of every map by one launch
+  for (size_t k : own) {
+    maps[k]->lru_counter++;
+    SGA_TRY(ivm_lru_sweep(ctx, maps[k]));
+  }
+  std::vector<IvmExport> exports;
+  std::vector<double> origins(3 * own.size());
+  for (size_t i = 0; i < own.size(); i++) {
+    const sga_index* idx = maps[own[i]];
+    const sga_cloud* cloud = clouds[own[i]];
+    double* o = origins.data() + 3 * i;
+    for (int a = 0; a < 3; a++) o[a] = idx->origin[a];
+    if (cloud->n > 0) {  // the device frame of the records follows the inserted scan, as in the lone call
+      const Pose12 P = insert_pose(T ? T + 16 * own[i] : nullptr, cloud->origin);
+      const double lo[3] = {P.t[0], P.t[1], P.t[2]};
+      choose_origin(lo, lo, o);
+    }
+    if (idx->n == 0) continue;
+    IvmExport e;
+    std::memset(&e, 0, sizeof(e));
+    e.mean64 = idx->vmean64.p;
+    e.cov64 = idx->vcov64.p;
+    e.means = idx->pts.p;
+    e.mcov = idx->cov.p;
+    e.ox = o[0], e.oy = o[1], e.oz = o[2];
+    e.n = static_cast<uint32_t>(idx->n);
+    exports.push_back(e);
+  }
+  SGA_TRY(ivm_forest_enqueue_export(ctx, exports, ch));
+  for (size_t i = 0; i < own.size(); i++)  // every fallible step of these maps is behind us: the records enqueued are relative to the new origin
+    for (int a = 0; a < 3; a++) maps[own[i]]->origin[a] = origins[3 * i + a];
+  // ---- the other members through the lone routine, one after the other
+  for (size_t k : lone) SGA_TRY(sga_voxelmap_insert(ctx, maps[k], clouds[k], T ? T + 16 * k : nullptr));
+  if (!own.empty() && !ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k : own) SGA_TRY(mark_ready(ctx, maps[k]->ready));
+  return SGA_OK;
+}
 }  // namespace
 
 void forest_count_launch() { g_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 void grid_forest_count_launch() { g_grid_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 void vox_forest_count_launch() { g_vox_forest_launches.fetch_add(1, std::memory_order_relaxed); }
+void ivm_forest_count_launch() { g_ivm_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 }  // namespace sga
 
 using namespace sga;
@@ -377,6 +516,36 @@ int sga_index_build_gaussian_voxelmap_batch(sga_context* ctx, const sga_cloud* c
   SGA_TRY(voxelmaps_batch(ctx, clouds, count, leaf, made));
   for (size_t k = 0; k < count; k++) out[k] = made[k].release();
   return SGA_OK;
+}
+
+int sga_debug_voxelmap_insert_batch_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_ivm_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_voxelmap_insert_batch_plan(sga_index* const* maps, const sga_cloud* const* clouds, size_t count, int out[6]) {
+  if (!out || (count > 0 && (!maps || !clouds))) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  SGA_TRY(insert_batch_check(maps, clouds, count));
+  const IvmForestPlan P = ivm_forest_plan(maps, clouds, count);
+  out[0] = static_cast<int>(P.forest.size());
+  out[1] = static_cast<int>(P.lone.size());
+  out[2] = static_cast<int>(P.empty.size());
+  out[3] = P.member_bits;
+  out[4] = P.end_bit;
+  out[5] = static_cast<int>(P.points);
+  return SGA_OK;
+}
+
+int sga_voxelmap_insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, size_t count) {
+  if (count == 0) return SGA_OK;
+  if (!ctx || !maps || !clouds) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(insert_batch_check(maps, clouds, count));
+  for (size_t k = 0; k < count; k++)
+    if (clouds[k]->device != ctx->device || maps[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud / map live on another device (member %zu)", k);
+  SGA_ENTER(ctx);
+  return insert_batch(ctx, maps, clouds, T, count);
 }
 
 int sga_index_build_kdtree_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, sga_index** out) {

@@ -19,16 +19,13 @@
 #include <rocprim/rocprim.hpp>
 
 #include "device_math.hpp"
+#include "forest.hpp"
+#include "sort_util.hpp"
 #include "voxel_hash.hpp"
 
 namespace sga {
 
 int ensure_temp(sga_context* ctx, size_t bytes);
-
-struct Pose12 {
-  double r[9];  // row-major rotation
-  double t[3];
-};
 
 __global__ void ivm_keys_kernel(const float4* __restrict__ pts, size_t n, Pose12 T, double inv_leaf, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
   const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
@@ -186,6 +183,193 @@ __global__ void ivm_export_kernel(uint32_t n, const double* __restrict__ mean64,
   o.zz = static_cast<float>(cov64[6 * v + 5]);
   o.pad0 = o.pad1 = 0.f;
   mcov[v] = o;
+}
+
+// ---- the insert forest: B inserts in one chain of launches (forest.hpp) -----------------------------------------
+// Kernels of their own beside the lone ones (whose code and register rows stay: profiles/batch_voxelmap_insert_kernel_resources.txt); the
+// arithmetic that decides a map's contents — the posed point, the voxel coordinates, the fp64 un-finalize / add / finalize — is the lone
+// kernels', statement for statement, with the pose and the pointers read from the call's tables instead of the kernel's arguments.
+static_assert(sizeof(IvmMember) % 8 == 0 && sizeof(IvmUpdate) % 8 == 0 && sizeof(IvmExport) % 8 == 0, "table entries are copied as 8-byte words");
+constexpr unsigned long long kIvmDropped = (1ull << kVoxKeyMemberShift) - 1;  // bit 48 and everything below: behind every voxel of the member
+
+// workgroup b: 256 points of the member m with prefix[m] <= b < prefix[m + 1].  ivm_keys_kernel's coordinates under section 3.14's key, and
+// the range of the member's voxel coordinates: reduced over the wave, then one atomic per wave, axis and end.
+__global__ __launch_bounds__(256) void ivm_keys_forest_kernel(const IvmMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const IvmMember& g = *uniform_const(members + m);
+  const uint32_t i = (blockIdx.x - prefix[m]) * 256u + threadIdx.x;
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+  if (i < g.n) {
+    const float4 p = g.pts[i];
+    const Pose12& T = g.T;
+    const double inv_leaf = g.inv_leaf;
+    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
+    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
+    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
+    const bool bad = abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20) || !(x == x) || !(y == y) || !(z == z);
+    const unsigned long long key = static_cast<unsigned long long>(static_cast<uint32_t>(cx) & 0xffffu) | (static_cast<unsigned long long>(static_cast<uint32_t>(cy) & 0xffffu) << 16) |
+                                   (static_cast<unsigned long long>(static_cast<uint32_t>(cz) & 0xffffu) << 32);
+    keys[g.off + i] = (static_cast<unsigned long long>(m) << kVoxKeyMemberShift) | (bad ? kIvmDropped : key);  // a member's dropped points sort last in its stretch
+    vals[g.off + i] = i;  // the index within the member
+    if (!bad) lo[0] = hi[0] = cx, lo[1] = hi[1] = cy, lo[2] = hi[2] = cz;
+  }
+  for (int a = 0; a < 3; a++)
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[a] = min(lo[a], __shfl_xor(lo[a], off));
+      hi[a] = max(hi[a], __shfl_xor(hi[a], off));
+    }
+  if ((threadIdx.x & 63u) == 0u && lo[0] <= hi[0])  // (a wave of dropped points only: nothing to report)
+    for (int a = 0; a < 3; a++) {
+      atomicMin(g.range + a, lo[a]);
+      atomicMax(g.range + 3 + a, hi[a]);
+    }
+}
+
+__global__ void ivm_heads_forest_kernel(const unsigned long long* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = keys[i];  // (the member number is part of the key: a member's first voxel never continues its neighbour's last)
+  flags[i] = ((k & (1ull << 48)) == 0ull && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
+}
+
+// Sorted position i of the concatenation.  The head of a run records the run's start and number and does ivm_lookup_kernel's work: the
+// voxel's LONE key, recomputed from the run's first point (the sort is stable: the earliest inserted one), looked up in the member's own
+// table; an existing voxel's id, or the rank key (member, index of the first point) of a new one, counted per member.  An existing voxel's
+// rank key carries the member number `total`: those runs sort behind every new one, in run order.
+// A member's counts are final when the launch has finished all its positions: every workgroup adds the positions it covered to the
+// member's second counter, and the one that completes the member hands run count, overflow word and new-voxel count to the host (the
+// last member to arrive publishes the call).
+__global__ __launch_bounds__(256) void ivm_starts_forest_kernel(const IvmMember* __restrict__ members, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ seg_id, const uint32_t* __restrict__ order,
+                                                                uint32_t n, uint32_t* __restrict__ seg_start, uint32_t* __restrict__ seg_vid, unsigned long long* __restrict__ rank_keys, uint32_t* __restrict__ seg_ids, const ForestBoxes hand) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n && flags[i]) {
+    const uint32_t m = static_cast<uint32_t>(keys[i] >> kVoxKeyMemberShift);
+    if (m < hand.total) {  // (always: the keys launch wrote every key with its member's number)
+      const IvmMember& g = members[m];
+      const uint32_t s = seg_id[i], first = order[i];
+      const float4 p = g.pts[first];
+      const Pose12& T = g.T;
+      const double inv_leaf = g.inv_leaf;
+      const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
+      const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
+      const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+      const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
+      const uint32_t hmask = g.hmask;
+      const uint32_t v = hmask ? ivm_find(g.hkeys, g.hvals, hmask, voxel_key(cx, cy, cz)) : 0xffffffffu;
+      seg_start[s] = i;
+      seg_vid[s] = v;
+      rank_keys[s] = v == 0xffffffffu ? ((static_cast<unsigned long long>(m) << kVoxRankMemberShift) | first) : (static_cast<unsigned long long>(hand.total) << kVoxRankMemberShift);
+      seg_ids[s] = s;
+      if (v == 0xffffffffu) atomicAdd(g.counters, 1u);
+    }
+  }
+  __syncthreads();
+  const uint32_t b0 = blockIdx.x * 256u, b1 = min(b0 + 256u, n);
+  const uint32_t m0 = static_cast<uint32_t>(keys[b0] >> kVoxKeyMemberShift), m1 = min(static_cast<uint32_t>(keys[b1 - 1u] >> kVoxKeyMemberShift), hand.total - 1u);
+  for (uint32_t m = m0 + threadIdx.x; m <= m1; m += 256u) {  // the members with positions in [b0, b1)
+    const IvmMember& g = members[m];
+    const uint32_t end = g.off + g.n;
+    const uint32_t covered = min(b1, end) - max(b0, g.off);
+    __threadfence();
+    if (__hip_atomic_fetch_add(g.counters + 1, covered, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + covered != g.n) continue;
+    const uint32_t r0 = seg_id[g.off], r1 = end < n ? seg_id[end] : seg_id[n - 1] + flags[n - 1];
+    bool overflow = false;
+    for (int a = 0; a < 3; a++) {
+      const long long lo = g.range[a], hi = g.range[3 + a];
+      overflow = overflow || (hi >= lo && hi - lo >= 65536);  // two voxels of the member may share a key
+    }
+    g.count_slot[1] = r1 - r0;
+    g.count_slot[2] = overflow ? 1ull : 0ull;
+    g.count_slot[3] = __hip_atomic_load(g.counters, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    forest_box_arrive(hand);
+  }
+}
+
+// workgroup b: 128 runs of the member that owns it, the member's new voxels first (in creation order: the ranks' order), then its existing
+// ones.  ivm_assign_kernel (voxel id = n_old + rank) and ivm_update_kernel's loop, statement for statement, over the run's entries up to
+// the end of the member's stretch (its dropped points carry another key); a new voxel's coordinates are those of the run's first point,
+// recomputed by the keys kernel's expression, and it goes into the member's own table under the lone key.
+__global__ __launch_bounds__(128) void ivm_update_forest_kernel(const IvmUpdate* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, uint32_t total_new, const uint32_t* __restrict__ seg_by_rank,
+                                                                const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_vid, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ order) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int mem = forest_member_of(prefix, count, blockIdx.x);
+  const IvmUpdate& g = *uniform_const(members + mem);
+  const uint32_t j = (blockIdx.x - prefix[mem]) * 128u + threadIdx.x;
+  if (j >= g.nseg) return;
+  const bool is_new = j < g.n_new;
+  const uint32_t s = seg_by_rank[is_new ? g.new0 + j : total_new + g.old0 + (j - g.n_new)];
+  const uint32_t v = is_new ? g.n_old + j : seg_vid[s];
+  const uint32_t first = seg_start[s];
+  const uint32_t end = g.end;
+  const unsigned long long key = keys[first];
+  const float4* __restrict__ pts = g.pts;
+  const Cov8* __restrict__ cov = g.cov;
+  double* __restrict__ mean64 = g.mean64;
+  double* __restrict__ cov64 = g.cov64;
+  const Pose12& T = g.T;
+  uint32_t N = is_new ? 0u : g.counts[v];
+  double m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
+  if (!is_new) {  // un-finalize: mean *= num_points, cov *= num_points
+    for (int k = 0; k < 3; k++) m[k] = mean64[3 * v + k] * static_cast<double>(N);
+    for (int k = 0; k < 6; k++) c[k] = cov64[6 * v + k] * static_cast<double>(N);
+  }
+  for (uint32_t i = first; i < end && keys[i] == key; ++i) {
+    const uint32_t src = order[i];
+    const float4 p = pts[src];
+    const Cov8 q = cov[src];
+    m[0] += T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
+    m[1] += T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
+    m[2] += T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    // R C R^T (T.matrix() * cov * T.matrix().transpose(): the translation column meets the zero row of the 4x4 covariance)
+    const double C[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
+    double RC[3][3];
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * C[0][b] + T.r[3 * a + 1] * C[1][b] + T.r[3 * a + 2] * C[2][b];
+    int k = 0;
+    for (int a = 0; a < 3; a++)
+      for (int b = a; b < 3; b++) c[k++] += RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+    N++;
+  }
+  for (int k = 0; k < 3; k++) mean64[3 * v + k] = m[k] / static_cast<double>(N);
+  for (int k = 0; k < 6; k++) cov64[6 * v + k] = c[k] / static_cast<double>(N);
+  g.counts[v] = N;
+  g.lru[v] = g.lru_counter;
+  if (is_new) {
+    const float4 p = pts[order[first]];
+    const double inv_leaf = g.inv_leaf;
+    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
+    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
+    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
+    g.coords[3 * v + 0] = cx;
+    g.coords[3 * v + 1] = cy;
+    g.coords[3 * v + 2] = cz;
+    ivm_hash_insert(g.hkeys, g.hvals, g.hmask, voxel_key(cx, cy, cz), v);
+  }
+}
+
+// workgroup b: 256 voxels of the map that owns it; ivm_export_kernel's body
+__global__ __launch_bounds__(256) void ivm_export_forest_kernel(const IvmExport* __restrict__ maps, const uint32_t* __restrict__ prefix_g, int count) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int mem = forest_member_of(prefix, count, blockIdx.x);
+  const IvmExport& g = *uniform_const(maps + mem);
+  const uint32_t v = (blockIdx.x - prefix[mem]) * 256u + threadIdx.x;
+  if (v >= g.n) return;
+  const double* __restrict__ mean64 = g.mean64;
+  const double* __restrict__ cov64 = g.cov64;
+  const double ox = g.ox, oy = g.oy, oz = g.oz;
+  g.means[v] = make_float4(static_cast<float>(mean64[3 * v] - ox), static_cast<float>(mean64[3 * v + 1] - oy), static_cast<float>(mean64[3 * v + 2] - oz), __uint_as_float(v));
+  Cov8 o;
+  o.xx = static_cast<float>(cov64[6 * v]);
+  o.xy = static_cast<float>(cov64[6 * v + 1]);
+  o.xz = static_cast<float>(cov64[6 * v + 2]);
+  o.yy = static_cast<float>(cov64[6 * v + 3]);
+  o.yz = static_cast<float>(cov64[6 * v + 4]);
+  o.zz = static_cast<float>(cov64[6 * v + 5]);
+  o.pad0 = o.pad1 = 0.f;
+  g.mcov[v] = o;
 }
 
 // ---- flat maps: IncrementalVoxelMap<FlatContainer<NRM, COV>> ------------------------------------------------------------------------
@@ -348,6 +532,216 @@ static int rebuild_hash(sga_context* ctx, sga_index* idx, size_t n_target) {
   return SGA_OK;
 }
 
+// capacity of the per-voxel arrays and of the table for n_total voxels (the map holds idx->n): sga_voxelmap_insert's conditions
+int ivm_reserve(sga_context* ctx, sga_index* idx, size_t n_total) {
+  const size_t n_old = idx->n;
+  if (n_total > idx->vcap) {
+    const size_t cap = std::max<size_t>(2 * n_total, 1024);
+    const bool flat = idx->kind == SGA_INDEX_FLATMAP;
+    if (flat) {
+      SGA_TRY(grow(ctx, idx->fpts64, 3 * kFlatCap * n_old, 3 * kFlatCap * cap));
+      if (idx->has_normals) SGA_TRY(grow(ctx, idx->fnrm64, 3 * kFlatCap * n_old, 3 * kFlatCap * cap));
+      if (idx->has_covs) SGA_TRY(grow(ctx, idx->fcov64, 6 * kFlatCap * n_old, 6 * kFlatCap * cap));
+    } else {
+      SGA_TRY(grow(ctx, idx->vmean64, 3 * n_old, 3 * cap));
+      SGA_TRY(grow(ctx, idx->vcov64, 6 * n_old, 6 * cap));
+    }
+    SGA_TRY(grow(ctx, idx->vcounts, n_old, cap));
+    SGA_TRY(grow(ctx, idx->vlru, n_old, cap));
+    SGA_TRY(grow(ctx, idx->vcoords, 3 * n_old, 3 * cap));
+    SGA_TRY(grow(ctx, idx->pts, 0, flat ? kFlatCap * cap : cap));
+    if (flat && idx->has_normals) SGA_TRY(grow(ctx, idx->nrm, 0, kFlatCap * cap));
+    if (!flat || idx->has_covs) SGA_TRY(grow(ctx, idx->cov, 0, flat ? kFlatCap * cap : cap));
+    idx->vcap = cap;
+  }
+  if (idx->hkeys.n == 0 || 2 * n_total > idx->hkeys.n) SGA_TRY(rebuild_hash(ctx, idx, n_total));
+  return SGA_OK;
+}
+
+// LRU sweep (incremental_voxelmap.hpp:76-88), when the counter (already incremented for this insert) says it is due
+int ivm_lru_sweep(sga_context* ctx, sga_index* idx) {
+  if (idx->lru_counter % idx->lru_clear_cycle == 0 && idx->n > 0) {
+    const uint32_t nv = static_cast<uint32_t>(idx->n);
+    DevBuf<uint32_t> keep, pos;
+    SGA_TRY(keep.alloc(nv));
+    SGA_TRY(pos.alloc(nv));
+    hipLaunchKernelGGL(ivm_keep_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, idx->vlru.p, idx->lru_horizon, idx->lru_counter, keep.p);
+    size_t tb = 0;
+    SGA_HIP(rocprim::exclusive_scan(nullptr, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
+    SGA_TRY(ensure_temp(ctx, tb));
+    SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
+    uint32_t last_keep = 0, last_pos = 0;
+    SGA_HIP(hipMemcpyAsync(&last_keep, keep.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+    SGA_HIP(hipMemcpyAsync(&last_pos, pos.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+    SGA_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t kept = last_pos + last_keep;
+    if (kept < nv) {
+      DevBuf<double> m2, n2, c2;
+      DevBuf<uint32_t> cnt2, lru2;
+      DevBuf<int> co2;
+      const bool flat = idx->kind == SGA_INDEX_FLATMAP;
+      SGA_TRY(m2.alloc((flat ? 3 * kFlatCap : 3) * idx->vcap));
+      if (flat && idx->has_normals) SGA_TRY(n2.alloc(3 * kFlatCap * idx->vcap));
+      if (!flat || idx->has_covs) SGA_TRY(c2.alloc((flat ? 6 * kFlatCap : 6) * idx->vcap));
+      SGA_TRY(cnt2.alloc(idx->vcap));
+      SGA_TRY(lru2.alloc(idx->vcap));
+      SGA_TRY(co2.alloc(3 * idx->vcap));
+      if (flat)
+        SGA_FLAT_DISPATCH(idx, fvm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->fpts64.p, idx->fnrm64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, n2.p, c2.p,
+                          cnt2.p, lru2.p, co2.p);
+      else
+        hipLaunchKernelGGL(ivm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->vmean64.p, idx->vcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, c2.p, cnt2.p, lru2.p, co2.p);
+      SGA_HIP(hipGetLastError());
+      SGA_HIP(hipStreamSynchronize(ctx->stream));
+      if (flat) {
+        idx->fpts64.swap(m2);
+        idx->fnrm64.swap(n2);
+        idx->fcov64.swap(c2);
+      } else {
+        idx->vmean64.swap(m2);
+        idx->vcov64.swap(c2);
+      }
+      idx->vcounts.swap(cnt2);
+      idx->vlru.swap(lru2);
+      idx->vcoords.swap(co2);
+      idx->n = kept;
+      SGA_TRY(rebuild_hash(ctx, idx, kept));
+    }
+  }
+  return SGA_OK;
+}
+
+// `table1`: [members][ranges: 6 ints per member][counters: 2 per member][ticket][prefix of the key grid: count + 1], written in pinned
+// memory, one copy command
+int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, IvmForestChain& ch) {
+  const size_t count = plan.forest.size(), N = plan.points;
+  if (count == 0) return SGA_OK;
+  ch.member_bits = plan.member_bits;
+  SGA_TRY(ch.keys.alloc(N));
+  SGA_TRY(ch.keys_sorted.alloc(N));
+  SGA_TRY(ch.vals.alloc(N));
+  SGA_TRY(ch.order.alloc(N));
+  SGA_TRY(ch.flags.alloc(N));
+  SGA_TRY(ch.seg_id.alloc(N));
+  SGA_TRY(ch.seg_start.alloc(N));
+  SGA_TRY(ch.seg_vid.alloc(N));
+  SGA_TRY(ch.rank_keys.alloc(N));
+  SGA_TRY(ch.seg_ids.alloc(N));
+  std::vector<IvmMember> members(count);
+  std::vector<uint32_t> prefix(count + 1, 0u);
+  const size_t member_words = count * (sizeof(IvmMember) / 8), range_words = 3 * count, counter_words = count, prefix_words = (prefix.size() + 1) / 2;
+  const size_t words = member_words + range_words + counter_words + 1 + prefix_words;
+  SGA_TRY(ch.table1.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
+  int* host_range = reinterpret_cast<int*>(host + member_words);
+  uint32_t off = 0;
+  for (size_t j = 0; j < count; j++) {
+    const size_t k = plan.forest[j];
+    const sga_cloud* c = clouds[k];
+    const sga_index* idx = maps[k];
+    IvmMember& g = members[j];
+    std::memset(&g, 0, sizeof(g));
+    g.pts = c->pts.p;
+    g.T = insert_pose(T ? T + 16 * k : nullptr, c->origin);
+    g.inv_leaf = 1.0 / idx->leaf;
+    g.hkeys = idx->hkeys.p;
+    g.hvals = idx->hvals.p;
+    g.range = reinterpret_cast<int*>(ch.table1.p + member_words) + 6 * j;
+    g.counters = reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words) + 2 * j;
+    g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
+    g.hmask = idx->n > 0 ? idx->hmask : 0u;
+    g.n = static_cast<uint32_t>(c->n);
+    g.off = off;
+    off += g.n;
+    for (int a = 0; a < 3; a++) host_range[6 * j + a] = INT_MAX, host_range[6 * j + 3 + a] = INT_MIN;
+    prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
+  }
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words + range_words + counter_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
+  ivm_forest_count_launch();
+  SGA_HIP(hipMemcpyAsync(ch.table1.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  const IvmMember* d_members = reinterpret_cast<const IvmMember*>(ch.table1.p);
+  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(ch.table1.p + member_words + range_words + counter_words + 1);
+  const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words + counter_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  const uint32_t n32 = static_cast<uint32_t>(N);
+  const dim3 grid((n32 + 255u) / 256u), block(256);
+  ivm_forest_count_launch();
+  hipLaunchKernelGGL(ivm_keys_forest_kernel, dim3(prefix[count]), block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.keys.p, ch.vals.p);
+  SGA_HIP(hipGetLastError());
+  ivm_forest_count_launch();
+  SGA_TRY(sort_pairs(ctx, ch.keys.p, ch.keys_sorted.p, ch.vals.p, ch.order.p, N, 0, static_cast<unsigned>(plan.end_bit)));
+  ivm_forest_count_launch();
+  hipLaunchKernelGGL(ivm_heads_forest_kernel, grid, block, 0, ctx->stream, ch.keys_sorted.p, n32, ch.flags.p);
+  SGA_HIP(hipGetLastError());
+  ivm_forest_count_launch();
+  size_t tb = 0;
+  SGA_HIP(rocprim::exclusive_scan(nullptr, tb, ch.flags.p, ch.seg_id.p, 0u, N, rocprim::plus<uint32_t>(), ctx->stream));
+  SGA_TRY(ensure_temp(ctx, tb));
+  SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, ch.flags.p, ch.seg_id.p, 0u, N, rocprim::plus<uint32_t>(), ctx->stream));
+  ivm_forest_count_launch();
+  hipLaunchKernelGGL(ivm_starts_forest_kernel, grid, block, 0, ctx->stream, d_members, ch.keys_sorted.p, ch.flags.p, ch.seg_id.p, ch.order.p, n32, ch.seg_start.p, ch.seg_vid.p, ch.rank_keys.p, ch.seg_ids.p, hand);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+
+// `table2`: [members][prefix of the update grid: count + 1].  One sort of all runs of the chain under the rank key — the members' new
+// voxels in creation order, member after member, then every existing voxel's run in run order — and the assign + update launch
+int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& members, size_t runs, uint32_t total_new, size_t members_in_chain, IvmForestChain& ch) {
+  const size_t count = members.size();
+  if (count == 0 || runs == 0) return SGA_OK;
+  std::vector<uint32_t> prefix(count + 1, 0u);
+  for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (members[j].nseg + 127u) / 128u;
+  if (prefix[count] == 0) return SGA_OK;
+  const size_t member_words = count * (sizeof(IvmUpdate) / 8), words = member_words + (count + 2) / 2;
+  SGA_TRY(ch.table2.alloc(words));
+  SGA_TRY(ch.rank_keys_sorted.alloc(runs));
+  SGA_TRY(ch.seg_by_rank.alloc(runs));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+  ivm_forest_count_launch();
+  SGA_HIP(hipMemcpyAsync(ch.table2.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  int rank_member_bits = 0;  // member numbers 0 .. members_in_chain (the last one: the runs of existing voxels)
+  while ((1ull << rank_member_bits) < members_in_chain + 1) rank_member_bits++;
+  ivm_forest_count_launch();
+  SGA_TRY(sort_pairs(ctx, ch.rank_keys.p, ch.rank_keys_sorted.p, ch.seg_ids.p, ch.seg_by_rank.p, runs, 0, static_cast<unsigned>(kVoxRankMemberShift + rank_member_bits)));
+  ivm_forest_count_launch();
+  hipLaunchKernelGGL(ivm_update_forest_kernel, dim3(prefix[count]), dim3(128), 0, ctx->stream, reinterpret_cast<const IvmUpdate*>(ch.table2.p), reinterpret_cast<const uint32_t*>(ch.table2.p + member_words), static_cast<int>(count),
+                     total_new, ch.seg_by_rank.p, ch.seg_start.p, ch.seg_vid.p, ch.keys_sorted.p, ch.order.p);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+
+// `table3`: [maps][prefix of the export grid: count + 1]: the fp32 records of every map of the call in one launch
+int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& maps, IvmForestChain& ch) {
+  const size_t count = maps.size();
+  if (count == 0) return SGA_OK;
+  std::vector<uint32_t> prefix(count + 1, 0u);
+  for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (maps[j].n + 255u) / 256u;
+  const size_t map_words = count * (sizeof(IvmExport) / 8), words = map_words + (count + 2) / 2;
+  SGA_TRY(ch.table3.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
+  std::memcpy(host, maps.data(), map_words * 8);
+  std::memcpy(host + map_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+  ivm_forest_count_launch();
+  SGA_HIP(hipMemcpyAsync(ch.table3.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  ivm_forest_count_launch();
+  hipLaunchKernelGGL(ivm_export_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, reinterpret_cast<const IvmExport*>(ch.table3.p), reinterpret_cast<const uint32_t*>(ch.table3.p + map_words), static_cast<int>(count));
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
 }  // namespace sga
 
 using namespace sga;
@@ -590,12 +984,7 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
   SGA_TRY(wait_ready(ctx, idx->ready));
   // The cloud's records live in its device frame (p' = p - o_c, common.hpp); the map's fp64 state, voxel coordinates and hash keys are the
   // CALLER's frame, exactly the reference's doubles: the kernels move a record by R p' + (R o_c + t).
-  Pose12 T;
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) T.r[3 * r + c] = T16 ? T16[4 * c + r] : (r == c ? 1.0 : 0.0);
-    T.t[r] = T16 ? T16[12 + r] : 0.0;
-  }
-  for (int r = 0; r < 3; r++) T.t[r] += T.r[3 * r] * cloud->origin[0] + T.r[3 * r + 1] * cloud->origin[1] + T.r[3 * r + 2] * cloud->origin[2];
+  const Pose12 T = insert_pose(T16, cloud->origin);
   // The fp32 records the factor kernels read are re-exported after every insert anyway: their device frame follows the inserted scan (the
   // moved origin of the cloud's frame, quantised), so a map that walks kilometres (scan-to-model odometry) keeps sub-millimetre records.
   // (the new origin is committed only where the records are exported below — an insert that fails on the way leaves the map's
@@ -656,27 +1045,7 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
       SGA_HIP(hipStreamSynchronize(ctx->stream));
       const size_t n_total = static_cast<size_t>(n_old) + n_new;
       if (n_total >= (1ull << 31)) return fail(SGA_ERR_INVALID, "voxel map too large");
-      // capacity of the per-voxel arrays and of the table
-      if (n_total > idx->vcap) {
-        const size_t cap = std::max<size_t>(2 * n_total, 1024);
-        const bool flat = idx->kind == SGA_INDEX_FLATMAP;
-        if (flat) {
-          SGA_TRY(grow(ctx, idx->fpts64, 3 * kFlatCap * static_cast<size_t>(n_old), 3 * kFlatCap * cap));
-          if (idx->has_normals) SGA_TRY(grow(ctx, idx->fnrm64, 3 * kFlatCap * static_cast<size_t>(n_old), 3 * kFlatCap * cap));
-          if (idx->has_covs) SGA_TRY(grow(ctx, idx->fcov64, 6 * kFlatCap * static_cast<size_t>(n_old), 6 * kFlatCap * cap));
-        } else {
-          SGA_TRY(grow(ctx, idx->vmean64, 3 * static_cast<size_t>(n_old), 3 * cap));
-          SGA_TRY(grow(ctx, idx->vcov64, 6 * static_cast<size_t>(n_old), 6 * cap));
-        }
-        SGA_TRY(grow(ctx, idx->vcounts, n_old, cap));
-        SGA_TRY(grow(ctx, idx->vlru, n_old, cap));
-        SGA_TRY(grow(ctx, idx->vcoords, 3 * static_cast<size_t>(n_old), 3 * cap));
-        SGA_TRY(grow(ctx, idx->pts, 0, flat ? kFlatCap * cap : cap));
-        if (flat && idx->has_normals) SGA_TRY(grow(ctx, idx->nrm, 0, kFlatCap * cap));
-        if (!flat || idx->has_covs) SGA_TRY(grow(ctx, idx->cov, 0, flat ? kFlatCap * cap : cap));
-        idx->vcap = cap;
-      }
-      if (idx->hkeys.n == 0 || 2 * n_total > idx->hkeys.n) SGA_TRY(rebuild_hash(ctx, idx, n_total));
+      SGA_TRY(ivm_reserve(ctx, idx, n_total));
       if (n_new > 0) hipLaunchKernelGGL(ivm_assign_kernel, dim3((n_new + 255) / 256), block, 0, ctx->stream, n_new, seg_by_rank.p, n_old, seg_vid.p);
       if (idx->kind == SGA_INDEX_FLATMAP)
         SGA_FLAT_DISPATCH(idx, fvm_update_kernel, sgrid, block, 0, ctx->stream, nseg, seg_start.p, seg_vid.p, static_cast<uint32_t>(n), keys_sorted.p, order.p, cloud->pts.p, cloud->nrm.p, cloud->cov.p, T, n_old,
@@ -692,54 +1061,7 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
   }
   // LRU sweep (incremental_voxelmap.hpp:76-88)
   idx->lru_counter++;
-  if (idx->lru_counter % idx->lru_clear_cycle == 0 && idx->n > 0) {
-    const uint32_t nv = static_cast<uint32_t>(idx->n);
-    DevBuf<uint32_t> keep, pos;
-    SGA_TRY(keep.alloc(nv));
-    SGA_TRY(pos.alloc(nv));
-    hipLaunchKernelGGL(ivm_keep_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, idx->vlru.p, idx->lru_horizon, idx->lru_counter, keep.p);
-    size_t tb = 0;
-    SGA_HIP(rocprim::exclusive_scan(nullptr, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
-    SGA_TRY(ensure_temp(ctx, tb));
-    SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
-    uint32_t last_keep = 0, last_pos = 0;
-    SGA_HIP(hipMemcpyAsync(&last_keep, keep.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    SGA_HIP(hipMemcpyAsync(&last_pos, pos.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    SGA_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t kept = last_pos + last_keep;
-    if (kept < nv) {
-      DevBuf<double> m2, n2, c2;
-      DevBuf<uint32_t> cnt2, lru2;
-      DevBuf<int> co2;
-      const bool flat = idx->kind == SGA_INDEX_FLATMAP;
-      SGA_TRY(m2.alloc((flat ? 3 * kFlatCap : 3) * idx->vcap));
-      if (flat && idx->has_normals) SGA_TRY(n2.alloc(3 * kFlatCap * idx->vcap));
-      if (!flat || idx->has_covs) SGA_TRY(c2.alloc((flat ? 6 * kFlatCap : 6) * idx->vcap));
-      SGA_TRY(cnt2.alloc(idx->vcap));
-      SGA_TRY(lru2.alloc(idx->vcap));
-      SGA_TRY(co2.alloc(3 * idx->vcap));
-      if (flat)
-        SGA_FLAT_DISPATCH(idx, fvm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->fpts64.p, idx->fnrm64.p, idx->fcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, n2.p, c2.p,
-                          cnt2.p, lru2.p, co2.p);
-      else
-        hipLaunchKernelGGL(ivm_compact_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, keep.p, pos.p, idx->vmean64.p, idx->vcov64.p, idx->vcounts.p, idx->vlru.p, idx->vcoords.p, m2.p, c2.p, cnt2.p, lru2.p, co2.p);
-      SGA_HIP(hipGetLastError());
-      SGA_HIP(hipStreamSynchronize(ctx->stream));
-      if (flat) {
-        idx->fpts64.swap(m2);
-        idx->fnrm64.swap(n2);
-        idx->fcov64.swap(c2);
-      } else {
-        idx->vmean64.swap(m2);
-        idx->vcov64.swap(c2);
-      }
-      idx->vcounts.swap(cnt2);
-      idx->vlru.swap(lru2);
-      idx->vcoords.swap(co2);
-      idx->n = kept;
-      SGA_TRY(rebuild_hash(ctx, idx, kept));
-    }
-  }
+  SGA_TRY(ivm_lru_sweep(ctx, idx));
   for (int k = 0; k < 3; k++) idx->origin[k] = new_origin[k];  // every fallible step is behind us: the records exported now are relative to it
   if (idx->n > 0) {
     if (idx->kind == SGA_INDEX_FLATMAP)

@@ -402,6 +402,57 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
             "relative_poses": rel, "iterations": iters, "estimated": est}
 
 
+def run_synthetic_model_batched(num_frames=20, streams=4, batched_insert=False, downsampling_resolution=0.25, num_neighbors=20, voxel_resolution=1.0, max_correspondence_distance=1.0, ctx=None):
+    """`streams` independent scan-to-model VGICP streams (ModelOdometry's protocol: register against the stream's own GaussianVoxelMap from
+    the previous pose, then insert the scan at the estimated pose) over the frozen synthetic sequence in lock-step on one context: stream
+    s starts at frame s, so round r gives stream s the frame s + r, while every stream has one (num_frames - streams + 1 rounds).  A round
+    preprocesses each stream's scan, registers all streams by ONE BatchProblem.align against their maps, then updates the maps — by one
+    api.insert_batch when batched_insert is set (the same maps, bit for bit: the results do not change), by one insert per stream
+    otherwise.  Returns per stream the poses (the first is the identity) and the iteration counts, the final map sizes, and the wall
+    time of the map updates per round."""
+    from . import synthetic
+
+    if streams < 1 or num_frames < streams:
+        raise ValueError("streams must be in [1, num_frames]")
+    ctx = ctx or api.Context(0)
+    setting = api.make_setting("VGICP", max_correspondence_distance=max_correspondence_distance)
+    maps = [api.GaussianVoxelMap(voxel_resolution, ctx=ctx) for _ in range(streams)]
+    poses = [[] for _ in range(streams)]
+    iterations = [[] for _ in range(streams)]
+    insert_s = 0.0
+    for r in range(num_frames - streams + 1):
+        clouds = []
+        for s in range(streams):
+            pts, _ = synthetic.kitti_like_scan(s + r)
+            cloud = api.voxelgrid_sampling(api.PointCloud(np.ascontiguousarray(pts[:, :3], dtype=np.float32), ctx=ctx), downsampling_resolution)
+            api.estimate_covariances(cloud, None, num_neighbors)
+            clouds.append(cloud)
+        if r == 0:
+            Ts = [np.eye(4) for _ in range(streams)]
+        else:
+            prev = [poses[s][-1] for s in range(streams)]
+            problems = [api.Problem(maps[s], clouds[s], prev[s], ctx=ctx) for s in range(streams)]
+            bp = api.BatchProblem(problems)
+            results = bp.align(setting, prev)
+            del bp  # before its problems
+            Ts = [res.T_target_source for res in results]
+            for s, res in enumerate(results):
+                iterations[s].append(res.iterations + 1)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        if batched_insert:
+            api.insert_batch(maps, clouds, Ts)
+        else:
+            for s in range(streams):
+                maps[s].insert(clouds[s], Ts[s])
+        ctx.synchronize()
+        insert_s += time.perf_counter() - t0
+        for s in range(streams):
+            poses[s].append(np.array(Ts[s], dtype=np.float64))
+    return {"frames": num_frames, "streams": streams, "poses": poses, "iterations": iterations, "num_voxels": [m.size() for m in maps],
+            "insert_ms_per_round": 1e3 * insert_s / max(1, num_frames - streams + 1)}
+
+
 def run_synthetic_pairs(num_frames, rank, world, device=0, **kw):
     """Frame-pair parallelism over ranks (the other way to spread C5 over GPUs): under the reference's protocol every pair (scan f-1, scan f)
     is registered from the identity (odometry_benchmark_small_gicp_omp.cpp:16-49), so the pairs are independent — rank r takes the
