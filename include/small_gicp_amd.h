@@ -275,6 +275,18 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
  * cloud the index was built over, exactly as with sga_problem_create.  Attributes must be present in the index (build it after
  * estimating them, or call sga_index_refresh_attributes). */
 int sga_problem_create_from_index(sga_context* ctx, const sga_index* target, const sga_index* source_index, const double init_T[16], sga_problem** out);
+/* registration.hpp:41 for B pairs: out[k] is what sga_problem_create(ctx, targets[k], sources[k], init_T + 16 k, &out[k]) makes — an
+ * ordinary sga_problem with its own buffers, the source in the lone call's order bit for bit, usable and destroyable like any other.
+ * Sources of 1 .. 262144 points against kd-tree, Gaussian or flat targets share ONE chain on the context's stream whatever B is: a table
+ * copy, a keys launch, one stable sort of the concatenation under (member, the member's lone key), one launch that gathers, writes the
+ * initial factor state and reduces every member's bounding box — and ONE host wait, for the boxes of all members.  Larger clouds, members
+ * with a projective target and empty sources go through the lone routine inside the call.  A target may serve several members, a cloud
+ * may appear several times; a mix of target kinds is fine here (sga_batch_create still refuses it).  A NULL member or a member on
+ * another device is refused before any device work with the lone call's status and message plus the member's number; a member with a
+ * non-finite coordinate fails the call with SGA_ERR_INVALID "source cloud contains non-finite coordinates (problem k)".  On any failure
+ * every out[k] is NULL.  count == 0 is SGA_OK. */
+int sga_problem_create_batch(sga_context* ctx, const sga_index* const* targets, const sga_cloud* const* sources,
+                             const double* init_T /* count x 16 column-major, or NULL: identities */, size_t count, sga_problem** out);
 int sga_problem_destroy(sga_problem* problem);
 /* Sum_i (H_i, b_i, e_i) at T over all source points with a correspondence; refreshes the factor state. */
 int sga_linearize(sga_context* ctx, sga_problem* problem, const sga_factor_params* params, const double T[16], double H[36], double b[6], double* e, uint64_t* num_inliers);

@@ -682,6 +682,36 @@ inline void insert_batch(sga_context* ctx, const std::vector<GaussianVoxelMap::P
   check(sga_voxelmap_insert_batch(ctx, ms.data(), cs.data(), Ts.empty() ? nullptr : T16.data(), ms.size()), "sga_voxelmap_insert_batch");
 }
 
+/// The problems of create_problems: ordinary sga_problem handles (sga_linearize, sga_align_problem, sga_batch_create, ...), destroyed with the set
+struct Problems {
+  std::vector<sga_problem*> h;
+  Problems() = default;
+  Problems(const Problems&) = delete;
+  Problems& operator=(const Problems&) = delete;
+  Problems(Problems&& o) noexcept : h(std::move(o.h)) { o.h.clear(); }
+  ~Problems() {
+    for (sga_problem* pb : h) sga_problem_destroy(pb);
+  }
+  size_t size() const { return h.size(); }
+  sga_problem* operator[](size_t k) const { return h[k]; }
+};
+/// sga_problem_create_batch: the problems of several (target, source cloud, initial guess) triples of one context (Ts empty: identities) by
+/// one chain of launches and one host wait; problem k is what sga_problem_create(ctx, targets[k], sources[k], Ts[k]) makes, its source in
+/// the same order bit for bit.  targets: the handles of KdTree / GaussianVoxelMap / IncrementalVoxelMap / ProjectiveSearch objects (`h`).
+inline Problems create_problems(sga_context* ctx, const std::vector<const sga_index*>& targets, const std::vector<std::shared_ptr<const PointCloud>>& sources, const std::vector<Isometry3d>& Ts = {}) {
+  if (targets.size() != sources.size() || (!Ts.empty() && Ts.size() != targets.size())) throw std::runtime_error("create_problems: as many targets as sources (and poses)");
+  std::vector<const sga_cloud*> cs;
+  std::vector<double> T16;
+  for (size_t k = 0; k < sources.size(); k++) {
+    cs.push_back(sources[k]->h);
+    if (!Ts.empty()) T16.insert(T16.end(), Ts[k].data(), Ts[k].data() + 16);
+  }
+  Problems out;
+  out.h.assign(targets.size(), nullptr);
+  check(sga_problem_create_batch(ctx, targets.data(), cs.data(), Ts.empty() ? nullptr : T16.data(), targets.size(), out.h.data()), "sga_problem_create_batch");
+  return out;
+}
+
 template <typename Reg>
 void copy_setting(Reg& reg, const RegistrationSetting& setting) {
   reg.criteria.rotation_eps = setting.rotation_eps;

@@ -87,6 +87,15 @@ int sga_debug_voxelmap_insert_batch_plan(sga_index* const* maps, const sga_cloud
  * and its table copies (growth, LRU sweeps and members that take the lone path inside the call are not counted): a round of B members
  * without growth counts as many as a round of one. */
 int sga_debug_voxelmap_insert_batch_launches(unsigned long long* launches);
+/* What sga_problem_create_batch(targets, sources, count) would do, decided by the very code the call itself runs (csrc/forest.hpp:
+ * problem_forest_plan): out[0] = members of the shared chain, out[1] = members that go through the lone routine (a projective target,
+ * more than 262144 points, past the cap of the concatenation), out[2] = members with an empty source, out[3] = points of the
+ * concatenation.  The members are checked for NULL as the call checks them.  No device work. */
+int sga_debug_problem_batch_plan(const sga_index* const* targets, const sga_cloud* const* sources, size_t count, int out[4]);
+/* Launches enqueued so far, in this process, by the shared chain of sga_problem_create_batch: its table copy, its two kernels and its one
+ * sort call (members that take the lone routine inside the call are not counted): a call of B chain members counts as many as a call of
+ * one. */
+int sga_debug_problem_batch_launches(unsigned long long* launches);
 /* Sets the launch epoch of the context's voxel-grid calls (the tag of ds_segments_kernel's status words; the next call uses epoch + 1, and
  * a call that finds 2^30 - 1 clears the words and starts again at 1) so that a test reaches the wrap-around a service meets after 2^30
  * calls.  Forwards only: an epoch below the current one, or above 2^30 - 1, is refused (words of earlier launches would read as current). */

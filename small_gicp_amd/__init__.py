@@ -24,6 +24,7 @@ from .api import (  # noqa: F401
     align_batch,
     build_gaussian_voxelmaps,
     build_kdtrees,
+    create_problems,
     default_context,
     estimate_covariances,
     estimate_covariances_batch,
@@ -47,6 +48,7 @@ from .api import (  # noqa: F401
     preprocess_batch,
     preprocess_points,
     preprocess_points_batch,
+    problem_batch_launches,
     unpack_accumulator,
     voxelgrid_sampling,
     voxelgrid_sampling_batch,

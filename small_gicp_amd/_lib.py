@@ -135,6 +135,9 @@ SYMBOLS = [
     ("sga_factor_params_default", None, [C.POINTER(FactorParams)]),
     ("sga_problem_create", C.c_int, [_vp, _vp, _vp, _dp, _pvp]),
     ("sga_problem_create_from_index", C.c_int, [_vp, _vp, _vp, _dp, _pvp]),
+    ("sga_problem_create_batch", C.c_int, [_vp, _pvp, _pvp, _dp, C.c_size_t, _pvp]),
+    ("sga_debug_problem_batch_plan", C.c_int, [_pvp, _pvp, C.c_size_t, C.POINTER(C.c_int)]),
+    ("sga_debug_problem_batch_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_problem_destroy", C.c_int, [_vp]),
     ("sga_linearize", C.c_int, [_vp, _vp, C.POINTER(FactorParams), _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64)]),
     ("sga_error", C.c_int, [_vp, _vp, C.POINTER(FactorParams), _dp, _dp]),

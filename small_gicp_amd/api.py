@@ -794,10 +794,13 @@ def make_setting(
 class Problem:
     """(target index, source cloud) pairing with device-resident factor state: the Reduction slot of Registration<>."""
 
-    def __init__(self, target, source, init_T=None, ctx=None):
+    def __init__(self, target, source, init_T=None, ctx=None, _handle=None):
         self.target, self.source = target, source
         self.ctx = ctx or source.ctx  # a problem may run on another context (stream) of the same device than the one that built its inputs
         self.h = C.c_void_p()
+        if _handle is not None:  # a problem made by create_problems: adopted as it is
+            self.h = _handle
+            return
         t16 = _T16(init_T)
         if isinstance(source, (KdTree, ProjectiveSearch)):  # the source by its own index: its kd order is taken as it is (no sort; a projective search is refused)
             check(load().sga_problem_create_from_index(self.ctx.h, target.h, source.h, _dp(t16), C.byref(self.h)))
@@ -967,6 +970,52 @@ class BatchProblem:
         return [RegistrationResult(res[k]) for k in range(B)]
 
 
+def _problem_members(targets, sources, ctx):
+    targets, sources = list(targets), list(sources)
+    if len(targets) != len(sources):
+        raise ValueError(f"{len(targets)} targets for {len(sources)} sources")
+    for t in targets:
+        if not isinstance(t, (KdTree, ProjectiveSearch, GaussianVoxelMap, _FlatVoxelMap)):
+            raise TypeError("create_problems takes KdTree / ProjectiveSearch / GaussianVoxelMap / IncrementalVoxelMap* targets")
+    for s in sources:
+        if not isinstance(s, PointCloud):
+            raise TypeError("create_problems takes PointCloud sources (a KdTree source: Problem(target, tree))")
+    ctx = ctx or (sources[0].ctx if sources else default_context())
+    ts = (C.c_void_p * max(1, len(targets)))(*[t.h.value for t in targets])
+    ss = (C.c_void_p * max(1, len(sources)))(*[s.h.value for s in sources])
+    return targets, sources, ctx, ts, ss
+
+
+def create_problems(targets, sources, init_Ts=None, ctx=None):
+    """sga_problem_create_batch: [Problem(targets[k], sources[k], init_Ts[k], ctx) for all k] (init_Ts None: identities) by one chain of
+    launches — one table copy, one keys launch, one stable sort, one gather / state / bounding-box launch — and one host wait, whatever
+    the number of pairs.  Every problem is an ordinary Problem, its source in the lone call's order bit for bit.  PointCloud sources of at
+    most 262144 points against KdTree, GaussianVoxelMap or IncrementalVoxelMap* targets share the chain; larger clouds, projective
+    targets and empty sources are paired one by one inside the call.  ctx: the context the problems run on (default: the first source's)."""
+    targets, sources, ctx, ts, ss = _problem_members(targets, sources, ctx)
+    t16 = None if init_Ts is None else _T16s(init_Ts, len(targets))
+    out = (C.c_void_p * max(1, len(targets)))()
+    check(load().sga_problem_create_batch(ctx.h, ts, ss, None if t16 is None else _dp(t16), len(targets), out))
+    return [Problem(t, s, ctx=ctx, _handle=C.c_void_p(out[k])) for k, (t, s) in enumerate(zip(targets, sources))]
+
+
+def _problem_batch_plan(targets, sources):
+    """Diagnostics (sga_debug_problem_batch_plan): what create_problems(targets, sources) would do — forest (members of the shared chain),
+    lone (members through the lone routine), empty (members with an empty source), points of the concatenation."""
+    targets, _, _, ts, ss = _problem_members(targets, sources, None)
+    out = (C.c_int * 4)()
+    check(load().sga_debug_problem_batch_plan(ts, ss, len(targets), out))
+    return {"forest": out[0], "lone": out[1], "empty": out[2], "points": out[3]}
+
+
+def problem_batch_launches():
+    """Diagnostics (sga_debug_problem_batch_launches): the table copies, kernels and sort calls enqueued so far by the shared chain of
+    create_problems."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_problem_batch_launches(C.byref(v)))
+    return v.value
+
+
 def align_batch(targets, sources, init_Ts=None, setting=None):
     """Register sources[k] (a PointCloud, or a KdTree taken in its own order) against targets[k] for all k in one batch; the targets are
     all KdTrees, all GaussianVoxelMaps or all flat maps (IncrementalVoxelMap*), and one target may appear several times.
@@ -978,7 +1027,11 @@ def align_batch(targets, sources, init_Ts=None, setting=None):
     if len(targets) != len(sources):
         raise ValueError("as many targets as sources")
     init = [None] * len(targets) if init_Ts is None else init_Ts
-    problems = [Problem(t, s, T) for t, s, T in zip(targets, sources, init)]
+    batched = len(targets) > 0 and all(isinstance(s, PointCloud) and s.ctx is sources[0].ctx for s in sources)
+    if batched and all(isinstance(t, (KdTree, ProjectiveSearch, GaussianVoxelMap, _FlatVoxelMap)) for t in targets):
+        problems = create_problems(targets, sources, init_Ts)  # one chain for all pairs; the same bits as the lone calls
+    else:
+        problems = [Problem(t, s, T) for t, s, T in zip(targets, sources, init)]
     batch = BatchProblem(problems)
     try:
         return batch.align(setting if setting is not None else make_setting("GICP"), init_Ts)

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "device_math.hpp"
 #include "kd_search.hpp"
 #include "uniform.hpp"
 
@@ -279,5 +280,59 @@ int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& ma
 int ivm_reserve(sga_context* ctx, sga_index* idx, size_t n_total);  // the per-voxel arrays and the table for n_total voxels, under sga_voxelmap_insert's conditions
 int ivm_lru_sweep(sga_context* ctx, sga_index* idx);                // the sweep of sga_voxelmap_insert (incremental_voxelmap.hpp:76-88) when the map's counter says it is due
 void ivm_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the chain (sga_debug_voxelmap_insert_batch_launches)
+
+// ---- the problem forest: sga_problem_create for B (target, source, pose) triples in one chain of launches ------
+// What the host decides about a batched problem creation before it launches anything (problem.hip: sga_problem_create_batch acts on it,
+// sga_debug_problem_batch_plan reports it).  A member joins the chain — members taken in the call's order — when its target is a kd-tree,
+// a Gaussian or a flat map and its source has 1 .. kVoxForestMaxMember points, while the concatenation stays within kGridForestMaxPoints
+// (48 bytes of scratch per point: two buffers of sort records and the sort's own).  Projective targets (their key is projective.hip's) and
+// larger clouds go through the lone routine; an empty source gets its problem as the lone call makes it.
+struct ProblemForestPlan {
+  size_t points = 0;  // the concatenation
+  std::vector<size_t> forest, lone, empty;
+};
+inline ProblemForestPlan problem_forest_plan(const sga_index* const* targets, const sga_cloud* const* sources, size_t count) {
+  ProblemForestPlan P;
+  for (size_t k = 0; k < count; k++) {
+    const size_t n = sources[k]->n;
+    if (n == 0)
+      P.empty.push_back(k);
+    else if (targets[k]->kind != SGA_INDEX_PROJECTIVE && n <= kVoxForestMaxMember && P.points + n <= kGridForestMaxPoints)
+      P.forest.push_back(k), P.points += n;
+    else
+      P.lone.push_back(k);
+  }
+  return P;
+}
+// The sort record of the chain: the lone key (63 bits of Morton code against a map: it does not fit under a member number in 64 bits)
+// behind the member, compared lexicographically by ONE stable merge sort; `index` — the point's position in its own cloud — rides along
+// and takes no part in the comparison, so points of equal key keep the input order, as the lone call's stable sort leaves them.
+struct alignas(16) ProblemKey {
+  unsigned long long key;
+  uint32_t member, index;
+};
+struct ProblemKeyLess {
+  __host__ __device__ __forceinline__ bool operator()(const ProblemKey& a, const ProblemKey& b) const { return a.member < b.member || (a.member == b.member && a.key < b.key); }
+};
+// One member of the chain (read with scalar loads): what source_keys_kernel / source_kd_keys_kernel, gather_source_kernel and
+// problem_state_init_kernel receive as arguments for it, and where its bounding box is reduced and handed over
+struct ProblemMember {
+  const float4* pts;  // the source
+  const Cov8* cov;    // or null
+  float4* opts;       // the problem's own arrays
+  Cov8* ocov;
+  int* corr;
+  int* hint;
+  int* hint2;
+  uint32_t* walked;
+  KdView kd;          // the target's tree (use_kd)
+  Rigid<float> T;     // the pose between the two device frames (pose_to_device)
+  float ox, oy, oz, inv;  // the key cells: origin and reciprocal size
+  int* box;                      // {min x, y, z, max x, y, z} (box_enc) in the call's table, identity values at the start
+  unsigned* done;                // positions of the member the last launch has finished: in the call's table, zero at the start
+  unsigned long long* box_slot;  // words 1..3 receive the box (pinned, device-mapped: the context's box block)
+  uint32_t n, off;               // the member's stretch of the concatenation
+  int use_kd, pad;               // 1: source_kd_keys_kernel's key, 0: source_keys_kernel's
+};
 
 }  // namespace sga

@@ -8,7 +8,9 @@
 #include <memory>
 #include <rocprim/rocprim.hpp>
 #include "device_math.hpp"
+#include "forest.hpp"
 #include "kd_search.hpp"
+#include "notes.hpp"
 #include "sort_util.hpp"
 #include "voxel_hash.hpp"
 
@@ -32,10 +34,8 @@ __device__ __forceinline__ unsigned long long spread3(unsigned long long v) {
   return v;
 }
 
-__global__ void source_keys_kernel(const float4* __restrict__ pts, size_t n, Rigid<float> T, float ox, float oy, float oz, float inv, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
+// the key of a source point against a voxel map (or an empty kd-tree): source_keys_kernel's and problem_keys_forest_kernel's
+__device__ __forceinline__ unsigned long long source_map_key(const float4 p, const Rigid<float>& T, float ox, float oy, float oz, float inv) {
   float qx, qy, qz;
   transform_point<float>(T, p.x, p.y, p.z, qx, qy, qz);
   // cell coordinates relative to the target grid, biased so that sources sticking out of the grid stay ordered
@@ -44,7 +44,13 @@ __global__ void source_keys_kernel(const float4* __restrict__ pts, size_t n, Rig
   cx = min(max(cx, 0ll), (1ll << 21) - 1);
   cy = min(max(cy, 0ll), (1ll << 21) - 1);
   cz = min(max(cz, 0ll), (1ll << 21) - 1);
-  keys[i] = spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2);
+  return spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2);
+}
+
+__global__ void source_keys_kernel(const float4* __restrict__ pts, size_t n, Rigid<float> T, float ox, float oy, float oz, float inv, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = source_map_key(pts[i], T, ox, oy, oz, inv);
   vals[i] = static_cast<uint32_t>(i);
 }
 
@@ -53,10 +59,7 @@ __global__ void source_keys_kernel(const float4* __restrict__ pts, size_t n, Rig
 // and walk nearly the same nodes in the same order: less divergence, better cache reuse than plain Morton order.
 // (Measured and dropped: grouping the source by search work — leaves scanned by a probe search — on top of this; the lanes of a
 // wave then finish together, but their loads scatter and the kernel got 11 % slower.)
-__global__ void source_kd_keys_kernel(const float4* __restrict__ pts, size_t n, Rigid<float> T, KdView kd, float ox, float oy, float oz, float inv, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
+__device__ __forceinline__ unsigned long long source_kd_key(const float4 p, const Rigid<float>& T, const KdView& kd, float ox, float oy, float oz, float inv) {
   float qx, qy, qz;
   transform_point<float>(T, p.x, p.y, p.z, qx, qy, qz);
   uint32_t node = 1;
@@ -72,7 +75,13 @@ __global__ void source_kd_keys_kernel(const float4* __restrict__ pts, size_t n, 
   cy = min(max(cy, 0ll), 1023ll);
   cz = min(max(cz, 0ll), 1023ll);
   const unsigned long long fine = (spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2)) & 0x3fffffffull;  // 30 bits
-  keys[i] = (leaf << 30) | fine;
+  return (leaf << 30) | fine;
+}
+
+__global__ void source_kd_keys_kernel(const float4* __restrict__ pts, size_t n, Rigid<float> T, KdView kd, float ox, float oy, float oz, float inv, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = source_kd_key(pts[i], T, kd, ox, oy, oz, inv);
   vals[i] = static_cast<uint32_t>(i);
 }
 
@@ -82,6 +91,82 @@ __global__ void gather_source_kernel(const uint32_t* __restrict__ order, size_t 
   const uint32_t s = order[i];
   opts[i] = pts[s];
   if (cov) ocov[i] = cov[s];
+}
+
+// ---- the problem forest: B problems in one chain of launches (forest.hpp) ----------------------------------------
+// Kernels of their own beside the lone ones (whose code and register rows stay: profiles/batch_problem_kernel_resources.txt).  A member's
+// key is the lone kernels' own device function with the member's pose, tree and cells read from the call's table; the branch on the
+// target's kind is uniform over the workgroup.
+static_assert(sizeof(ProblemMember) % 8 == 0 && sizeof(ProblemKey) == 16, "table entries are copied as 8-byte words; a sort record is one dwordx4");
+
+// workgroup b: 256 points of the member m with prefix[m] <= b < prefix[m + 1]
+__global__ __launch_bounds__(256) void problem_keys_forest_kernel(const ProblemMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, ProblemKey* __restrict__ recs) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const ProblemMember& g = *uniform_const(members + m);
+  const uint32_t i = (blockIdx.x - prefix[m]) * 256u + threadIdx.x;
+  if (i >= g.n) return;
+  const float4 p = g.pts[i];
+  ProblemKey r;
+  r.key = g.use_kd ? source_kd_key(p, g.T, g.kd, g.ox, g.oy, g.oz, g.inv) : source_map_key(p, g.T, g.ox, g.oy, g.oz, g.inv);
+  r.member = static_cast<uint32_t>(m);
+  r.index = i;
+  recs[g.off + i] = r;
+}
+
+// The rest of the chain, on the same grid.  Position i of member m in the sorted concatenation: gather_source_kernel's copy into the
+// member's own arrays, problem_state_init_kernel's "none" for it, and bbox_note_kernel's box (a non-finite coordinate counts as +inf)
+// over the points the workgroup gathered: wave shuffles, one LDS stage, six atomics per workgroup into the member's accumulator.  Every
+// workgroup adds the positions it covered to the member's counter; the one that completes the member writes its box into the box block
+// (the last member to arrive publishes the call).
+__global__ __launch_bounds__(256) void problem_finish_forest_kernel(const ProblemMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, const ProblemKey* __restrict__ sorted, const ForestBoxes hand) {
+  __shared__ float sh_box[4][6];
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const ProblemMember& g = *uniform_const(members + m);
+  const uint32_t i0 = (blockIdx.x - prefix[m]) * 256u, i = i0 + threadIdx.x, n = g.n;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  if (i < n) {
+    const uint32_t s = min(sorted[g.off + i].index, n - 1u);  // (always the index itself: the keys launch wrote every record of the stretch)
+    float4 p = g.pts[s];
+    g.opts[i] = p;
+    if (g.cov) g.ocov[i] = g.cov[s];
+    g.corr[i] = g.hint[i] = g.hint2[i] = -1;
+    if (i < n / 64u + 1u) g.walked[i] = 0u;
+    p.x = fabsf(p.x) <= 3.4028234e38f ? p.x : INFINITY;
+    p.y = fabsf(p.y) <= 3.4028234e38f ? p.y : INFINITY;
+    p.z = fabsf(p.z) <= 3.4028234e38f ? p.z : INFINITY;
+    lo[0] = hi[0] = p.x, lo[1] = hi[1] = p.y, lo[2] = hi[2] = p.z;
+  }
+  for (int a = 0; a < 3; a++)
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off));
+      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off));
+    }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int a = 0; a < 3; a++) sh_box[wave][a] = lo[a], sh_box[wave][3 + a] = hi[a];
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int a = threadIdx.x;
+    float v = sh_box[0][a];
+    for (int w = 1; w < 4; w++) v = a < 3 ? fminf(v, sh_box[w][a]) : fmaxf(v, sh_box[w][a]);
+    if (a < 3)
+      atomicMin(g.box + a, box_enc(v));
+    else
+      atomicMax(g.box + a, box_enc(v));
+  }
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const uint32_t covered = min(i0 + 256u, n) - i0;
+  if (__hip_atomic_fetch_add(g.done, covered, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + covered != n) return;
+  for (int a = 0; a < 3; a++) {
+    const unsigned l = static_cast<unsigned>(__hip_atomic_load(g.box + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const unsigned h = static_cast<unsigned>(__hip_atomic_load(g.box + 3 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    g.box_slot[1 + a] = static_cast<unsigned long long>(l) | (static_cast<unsigned long long>(h) << 32);
+  }
+  forest_box_arrive(hand);
 }
 
 // Factor state back in the caller's source order with original target indices.
@@ -268,7 +353,7 @@ __global__ void problem_state_init_kernel(int* __restrict__ corr, int* __restric
   if (i < n / 64 + 1) walked[i] = 0u;
 }
 
-static int problem_alloc_state(sga_context* ctx, sga_problem* pb, size_t n, bool has_covs, bool own_arrays = true) {
+static int problem_alloc_state(sga_context* ctx, sga_problem* pb, size_t n, bool has_covs, bool own_arrays = true, bool init_state = true) {
   pb->owner = ctx;
   SGA_TRY(pb->partials.alloc(problem_partials_doubles(n)));
   SGA_TRY(pb->walked.alloc(n / 64 + 1));
@@ -284,8 +369,10 @@ static int problem_alloc_state(sga_context* ctx, sga_problem* pb, size_t n, bool
     SGA_TRY(pb->maha.alloc(n * 6));  // only ever read where corr >= 0, i.e. after a pass has written it: no fill
   }
   // correspondences and certificates start as "none": one launch (four fills cost four launches, which is what a 15k-point scan pays for)
-  hipLaunchKernelGGL(problem_state_init_kernel, dim3((n + 255) / 256 + 1), dim3(256), 0, ctx->stream, pb->corr.p, pb->hint.p, pb->hint2.p, pb->walked.p, n);
-  SGA_HIP(hipGetLastError());
+  if (init_state) {  // (a member of a batched creation: problem_finish_forest_kernel writes the same)
+    hipLaunchKernelGGL(problem_state_init_kernel, dim3((n + 255) / 256 + 1), dim3(256), 0, ctx->stream, pb->corr.p, pb->hint.p, pb->hint2.p, pb->walked.p, n);
+    SGA_HIP(hipGetLastError());
+  }
   pb->state_fresh = true;
   return SGA_OK;
 }
@@ -324,16 +411,25 @@ int sga_problem_create_from_index(sga_context* ctx, const sga_index* target, con
   return SGA_OK;
 }
 
-int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_cloud* source, const double init_T[16], sga_problem** out) {
-  if (!ctx || !target || !source || !out) return fail(SGA_ERR_INVALID, "null argument");
-  if (target->device != ctx->device || source->device != ctx->device) return fail(SGA_ERR_INVALID, "target/source live on another device");
-  *out = nullptr;
-  SGA_ENTER(ctx);
-  SGA_TRY(wait_ready(ctx, target->ready));  // inputs produced on another context in stream-ordered mode (common.hpp: Ready)
-  SGA_TRY(wait_ready(ctx, source->ready));
-  static const double I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  double T[16];
-  pose_to_device(init_T ? init_T : I16, source->origin, target->origin, T);  // the sort keys are computed from device-frame records (common.hpp)
+static const double kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
+// the cells of the sort key against `target`: their origin and reciprocal size
+static void source_key_cells(const sga_index* target, float* ox, float* oy, float* oz, float* inv) {
+  *ox = *oy = *oz = 0.f;
+  *inv = 1.f;
+  if (target->kind == SGA_INDEX_KDTREE) {
+    *ox = target->bbox_lo[0];
+    *oy = target->bbox_lo[1];
+    *oz = target->bbox_lo[2];
+    const float ext = fmaxf(fmaxf(target->bbox_hi[0] - *ox, target->bbox_hi[1] - *oy), fmaxf(target->bbox_hi[2] - *oz, 1e-6f));
+    *inv = 512.f / ext;  // 10-bit Morton cells over the target's extent refine the kd-leaf key
+  } else if (target->kind != SGA_INDEX_PROJECTIVE) {
+    *inv = static_cast<float>(4.0 / target->leaf);  // quarter-voxel cells: neighbouring lanes probe the same voxel
+  }
+}
+
+// what sga_problem_create sets up before any device work
+static std::unique_ptr<sga_problem> problem_new(sga_context* ctx, const sga_index* target, const sga_cloud* source) {
   std::unique_ptr<sga_problem> pb(new sga_problem);
   pb->device = ctx->device;
   pb->target = target;
@@ -341,6 +437,16 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
   for (int k = 0; k < 3; k++) pb->src_origin[k] = source->origin[k];
   pb->has_normals = source->has_normals;
   pb->has_covs = source->has_covs;
+  return pb;
+}
+
+// sga_problem_create behind its argument checks, inside the entry point; member >= 0: a member of sga_problem_create_batch, named in the messages
+static int problem_create_lone(sga_context* ctx, const sga_index* target, const sga_cloud* source, const double init_T[16], long long member, sga_problem** out) {
+  SGA_TRY(wait_ready(ctx, target->ready));  // inputs produced on another context in stream-ordered mode (common.hpp: Ready)
+  SGA_TRY(wait_ready(ctx, source->ready));
+  double T[16];
+  pose_to_device(init_T ? init_T : kIdentity16, source->origin, target->origin, T);  // the sort keys are computed from device-frame records (common.hpp)
+  std::unique_ptr<sga_problem> pb = problem_new(ctx, target, source);
   const size_t n = source->n;
   SGA_TRY(problem_alloc_state(ctx, pb.get(), n, source->has_covs));
   if (n > 0) {
@@ -350,16 +456,8 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
     SGA_TRY(keys_sorted.alloc(n));
     SGA_TRY(vals.alloc(n));
     SGA_TRY(order.alloc(n));
-    float ox = 0, oy = 0, oz = 0, inv = 1.f;
-    if (target->kind == SGA_INDEX_KDTREE) {
-      ox = target->bbox_lo[0];
-      oy = target->bbox_lo[1];
-      oz = target->bbox_lo[2];
-      const float ext = fmaxf(fmaxf(target->bbox_hi[0] - ox, target->bbox_hi[1] - oy), fmaxf(target->bbox_hi[2] - oz, 1e-6f));
-      inv = 512.f / ext;  // 10-bit Morton cells over the target's extent refine the kd-leaf key
-    } else if (target->kind != SGA_INDEX_PROJECTIVE) {
-      inv = static_cast<float>(4.0 / target->leaf);  // quarter-voxel cells: neighbouring lanes probe the same voxel
-    }
+    float ox, oy, oz, inv;
+    source_key_cells(target, &ox, &oy, &oz, &inv);
     if (target->kind == SGA_INDEX_PROJECTIVE) {
       SGA_TRY(projective_source_keys(ctx, target, source->pts.p, n, T, keys.p, vals.p));  // u-major pixel: neighbouring lanes scan overlapping windows
     } else if (target->kind == SGA_INDEX_KDTREE && target->n > 0) {
@@ -374,9 +472,185 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
     SGA_HIP(hipGetLastError());
     SGA_TRY(cloud_bbox(ctx, source->pts.p, n, pb->bbox_lo, pb->bbox_hi));  // synchronises the stream
     for (int k = 0; k < 3; k++)  // the box bounds the motion between two poses (warm passes): a non-finite point would make that bound meaningless
-      if (!std::isfinite(pb->bbox_lo[k]) || !std::isfinite(pb->bbox_hi[k])) return fail(SGA_ERR_INVALID, "source cloud contains non-finite coordinates");
+      if (!std::isfinite(pb->bbox_lo[k]) || !std::isfinite(pb->bbox_hi[k]))
+        return member < 0 ? fail(SGA_ERR_INVALID, "source cloud contains non-finite coordinates") : fail(SGA_ERR_INVALID, "source cloud contains non-finite coordinates (problem %lld)", member);
   }
   *out = pb.release();
+  return SGA_OK;
+}
+
+int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_cloud* source, const double init_T[16], sga_problem** out) {
+  if (!ctx || !target || !source || !out) return fail(SGA_ERR_INVALID, "null argument");
+  if (target->device != ctx->device || source->device != ctx->device) return fail(SGA_ERR_INVALID, "target/source live on another device");
+  *out = nullptr;
+  SGA_ENTER(ctx);
+  return problem_create_lone(ctx, target, source, init_T, -1, out);
+}
+
+// ---- sga_problem_create for every member ------------------------------------------------------------------------
+namespace {
+std::atomic<unsigned long long> g_problem_forest_launches{0};
+void problem_forest_count_launch() { g_problem_forest_launches.fetch_add(1, std::memory_order_relaxed); }
+
+// the argument checks of sga_problem_create_batch and of its plan that need no context (status and message as the lone call's, naming the member)
+int problem_batch_check(const sga_index* const* targets, const sga_cloud* const* sources, size_t count) {
+  for (size_t k = 0; k < count; k++) {
+    if (!targets[k]) return fail(SGA_ERR_INVALID, "null argument: targets[%zu] is NULL", k);
+    if (!sources[k]) return fail(SGA_ERR_INVALID, "null argument: sources[%zu] is NULL", k);
+  }
+  return SGA_OK;
+}
+
+// The chain of the plan's members enqueued on the context's stream: the table ([members][boxes: 6 ints per member][done: one counter per
+// member][ticket][prefix of the grid: count + 1], written in pinned memory, one copy command), the keys launch, ONE stable sort of the
+// concatenation and the finish launch.  Member j's box arrives in words 4 j + 5 .. 4 j + 7 of the context's box block, then `seq` in word 0.
+struct ProblemForestChain {
+  DevBuf<ProblemKey> recs, recs_sorted;
+  DevBuf<unsigned long long> table;
+};
+int problem_forest_enqueue(sga_context* ctx, const sga_index* const* targets, const sga_cloud* const* sources, const double* init_T, const ProblemForestPlan& plan, const std::vector<std::unique_ptr<sga_problem>>& made,
+                           unsigned long long seq, ProblemForestChain& ch) {
+  const size_t count = plan.forest.size(), N = plan.points;
+  SGA_TRY(ch.recs.alloc(N));
+  SGA_TRY(ch.recs_sorted.alloc(N));
+  std::vector<ProblemMember> members(count);
+  std::vector<uint32_t> prefix(count + 1, 0u);
+  const size_t member_words = count * (sizeof(ProblemMember) / 8), box_words = 3 * count, done_words = (count + 1) / 2, prefix_words = (prefix.size() + 1) / 2;
+  const size_t words = member_words + box_words + done_words + 1 + prefix_words;
+  SGA_TRY(ch.table.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
+  int* host_box = reinterpret_cast<int*>(host + member_words);
+  uint32_t off = 0;
+  for (size_t j = 0; j < count; j++) {
+    const size_t k = plan.forest[j];
+    const sga_index* target = targets[k];
+    const sga_cloud* source = sources[k];
+    sga_problem* pb = made[k].get();
+    double T[16];
+    pose_to_device(init_T ? init_T + 16 * k : kIdentity16, source->origin, target->origin, T);
+    ProblemMember& g = members[j];
+    std::memset(&g, 0, sizeof(g));
+    g.pts = source->pts.p;
+    g.cov = source->cov.p;
+    g.opts = pb->pts.p;
+    g.ocov = pb->cov.p;
+    g.corr = pb->corr.p;
+    g.hint = pb->hint.p;
+    g.hint2 = pb->hint2.p;
+    g.walked = pb->walked.p;
+    g.use_kd = target->kind == SGA_INDEX_KDTREE && target->n > 0 ? 1 : 0;
+    if (g.use_kd) g.kd = make_kd_view(target);
+    g.T = rigid_from_colmajor<float>(T);
+    source_key_cells(target, &g.ox, &g.oy, &g.oz, &g.inv);
+    g.box = reinterpret_cast<int*>(ch.table.p + member_words) + 6 * j;
+    g.done = reinterpret_cast<unsigned*>(ch.table.p + member_words + box_words) + j;
+    g.box_slot = ctx->h_forest_dev + 4 + 4 * j;
+    g.n = static_cast<uint32_t>(source->n);
+    g.off = off;
+    off += g.n;
+    for (int a = 0; a < 3; a++) host_box[6 * j + a] = kBoxEncPosInf, host_box[6 * j + 3 + a] = kBoxEncNegInf;
+    prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
+  }
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words + box_words + done_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
+  problem_forest_count_launch();
+  SGA_HIP(hipMemcpyAsync(ch.table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  const ProblemMember* d_members = reinterpret_cast<const ProblemMember*>(ch.table.p);
+  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(ch.table.p + member_words + box_words + done_words + 1);
+  const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table.p + member_words + box_words + done_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  const dim3 grid(prefix[count]), block(256);
+  problem_forest_count_launch();
+  hipLaunchKernelGGL(problem_keys_forest_kernel, grid, block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.recs.p);
+  SGA_HIP(hipGetLastError());
+  problem_forest_count_launch();
+  size_t tb = 0;
+  SGA_HIP(rocprim::merge_sort(nullptr, tb, ch.recs.p, ch.recs_sorted.p, N, ProblemKeyLess(), ctx->stream));
+  SGA_TRY(ensure_temp(ctx, tb));
+  SGA_HIP(rocprim::merge_sort(ctx->d_temp.p, tb, ch.recs.p, ch.recs_sorted.p, N, ProblemKeyLess(), ctx->stream));
+  problem_forest_count_launch();
+  hipLaunchKernelGGL(problem_finish_forest_kernel, grid, block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.recs_sorted.p, hand);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+
+// The members of the plan's chain share the launches above and ONE host wait, for their boxes; empty sources and the members the plan
+// leaves out go through the lone routine afterwards, one after the other.
+int problems_batch(sga_context* ctx, const sga_index* const* targets, const sga_cloud* const* sources, const double* init_T, size_t count, std::vector<std::unique_ptr<sga_problem>>& made) {
+  made.resize(count);
+  for (size_t k = 0; k < count; k++) {
+    SGA_TRY(wait_ready(ctx, targets[k]->ready));  // inputs produced on another context in stream-ordered mode (common.hpp: Ready)
+    SGA_TRY(wait_ready(ctx, sources[k]->ready));
+  }
+  const ProblemForestPlan plan = problem_forest_plan(targets, sources, count);
+  ProblemForestChain ch;  // lives to the end of the call (then: the stream's free list)
+  if (!plan.forest.empty()) {
+    // ---- every allocation of every member, then the launches
+    for (size_t k : plan.forest) {
+      made[k] = problem_new(ctx, targets[k], sources[k]);
+      SGA_TRY(problem_alloc_state(ctx, made[k].get(), sources[k]->n, sources[k]->has_covs, /*own_arrays=*/true, /*init_state=*/false));
+    }
+    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
+    const unsigned long long seq = ++ctx->forest_seq;
+    if (const int rc = problem_forest_enqueue(ctx, targets, sources, init_T, plan, made, seq, ch); rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block and the members' arrays: nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    // ---- the one wait: the boxes of all members
+    SGA_TRY(forest_boxes_wait(ctx, seq, "boxes of a batched problem creation"));
+    for (size_t j = 0; j < plan.forest.size(); j++) {
+      sga_problem* pb = made[plan.forest[j]].get();
+      box_note_decode(ctx->h_forest + 4 + 4 * j + 1, pb->bbox_lo, pb->bbox_hi);
+      for (int a = 0; a < 3; a++)
+        if (!std::isfinite(pb->bbox_lo[a]) || !std::isfinite(pb->bbox_hi[a])) return fail(SGA_ERR_INVALID, "source cloud contains non-finite coordinates (problem %zu)", plan.forest[j]);
+    }
+  }
+  auto lone = [&](size_t k) -> int {
+    sga_problem* one = nullptr;
+    SGA_TRY(problem_create_lone(ctx, targets[k], sources[k], init_T ? init_T + 16 * k : nullptr, static_cast<long long>(k), &one));
+    made[k].reset(one);
+    return SGA_OK;
+  };
+  for (size_t k : plan.empty) SGA_TRY(lone(k));
+  for (size_t k : plan.lone) SGA_TRY(lone(k));
+  return SGA_OK;
+}
+}  // namespace
+
+int sga_debug_problem_batch_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_problem_forest_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_problem_batch_plan(const sga_index* const* targets, const sga_cloud* const* sources, size_t count, int out[4]) {
+  if (!out || (count > 0 && (!targets || !sources))) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 4; k++) out[k] = 0;
+  SGA_TRY(problem_batch_check(targets, sources, count));
+  const ProblemForestPlan P = problem_forest_plan(targets, sources, count);
+  out[0] = static_cast<int>(P.forest.size());
+  out[1] = static_cast<int>(P.lone.size());
+  out[2] = static_cast<int>(P.empty.size());
+  out[3] = static_cast<int>(P.points);
+  return SGA_OK;
+}
+
+int sga_problem_create_batch(sga_context* ctx, const sga_index* const* targets, const sga_cloud* const* sources, const double* init_T, size_t count, sga_problem** out) {
+  if (count == 0) return SGA_OK;
+  if (out)
+    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  if (!ctx || !targets || !sources || !out) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(problem_batch_check(targets, sources, count));
+  for (size_t k = 0; k < count; k++)
+    if (targets[k]->device != ctx->device || sources[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "target/source live on another device (problem %zu)", k);
+  SGA_ENTER(ctx);
+  std::vector<std::unique_ptr<sga_problem>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
+  SGA_TRY(problems_batch(ctx, targets, sources, init_T, count, made));
+  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
   return SGA_OK;
 }
 

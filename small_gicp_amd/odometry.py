@@ -326,7 +326,7 @@ def run_synthetic(num_frames=20, pinned=False, **kw):
 
 
 def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, batched_preprocessing=False, batched_downsampling=False,
-                          registration_type="GICP", voxel_resolution=1.0, batched_voxelmaps=False):
+                          registration_type="GICP", voxel_resolution=1.0, batched_voxelmaps=False, batched_problems=False):
     """The flow protocol (every pair (i - 1, i) registered from the identity, the relative poses multiplied up in frame order:
     odometry_benchmark_small_gicp_tbb_flow.cpp:73-110) with the registrations BATCHED: the scans are preprocessed as OnlineOdometry does,
     then groups of `batch` consecutive pairs are registered by one BatchProblem.align each — one search + factor launch, one row
@@ -338,7 +338,9 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
     same clouds, bit for bit); without it the scans are downsampled one by one.
     registration_type: "GICP" (every pair against the kd-tree of scan i - 1) or "VGICP" (against the Gaussian voxel map of scan i - 1 at
     voxel_resolution).  batched_voxelmaps: the maps of every `batch` scans are made by one api.build_gaussian_voxelmaps (the same maps,
-    bit for bit: the results do not change); without it by GaussianVoxelMap.from_cloud one by one."""
+    bit for bit: the results do not change); without it by GaussianVoxelMap.from_cloud one by one.
+    batched_problems: the problems of a group of VGICP pairs are made by one api.create_problems (the same source orders, bit for bit: the
+    results do not change); without it, and for GICP pairs (the scan by its own index: no sort to batch), by Problem one by one."""
     from . import synthetic
 
     if batch < 1:
@@ -385,7 +387,10 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
         for first in range(1, num_frames, batch):
             group = range(first, min(first + batch, num_frames))
             src = 0 if registration_type == "VGICP" else 1  # kd-tree targets: the scan by its own index, as OnlineOdometry; map targets: the scan's cloud
-            problems = [api.Problem(targets[i - 1], frames[i][src], np.eye(4), ctx=ctx) for i in group]
+            if batched_problems and src == 0:
+                problems = api.create_problems([targets[i - 1] for i in group], [frames[i][0] for i in group], [np.eye(4)] * len(group), ctx=ctx)
+            else:
+                problems = [api.Problem(targets[i - 1], frames[i][src], np.eye(4), ctx=ctx) for i in group]
             bp = api.BatchProblem(problems)
             for r in bp.align(setting):
                 rel.append(r.T_target_source)
@@ -402,13 +407,15 @@ def run_synthetic_batched(num_frames=20, batch=8, downsampling_resolution=0.25, 
             "relative_poses": rel, "iterations": iters, "estimated": est}
 
 
-def run_synthetic_model_batched(num_frames=20, streams=4, batched_insert=False, downsampling_resolution=0.25, num_neighbors=20, voxel_resolution=1.0, max_correspondence_distance=1.0, ctx=None):
+def run_synthetic_model_batched(num_frames=20, streams=4, batched_insert=False, downsampling_resolution=0.25, num_neighbors=20, voxel_resolution=1.0, max_correspondence_distance=1.0, ctx=None,
+                                batched_problems=False):
     """`streams` independent scan-to-model VGICP streams (ModelOdometry's protocol: register against the stream's own GaussianVoxelMap from
     the previous pose, then insert the scan at the estimated pose) over the frozen synthetic sequence in lock-step on one context: stream
     s starts at frame s, so round r gives stream s the frame s + r, while every stream has one (num_frames - streams + 1 rounds).  A round
     preprocesses each stream's scan, registers all streams by ONE BatchProblem.align against their maps, then updates the maps — by one
     api.insert_batch when batched_insert is set (the same maps, bit for bit: the results do not change), by one insert per stream
-    otherwise.  Returns per stream the poses (the first is the identity) and the iteration counts, the final map sizes, and the wall
+    otherwise; batched_problems: the round's problems are made by one api.create_problems (the same source orders, bit for bit), by one
+    Problem per stream otherwise.  Returns per stream the poses (the first is the identity) and the iteration counts, the final map sizes, and the wall
     time of the map updates per round."""
     from . import synthetic
 
@@ -431,7 +438,7 @@ def run_synthetic_model_batched(num_frames=20, streams=4, batched_insert=False, 
             Ts = [np.eye(4) for _ in range(streams)]
         else:
             prev = [poses[s][-1] for s in range(streams)]
-            problems = [api.Problem(maps[s], clouds[s], prev[s], ctx=ctx) for s in range(streams)]
+            problems = api.create_problems(maps, clouds, prev, ctx=ctx) if batched_problems else [api.Problem(maps[s], clouds[s], prev[s], ctx=ctx) for s in range(streams)]
             bp = api.BatchProblem(problems)
             results = bp.align(setting, prev)
             del bp  # before its problems
