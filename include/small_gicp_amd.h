@@ -106,6 +106,54 @@ int sga_cloud_download(sga_context* ctx, const sga_cloud* cloud, float* xyz, flo
 /* the same with the points in double (device record + origin, added in double): what a caller far from the origin wants back */
 int sga_cloud_download_f64(sga_context* ctx, const sga_cloud* cloud, double* xyz, float* normals, float* cov6);
 
+/* ---- device-resident data: clouds, queries and results that never touch the host ------------------------------------------------
+ * A caller whose scan is in device memory already (a tensor from a driver, a range image unprojected on the device, the output of its
+ * own filter) hands over the device pointer; results are written into device arrays of the caller's.  One struct describes an array:
+ * rows of `stride` elements of which the first `cols` are used, so an N x 4 KITTI scan goes down as cols 3, stride 4 without a copy.
+ *
+ * Ordering, the same for the four calls.  user_stream is the hipStream_t the caller produced the inputs on and will consume the outputs
+ * on (NULL: the null stream).  Unless it is the context's own stream, or flags has SGA_IO_NO_ORDER, the call records an event on
+ * user_stream, makes the context's stream wait for it ahead of the first kernel that touches the caller's memory, records a second
+ * event behind the last such kernel and makes user_stream wait for that one before it returns: work the caller enqueues on user_stream
+ * afterwards (a caching allocator handing the block out again included) is ordered behind the library's accesses.  The host waits for
+ * neither.  A blocking context synchronises its stream once at the end, as everywhere; a stream-ordered context returns with the work
+ * enqueued.  With SGA_IO_NO_ORDER the caller orders the two streams itself.
+ *
+ * Refusals (SGA_ERR_INVALID, before any launch): null arguments; 2^31 rows or more; a dtype, cols or stride other than the struct
+ * allows; cols the array cannot have; normals / covariances asked from a cloud without them; a data pointer that is not device
+ * memory of the context's device (host memory, pinned or pageable, is named as such, with the host entry point that takes it); a
+ * data pointer whose [data, data + rows * stride * element size) is not inside the allocation the runtime knows it by.  These checks
+ * are what keeps a caller's wrong row count from faulting the device. */
+enum { SGA_F32 = 0, SGA_F64 = 1 };
+typedef struct sga_device_array {
+  const void* data; /* device memory of the context's device (written through by the export call) */
+  int dtype;        /* SGA_F32 | SGA_F64 */
+  int cols;         /* layout of a row: points 3, normals 3, covariances 6 (xx xy xz yy yz zz) | 9 (3x3) | 16 (4x4, the reference's) */
+  int stride;       /* elements from one row to the next, >= cols */
+} sga_device_array;
+enum { SGA_IO_NO_ORDER = 1, SGA_IO_RELATIVE = 2 };
+/* The cloud of n points from device arrays; normals / covs may be NULL and may differ from the points in dtype.  origin NULL: absolute
+ * coordinates, the origin chosen from the box of the finite coordinates as sga_cloud_create_f32 / _f64 choose it (the box comes back
+ * from the device as a note: the one host wait the data forces); origin given: absolute coordinates recentred about it, the
+ * subtraction done in double (sga_cloud_create_f64_origin); origin given with SGA_IO_RELATIVE: the records are taken as they are
+ * (sga_cloud_create_f32_origin).  The result is an ordinary cloud with the records, the origin and the bounding box the host entry
+ * point makes from the same values, bit for bit; covariances given as 3x3 or 4x4 rows contribute m[0], m[1], m[2], m[5], m[6], m[10] (of
+ * the 4x4).  With origin given a stream-ordered context waits for nothing; its cloud then carries no bounding box (the box only shortens
+ * the voxel grid's sort keys, results do not depend on it).  n == 0 is SGA_OK with *out = NULL: nothing is examined and no cloud is
+ * made (an empty cloud comes from sga_cloud_create_f32 with n = 0). */
+int sga_cloud_create_device(sga_context* ctx, const sga_device_array* points, const sga_device_array* normals, const sga_device_array* covs, size_t n, const double origin[3], void* user_stream, int flags, sga_cloud** out);
+/* sga_cloud_download / _f64 into device arrays of the caller's (any of the three may be NULL; those given share one dtype): the points in
+ * the caller's frame — the origin is added in double, the sum rounded to dtype —, normals 3 per row, covariances 6, 9 (the symmetric
+ * 3x3) or 16 (4x4, fourth row and column zero) per row.  Elements of a row past its cols are left untouched. */
+int sga_cloud_export_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* points, const sga_device_array* normals, const sga_device_array* covs, void* user_stream, int flags);
+/* sga_index_knn for m queries in device memory (float or double rows; the search runs on fl32(double(q) - origin of the index), computed
+ * by a kernel): d_idx m*k int64 and d_sq_dist m*k floats, device memory of the caller's.  kd-trees, Gaussian and flat voxel maps, with
+ * the kernels, k limits and messages of the host call; a projective index is SGA_ERR_UNSUPPORTED, and the double distances of
+ * sga_index_knn_f64 stay a host-only form.  m == 0 is SGA_OK with nothing examined. */
+int sga_index_knn_device(sga_context* ctx, const sga_index* index, const sga_device_array* queries, size_t m, int k, double max_sq_dist, int64_t* d_idx, float* d_sq_dist, void* user_stream, int flags);
+/* sga_problem_get_factors into device memory: d_target_index n int64, d_mahalanobis6 n*6 floats (one of them may be NULL). */
+int sga_problem_get_factors_device(sga_context* ctx, const sga_problem* problem, int64_t* d_target_index, float* d_mahalanobis6, void* user_stream, int flags);
+
 /* ---- preprocessing (registration_helper.cpp:22-34 preprocess_points) ----------------------------------------------- */
 /* util/downsampling.hpp:23-78 voxelgrid_sampling: centroid per occupied voxel, output in ascending packed-key order. */
 int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf_size, sga_cloud** out);

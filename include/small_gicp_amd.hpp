@@ -119,6 +119,24 @@ struct PointCloud {
   PointCloud& operator=(const PointCloud&) = delete;
   ~PointCloud() { sga_cloud_destroy(h); }
 
+  /// A cloud from arrays that live in device memory of the context's device (sga_cloud_create_device: hipMalloc'd memory, a tensor's
+  /// data pointer), read where they are: rows of `stride` elements, float or double.  origin NULL: chosen by the library; given: the
+  /// points are recentred about it (with SGA_IO_RELATIVE in flags: they are relative to it already).  stream: the hipStream_t the arrays
+  /// were written on; the library orders itself behind it and the stream's later work behind its reads (small_gicp_amd.h).
+  static Ptr from_device(sga_context* context, const sga_device_array& points, size_t n, const sga_device_array* normals = nullptr, const sga_device_array* covs = nullptr, const double* origin = nullptr, void* stream = nullptr,
+                         int flags = 0) {
+    sga_cloud* made = nullptr;
+    if (n == 0)
+      check(sga_cloud_create_f32(context, nullptr, nullptr, nullptr, 0, &made), "sga_cloud_create_f32");
+    else
+      check(sga_cloud_create_device(context, &points, normals, covs, n, origin, stream, flags, &made), "sga_cloud_create_device");
+    return std::make_shared<PointCloud>(made, context);
+  }
+  /// The cloud into device arrays of the caller's (sga_cloud_export_device; any may be NULL): points in the caller's frame, normals, covariances.
+  void export_device(const sga_device_array* points, const sga_device_array* normals = nullptr, const sga_device_array* covs = nullptr, void* stream = nullptr, int flags = 0) const {
+    check(sga_cloud_export_device(ctx, h, points, normals, covs, stream, flags), "sga_cloud_export_device");
+  }
+
   size_t size() const {
     size_t n = 0;
     sga_cloud_size(h, &n);
@@ -173,6 +191,12 @@ private:
   mutable std::vector<double> host_xyz;
   mutable std::vector<float> host_nrm, host_cov;
 };
+
+/// kNN for m queries in device memory against a kd-tree, a Gaussian or a flat voxel map (sga_index_knn_device): d_idx m*k int64 and
+/// d_sq_dist m*k floats are device memory of the caller's; -1 / inf = none.
+inline void knn_device(sga_context* ctx, const sga_index* index, const sga_device_array& queries, size_t m, int k, int64_t* d_idx, float* d_sq_dist, double max_sq_dist = -1.0, void* stream = nullptr, int flags = 0) {
+  check(sga_index_knn_device(ctx, index, &queries, m, k, max_sq_dist, d_idx, d_sq_dist, stream, flags), "sga_index_knn_device");
+}
 
 /// ann/kdtree.hpp:248-291 KdTree<PointCloud>: exact nearest-neighbour index over a cloud (GPU kd-tree).
 struct KdTree {

@@ -64,6 +64,16 @@ ERROR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c
 BATCH_LINEARIZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64))
 BATCH_ERROR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_double), C.POINTER(C.c_double))
 
+class DeviceArray(C.Structure):
+    """sga_device_array: strided rows in device memory (data, dtype F32 | F64, cols, stride in elements)."""
+
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("cols", C.c_int), ("stride", C.c_int)]
+
+
+F32, F64 = 0, 1
+IO_NO_ORDER, IO_RELATIVE = 1, 2
+_da = C.POINTER(DeviceArray)
+
 # every symbol include/small_gicp_amd.h and include/small_gicp_amd_debug.h declare: (name, restype, argtypes)
 _vp, _dp, _fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float)
 _pvp = C.POINTER(C.c_void_p)
@@ -90,6 +100,10 @@ SYMBOLS = [
     ("sga_cloud_has", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sga_cloud_download", C.c_int, [_vp, _vp, _fp, _fp, _fp]),
     ("sga_cloud_download_f64", C.c_int, [_vp, _vp, _dp, _fp, _fp]),
+    ("sga_cloud_create_device", C.c_int, [C.c_void_p, _da, _da, _da, C.c_size_t, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("sga_cloud_export_device", C.c_int, [C.c_void_p, C.c_void_p, _da, _da, _da, C.c_void_p, C.c_int]),
+    ("sga_index_knn_device", C.c_int, [C.c_void_p, C.c_void_p, _da, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("sga_problem_get_factors_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("sga_voxelgrid_sampling", C.c_int, [_vp, _vp, C.c_double, _pvp]),
     ("sga_estimate_normals_covariances", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     ("sga_index_build_kdtree", C.c_int, [_vp, _vp, _pvp]),

@@ -219,6 +219,31 @@ class PointCloud:
             load().sga_cloud_destroy(self.h)
             self.h = C.c_void_p()
 
+    @staticmethod
+    def from_torch(points, normals=None, covs=None, ctx=None, origin=None, relative=False, stream=None):
+        """A cloud from torch tensors on the context's device, without a copy and without touching the host (sga_cloud_create_device):
+        points (N,3) float32 / float64 — or a view such as scan[:, :3] of an (N,4) tensor: any row stride, last-dimension stride 1 —,
+        normals (N,3), covs (N,6), (N,3,3) or (N,4,4).  origin None: chosen by the library as for host arrays; origin given: the points
+        are recentred about it in double; relative=True: the points are relative to origin already.  stream: the hipStream_t the tensors
+        were produced on (default: torch's current stream of the device); the library orders its reads behind it and the stream's later
+        work behind its reads.  ValueError, before the library is called, for a CPU tensor, another device, another dtype or a
+        transposed view."""
+        return _cloud_from_torch(points, normals, covs, ctx, origin, relative, stream)
+
+    @staticmethod
+    def from_device_pointer(ptr, n, dtype=np.float32, stride=3, normals_ptr=None, normals_stride=3, covs_ptr=None, covs_cols=6, covs_stride=None, ctx=None, origin=None, relative=False, stream=0):
+        """from_torch for callers without torch: ptr is device memory of the context's device (hipMalloc) holding n rows of `stride`
+        elements of `dtype`, the first three of each a point; normals_ptr / covs_ptr likewise.  stream: the hipStream_t the memory was
+        written on (0: the null stream)."""
+        return _cloud_from_device_pointer(ptr, n, dtype, stride, normals_ptr, normals_stride, covs_ptr, covs_cols, covs_stride, ctx, origin, relative, stream)
+
+    def to_torch(self, points=True, normals=False, covs=False, dtype=None, stream=None, out=None):
+        """New tensors on the cloud's device written by the library (sga_cloud_export_device): points (N,3) in the caller's frame
+        (origin added in double, rounded to dtype: torch.float32 by default, or torch.float64), normals (N,3), covs (N,6); one tensor, or
+        a tuple in that order.  out: an (N,3) tensor or view (any row stride) to write the points into instead.  The tensors are ready
+        for work on `stream` (default: torch's current stream)."""
+        return _cloud_to_torch(self, points, normals, covs, dtype, stream, out)
+
     def origin(self):
         """Origin of the cloud's device frame (the device holds fl32(p - origin)); zero for clouds centred within 64 m of the origin."""
         o = np.zeros(3)
@@ -368,6 +393,11 @@ class KdTree:
     def batch_nearest_neighbor_search(self, pts, num_threads=1):
         idx, d2 = self.batch_knn_search(pts, 1)
         return idx[:, 0], d2[:, 0]
+
+    def batch_knn_search_torch(self, queries, k, max_sq_dist=-1.0, stream=None):
+        """batch_knn_search for queries in device memory (sga_index_knn_device): a (m,3) or (m,4) float32 / float64 tensor on the
+        index's device -> (indices (m,k) int64, squared distances (m,k) float32) tensors; -1 / inf = none."""
+        return _knn_torch(self, queries, k, max_sq_dist, stream)
 
     def knn_search(self, pt, k):
         idx, d2 = self.batch_knn_search(np.asarray(pt, dtype=np.float64).reshape(1, -1), k)
@@ -519,6 +549,11 @@ class GaussianVoxelMap:
     def batch_knn_search(self, pts, k, max_sq_dist=-1.0):
         return _voxelmap_knn(self, pts, k, max_sq_dist)
 
+    def batch_knn_search_torch(self, queries, k, max_sq_dist=-1.0, stream=None):
+        """batch_knn_search for queries in device memory (sga_index_knn_device): a (m,3) or (m,4) float32 / float64 tensor on the
+        index's device -> (indices (m,k) int64, squared distances (m,k) float32) tensors; -1 / inf = none."""
+        return _knn_torch(self, queries, k, max_sq_dist, stream)
+
     def knn_search(self, pt, k):
         idx, d2 = _voxelmap_knn(self, np.asarray(pt, dtype=np.float64).reshape(1, -1), k)
         return idx[0], d2[0]
@@ -584,6 +619,11 @@ class _FlatVoxelMap:
 
     def batch_knn_search(self, pts, k, max_sq_dist=-1.0):
         return _voxelmap_knn(self, pts, k, max_sq_dist)
+
+    def batch_knn_search_torch(self, queries, k, max_sq_dist=-1.0, stream=None):
+        """batch_knn_search for queries in device memory (sga_index_knn_device): a (m,3) or (m,4) float32 / float64 tensor on the
+        index's device -> (indices (m,k) int64, squared distances (m,k) float32) tensors; -1 / inf = none."""
+        return _knn_torch(self, queries, k, max_sq_dist, stream)
 
     def knn_search(self, pt, k):
         idx, d2 = _voxelmap_knn(self, np.asarray(pt, dtype=np.float64).reshape(1, -1), k)
@@ -876,6 +916,10 @@ class Problem:
         check(load().sga_problem_get_factors(self.ctx.h, self.h, ti.ctypes.data_as(C.POINTER(C.c_int64)), _fp(m6)))
         return ti, m6
 
+    def factors_torch(self, stream=None):
+        """factors() as tensors on the problem's device (sga_problem_get_factors_device): (target_index (n,) int64, mahalanobis6 (n,6) float32)."""
+        return _factors_torch(self, stream)
+
     ROUTES = ("factors", "grid", "certify", "fused_lane", "fused_queue", "queue", "lane")  # enum class Route (csrc/linearize.hip)
 
     def last_plan(self):
@@ -1144,6 +1188,158 @@ def _voxelmap_knn(vm, pts, k, max_sq_dist=-1.0):
     d2 = np.empty((len(q), k), np.float64)
     check(load().sga_index_knn_f64(vm.ctx.h, vm.h, _dp(q), len(q), int(k), float(max_sq_dist), idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(d2)))
     return idx, d2
+
+
+# ---- device-resident data (sga_*_device) -----------------------------------------------------------------------
+# torch is imported inside these functions only: the package itself does not need it.
+_IO_DTYPES = {"float32": _lib.F32, "float64": _lib.F64}
+
+
+def _device_array(ptr, dtype, cols, stride):
+    a = _lib.DeviceArray()
+    a.data, a.dtype, a.cols, a.stride = int(ptr), int(dtype), int(cols), int(stride)
+    return a
+
+
+def _torch_rows(t, what, ctx, cols_allowed):
+    """A tensor of strided rows -> (sga_device_array, rows): 2-D (or (N,3,3) / (N,4,4) covariances whose matrices are contiguous),
+    float32 / float64, last-dimension stride 1, any row stride, on the device of `ctx` (None: any GPU; the caller compares later).
+    ValueError for anything else, before a context or the library is needed."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what} must be a torch.Tensor")
+    if t.dim() == 3:  # (N,3,3) / (N,4,4): the matrices row-major and contiguous
+        if t.shape[1] != t.shape[2] or (t.shape[0] > 0 and (t.stride(2) != 1 or t.stride(1) != t.shape[2])):
+            raise ValueError(f"{what}: (N,3,3) or (N,4,4) with contiguous matrices")
+        cols, stride = t.shape[1] * t.shape[2], t.stride(0)
+    elif t.dim() == 2:
+        cols, stride = t.shape[1], t.stride(0)
+        if t.shape[0] > 0 and t.stride(1) != 1:
+            raise ValueError(f"{what}: the last dimension must have stride 1 (a transposed view does not)")
+    else:
+        raise ValueError(f"{what} must be 2-D, not {t.dim()}-D")
+    name = str(t.dtype).replace("torch.", "")
+    if name not in _IO_DTYPES:
+        raise ValueError(f"{what} must be float32 or float64, not {t.dtype}")
+    if cols not in cols_allowed:
+        raise ValueError(f"{what}: {cols} columns, expected one of {sorted(cols_allowed)}")
+    if t.shape[0] > 1 and stride < cols:
+        raise ValueError(f"{what}: row stride {stride} < {cols} columns")
+    if not t.is_cuda:
+        raise ValueError(f"{what} is a CPU tensor: it must live on the context's device (host arrays: PointCloud(points))")
+    if ctx is not None and t.device.index != int(ctx.device):
+        raise ValueError(f"{what} lives on {t.device}, the context on cuda:{ctx.device}")
+    return _device_array(t.data_ptr(), _IO_DTYPES[name], cols, stride if t.shape[0] > 1 else cols), t.shape[0]
+
+
+def _torch_stream(ctx, stream):
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream(int(ctx.device))
+    return int(getattr(stream, "cuda_stream", stream))  # a torch.cuda.Stream, or the hipStream_t as an integer
+
+
+def _cloud_from_device_arrays(ctx, pa, na, ca, n, origin, relative, stream):
+    if relative and origin is None:
+        raise ValueError("relative=True needs an origin")
+    o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+    if n == 0:
+        return PointCloud(ctx=ctx)
+    h = C.c_void_p()
+    ref = lambda a: None if a is None else C.byref(a)  # noqa: E731
+    check(load().sga_cloud_create_device(ctx.h, ref(pa), ref(na), ref(ca), int(n), _dp(o), C.c_void_p(int(stream)), _lib.IO_RELATIVE if relative else 0, C.byref(h)))
+    return PointCloud(ctx=ctx, _handle=h)
+
+
+def _cloud_from_torch(points, normals=None, covs=None, ctx=None, origin=None, relative=False, stream=None):
+    pa, n = _torch_rows(points, "points", ctx, (3,))
+    if ctx is None:  # (after the first checks: a tensor that cannot be taken is refused without a device)
+        ctx = default_context()
+        _torch_rows(points, "points", ctx, (3,))
+    na = ca = None
+    if normals is not None:
+        na, nn = _torch_rows(normals, "normals", ctx, (3,))
+        if nn != n:
+            raise ValueError("normals must have one row per point")
+    if covs is not None:
+        ca, nc = _torch_rows(covs, "covs", ctx, (6, 9, 16))
+        if nc != n:
+            raise ValueError("covs must have one row per point")
+    return _cloud_from_device_arrays(ctx, pa, na, ca, n, origin, relative, _torch_stream(ctx, stream))
+
+
+def _cloud_from_device_pointer(ptr, n, dtype=np.float32, stride=3, normals_ptr=None, normals_stride=3, covs_ptr=None, covs_cols=6, covs_stride=None, ctx=None, origin=None, relative=False, stream=0):
+    name = np.dtype(dtype).name
+    if name not in _IO_DTYPES:
+        raise ValueError("dtype must be float32 or float64")
+    ctx = ctx or default_context()
+    dt = _IO_DTYPES[name]
+    pa = _device_array(ptr, dt, 3, stride)
+    na = None if normals_ptr is None else _device_array(normals_ptr, dt, 3, normals_stride)
+    ca = None if covs_ptr is None else _device_array(covs_ptr, dt, covs_cols, covs_cols if covs_stride is None else covs_stride)
+    return _cloud_from_device_arrays(ctx, pa, na, ca, n, origin, relative, stream or 0)
+
+
+def _cloud_to_torch(self, points=True, normals=False, covs=False, dtype=None, stream=None, out=None):
+    """PointCloud.to_torch: the result tensors are allocated on `stream`, so torch's allocator orders their reuse behind it."""
+    import torch
+
+    dtype = torch.float32 if dtype is None else dtype
+    name = str(dtype).replace("torch.", "")
+    if name not in _IO_DTYPES:
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+    n = self.size()
+    dev = torch.device("cuda", int(self.ctx.device))
+    s = _torch_stream(self.ctx, stream)
+    res, arrs = [], [None, None, None]
+    with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)) if stream is not None else torch.cuda.device(dev):
+        for slot, (want, cols) in enumerate(((points, 3), (normals, 3), (covs, 6))):
+            if not want:
+                continue
+            if slot == 0 and out is not None:
+                t = out
+                if t.dtype != dtype or t.shape[0] != n:
+                    raise ValueError("out must have one row per point and the requested dtype")
+            else:
+                t = torch.empty((n, cols), dtype=dtype, device=dev)
+            arrs[slot] = _torch_rows(t, ("points", "normals", "covs")[slot], self.ctx, (cols,))[0]
+            res.append(t)
+    if n > 0 and res:
+        ref = lambda a: None if a is None else C.byref(a)  # noqa: E731
+        check(load().sga_cloud_export_device(self.ctx.h, self.h, ref(arrs[0]), ref(arrs[1]), ref(arrs[2]), C.c_void_p(s), 0))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def _knn_torch(self, queries, k, max_sq_dist=-1.0, stream=None):
+    import torch
+
+    qa, m = _torch_rows(queries, "queries", self.ctx, (3, 4))
+    qa.cols = 3  # an (m,4) tensor of homogeneous points: the first three columns of every row
+    k = int(k)
+    dev = torch.device("cuda", int(self.ctx.device))
+    s = _torch_stream(self.ctx, stream)
+    with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)) if stream is not None else torch.cuda.device(dev):
+        idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+        d2 = torch.empty((m, k), dtype=torch.float32, device=dev)
+    if m > 0:
+        check(load().sga_index_knn_device(self.ctx.h, self.h, C.byref(qa), int(m), k, float(max_sq_dist), C.c_void_p(idx.data_ptr()), C.c_void_p(d2.data_ptr()), C.c_void_p(s), 0))
+    return idx, d2
+
+
+def _factors_torch(self, stream=None):
+    import torch
+
+    n = self.source.size()
+    dev = torch.device("cuda", int(self.ctx.device))
+    s = _torch_stream(self.ctx, stream)
+    with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)) if stream is not None else torch.cuda.device(dev):
+        ti = torch.empty((n,), dtype=torch.int64, device=dev)
+        m6 = torch.empty((n, 6), dtype=torch.float32, device=dev)
+    if n > 0:
+        check(load().sga_problem_get_factors_device(self.ctx.h, self.h, C.c_void_p(ti.data_ptr()), C.c_void_p(m6.data_ptr()), C.c_void_p(s), 0))
+    return ti, m6
 
 
 def set_warm_limit(warm_delta_m):

@@ -155,6 +155,10 @@ struct sga_context {
   uint64_t comm_calls = 0;
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // sga_debug_timer_*: GPU time between two points of the stream
   hipEvent_t ev_aux = nullptr;   // small read-backs that must not wait for the work enqueued behind them (stream-ordered mode)
+  // device_io.hip: the two events that order a caller's stream against the context's (made on first use), and the 64-bit accumulator
+  // of a double cloud's bounding box {min x y z, max x y z (ordered encoding), arrival counter, 0}: identity values between launches
+  hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
+  sga::DevBuf<unsigned long long> d_box64;
   bool stream_ordered = false;   // sga_context_set_stream_ordered: preprocessing entry points return once their work is enqueued
   bool mid_recorded = false;
   double search_ms = 0.0;

@@ -583,6 +583,8 @@ int sga_context_destroy(sga_context* ctx) {
   if (ctx->ev_mid) (void)hipEventDestroy(ctx->ev_mid);
   if (ctx->ev_comm) (void)hipEventDestroy(ctx->ev_comm);
   if (ctx->ev_aux) (void)hipEventDestroy(ctx->ev_aux);
+  if (ctx->ev_io_in) (void)hipEventDestroy(ctx->ev_io_in);
+  if (ctx->ev_io_out) (void)hipEventDestroy(ctx->ev_io_out);
   if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
   if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
   if (ctx->h_accum) (void)hipHostFree(ctx->h_accum);
@@ -896,13 +898,15 @@ static void copy_with_box(const float* src, float* dst, size_t n, double lo[3], 
 }
 
 // Is [p, p + bytes) pinned host memory a kernel of this device can read (hipHostMalloc / hipHostRegister / sga_host_alloc)?  -> its device address
-static const void* pinned_device_view(const void* p, size_t bytes) {
+// on_device (optional): set when p is device memory, which no host entry point takes
+static const void* pinned_device_view(const void* p, size_t bytes, bool* on_device = nullptr) {
   if (p == nullptr) return nullptr;
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) {
     (void)hipGetLastError();  // an ordinary (pageable) pointer: not an error of ours
     return nullptr;
   }
+  if (on_device != nullptr && a.type == hipMemoryTypeDevice) *on_device = true;
   if (a.type != hipMemoryTypeHost || a.devicePointer == nullptr) return nullptr;
   (void)bytes;
   return a.devicePointer;
@@ -938,7 +942,10 @@ static int cloud_upload(sga_context* ctx, const float* xyz, const float* normals
   const size_t fx = n * 3, fn = normals ? n * 3 : 0, fc = cov6 ? n * 6 : 0;
   const dim3 grid((n + 255) / 256), block(256);
   static const bool zero_copy = !(getenv("SGA_UPLOAD_PINNED") && atoi(getenv("SGA_UPLOAD_PINNED")) == 0);
-  const float* dx = zero_copy ? static_cast<const float*>(pinned_device_view(xyz, fx * sizeof(float))) : nullptr;
+  bool on_device = false;
+  const float* view = static_cast<const float*>(pinned_device_view(xyz, fx * sizeof(float), &on_device));
+  if (on_device) return fail(SGA_ERR_INVALID, "xyz is device memory: clouds that live on the device are made by sga_cloud_create_device");
+  const float* dx = zero_copy ? view : nullptr;
   const float* dn = (dx && normals) ? static_cast<const float*>(pinned_device_view(normals, fn * sizeof(float))) : nullptr;
   const float* dc = (dx && cov6) ? static_cast<const float*>(pinned_device_view(cov6, fc * sizeof(float))) : nullptr;
   double lo[3], hi[3];

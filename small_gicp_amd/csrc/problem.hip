@@ -19,6 +19,7 @@ namespace sga {
 int ensure_temp(sga_context* ctx, size_t bytes);
 size_t problem_partials_doubles(size_t n);
 int problem_ensure_maha(sga_context* ctx, sga_problem* pb);
+int problem_factors_enqueue(sga_context* ctx, const sga_problem* pb, long long* d_idx, float* d_m);  // below: the launch of sga_problem_get_factors
 int cloud_bbox(sga_context* ctx, const float4* pts, size_t n, float lo[3], float hi[3]);
 // projective.hip
 int projective_source_keys(sga_context* ctx, const sga_index* idx, const float4* pts, size_t n, const double T_dev[16], unsigned long long* keys, uint32_t* vals);
@@ -697,15 +698,7 @@ int sga_problem_get_factors(sga_context* ctx, const sga_problem* pb, int64_t* ta
   DevBuf<float> d_m;
   if (target_index) SGA_TRY(d_idx.alloc(n));
   if (mahalanobis6) SGA_TRY(d_m.alloc(n * 6));
-  if (mahalanobis6) SGA_TRY(problem_ensure_maha(ctx, const_cast<sga_problem*>(pb)));  // written on demand (linearize.hip)
-  const float4* tpts = pb->target->kind != SGA_INDEX_KDTREE ? pb->target->pts.p : pb->target->kd_pts.p;
-  const int is_flat = pb->target->kind == SGA_INDEX_FLATMAP ? 1 : 0;
-  const bool has_maha = pb->lin_factor == SGA_GICP && pb->maha_valid;  // only GICP has a mahalanobis matrix (gicp_factor.hpp:57-60); the cache is never pre-filled: zeros otherwise
-  if (has_maha && pb->last_math == SGA_MATH_FP64 && pb->maha64.p != nullptr)  // the last linearize cached its mahalanobis in fp64
-    hipLaunchKernelGGL((export_factors_kernel<double>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pb->src_pts(), pb->corr.p, pb->maha64.p, n, tpts, is_flat, d_idx.p, d_m.p);
-  else
-    hipLaunchKernelGGL((export_factors_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pb->src_pts(), pb->corr.p, has_maha ? pb->maha.p : static_cast<const float*>(nullptr), n, tpts, is_flat, d_idx.p, d_m.p);
-  SGA_HIP(hipGetLastError());
+  SGA_TRY(problem_factors_enqueue(ctx, pb, d_idx.p, d_m.p));
   if (target_index) SGA_HIP(hipMemcpyAsync(target_index, d_idx.p, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   if (mahalanobis6) SGA_HIP(hipMemcpyAsync(mahalanobis6, d_m.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   SGA_HIP(hipStreamSynchronize(ctx->stream));
@@ -788,6 +781,53 @@ static int index_knn_impl(sga_context* ctx, const sga_index* index, const float*
     for (size_t i = 0; i < m * k; i++) sq_dist64[i] = dst[i];
   return SGA_OK;
 }
+
+}  // extern "C"
+
+// device_io.hip (sga_index_knn_device, sga_problem_get_factors_device): the launches of index_knn_impl and of sga_problem_get_factors
+// (which goes through problem_factors_enqueue itself) on buffers that are on the device already — the same kernels, the same k limits
+// and messages, no copy and no wait.  The caller has entered the context, waited for the index and handles an empty index itself.
+namespace sga {
+int index_knn_check_k(const sga_index* index, int k) {
+  if (k < 1 || k > 128) return fail(SGA_ERR_INVALID, "k must be in [1,128]");
+  if (index->kind == SGA_INDEX_KDTREE && index->n > 0 && k > kKnnMaxK) return fail(SGA_ERR_INVALID, "k must be <= %d for a kd-tree (LDS per workgroup)", kKnnMaxK);
+  return SGA_OK;
+}
+int index_knn_enqueue(sga_context* ctx, const sga_index* index, const float* d_q, size_t m, int k, double max_sq_dist, long long* d_idx, float* d_sq_dist) {
+  SGA_TRY(index_knn_check_k(index, k));
+  const float max_sq = max_sq_dist < 0 ? INFINITY : static_cast<float>(max_sq_dist);
+  if (index->kind == SGA_INDEX_VOXELMAP || index->kind == SGA_INDEX_FLATMAP) {
+    const FlatView v{index->hkeys.p, index->hvals.p, index->hmask, 1.0 / index->leaf, index->vcounts.p, index->search_offsets, {index->origin[0], index->origin[1], index->origin[2]}};
+    if (index->kind == SGA_INDEX_FLATMAP)
+      hipLaunchKernelGGL(voxel_knn_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, v, index->pts.p, d_q, m, k, max_sq, d_idx, d_sq_dist);
+    else
+      hipLaunchKernelGGL(voxel_knn_kernel<false>, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, v, index->pts.p, d_q, m, k, max_sq, d_idx, d_sq_dist);
+  } else if (index->kind == SGA_INDEX_KDTREE) {
+    const size_t shmem = (static_cast<size_t>((k + 3) & ~3) * 8 + kKdMaxDepth * 4) * kKnnBlock;
+    KdView kv = make_kd_view(index);
+    hipLaunchKernelGGL(knn_kernel<false>, dim3((m + kKnnBlock - 1) / kKnnBlock), dim3(kKnnBlock), shmem, ctx->stream, kv, d_q, m, k, max_sq, d_idx, d_sq_dist, nullptr, nullptr, 0.0);
+  } else {
+    return fail(SGA_ERR_UNSUPPORTED, "no device-resident kNN for this kind of index");
+  }
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+int problem_factors_enqueue(sga_context* ctx, const sga_problem* pb, long long* d_idx, float* d_m) {
+  const size_t n = pb->n;
+  if (d_m) SGA_TRY(problem_ensure_maha(ctx, const_cast<sga_problem*>(pb)));  // written on demand (linearize.hip)
+  const float4* tpts = pb->target->kind != SGA_INDEX_KDTREE ? pb->target->pts.p : pb->target->kd_pts.p;
+  const int is_flat = pb->target->kind == SGA_INDEX_FLATMAP ? 1 : 0;
+  const bool has_maha = pb->lin_factor == SGA_GICP && pb->maha_valid;  // only GICP has a mahalanobis matrix (gicp_factor.hpp:57-60); the cache is never pre-filled: zeros otherwise
+  if (has_maha && pb->last_math == SGA_MATH_FP64 && pb->maha64.p != nullptr)  // the last linearize cached its mahalanobis in fp64
+    hipLaunchKernelGGL((export_factors_kernel<double>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pb->src_pts(), pb->corr.p, pb->maha64.p, n, tpts, is_flat, d_idx, d_m);
+  else
+    hipLaunchKernelGGL((export_factors_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pb->src_pts(), pb->corr.p, has_maha ? pb->maha.p : static_cast<const float*>(nullptr), n, tpts, is_flat, d_idx, d_m);
+  SGA_HIP(hipGetLastError());
+  return SGA_OK;
+}
+}  // namespace sga
+
+extern "C" {
 
 int sga_index_knn(sga_context* ctx, const sga_index* index, const float* queries, size_t m, int k, double max_sq_dist, int64_t* idx, float* sq_dist) {
   return index_knn_impl(ctx, index, queries, nullptr, m, k, max_sq_dist, idx, sq_dist, nullptr);
