@@ -33,7 +33,7 @@ int fail(int code, const char* fmt, ...);
 
 // ---- device memory --------------------------------------------------------------------------------------------------------
 // hipMalloc / hipFree cost tens of microseconds each and hipFree synchronises the device; a registration of a 30k-point scan
-// allocates ~30 buffers.  Freed blocks are therefore kept in size-bucketed free lists (context.hip) and handed out again — in
+// allocates ~30 buffers.  Freed blocks are therefore kept in size-bucketed free lists (allocator.hip) and handed out again — in
 // STREAM ORDER, because work is asynchronous (sga_linearize_async, borrowed streams, several contexts on one device):
 //   * a block freed inside an entry point (the thread's current stream, SGA_ENTER) goes to THAT stream's list and is only handed to
 //     later allocations on the same stream, which run after everything that touched it;
@@ -50,6 +50,9 @@ struct StreamScope {  // the calling thread's current stream for dev_alloc / dev
   hipStream_t prev;
   unsigned long long prev_epoch;
 };
+// a context's stream joins / leaves the streams the allocator knows (leaves: synchronised; the last one gives the cached memory back)
+void dev_cache_context_created(int device, hipStream_t stream);
+void dev_cache_context_destroyed(int device, hipStream_t stream);
 #define SGA_ENTER(ctx)                        \
   SGA_HIP(hipSetDevice((ctx)->device));       \
   ::sga::StreamScope _sga_stream_scope((ctx)->stream)
@@ -106,13 +109,13 @@ struct sga_context {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = false;
-  bool registered = false;  // known to the allocator (context.hip)
+  bool registered = false;  // known to the allocator (allocator.hip)
   // scratch
   sga::DevBuf<double> d_accum;    // 128 doubles: a linearization result (30, or 96 with the error model)
   sga::DevBuf<unsigned> d_ticket; // arrival counter of the reduction kernel (reduce_rows.hpp), zero between launches
   double* h_accum = nullptr;      // pinned + device-mapped: [0, 128) a result, word 128 = sequence number of the last published result
   double* h_accum_dev = nullptr;  // device address of h_accum
-  // pinned, device-mapped staging ring for uploads from pageable memory (context.hip): the pack kernel reads a slot over PCIe while
+  // pinned, device-mapped staging ring for uploads from pageable memory (cloud.hip): the pack kernel reads a slot over PCIe while
   // the host fills the next one; a slot is reused once the event recorded behind its reader has completed
   struct StageSlot {
     void* host = nullptr;
@@ -155,8 +158,8 @@ struct sga_context {
   uint64_t comm_calls = 0;
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // sga_debug_timer_*: GPU time between two points of the stream
   hipEvent_t ev_aux = nullptr;   // small read-backs that must not wait for the work enqueued behind them (stream-ordered mode)
-  // device_io.hip: the two events that order a caller's stream against the context's (made on first use), and the 64-bit accumulator
-  // of a double cloud's bounding box {min x y z, max x y z (ordered encoding), arrival counter, 0}: identity values between launches
+  // device_io.hpp: the two events that order a caller's stream against the context's (made on first use), and (cloud.hip) the 64-bit
+  // accumulator of a double cloud's bounding box {min x y z, max x y z (ordered encoding), arrival counter, 0}: identity values between launches
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
   sga::DevBuf<unsigned long long> d_box64;
   bool stream_ordered = false;   // sga_context_set_stream_ordered: preprocessing entry points return once their work is enqueued
@@ -178,7 +181,7 @@ struct sga_context {
   bool sharded() const { return comm != nullptr || comm_fn != nullptr; }
 };
 
-// context.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
+// cloud.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
 // the event that stage_release records behind its reader has completed.
 int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot** out);
 int stage_release(sga_context* ctx, sga_context::StageSlot* slot);

@@ -1,12 +1,51 @@
-// Device frames (common.hpp) at the C-ABI boundary: the caller's pose -> the pose between the two device frames, a system of the
-// source's device frame -> the caller's twist convention (on the host and, for the asynchronous entry points, on the device), and the
-// check that the ranks of a sharded registration share one source frame.
+// Device frames (common.hpp): the choice of an origin and, at the C-ABI boundary, the caller's pose -> the pose between the two device
+// frames, a system of the source's device frame -> the caller's twist convention (on the host and, for the asynchronous entry points, on
+// the device), and the check that the ranks of a sharded registration share one source frame.
 #include "batch.hpp"
 #include "common.hpp"
+
+#include <cmath>
 
 namespace sga {
 
 int comm_allreduce_sum(sga_context* ctx, double* d_buf, size_t count);  // comm.hip
+
+void choose_origin(const double lo[3], const double hi[3], double origin[3]) {
+  for (int k = 0; k < 3; k++) {
+    origin[k] = 0.0;
+    if (!(lo[k] <= hi[k])) continue;  // empty or non-finite
+    const double c = 0.5 * (lo[k] + hi[k]);
+    if (c - c != 0.0) continue;
+    origin[k] = kOriginQuantum * std::nearbyint(c / kOriginQuantum);
+  }
+}
+
+void pose_to_device(const double T[16], const double o_s[3], const double o_t[3], double Td[16]) {
+  for (int i = 0; i < 16; i++) Td[i] = T[i];
+  for (int r = 0; r < 3; r++) Td[12 + r] = (T[r] * o_s[0] + T[4 + r] * o_s[1] + T[8 + r] * o_s[2]) + (T[12 + r] - o_t[r]);  // R o_s + (t - o_t)
+}
+
+void system_to_caller(const double o[3], double H[36], double b[6]) {
+  // A = [[I, 0], [X, I]], X = -skew(o):  H = A^T H' A, b = A^T b'  (J = J' A with J' = [R skew(p'), -R], p = p' + o)
+  const double X[3][3] = {{0, o[2], -o[1]}, {-o[2], 0, o[0]}, {o[1], -o[0], 0}};
+  double HA[6][6];  // H' A: columns 0..2 get H'[:, 3..5] X added
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      double v = H[6 * i + j];
+      if (j < 3)
+        for (int k = 0; k < 3; k++) v += H[6 * i + 3 + k] * X[k][j];
+      HA[i][j] = v;
+    }
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      double v = HA[i][j];
+      if (i < 3)
+        for (int k = 0; k < 3; k++) v += X[k][i] * HA[3 + k][j];  // (A^T)[i][3 + k] = X[k][i]
+      H[6 * i + j] = v;
+    }
+  for (int i = 0; i < 3; i++)
+    for (int k = 0; k < 3; k++) b[i] += X[k][i] * b[3 + k];
+}
 
 // ---- device frames (common.hpp): what crosses the boundary is converted HERE, everything below works between the two device frames ----
 bool problem_framed(const sga_problem* pb) { return !origin_is_zero(pb->src_origin) || !origin_is_zero(pb->target->origin); }
@@ -30,7 +69,7 @@ __global__ void frame_accumulator_kernel(double* __restrict__ acc, double ox, do
       k++;
     }
   for (int i = 0; i < 6; i++) b[i] = acc[21 + i];
-  const double X[3][3] = {{0, oz, -oy}, {-oz, 0, ox}, {oy, -ox, 0}};  // -skew(o), see system_to_caller (context.hip)
+  const double X[3][3] = {{0, oz, -oy}, {-oz, 0, ox}, {oy, -ox, 0}};  // -skew(o), see system_to_caller above
   double HA[6][6];
   for (int i = 0; i < 6; i++)
     for (int j = 0; j < 6; j++) {
@@ -110,6 +149,14 @@ int problem_check_shard_frames(sga_context* ctx, sga_problem* pb) {
 using namespace sga;
 
 extern "C" {
+
+int sga_index_origin(const sga_index* index, double origin[3]) {
+  if (!index || !origin) return fail(SGA_ERR_INVALID, "null argument");
+  for (int k = 0; k < 3; k++) origin[k] = index->origin[k];
+  return SGA_OK;
+}
+
+void sga_choose_origin(const double lo[3], const double hi[3], double origin[3]) { choose_origin(lo, hi, origin); }
 
 void sga_debug_shard_frame_pack(const double origin[3], double out[SGA_FRAME_CHECK_DOUBLES]) { shard_frame_pack(origin, out); }
 int sga_debug_shard_frame_agree(const double sum[SGA_FRAME_CHECK_DOUBLES]) { return shard_frame_agree(sum) ? 1 : 0; }

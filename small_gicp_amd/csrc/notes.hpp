@@ -15,7 +15,7 @@ namespace sga {
 constexpr int kNoteSlots = 4;  // notes in flight per context (slot = seq % kNoteSlots); every producer waits for its own note before it returns
 constexpr int kNoteWords = 8;  // per slot: word 0 = the sequence number, words 1..7 = payload
 
-// host side (context.hip)
+// host side (context.hip: notes, late notes and the wait)
 // The ONE host wait for a word the device publishes with a system-scope release (notes, linearization results, the boxes of a forest
 // call): acquire loads of the pinned `word` until it shows `seq`, a pause between them and a yield once a wait is long; every 4096
 // spins the stream is asked, and when it has drained without publishing (a fault) or 20 s have passed it is synchronised — a HIP error

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <memory>
 #include <rocprim/rocprim.hpp>
+#include "device_io.hpp"
 #include "device_math.hpp"
 #include "forest.hpp"
 #include "kd_search.hpp"
@@ -784,9 +785,10 @@ static int index_knn_impl(sga_context* ctx, const sga_index* index, const float*
 
 }  // extern "C"
 
-// device_io.hip (sga_index_knn_device, sga_problem_get_factors_device): the launches of index_knn_impl and of sga_problem_get_factors
-// (which goes through problem_factors_enqueue itself) on buffers that are on the device already — the same kernels, the same k limits
-// and messages, no copy and no wait.  The caller has entered the context, waited for the index and handles an empty index itself.
+// sga_index_knn_device, sga_problem_get_factors_device (below): the launches of index_knn_impl and of
+// sga_problem_get_factors (which goes through problem_factors_enqueue itself) on buffers that are on the device already — the same
+// kernels, the same k limits and messages, no copy and no wait.  The caller has entered the context, waited for the index and handles an
+// empty index itself.
 namespace sga {
 int index_knn_check_k(const sga_index* index, int k) {
   if (k < 1 || k > 128) return fail(SGA_ERR_INVALID, "k must be in [1,128]");
@@ -825,6 +827,29 @@ int problem_factors_enqueue(sga_context* ctx, const sga_problem* pb, long long* 
   SGA_HIP(hipGetLastError());
   return SGA_OK;
 }
+
+// kNN queries (strided float or double rows) -> m x 3 floats in the index's device frame: fl32(double(q) - origin)
+template <typename T>
+__global__ __launch_bounds__(kIoBlock) void knn_queries_kernel(const T* __restrict__ q, int stride, size_t m, double ox, double oy, double oz, float* __restrict__ out) {
+  __shared__ T sh[kIoTile];
+  const size_t base = blockIdx.x * static_cast<size_t>(kIoBlock);
+  const size_t i = base + threadIdx.x;
+  const int sel3[3] = {0, 1, 2};
+  T p[3];
+  load_rows<T, 3>(q, base, m, stride, sel3, sh, p);
+  if (i >= m) return;
+  out[3 * i] = static_cast<float>(static_cast<double>(p[0]) - ox);
+  out[3 * i + 1] = static_cast<float>(static_cast<double>(p[1]) - oy);
+  out[3 * i + 2] = static_cast<float>(static_cast<double>(p[2]) - oz);
+}
+
+// the results of a search in an empty index: no neighbour anywhere
+__global__ __launch_bounds__(kIoBlock) void knn_fill_none_kernel(long long* __restrict__ idx, float* __restrict__ d2, size_t count) {
+  const size_t i = blockIdx.x * static_cast<size_t>(kIoBlock) + threadIdx.x;
+  if (i >= count) return;
+  idx[i] = -1ll;
+  d2[i] = INFINITY;
+}
 }  // namespace sga
 
 extern "C" {
@@ -835,6 +860,55 @@ int sga_index_knn(sga_context* ctx, const sga_index* index, const float* queries
 
 int sga_index_knn_f64(sga_context* ctx, const sga_index* index, const double* queries, size_t m, int k, double max_sq_dist, int64_t* idx, double* sq_dist) {
   return index_knn_impl(ctx, index, nullptr, queries, m, k, max_sq_dist, idx, nullptr, sq_dist);
+}
+
+int sga_index_knn_device(sga_context* ctx, const sga_index* index, const sga_device_array* queries, size_t m, int k, double max_sq_dist, int64_t* d_idx, float* d_sq_dist, void* user_stream, int flags) {
+  if (m == 0) return SGA_OK;
+  if (!ctx || !index || !queries || !d_idx || !d_sq_dist) return fail(SGA_ERR_INVALID, "null argument");
+  if (m >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many queries (%zu; limit 2^31-1)", m);
+  if (k < 1 || k > 128) return fail(SGA_ERR_INVALID, "k must be in [1,128]");
+  SGA_TRY(check_layout(queries, "queries", false));
+  if (index->device != ctx->device) return fail(SGA_ERR_INVALID, "index lives on another device");
+  if (index->kind == SGA_INDEX_PROJECTIVE) return fail(SGA_ERR_UNSUPPORTED, "sga_index_knn_device does not search projective indices (host queries: sga_index_knn)");
+  SGA_TRY(index_knn_check_k(index, k));
+  SGA_TRY(check_array(ctx, queries, m, "queries", queries->dtype == SGA_F64 ? "sga_index_knn_f64" : "sga_index_knn"));
+  SGA_TRY(check_device_range(ctx, d_idx, m * static_cast<size_t>(k) * sizeof(int64_t), sizeof(int64_t), "d_idx", "sga_index_knn"));
+  SGA_TRY(check_device_range(ctx, d_sq_dist, m * static_cast<size_t>(k) * sizeof(float), sizeof(float), "d_sq_dist", "sga_index_knn"));
+  SGA_ENTER(ctx);
+  SGA_TRY(wait_ready(ctx, index->ready));
+  const bool empty = index->n == 0 || (index->kind != SGA_INDEX_KDTREE && index->hkeys.p == nullptr);
+  DevBuf<float> d_q;
+  if (!empty) SGA_TRY(d_q.alloc(m * 3));
+  IoOrder ord;
+  SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+  if (empty) {
+    const size_t count = m * static_cast<size_t>(k);
+    hipLaunchKernelGGL(knn_fill_none_kernel, dim3((count + kIoBlock - 1) / kIoBlock), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<long long*>(d_idx), d_sq_dist, count);
+    SGA_HIP(hipGetLastError());
+  } else {
+    const dim3 grid((m + kIoBlock - 1) / kIoBlock), block(kIoBlock);
+    if (queries->dtype == SGA_F64)
+      hipLaunchKernelGGL(knn_queries_kernel<double>, grid, block, 0, ctx->stream, static_cast<const double*>(queries->data), queries->stride, m, index->origin[0], index->origin[1], index->origin[2], d_q.p);
+    else
+      hipLaunchKernelGGL(knn_queries_kernel<float>, grid, block, 0, ctx->stream, static_cast<const float*>(queries->data), queries->stride, m, index->origin[0], index->origin[1], index->origin[2], d_q.p);
+    SGA_HIP(hipGetLastError());
+    SGA_TRY(index_knn_enqueue(ctx, index, d_q.p, m, k, max_sq_dist, reinterpret_cast<long long*>(d_idx), d_sq_dist));
+  }
+  return io_end(ctx, ord);
+}
+
+int sga_problem_get_factors_device(sga_context* ctx, const sga_problem* problem, int64_t* d_target_index, float* d_mahalanobis6, void* user_stream, int flags) {
+  if (!ctx || !problem || (!d_target_index && !d_mahalanobis6)) return fail(SGA_ERR_INVALID, "null argument");
+  if (problem->device != ctx->device) return fail(SGA_ERR_INVALID, "problem lives on another device");
+  const size_t n = problem->n;
+  if (n == 0) return SGA_OK;
+  if (d_target_index) SGA_TRY(check_device_range(ctx, d_target_index, n * sizeof(int64_t), sizeof(int64_t), "d_target_index", "sga_problem_get_factors"));
+  if (d_mahalanobis6) SGA_TRY(check_device_range(ctx, d_mahalanobis6, n * 6 * sizeof(float), sizeof(float), "d_mahalanobis6", "sga_problem_get_factors"));
+  SGA_ENTER(ctx);
+  IoOrder ord;
+  SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+  SGA_TRY(problem_factors_enqueue(ctx, problem, reinterpret_cast<long long*>(d_target_index), d_mahalanobis6));
+  return io_end(ctx, ord);
 }
 
 }  // extern "C"
