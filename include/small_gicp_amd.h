@@ -98,6 +98,30 @@ void sga_choose_origin(const double lo[3], const double hi[3], double origin[3])
 /* A new cloud holding points [first, first + count) of `cloud` with their normals / covariances (device copy): the source shard of one
  * rank when a registration is spread over GPUs (reduction_omp.hpp:32-58 is the loop being partitioned). */
 int sga_cloud_slice(sga_context* ctx, const sga_cloud* cloud, size_t first, size_t count, sga_cloud** out);
+/* Posed clouds joined into one cloud — the last K keyframes at their estimated poses as one target — without leaving the device.  In the
+ * reference this is a host loop over points, normals and covs (src/test/registration_test.cpp:84: pt = T * pt per point); here one table
+ * and ONE launch whatever count is.  *out holds the points of clouds[0], then clouds[1], ... each in its own order, the index word of a
+ * point its position in *out.  T: count poses, column-major 4x4 (NULL: identities).  R_m is the upper-left 3x3 of T_m taken as it is
+ * (the reference's T * p: nothing is renormalised); with o_m the member's origin, c_m = R_m o_m + t_m — per row
+ * ((R0 o0 + R1 o1) + R2 o2) + t, every operation rounded on its own — and o the output's origin, a record r of member m becomes
+ *   fl32(R_m r + (c_m - o)),
+ * c_m - o formed once per member on the host, the rest evaluated in double on the device and rounded once: a submap kilometres from the
+ * origin keeps its millimetres.  Normals become fl32(R_m n), covariances the six entries of fl32(R_m C R_m^T), both evaluated in double
+ * from the fp32 records.  ATTRIBUTES: the output has normals only if every non-empty member has them, and covariances only if every
+ * non-empty member has them; otherwise the attribute is dropped (sga_cloud_has tells).  A non-finite point stays non-finite and takes no
+ * part in the bounding box.
+ *   origin given: o is that; a stream-ordered context waits for nothing and its cloud carries no bounding box (sga_cloud_create_device's
+ *     contract), a blocking context keeps the box of the records with the cloud.
+ *   origin NULL: o = sga_choose_origin of the bounding box of the finite posed points R_m r + c_m, reduced on the device in double (the
+ *     one host wait the data forces).  The records are first written for the origin zero — their box is that box —; when the rule chooses
+ *     another origin a second launch writes them again FROM THE MEMBERS' RECORDS: the result never depends on the route.
+ * A cloud may appear several times under different poses; members made by another context of the same device are waited for; empty
+ * members take no part.  count == 0, or empty members only: an empty cloud without attributes at the given origin (or zero), no device
+ * work.  Refusals (SGA_ERR_INVALID, before any device work, *out = NULL as on every failure): NULL ctx, clouds or out; a NULL member, a
+ * non-finite entry of a pose (both named by number) or of origin; more than 2^15 members; a member on another device; 2^31 points or
+ * more in all.  sga_cloud_transform is the merge of one member. */
+int sga_cloud_merge(sga_context* ctx, const sga_cloud* const* clouds, const double* T /* count x 16 column-major, or NULL: identities */, size_t count, const double origin[3] /* or NULL */, sga_cloud** out);
+int sga_cloud_transform(sga_context* ctx, const sga_cloud* cloud, const double T[16], const double origin[3], sga_cloud** out);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

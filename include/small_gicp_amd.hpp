@@ -137,6 +137,14 @@ struct PointCloud {
     check(sga_cloud_export_device(ctx, h, points, normals, covs, stream, flags), "sga_cloud_export_device");
   }
 
+  /// This cloud posed by T as a new cloud on the device (sga_cloud_transform: points T * p, normals R n, covariances R C R^T — the loop of
+  /// src/test/registration_test.cpp:84 over points, normals and covs); origin: the new cloud's device-frame origin (NULL: chosen by the library).
+  Ptr transformed(const Isometry3d& T, const double* origin = nullptr) const {
+    sga_cloud* made = nullptr;
+    check(sga_cloud_transform(ctx, h, T.data(), origin, &made), "sga_cloud_transform");
+    return std::make_shared<PointCloud>(made, ctx);
+  }
+
   size_t size() const {
     size_t n = 0;
     sga_cloud_size(h, &n);
@@ -704,6 +712,23 @@ inline void insert_batch(sga_context* ctx, const std::vector<GaussianVoxelMap::P
     if (!Ts.empty()) T16.insert(T16.end(), Ts[k].data(), Ts[k].data() + 16);
   }
   check(sga_voxelmap_insert_batch(ctx, ms.data(), cs.data(), Ts.empty() ? nullptr : T16.data(), ms.size()), "sga_voxelmap_insert_batch");
+}
+
+/// sga_cloud_merge: the clouds posed by Ts (empty: identities) joined into one cloud — clouds[0]'s points, then clouds[1]'s, ... — by one
+/// table copy and one launch whatever their number: the last K keyframes at their estimated poses as one registration target.  Normals
+/// and covariances ride along rotated, each kept only if every non-empty member has it.  origin: the output's device-frame origin (NULL:
+/// chosen by the library from the bounding box of the posed points, which costs one host wait).
+inline PointCloud::Ptr merge_clouds(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds, const std::vector<Isometry3d>& Ts = {}, const double* origin = nullptr) {
+  if (!Ts.empty() && Ts.size() != clouds.size()) throw std::runtime_error("merge_clouds: as many poses as clouds");
+  std::vector<const sga_cloud*> cs;
+  std::vector<double> T16;
+  for (size_t k = 0; k < clouds.size(); k++) {
+    cs.push_back(clouds[k]->h);
+    if (!Ts.empty()) T16.insert(T16.end(), Ts[k].data(), Ts[k].data() + 16);
+  }
+  sga_cloud* made = nullptr;
+  check(sga_cloud_merge(ctx, cs.data(), Ts.empty() ? nullptr : T16.data(), cs.size(), origin, &made), "sga_cloud_merge");
+  return std::make_shared<PointCloud>(made, ctx);
 }
 
 /// The problems of create_problems: ordinary sga_problem handles (sga_linearize, sga_align_problem, sga_batch_create, ...), destroyed with the set

@@ -96,6 +96,12 @@ int sga_debug_problem_batch_plan(const sga_index* const* targets, const sga_clou
  * sort call (members that take the lone routine inside the call are not counted): a call of B chain members counts as many as a call of
  * one. */
 int sga_debug_problem_batch_launches(unsigned long long* launches);
+/* Launches enqueued so far, in this process, by sga_cloud_merge / sga_cloud_transform: per pass one table copy and one kernel, whatever
+ * the number of members (a second pass only when origin == NULL chooses an origin other than zero). */
+int sga_debug_cloud_merge_launches(unsigned long long* launches);
+/* The bounding box of its finite records (device frame) that a cloud carries, when its producer knew it (uploads, sga_cloud_merge; the
+ * voxel grid sorts short keys with it): *has_box = 0 and zeros when it carries none. */
+int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]);
 /* Sets the launch epoch of the context's voxel-grid calls (the tag of ds_segments_kernel's status words; the next call uses epoch + 1, and
  * a call that finds 2^30 - 1 clears the words and starts again at 1) so that a test reaches the wrap-around a service meets after 2^30
  * calls.  Forwards only: an epoch below the current one, or above 2^30 - 1, is refused (words of earlier launches would read as current). */

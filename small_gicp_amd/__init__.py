@@ -24,6 +24,7 @@ from .api import (  # noqa: F401
     align_batch,
     build_gaussian_voxelmaps,
     build_kdtrees,
+    cloud_merge_launches,
     create_problems,
     default_context,
     estimate_covariances,
@@ -41,6 +42,7 @@ from .api import (  # noqa: F401
     set_search_mode,
     set_warm_limit,
     make_setting,
+    merge_clouds,
     optimize,
     optimize_batch,
     pinned_copy,

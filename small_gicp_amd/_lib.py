@@ -95,6 +95,10 @@ SYMBOLS = [
     ("sga_index_origin", C.c_int, [_vp, _dp]),
     ("sga_choose_origin", None, [_dp, _dp, _dp]),
     ("sga_cloud_slice", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _pvp]),
+    ("sga_cloud_merge", C.c_int, [_vp, _pvp, _dp, C.c_size_t, _dp, _pvp]),
+    ("sga_cloud_transform", C.c_int, [_vp, _vp, _dp, _dp, _pvp]),
+    ("sga_debug_cloud_merge_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     ("sga_cloud_has", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -274,6 +274,10 @@ class PointCloud:
         check(load().sga_cloud_slice(self.ctx.h, self.h, int(first), int(count), C.byref(h)))
         return PointCloud(ctx=self.ctx, _handle=h)
 
+    def transformed(self, T, origin=None):
+        """A new cloud holding this one's points, normals and covariances posed by T (4x4; sga_cloud_transform): merge_clouds of one member."""
+        return merge_clouds([self], [T], origin)
+
     def empty(self):
         return self.size() == 0
 
@@ -284,6 +288,13 @@ class PointCloud:
         out = (C.c_int * 9)()
         check(load().sga_debug_voxelgrid_plan(self.h, float(leaf), out))
         return {"key_bytes": out[0], "bits": (out[1], out[2], out[3]), "total": out[4], "box": bool(out[5]), "sort": out[6], "tiles": out[7], "speculative": bool(out[8])}
+
+    def _box(self):
+        """Diagnostics (sga_debug_cloud_box): (lo (3,), hi (3,)) float32, the box of the finite records in the device frame that the cloud
+        carries, or None when it carries none."""
+        has, lo, hi = C.c_int(), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(load().sga_debug_cloud_box(self.h, C.byref(has), _fp(lo), _fp(hi)))
+        return (lo, hi) if has.value else None
 
     def _has(self):
         a, b = C.c_int(), C.c_int()
@@ -1544,6 +1555,34 @@ def _voxelmap_batch_plan(clouds, leaf_size):
     out = (C.c_int * 6)()
     check(load().sga_debug_voxelmap_batch_plan(hs, len(clouds), float(leaf_size), out))
     return {"forest": out[0], "lone": out[1], "empty": out[2], "member_bits": out[3], "end_bit": out[4], "points": out[5]}
+
+
+def merge_clouds(clouds, Ts=None, origin=None, ctx=None):
+    """sga_cloud_merge: the clouds posed by Ts (4x4 each; None: identities) joined into one PointCloud — the last K keyframes at their
+    estimated poses as one registration target — by one table copy and one launch, whatever their number.  The output holds clouds[0]'s
+    points, then clouds[1]'s, ...; a record r of a member with pose (R, t) and origin o_m becomes fl32(R r + ((R o_m + t) - o)), evaluated
+    in double; normals R n and covariances R C R^T ride along, each kept only if every non-empty member has it.  origin: the output's
+    device-frame origin o (None: chosen by the library from the bounding box of the posed points, which costs the one host wait).  The
+    members may belong to several contexts of one device (another device: the library refuses); ctx: the context the merge runs on
+    (default: the first cloud's)."""
+    clouds = list(clouds)
+    for c in clouds:
+        if not isinstance(c, PointCloud):
+            raise TypeError("merge_clouds takes PointCloud objects")
+    ctx = ctx or (clouds[0].ctx if clouds else default_context())
+    hs = (C.c_void_p * max(1, len(clouds)))(*[c.h.value for c in clouds])
+    t16 = None if Ts is None else _T16s(Ts, len(clouds))
+    o = None if origin is None else np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    h = C.c_void_p()
+    check(load().sga_cloud_merge(ctx.h, hs, None if t16 is None else _dp(t16), len(clouds), _dp(o), C.byref(h)))
+    return PointCloud(ctx=ctx, _handle=h)
+
+
+def cloud_merge_launches():
+    """Diagnostics (sga_debug_cloud_merge_launches): table copies and kernels enqueued so far by merge_clouds / PointCloud.transformed."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_merge_launches(C.byref(v)))
+    return v.value
 
 
 def voxelmap_batch_launches():

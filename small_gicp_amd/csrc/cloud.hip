@@ -1,7 +1,8 @@
 // Clouds: every sga_cloud_* entry point.  Host arrays (pageable through the context's pinned staging ring, pinned ones read in place)
 // and device arrays of the caller's become the 16 / 16 / 32-byte device records through ONE pack kernel, and
-// leave through ONE unpack kernel; slices, downloads and the small getters.
+// leave through ONE unpack kernel; slices, downloads and the small getters; posed clouds joined into one.
 #include "device_io.hpp"
+#include "forest.hpp"
 #include "notes.hpp"
 
 #include <cmath>
@@ -218,6 +219,68 @@ __global__ void slice_cloud_kernel(const float4* __restrict__ pts, const float4*
   if (cov) ocov[i] = cov[first + i];
 }
 
+// One member of a merge (read with scalar loads): its records, its pose with the offset between the two device
+// frames folded in — t = (R o_m + t_m) - o, formed on the host in double — and its stretch of the output.
+struct MergeMember {
+  const float4* pts;
+  const float4* nrm;  // read only when the output keeps the attribute
+  const Cov8* cov;
+  Pose12 T;
+  uint32_t n, off;
+};
+static_assert(sizeof(MergeMember) % 8 == 0, "the table is copied in 8-byte words");
+
+// Posed clouds -> one cloud: workgroup b moves 256 points of the member m with prefix[m] <= b < prefix[m + 1] to their place in the
+// concatenation.  Points R r + t, normals R n and covariances R C R^T are evaluated in double from the fp32 records, with the insert
+// kernels' expressions (voxelmap.hip: fvm_update_kernel, ivm_update_kernel), and rounded once; w is the point's index in the output.  box != null: the
+// bounding box of the posed points that are finite, taken BEFORE the rounding (which is monotone: the rounded box bounds the records
+// exactly), leaves as a note in payload words 1..6 (box64_reduce_publish).
+__global__ __launch_bounds__(kIoBlock) void merge_cloud_kernel(const MergeMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov,
+                                                               unsigned long long* __restrict__ box, unsigned long long* __restrict__ note_slot, unsigned long long seq) {
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const MergeMember& g = *uniform_const(members + m);
+  const uint32_t i = (blockIdx.x - prefix[m]) * static_cast<uint32_t>(kIoBlock) + threadIdx.x;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  if (i < g.n) {
+    const Pose12& T = g.T;
+    const uint32_t j = g.off + i;
+    const float4 p = g.pts[i];
+    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
+    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
+    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    opts[j] = make_float4(static_cast<float>(x), static_cast<float>(y), static_cast<float>(z), __uint_as_float(j));
+    if (x - x == 0.0 && y - y == 0.0 && z - z == 0.0) lo[0] = hi[0] = x, lo[1] = hi[1] = y, lo[2] = hi[2] = z;  // a non-finite point stays out of the box
+    if (onrm != nullptr) {
+      const float4 q = g.nrm[i];
+      double N[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) N[a] = T.r[3 * a] * q.x + T.r[3 * a + 1] * q.y + T.r[3 * a + 2] * q.z;
+      onrm[j] = make_float4(static_cast<float>(N[0]), static_cast<float>(N[1]), static_cast<float>(N[2]), 0.f);
+    }
+    if (ocov != nullptr) {
+      const float4* cin = reinterpret_cast<const float4*>(g.cov + i);
+      const float4 c0 = cin[0], c1 = cin[1];  // xx xy xz yy | yz zz 0 0
+      const double Cm[3][3] = {{c0.x, c0.y, c0.z}, {c0.y, c0.w, c1.x}, {c0.z, c1.x, c1.y}};
+      double RC[3][3], C6[6];
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++) C6[k++] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+      float4* cout = reinterpret_cast<float4*>(ocov + j);
+      cout[0] = make_float4(static_cast<float>(C6[0]), static_cast<float>(C6[1]), static_cast<float>(C6[2]), static_cast<float>(C6[3]));
+      cout[1] = make_float4(static_cast<float>(C6[4]), static_cast<float>(C6[5]), 0.f, 0.f);
+    }
+  }
+  if (box == nullptr) return;  // (uniform)
+  box64_reduce_publish(lo, hi, box, note_slot, seq);
+}
+
 namespace {
 
 // the 64-bit box accumulator, made on first use
@@ -317,6 +380,134 @@ void cloud_set_box(sga_cloud* c, const double lo[3], const double hi[3], bool re
     c->box_lo[k] = outward ? std::nextafterf(l, -INFINITY) : l;
     c->box_hi[k] = outward ? std::nextafterf(h, INFINITY) : h;
   }
+}
+
+// ---- sga_cloud_merge -----------------------------------------------------------------------------------------
+std::atomic<unsigned long long> g_merge_launches{0};
+constexpr size_t kMergeMaxMembers = 1u << 15;
+
+// Member m's pose for an output frame at `o`: R as given (column-major T16, null: the identity), t = c - o with c = R o_m + t_m the
+// member's origin in the caller's frame.  Every product and sum is rounded on its own, in the order written (no contraction): the
+// offset is a function of the inputs alone, and c - o — the form of pose_to_device — is formed ONCE here, so a merge far from the origin
+// cancels nothing on the device.
+Pose12 merge_pose(const double* T16, const double o_m[3], const double o[3]) {
+#pragma clang fp contract(off)
+  Pose12 T;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) T.r[3 * r + c] = T16 ? T16[4 * c + r] : (r == c ? 1.0 : 0.0);
+    const double t = T16 ? T16[12 + r] : 0.0;
+    const double c = ((T.r[3 * r] * o_m[0] + T.r[3 * r + 1] * o_m[1]) + T.r[3 * r + 2] * o_m[2]) + t;
+    T.t[r] = c - o[r];
+  }
+  return T;
+}
+
+// One pass over the non-empty members `live`: the table ([members][prefix of the grid: live + 1 words of 32 bits], written in the
+// staging ring, one copy command) and ONE launch over the concatenation.  want_box: the box of the finite posed points, relative to o,
+// arrives as a note the call waits for (lo > hi: no finite point).
+int merge_pass(sga_context* ctx, const sga_cloud* const* clouds, const double* T, const std::vector<size_t>& live, const double o[3], sga_cloud* c, bool want_box, DevBuf<unsigned long long>& table, double lo[3], double hi[3]) {
+  const size_t count = live.size();
+  std::vector<MergeMember> members(count);
+  std::vector<uint32_t> prefix(count + 1, 0u);
+  uint32_t off = 0;
+  for (size_t j = 0; j < count; j++) {
+    const size_t k = live[j];
+    MergeMember& g = members[j];
+    std::memset(&g, 0, sizeof(g));
+    g.pts = clouds[k]->pts.p;
+    g.nrm = c->has_normals ? clouds[k]->nrm.p : nullptr;
+    g.cov = c->has_covs ? clouds[k]->cov.p : nullptr;
+    g.T = merge_pose(T ? T + 16 * k : nullptr, clouds[k]->origin, o);
+    g.n = static_cast<uint32_t>(clouds[k]->n);
+    g.off = off;
+    off += g.n;
+    prefix[j + 1] = prefix[j] + (g.n + kIoBlock - 1u) / kIoBlock;
+  }
+  const size_t member_words = count * (sizeof(MergeMember) / 8), words = member_words + (prefix.size() + 1) / 2;
+  SGA_TRY(table.alloc(words));
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  host[words - 1] = 0ull;
+  std::memcpy(host, members.data(), member_words * 8);
+  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+  g_merge_launches.fetch_add(1, std::memory_order_relaxed);
+  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  SGA_TRY(stage_release(ctx, slot));
+  unsigned long long* note = nullptr;
+  const unsigned long long seq = want_box ? note_begin(ctx, &note) : 0ull;
+  g_merge_launches.fetch_add(1, std::memory_order_relaxed);
+  hipLaunchKernelGGL(merge_cloud_kernel, dim3(prefix[count]), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<const MergeMember*>(table.p), reinterpret_cast<const uint32_t*>(table.p + member_words), static_cast<int>(count), c->pts.p,
+                     c->nrm.p, c->cov.p, want_box ? ctx->d_box64.p : nullptr, note, seq);
+  SGA_HIP(hipGetLastError());
+  if (want_box) {
+    unsigned long long payload[kNoteWords - 1];
+    SGA_TRY(note_wait(ctx, seq, payload));
+    for (int k = 0; k < 3; k++) lo[k] = box_dec64(payload[k]), hi[k] = box_dec64(payload[3 + k]);
+  }
+  return SGA_OK;
+}
+
+int cloud_merge(sga_context* ctx, const sga_cloud* const* clouds, const double* T, size_t count, const double origin[3], sga_cloud** out) {
+  if (out) *out = nullptr;  // on any failure *out is NULL
+  if (!ctx || !out || (count > 0 && !clouds)) return fail(SGA_ERR_INVALID, "null argument");
+  if (count > kMergeMaxMembers) return fail(SGA_ERR_INVALID, "too many members (%zu; limit %zu)", count, kMergeMaxMembers);
+  for (size_t k = 0; k < count; k++)
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "null argument: clouds[%zu] is NULL", k);
+  for (size_t k = 0; T != nullptr && k < count; k++)
+    for (int e = 0; e < 16; e++)
+      if (!(T[16 * k + e] - T[16 * k + e] == 0.0)) return fail(SGA_ERR_INVALID, "pose %zu has a non-finite entry", k);
+  for (int k = 0; origin != nullptr && k < 3; k++)
+    if (!(origin[k] - origin[k] == 0.0)) return fail(SGA_ERR_INVALID, "origin has a non-finite entry");
+  // ---- (from here on the handles are read)
+  size_t total = 0;
+  std::vector<size_t> live;  // empty members take no workgroups
+  bool normals = true, covs = true;  // an attribute is kept when every non-empty member has it
+  for (size_t k = 0; k < count; k++) {
+    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
+    if (clouds[k]->n == 0) continue;
+    live.push_back(k);
+    total += clouds[k]->n;
+    normals = normals && clouds[k]->has_normals;
+    covs = covs && clouds[k]->has_covs;
+  }
+  if (total >= (1ull << 31)) return fail(SGA_ERR_INVALID, "merged cloud too large (%zu points; limit 2^31-1)", total);
+  if (total > 0) SGA_HIP(hipSetDevice(ctx->device));  // (no member, or empty members only: no attributes, no device work)
+  StreamScope stream_scope(ctx->stream);
+  std::unique_ptr<sga_cloud> c(new sga_cloud);
+  c->device = ctx->device;
+  c->n = total;
+  for (int k = 0; k < 3; k++) c->origin[k] = origin ? origin[k] : 0.0;
+  if (total == 0) {
+    *out = c.release();
+    return SGA_OK;
+  }
+  c->has_normals = normals;
+  c->has_covs = covs;
+  SGA_TRY(c->pts.alloc(total));
+  if (normals) SGA_TRY(c->nrm.alloc(total));
+  if (covs) SGA_TRY(c->cov.alloc(total));
+  // The box of the finite posed points.  The origin is chosen from it (origin == NULL: the one host wait the data forces); a blocking
+  // context, which waits anyway, also keeps it with the cloud.  A stream-ordered context with the origin given waits for nothing and its
+  // cloud carries no box — sga_cloud_create_device's contract.
+  const bool want_box = origin == nullptr || !ctx->stream_ordered;
+  if (want_box) SGA_TRY(ensure_box64(ctx));
+  for (size_t k : live) SGA_TRY(wait_ready(ctx, clouds[k]->ready));  // made by another context in stream-ordered mode (common.hpp: Ready)
+  DevBuf<unsigned long long> table, table2;  // live to the end of the call (then: the stream's free list)
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  // origin == NULL: the first pass writes the records for the origin zero, so its box IS the box of the posed points in the caller's
+  // frame — the same numbers whatever follows.  An origin other than zero (a submap far from the origin: rare) takes a second pass, which
+  // starts from the members' records again and brings the box of its own records.
+  SGA_TRY(merge_pass(ctx, clouds, T, live, c->origin, c.get(), want_box, table, lo, hi));
+  if (origin == nullptr) {
+    choose_origin(lo, hi, c->origin);
+    if (!origin_is_zero(c->origin)) SGA_TRY(merge_pass(ctx, clouds, T, live, c->origin, c.get(), true, table2, lo, hi));
+  }
+  // (a note has shown that the last launch is over; without one the context is stream-ordered)
+  cloud_set_box(c.get(), lo, hi, true, false);  // the rounding is monotone: the rounded box of the unrounded records is the box of the records
+  SGA_TRY(mark_ready(ctx, c->ready));
+  *out = c.release();
+  return SGA_OK;
 }
 
 }  // namespace
@@ -632,6 +823,24 @@ int sga_cloud_slice(sga_context* ctx, const sga_cloud* cloud, size_t first, size
     }
   }
   *out = c;
+  return SGA_OK;
+}
+
+// Posed clouds joined into one (the host loop of src/test/registration_test.cpp:84 over points, normals and covs, on the device)
+int sga_cloud_merge(sga_context* ctx, const sga_cloud* const* clouds, const double* T, size_t count, const double origin[3], sga_cloud** out) { return cloud_merge(ctx, clouds, T, count, origin, out); }
+
+int sga_cloud_transform(sga_context* ctx, const sga_cloud* cloud, const double T[16], const double origin[3], sga_cloud** out) { return cloud_merge(ctx, &cloud, T, 1, origin, out); }
+
+int sga_debug_cloud_merge_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_merge_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
+
+int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]) {
+  if (!cloud || !has_box || !lo || !hi) return fail(SGA_ERR_INVALID, "null argument");
+  *has_box = cloud->has_box ? 1 : 0;
+  for (int k = 0; k < 3; k++) lo[k] = cloud->has_box ? cloud->box_lo[k] : 0.f, hi[k] = cloud->has_box ? cloud->box_hi[k] : 0.f;
   return SGA_OK;
 }
 

@@ -163,6 +163,107 @@ def run_synthetic_model(num_frames=20, **kw):
     }
 
 
+class SubmapOdometry:
+    """Scan-to-SUBMAP GICP odometry against an exact kd-tree: the target of a scan is ONE cloud made of the last `window` preprocessed
+    scans at their estimated world poses (api.merge_clouds: one launch, the covariances ride along rotated, nothing is estimated twice)
+    and the KdTree over it; the scan is registered from the previous pose, as ModelOdometry does.  Per scan the preprocessing is
+    OnlineOdometry's.  The driver names the submap's device-frame origin itself — the library's rule applied to the previous position —
+    so the stream-ordered context never waits for a bounding box."""
+
+    def __init__(self, window=5, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, record=False):
+        if window < 1:
+            raise ValueError("window must be at least 1")
+        self.window = window
+        self.res = downsampling_resolution
+        self.k = num_neighbors
+        self.setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
+        self._own_ctx = ctx is None
+        self.ctx = ctx or api.Context(0)
+        self._prev_mode = self.ctx.set_stream_ordered(True)
+        self.keyframes = []  # (cloud, T_world) of the last `window` scans
+        self.T_world = np.eye(4)
+        self.reg_ms, self.total_ms, self.iterations = [], [], []
+        self.record = record
+        self.records = []  # record=True: (submap cloud, scan cloud, initial pose, result pose, iterations) per registered scan
+
+    def close(self):
+        """Give a borrowed context its previous mode back (synchronises it)."""
+        if self.ctx is not None and not self._own_ctx:
+            self.ctx.set_stream_ordered(self._prev_mode)
+        self.keyframes = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _submap_origin(self):
+        p = np.ascontiguousarray(self.T_world[:3, 3], dtype=np.float64)
+        o = np.zeros(3)
+        api.load().sga_choose_origin(api._dp(p), api._dp(p), api._dp(o))
+        return o
+
+    def estimate(self, points):
+        """points: (N,3|4) float32 in the sensor frame. Returns T_world_sensor of this scan."""
+        t0 = time.perf_counter()
+        raw = api.PointCloud(points, ctx=self.ctx)
+        cloud = api.voxelgrid_sampling(raw, self.res)
+        self.ctx.synchronize()
+        t1 = time.perf_counter()
+        tree = api.KdTree(cloud)
+        api.estimate_covariances(cloud, tree, self.k)
+        if self.keyframes:
+            submap = api.merge_clouds([c for c, _ in self.keyframes], [T for _, T in self.keyframes], origin=self._submap_origin(), ctx=self.ctx)
+            target = api.KdTree(submap)
+            init = self.T_world.copy()
+            res = api.Problem(target, tree, init).align(self.setting, init)
+            self.T_world = res.T_target_source
+            self.iterations.append(res.iterations + 1)
+            if self.record:
+                self.records.append((submap, cloud, init, self.T_world.copy(), res.iterations + 1))
+        self.ctx.synchronize()
+        t2 = time.perf_counter()
+        self.keyframes = (self.keyframes + [(cloud, self.T_world.copy())])[-self.window :]
+        self.reg_ms.append(1e3 * (t2 - t1))
+        self.total_ms.append(1e3 * (t2 - t0))
+        return self.T_world.copy()
+
+
+def run_synthetic_submap(num_frames=20, window=5, **kw):
+    """SubmapOdometry over the frozen synthetic sequence (keyword arguments go to SubmapOdometry); absolute trajectory error against the
+    generator's ground truth.  The return value has run_synthetic_model's shape (num_points: the last submap's size, in place of num_voxels)."""
+    from . import synthetic
+
+    odom = SubmapOdometry(window=window, **kw)
+    est, gt = [], []
+    T0 = None
+    for f in range(num_frames):
+        pts, Tws = synthetic.kitti_like_scan(f)
+        if T0 is None:
+            T0 = Tws
+        est.append(odom.estimate(pts))
+        gt.append(np.linalg.inv(T0) @ Tws)
+    ate = [float(np.linalg.norm(e[:3, 3] - g[:3, 3])) for e, g in zip(est, gt)]
+    skip = 2 if num_frames > 4 else 1  # (as run_synthetic: the first frames carry first-touch allocations)
+    out = {
+        "frames": num_frames,
+        "window": window,
+        "registration_ms_per_scan": float(np.mean(odom.reg_ms[skip:])) if len(odom.reg_ms) > skip else float("nan"),
+        "total_ms_per_scan": float(np.mean(odom.total_ms[skip:])) if len(odom.total_ms) > skip else float("nan"),
+        "total_ms_per_scan_median": float(np.median(odom.total_ms[skip:])) if len(odom.total_ms) > skip else float("nan"),
+        "mean_iterations": float(np.mean(odom.iterations)) if odom.iterations else 0.0,
+        "ate_trans_m_max": max(ate),
+        "num_points": sum(c.size() for c, _ in odom.keyframes),
+        "estimated": est,
+        "ground_truth": gt,
+    }
+    if odom.record:
+        out["records"] = odom.records
+    odom.close()
+    return out
+
+
 class PipelinedOdometry:
     """The same scan-to-scan odometry as a flow of stages over HIP streams (one context each) — the HIP-stream analogue of the reference's
     TBB flow graph (src/benchmark/odometry_benchmark_small_gicp_tbb_flow.cpp:55-141):
