@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "forest.hpp"
 #include "notes.hpp"
+#include "voxel_steps.hpp"
 
 namespace sga {
 int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
@@ -204,14 +205,14 @@ int voxelmaps_batch_check(const sga_cloud* const* clouds, size_t count, double l
 }
 
 // sga_index_build_gaussian_voxelmap for every member.  The members of the plan's chain share the launches
-// (index_build.hip: vox_forest_enqueue_runs, vox_forest_enqueue_finalize) and ONE host wait, for their voxel counts and overflow words;
+// (voxelmap_build.hip: vox_forest_enqueue_runs, vox_forest_enqueue_finalize) and ONE host wait, for their voxel counts and overflow words;
 // behind it every index is allocated at its exact size.  Members the plan leaves out, and members whose key overflowed, go through the
 // lone routine afterwards.
 int voxelmaps_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, std::vector<std::unique_ptr<sga_index>>& made) {
   made.resize(count);
   for (size_t k = 0; k < count; k++) SGA_TRY(wait_ready(ctx, clouds[k]->ready));
   const VoxForestPlan plan = vox_forest_plan(clouds, count);
-  VoxForestChain ch;
+  VoxelForestChain ch;
   std::vector<size_t> lone = plan.lone;
   std::vector<VoxMember> members;  // of the stage behind the wait
   std::vector<size_t> built;       // their positions in the call
@@ -319,7 +320,7 @@ int insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* cons
     SGA_TRY(wait_ready(ctx, maps[k]->ready));
   }
   const IvmForestPlan plan = ivm_forest_plan(maps, clouds, count);
-  IvmForestChain ch;
+  VoxelForestChain ch;
   std::vector<size_t> lone = plan.lone;
   std::vector<size_t> own;  // the maps whose counter, sweep and export are this call's: the chain's members that did not overflow, and the empty ones
   if (!plan.forest.empty()) {

@@ -3,6 +3,7 @@
 // leave through ONE unpack kernel; slices, downloads and the small getters; posed clouds joined into one.
 #include "device_io.hpp"
 #include "forest.hpp"
+#include "voxel_steps.hpp"
 #include "notes.hpp"
 
 #include <cmath>
@@ -425,15 +426,12 @@ int merge_pass(sga_context* ctx, const sga_cloud* const* clouds, const double* T
   }
   const size_t member_words = count * (sizeof(MergeMember) / 8), words = member_words + (prefix.size() + 1) / 2;
   SGA_TRY(table.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  host[words - 1] = 0ull;
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-  g_merge_launches.fetch_add(1, std::memory_order_relaxed);
-  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
+  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
+    host[words - 1] = 0ull;
+    std::memcpy(host, members.data(), member_words * 8);
+    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+    g_merge_launches.fetch_add(1, std::memory_order_relaxed);
+  }));
   unsigned long long* note = nullptr;
   const unsigned long long seq = want_box ? note_begin(ctx, &note) : 0ull;
   g_merge_launches.fetch_add(1, std::memory_order_relaxed);

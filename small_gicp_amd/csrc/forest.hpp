@@ -77,6 +77,18 @@ __device__ __forceinline__ int forest_member_of(const uint32_t* prefix, int coun
   return lo;
 }
 
+// A call's table on its way to the device: a slot of the context's pinned staging ring is acquired, `fill` writes the `words` 8-byte
+// words of the table into it, ONE copy command carries them to `dst`, and the slot is released behind the copy.
+template <typename Fill>
+int upload_table(sga_context* ctx, unsigned long long* dst, size_t words, Fill&& fill) {
+  sga_context::StageSlot* slot = nullptr;
+  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
+  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  fill(host);
+  SGA_HIP(hipMemcpyAsync(dst, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+  return stage_release(ctx, slot);
+}
+
 // index_build.hip: the build of all `trees` (every field but spacing_acc filled in by the caller) enqueued on the context's stream;
 // `table` (device memory: the trees, the launches' member lists, the accumulators) must live until the kernels have run
 int forest_build(sga_context* ctx, std::vector<ForestTree>& trees, unsigned long long* box_seq_word, unsigned long long box_seq, DevBuf<unsigned long long>& table);
@@ -109,102 +121,47 @@ GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, do
 // member j (room for the member's point count); member j's run count arrives in word 4 j + 5 of the context's box block, then `seq` in word 0
 int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq);
 void grid_forest_count_launch();  // batch_preprocess.hip: every kernel and sort of grid_forest_enqueue (sga_debug_voxelgrid_batch_launches)
-// ---- the voxel-map forest: sga_index_build_gaussian_voxelmap for B clouds in one chain of launches -----------
-// The members' points are concatenated (member m at [off, off + n)) and sorted ONCE, stably, under the key
-//   (m << 49) | (cz & 0xffff) << 32 | (cy & 0xffff) << 16 | (cx & 0xffff);   a dropped point: (m << 49) | (2^49 - 1), last of its member
-// — the voxel coordinates being voxel_keys_kernel's.  The key separates the voxels of a member exactly when every axis of the member spans
-// fewer than 65536 voxels; the keys launch reduces the range, the runs stage raises the member's overflow word beside its voxel count,
-// and the host rebuilds such a member by the lone routine.
+// ---- the voxel forests (DESIGN.md sections 3.14 and 3.15): sga_index_build_gaussian_voxelmap for B clouds, sga_voxelmap_insert for B
+// (Gaussian map, cloud, pose) triples, each in one chain of launches.  The sort key, the tables and the stages: voxel_steps.hpp.
 constexpr size_t kVoxForestMaxMember = 262144;    // points of a member of the chain (2^18: a run's first point takes 18 bits of the rank key)
 constexpr size_t kVoxForestMaxMembers = 1u << 15;  // the member number's bits above bit 49
 constexpr int kVoxKeyMemberShift = 49, kVoxRankMemberShift = 18;
+constexpr uint32_t kForestMaxPoints = 1024 * 32;  // = kSplitMaxPoints (index_build.hip): the clouds the split kernel holds whole
+// What the host decides about a batched call before it launches anything.
 struct VoxForestPlan {
   int member_bits = 0;  // bits_for(members of the chain)
   int end_bit = 0;      // the sort's: 49 + member_bits; 0: no member in the chain
   size_t points = 0;    // the concatenation
   std::vector<size_t> forest, lone, empty;  // positions of the members in the chain / through the lone routine / without points
+  // member k with n >= 1 points joins the chain — members taken in the call's order — while the chain has room: at most kVoxForestMaxMember
+  // points, the concatenation within kGridForestMaxPoints and the chain within kVoxForestMaxMembers members
+  bool join(size_t k, size_t n) {
+    if (n > kVoxForestMaxMember || points + n > kGridForestMaxPoints || forest.size() >= kVoxForestMaxMembers) return false;
+    forest.push_back(k), points += n;
+    return true;
+  }
+  void close() {
+    if (forest.empty()) return;
+    while ((1ull << member_bits) < forest.size()) member_bits++;
+    end_bit = kVoxKeyMemberShift + member_bits;
+  }
 };
-// What the host decides about a batched voxel-map call before it launches anything: a member joins the chain — members taken in the
-// call's order — with 1 .. kVoxForestMaxMember points while the concatenation stays within kGridForestMaxPoints and the chain within
-// kVoxForestMaxMembers members; every other non-empty member goes through the lone routine.
+using IvmForestPlan = VoxForestPlan;
+// the build: every non-empty member that finds no room goes through the lone routine
 inline VoxForestPlan vox_forest_plan(const sga_cloud* const* clouds, size_t count) {
   VoxForestPlan P;
   for (size_t k = 0; k < count; k++) {
     const size_t n = clouds[k]->n;
     if (n == 0)
       P.empty.push_back(k);
-    else if (n <= kVoxForestMaxMember && P.points + n <= kGridForestMaxPoints && P.forest.size() < kVoxForestMaxMembers)
-      P.forest.push_back(k), P.points += n;
-    else
+    else if (!P.join(k, n))
       P.lone.push_back(k);
   }
-  if (!P.forest.empty()) {
-    while ((1ull << P.member_bits) < P.forest.size()) P.member_bits++;
-    P.end_bit = kVoxKeyMemberShift + P.member_bits;
-  }
+  P.close();
   return P;
 }
-
-// One member of the chain (read with scalar loads).  The first block is what voxel_keys_kernel receives, used by the stage before the
-// host's wait; the second is what voxel_finalize_kernel receives, known once the host has the voxel counts and filled in for the stage
-// behind the wait (a second table: the members that did not overflow, and the empty members, whose tables are cleared with the others').
-struct VoxMember {
-  const float4* pts;
-  const Cov8* cov;
-  double ox, oy, oz;
-  int* range;                      // {min x, y, z, max x, y, z} of the voxel coordinates: in the call's table, set up with it
-  unsigned long long* count_slot;  // word 1 receives the member's voxel count, word 2 its overflow word (pinned, device-mapped: the box block)
-  uint32_t n, off;                 // the member's stretch of the concatenation
-  float4* means;
-  Cov8* mcov;
-  int* coords;
-  uint32_t* counts;
-  unsigned long long* hkeys;
-  uint32_t* hvals;
-  uint32_t hmask, nvox;
-  uint32_t run0, pad;              // the member's first run among the runs of the whole chain
-};
-// the chain's scratch: lives from the first stage to the end of the call (then: the stream's free list)
-struct VoxForestChain {
-  DevBuf<unsigned long long> keys, keys_sorted, rank_keys, rank_keys_sorted, table1, table2;
-  DevBuf<uint32_t> vals, order, flags, seg_id, seg_start, seg_ids, seg_by_rank;
-  size_t points = 0;
-  int member_bits = 0;
-};
-// index_build.hip: keys, sort, runs of the plan's chain enqueued on the context's stream; member j's voxel count arrives in word 4 j + 5 of
-// the context's box block, its overflow word in word 4 j + 6, then `seq` in word 0
-int vox_forest_enqueue_runs(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const VoxForestPlan& plan, unsigned long long seq, VoxForestChain& ch);
-// the ranks' sort over `runs` runs, the clearing of every member's hash table and the finalize launch (members: second block filled in)
-int vox_forest_enqueue_finalize(sga_context* ctx, const std::vector<VoxMember>& members, size_t runs, double leaf, VoxForestChain& ch);
-void vox_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the two (sga_debug_voxelmap_batch_launches)
-constexpr uint32_t kForestMaxPoints = 1024 * 32;  // = kSplitMaxPoints (index_build.hip): the clouds the split kernel holds whole
-
-// ---- the insert forest: sga_voxelmap_insert for B (Gaussian map, cloud, pose) triples in one chain of launches --
-// The key, the sort, the runs and the rank key are section 3.14's; the voxel coordinates are ivm_keys_kernel's (the posed point in double).
-struct Pose12 {
-  double r[9];  // row-major rotation
-  double t[3];
-};
-// the pose sga_voxelmap_insert hands its kernels: T16 column-major (null: the identity), the cloud's device-frame origin folded in (R o_c + t)
-inline Pose12 insert_pose(const double* T16, const double origin[3]) {
-  Pose12 T;
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) T.r[3 * r + c] = T16 ? T16[4 * c + r] : (r == c ? 1.0 : 0.0);
-    T.t[r] = T16 ? T16[12 + r] : 0.0;
-  }
-  for (int r = 0; r < 3; r++) T.t[r] += T.r[3 * r] * origin[0] + T.r[3 * r + 1] * origin[1] + T.r[3 * r + 2] * origin[2];
-  return T;
-}
-// What the host decides about a batched insert before it launches anything.  A member joins the chain — members taken in the call's
-// order — when its map is a Gaussian incremental map and its cloud has 1 .. kVoxForestMaxMember points, while the concatenation stays
-// within kGridForestMaxPoints and the chain within kVoxForestMaxMembers members.  A Gaussian map with an empty cloud takes no part in
-// the chain's kernels (its counter, its sweep and its export are the call's).  Flat maps and larger clouds go through the lone routine.
-struct IvmForestPlan {
-  int member_bits = 0;  // bits_for(members of the chain)
-  int end_bit = 0;      // the sort's: 49 + member_bits; 0: no member in the chain
-  size_t points = 0;    // the concatenation
-  std::vector<size_t> forest, lone, empty;
-};
+// the insert: a member joins when its map is a Gaussian incremental map.  A Gaussian map with an empty cloud takes no part in the chain's
+// kernels (its counter, its sweep and its export are the call's).  Flat maps and the clouds that find no room go through the lone routine.
 inline IvmForestPlan ivm_forest_plan(const sga_index* const* maps, const sga_cloud* const* clouds, size_t count) {
   IvmForestPlan P;
   for (size_t k = 0; k < count; k++) {
@@ -213,73 +170,12 @@ inline IvmForestPlan ivm_forest_plan(const sga_index* const* maps, const sga_clo
       P.lone.push_back(k);
     else if (n == 0)
       P.empty.push_back(k);
-    else if (n <= kVoxForestMaxMember && P.points + n <= kGridForestMaxPoints && P.forest.size() < kVoxForestMaxMembers)
-      P.forest.push_back(k), P.points += n;
-    else
+    else if (!P.join(k, n))
       P.lone.push_back(k);
   }
-  if (!P.forest.empty()) {
-    while ((1ull << P.member_bits) < P.forest.size()) P.member_bits++;
-    P.end_bit = kVoxKeyMemberShift + P.member_bits;
-  }
+  P.close();
   return P;
 }
-
-// One member of the chain before the host's wait (table 1, read with scalar loads): what ivm_keys_kernel and ivm_lookup_kernel receive
-struct IvmMember {
-  const float4* pts;
-  Pose12 T;
-  double inv_leaf;
-  const unsigned long long* hkeys;  // the map's table as it is before the insert
-  const uint32_t* hvals;
-  int* range;                       // {min x, y, z, max x, y, z} of the voxel coordinates: in the call's table, set up with it
-  unsigned* counters;               // {new voxels, positions of the member the starts launch has finished}: in the call's table, zero at the start
-  unsigned long long* count_slot;   // word 1: runs, word 2: overflow word, word 3: new voxels (pinned, device-mapped: the box block)
-  uint32_t hmask;                   // 0: the map holds no voxel
-  uint32_t n, off, pad;             // the member's stretch of the concatenation
-};
-// One member behind the wait (table 2): what ivm_assign_kernel and ivm_update_kernel receive, the map's arrays after growth
-struct IvmUpdate {
-  const float4* pts;
-  const Cov8* cov;
-  Pose12 T;
-  double inv_leaf;
-  double* mean64;
-  double* cov64;
-  uint32_t* counts;
-  uint32_t* lru;
-  int* coords;
-  unsigned long long* hkeys;
-  uint32_t* hvals;
-  uint32_t hmask, n_old, lru_counter;
-  uint32_t nseg, n_new;    // the member's runs; the new voxels among them
-  uint32_t new0, old0;     // position of the member's first new / first existing run in the ranks' order
-  uint32_t end;            // end of the member's stretch of the concatenation
-};
-// One map of the export launch (table 3): ivm_export_kernel's arguments
-struct IvmExport {
-  const double* mean64;
-  const double* cov64;
-  float4* means;
-  Cov8* mcov;
-  double ox, oy, oz;
-  uint32_t n, pad;
-};
-struct IvmForestChain {
-  DevBuf<unsigned long long> keys, keys_sorted, rank_keys, rank_keys_sorted, table1, table2, table3;
-  DevBuf<uint32_t> vals, order, flags, seg_id, seg_start, seg_vid, seg_ids, seg_by_rank;
-  int member_bits = 0;
-};
-// voxelmap.hip.  Keys, sort, heads, scan, starts + lookup of the plan's chain: member j's run count, overflow word and new-voxel count
-// arrive in words 4 j + 5 .. 4 j + 7 of the context's box block, then `seq` in word 0
-int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, IvmForestChain& ch);
-// the ranks' sort over `runs` runs (`total_new` of them new voxels) of `members_in_chain` members and the assign + update launch (members: the
-// ones that did not overflow)
-int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& members, size_t runs, uint32_t total_new, size_t members_in_chain, IvmForestChain& ch);
-int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& maps, IvmForestChain& ch);
-int ivm_reserve(sga_context* ctx, sga_index* idx, size_t n_total);  // the per-voxel arrays and the table for n_total voxels, under sga_voxelmap_insert's conditions
-int ivm_lru_sweep(sga_context* ctx, sga_index* idx);                // the sweep of sga_voxelmap_insert (incremental_voxelmap.hpp:76-88) when the map's counter says it is due
-void ivm_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the chain (sga_debug_voxelmap_insert_batch_launches)
 
 // ---- the problem forest: sga_problem_create for B (target, source, pose) triples in one chain of launches ------
 // What the host decides about a batched problem creation before it launches anything (problem.hip: sga_problem_create_batch acts on it,

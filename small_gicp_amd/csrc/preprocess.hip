@@ -610,13 +610,10 @@ int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, in
   }
   const size_t member_words = count * (sizeof(ForestFeat) / 8), words = member_words + (count + 1);
   SGA_TRY(table.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
+  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
+    std::memcpy(host, members.data(), member_words * 8);
+    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+  }));
   const ForestFeat* d_members = reinterpret_cast<const ForestFeat*>(table.p);
   const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(table.p + member_words);
   forest_count_launch();

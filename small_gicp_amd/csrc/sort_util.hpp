@@ -31,4 +31,15 @@ int sort_pairs(sga_context* ctx, Key* keys_in, Key* keys_out, Val* vals_in, Val*
   }
   return SGA_OK;
 }
+
+// out[i] = in[0] + .. + in[i - 1] on the context's stream with the context's scratch (rocPRIM: the size query, then the scan).
+// (A template, so that the scan's kernels are instantiated only in the translation units that call it.)
+template <typename T>
+int exclusive_scan(sga_context* ctx, T* in, T* out, size_t n) {
+  size_t tb = 0;
+  SGA_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
+  SGA_TRY(ensure_temp(ctx, tb));
+  SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
+  return SGA_OK;
+}
 }  // namespace sga

@@ -18,33 +18,19 @@
 #include <memory>
 #include <rocprim/rocprim.hpp>
 
-#include "device_math.hpp"
-#include "forest.hpp"
 #include "sort_util.hpp"
-#include "voxel_hash.hpp"
+#include "voxel_steps.hpp"
 
 namespace sga {
-
-int ensure_temp(sga_context* ctx, size_t bytes);
 
 __global__ void ivm_keys_kernel(const float4* __restrict__ pts, size_t n, Pose12 T, double inv_leaf, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
   const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
   if (i >= n) return;
   const float4 p = pts[i];
-  const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-  const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-  const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-  const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
-  const bool bad = abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20) || !(x == x) || !(y == y) || !(z == z);
+  int cx, cy, cz;
+  const bool bad = insert_coords(T, p, inv_leaf, cx, cy, cz);
   keys[i] = bad ? SGA_HASH_EMPTY : voxel_key(cx, cy, cz);  // out-of-range points sort last and are dropped
   vals[i] = static_cast<uint32_t>(i);
-}
-
-__global__ void ivm_heads_kernel(const unsigned long long* __restrict__ keys, size_t n, uint32_t* __restrict__ flags) {
-  const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = keys[i];
-  flags[i] = (k != SGA_HASH_EMPTY && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
 }
 
 __global__ void ivm_segments_kernel(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ seg_id, const uint32_t* __restrict__ order, size_t n, uint32_t* __restrict__ seg_start, uint32_t* __restrict__ seg_first) {
@@ -85,25 +71,13 @@ __global__ void ivm_assign_kernel(uint32_t n_new, const uint32_t* __restrict__ s
   if (r < n_new) seg_vid[seg_by_rank[r]] = n_old + r;
 }
 
-__device__ __forceinline__ void ivm_hash_insert(unsigned long long* __restrict__ hkeys, uint32_t* __restrict__ hvals, uint32_t hmask, unsigned long long key, uint32_t v) {
-  uint32_t slot = voxel_hash(key) & hmask;
-  for (;;) {
-    const unsigned long long prev = atomicCAS(&hkeys[slot], SGA_HASH_EMPTY, key);
-    if (prev == SGA_HASH_EMPTY) {
-      hvals[slot] = v;
-      return;
-    }
-    slot = (slot + 1) & hmask;
-  }
-}
-
 __global__ void ivm_rehash_kernel(uint32_t n, const int* __restrict__ coords, unsigned long long* __restrict__ hkeys, uint32_t* __restrict__ hvals, uint32_t hmask) {
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
-  ivm_hash_insert(hkeys, hvals, hmask, voxel_key(coords[3 * v], coords[3 * v + 1], coords[3 * v + 2]), v);
+  voxel_hash_insert(hkeys, hvals, hmask, voxel_key(coords[3 * v], coords[3 * v + 1], coords[3 * v + 2]), v);
 }
 
-// One lane per voxel of the batch: GaussianVoxel::add for its points in insertion order, then finalize (gaussian_voxelmap.hpp:32-53).
+// One lane per voxel of the batch
 __global__ void ivm_update_kernel(
   uint32_t nseg, const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_vid, uint32_t n_valid, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ order, const float4* __restrict__ pts,
   const Cov8* __restrict__ cov, Pose12 T, uint32_t n_old, uint32_t lru_counter, double* __restrict__ mean64, double* __restrict__ cov64, uint32_t* __restrict__ counts, uint32_t* __restrict__ lru, int* __restrict__ coords,
@@ -114,38 +88,11 @@ __global__ void ivm_update_kernel(
   const uint32_t first = seg_start[s];
   const unsigned long long key = keys[first];
   const bool is_new = v >= n_old;
-  uint32_t N = is_new ? 0u : counts[v];
-  double m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
-  if (!is_new) {  // un-finalize: mean *= num_points, cov *= num_points
-    for (int k = 0; k < 3; k++) m[k] = mean64[3 * v + k] * static_cast<double>(N);
-    for (int k = 0; k < 6; k++) c[k] = cov64[6 * v + k] * static_cast<double>(N);
-  }
-  for (uint32_t i = first; i < n_valid && keys[i] == key; ++i) {
-    const uint32_t src = order[i];
-    const float4 p = pts[src];
-    const Cov8 q = cov[src];
-    m[0] += T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    m[1] += T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    m[2] += T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-    // R C R^T (T.matrix() * cov * T.matrix().transpose(): the translation column meets the zero row of the 4x4 covariance)
-    const double C[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
-    double RC[3][3];
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * C[0][b] + T.r[3 * a + 1] * C[1][b] + T.r[3 * a + 2] * C[2][b];
-    int k = 0;
-    for (int a = 0; a < 3; a++)
-      for (int b = a; b < 3; b++) c[k++] += RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
-    N++;
-  }
-  for (int k = 0; k < 3; k++) mean64[3 * v + k] = m[k] / static_cast<double>(N);
-  for (int k = 0; k < 6; k++) cov64[6 * v + k] = c[k] / static_cast<double>(N);
-  counts[v] = N;
+  gaussian_voxel_add(v, is_new, first, n_valid, key, keys, order, pts, cov, T, mean64, cov64, counts);
   lru[v] = lru_counter;
   if (is_new) {
-    coords[3 * v + 0] = static_cast<int>(key & 0x1fffffu) - (1 << 20);
-    coords[3 * v + 1] = static_cast<int>((key >> 21) & 0x1fffffu) - (1 << 20);
-    coords[3 * v + 2] = static_cast<int>((key >> 42) & 0x1fffffu) - (1 << 20);
-    ivm_hash_insert(hkeys, hvals, hmask, key, v);
+    voxel_key_coords(key, coords + 3 * v);
+    voxel_hash_insert(hkeys, hvals, hmask, key, v);
   }
 }
 
@@ -169,31 +116,20 @@ __global__ void ivm_compact_kernel(
   lru_out[w] = lru_in[v];
 }
 
-// (ox, oy, oz): origin of the map's device frame (common.hpp) — the fp64 state is the caller's frame, the fp32 records the kernels read are not
 __global__ void ivm_export_kernel(uint32_t n, const double* __restrict__ mean64, const double* __restrict__ cov64, double ox, double oy, double oz, float4* __restrict__ means, Cov8* __restrict__ mcov) {
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
-  means[v] = make_float4(static_cast<float>(mean64[3 * v] - ox), static_cast<float>(mean64[3 * v + 1] - oy), static_cast<float>(mean64[3 * v + 2] - oz), __uint_as_float(v));
-  Cov8 o;
-  o.xx = static_cast<float>(cov64[6 * v]);
-  o.xy = static_cast<float>(cov64[6 * v + 1]);
-  o.xz = static_cast<float>(cov64[6 * v + 2]);
-  o.yy = static_cast<float>(cov64[6 * v + 3]);
-  o.yz = static_cast<float>(cov64[6 * v + 4]);
-  o.zz = static_cast<float>(cov64[6 * v + 5]);
-  o.pad0 = o.pad1 = 0.f;
-  mcov[v] = o;
+  gaussian_voxel_export(v, mean64, cov64, ox, oy, oz, means, mcov);
 }
 
-// ---- the insert forest: B inserts in one chain of launches (forest.hpp) -----------------------------------------
-// Kernels of their own beside the lone ones (whose code and register rows stay: profiles/batch_voxelmap_insert_kernel_resources.txt); the
-// arithmetic that decides a map's contents — the posed point, the voxel coordinates, the fp64 un-finalize / add / finalize — is the lone
-// kernels', statement for statement, with the pose and the pointers read from the call's tables instead of the kernel's arguments.
+// ---- the insert forest: B inserts in one chain of launches (voxel_steps.hpp) -------------------------------------
+// Kernels of their own beside the lone ones: the pose and the pointers come from the call's tables instead of the kernel's arguments; what
+// decides a map's contents — the posed point, the voxel coordinates, the fp64 un-finalize / add / finalize — are the functions the lone
+// kernels call.
 static_assert(sizeof(IvmMember) % 8 == 0 && sizeof(IvmUpdate) % 8 == 0 && sizeof(IvmExport) % 8 == 0, "table entries are copied as 8-byte words");
-constexpr unsigned long long kIvmDropped = (1ull << kVoxKeyMemberShift) - 1;  // bit 48 and everything below: behind every voxel of the member
 
-// workgroup b: 256 points of the member m with prefix[m] <= b < prefix[m + 1].  ivm_keys_kernel's coordinates under section 3.14's key, and
-// the range of the member's voxel coordinates: reduced over the wave, then one atomic per wave, axis and end.
+// workgroup b: 256 points of the member m with prefix[m] <= b < prefix[m + 1].  ivm_keys_kernel's coordinates under the forests' key, and
+// the range of the member's voxel coordinates.
 __global__ __launch_bounds__(256) void ivm_keys_forest_kernel(const IvmMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
   const uint32_t* prefix = uniform_const(prefix_g);
   const int m = forest_member_of(prefix, count, blockIdx.x);
@@ -202,36 +138,13 @@ __global__ __launch_bounds__(256) void ivm_keys_forest_kernel(const IvmMember* _
   int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
   if (i < g.n) {
     const float4 p = g.pts[i];
-    const Pose12& T = g.T;
-    const double inv_leaf = g.inv_leaf;
-    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-    const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
-    const bool bad = abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20) || !(x == x) || !(y == y) || !(z == z);
-    const unsigned long long key = static_cast<unsigned long long>(static_cast<uint32_t>(cx) & 0xffffu) | (static_cast<unsigned long long>(static_cast<uint32_t>(cy) & 0xffffu) << 16) |
-                                   (static_cast<unsigned long long>(static_cast<uint32_t>(cz) & 0xffffu) << 32);
-    keys[g.off + i] = (static_cast<unsigned long long>(m) << kVoxKeyMemberShift) | (bad ? kIvmDropped : key);  // a member's dropped points sort last in its stretch
+    int cx, cy, cz;
+    const bool bad = insert_coords(g.T, p, g.inv_leaf, cx, cy, cz);
+    keys[g.off + i] = forest_voxel_key(m, cx, cy, cz, bad);  // a member's dropped points sort last in its stretch
     vals[g.off + i] = i;  // the index within the member
     if (!bad) lo[0] = hi[0] = cx, lo[1] = hi[1] = cy, lo[2] = hi[2] = cz;
   }
-  for (int a = 0; a < 3; a++)
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off));
-    }
-  if ((threadIdx.x & 63u) == 0u && lo[0] <= hi[0])  // (a wave of dropped points only: nothing to report)
-    for (int a = 0; a < 3; a++) {
-      atomicMin(g.range + a, lo[a]);
-      atomicMax(g.range + 3 + a, hi[a]);
-    }
-}
-
-__global__ void ivm_heads_forest_kernel(const unsigned long long* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flags) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = keys[i];  // (the member number is part of the key: a member's first voxel never continues its neighbour's last)
-  flags[i] = ((k & (1ull << 48)) == 0ull && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
+  forest_range_reduce(lo, hi, g.range);
 }
 
 // Sorted position i of the concatenation.  The head of a run records the run's start and number and does ivm_lookup_kernel's work: the
@@ -250,12 +163,8 @@ __global__ __launch_bounds__(256) void ivm_starts_forest_kernel(const IvmMember*
       const IvmMember& g = members[m];
       const uint32_t s = seg_id[i], first = order[i];
       const float4 p = g.pts[first];
-      const Pose12& T = g.T;
-      const double inv_leaf = g.inv_leaf;
-      const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-      const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-      const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-      const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
+      int cx, cy, cz;
+      insert_coords(g.T, p, g.inv_leaf, cx, cy, cz);
       const uint32_t hmask = g.hmask;
       const uint32_t v = hmask ? ivm_find(g.hkeys, g.hvals, hmask, voxel_key(cx, cy, cz)) : 0xffffffffu;
       seg_start[s] = i;
@@ -275,22 +184,17 @@ __global__ __launch_bounds__(256) void ivm_starts_forest_kernel(const IvmMember*
     __threadfence();
     if (__hip_atomic_fetch_add(g.counters + 1, covered, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + covered != g.n) continue;
     const uint32_t r0 = seg_id[g.off], r1 = end < n ? seg_id[end] : seg_id[n - 1] + flags[n - 1];
-    bool overflow = false;
-    for (int a = 0; a < 3; a++) {
-      const long long lo = g.range[a], hi = g.range[3 + a];
-      overflow = overflow || (hi >= lo && hi - lo >= 65536);  // two voxels of the member may share a key
-    }
     g.count_slot[1] = r1 - r0;
-    g.count_slot[2] = overflow ? 1ull : 0ull;
+    g.count_slot[2] = forest_range_overflows(g.range) ? 1ull : 0ull;
     g.count_slot[3] = __hip_atomic_load(g.counters, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     forest_box_arrive(hand);
   }
 }
 
 // workgroup b: 128 runs of the member that owns it, the member's new voxels first (in creation order: the ranks' order), then its existing
-// ones.  ivm_assign_kernel (voxel id = n_old + rank) and ivm_update_kernel's loop, statement for statement, over the run's entries up to
-// the end of the member's stretch (its dropped points carry another key); a new voxel's coordinates are those of the run's first point,
-// recomputed by the keys kernel's expression, and it goes into the member's own table under the lone key.
+// ones.  ivm_assign_kernel (voxel id = n_old + rank) and ivm_update_kernel's add over the run's entries up to the end of the member's
+// stretch (its dropped points carry another key); a new voxel's coordinates are those of the run's first point, by the keys kernel's
+// function, and it goes into the member's own table under the lone key.
 __global__ __launch_bounds__(128) void ivm_update_forest_kernel(const IvmUpdate* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, uint32_t total_new, const uint32_t* __restrict__ seg_by_rank,
                                                                 const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_vid, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ order) {
   const uint32_t* prefix = uniform_const(prefix_g);
@@ -302,74 +206,28 @@ __global__ __launch_bounds__(128) void ivm_update_forest_kernel(const IvmUpdate*
   const uint32_t s = seg_by_rank[is_new ? g.new0 + j : total_new + g.old0 + (j - g.n_new)];
   const uint32_t v = is_new ? g.n_old + j : seg_vid[s];
   const uint32_t first = seg_start[s];
-  const uint32_t end = g.end;
-  const unsigned long long key = keys[first];
   const float4* __restrict__ pts = g.pts;
-  const Cov8* __restrict__ cov = g.cov;
-  double* __restrict__ mean64 = g.mean64;
-  double* __restrict__ cov64 = g.cov64;
-  const Pose12& T = g.T;
-  uint32_t N = is_new ? 0u : g.counts[v];
-  double m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
-  if (!is_new) {  // un-finalize: mean *= num_points, cov *= num_points
-    for (int k = 0; k < 3; k++) m[k] = mean64[3 * v + k] * static_cast<double>(N);
-    for (int k = 0; k < 6; k++) c[k] = cov64[6 * v + k] * static_cast<double>(N);
-  }
-  for (uint32_t i = first; i < end && keys[i] == key; ++i) {
-    const uint32_t src = order[i];
-    const float4 p = pts[src];
-    const Cov8 q = cov[src];
-    m[0] += T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    m[1] += T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    m[2] += T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-    // R C R^T (T.matrix() * cov * T.matrix().transpose(): the translation column meets the zero row of the 4x4 covariance)
-    const double C[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
-    double RC[3][3];
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * C[0][b] + T.r[3 * a + 1] * C[1][b] + T.r[3 * a + 2] * C[2][b];
-    int k = 0;
-    for (int a = 0; a < 3; a++)
-      for (int b = a; b < 3; b++) c[k++] += RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
-    N++;
-  }
-  for (int k = 0; k < 3; k++) mean64[3 * v + k] = m[k] / static_cast<double>(N);
-  for (int k = 0; k < 6; k++) cov64[6 * v + k] = c[k] / static_cast<double>(N);
-  g.counts[v] = N;
+  gaussian_voxel_add(v, is_new, first, g.end, keys[first], keys, order, pts, g.cov, g.T, g.mean64, g.cov64, g.counts);
   g.lru[v] = g.lru_counter;
   if (is_new) {
     const float4 p = pts[order[first]];
-    const double inv_leaf = g.inv_leaf;
-    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
-    const int cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
+    int cx, cy, cz;
+    insert_coords(g.T, p, g.inv_leaf, cx, cy, cz);
     g.coords[3 * v + 0] = cx;
     g.coords[3 * v + 1] = cy;
     g.coords[3 * v + 2] = cz;
-    ivm_hash_insert(g.hkeys, g.hvals, g.hmask, voxel_key(cx, cy, cz), v);
+    voxel_hash_insert(g.hkeys, g.hvals, g.hmask, voxel_key(cx, cy, cz), v);
   }
 }
 
-// workgroup b: 256 voxels of the map that owns it; ivm_export_kernel's body
+// workgroup b: 256 voxels of the map that owns it
 __global__ __launch_bounds__(256) void ivm_export_forest_kernel(const IvmExport* __restrict__ maps, const uint32_t* __restrict__ prefix_g, int count) {
   const uint32_t* prefix = uniform_const(prefix_g);
   const int mem = forest_member_of(prefix, count, blockIdx.x);
   const IvmExport& g = *uniform_const(maps + mem);
   const uint32_t v = (blockIdx.x - prefix[mem]) * 256u + threadIdx.x;
   if (v >= g.n) return;
-  const double* __restrict__ mean64 = g.mean64;
-  const double* __restrict__ cov64 = g.cov64;
-  const double ox = g.ox, oy = g.oy, oz = g.oz;
-  g.means[v] = make_float4(static_cast<float>(mean64[3 * v] - ox), static_cast<float>(mean64[3 * v + 1] - oy), static_cast<float>(mean64[3 * v + 2] - oz), __uint_as_float(v));
-  Cov8 o;
-  o.xx = static_cast<float>(cov64[6 * v]);
-  o.xy = static_cast<float>(cov64[6 * v + 1]);
-  o.xz = static_cast<float>(cov64[6 * v + 2]);
-  o.yy = static_cast<float>(cov64[6 * v + 3]);
-  o.yz = static_cast<float>(cov64[6 * v + 4]);
-  o.zz = static_cast<float>(cov64[6 * v + 5]);
-  o.pad0 = o.pad1 = 0.f;
-  g.mcov[v] = o;
+  gaussian_voxel_export(v, g.mean64, g.cov64, g.ox, g.oy, g.oz, g.means, g.mcov);
 }
 
 // ---- flat maps: IncrementalVoxelMap<FlatContainer<NRM, COV>> ------------------------------------------------------------------------
@@ -394,9 +252,8 @@ __global__ void fvm_update_kernel(
     if (cnt >= max_points) break;  // every further point of this batch would be rejected as well
     const uint32_t src = order[i];
     const float4 p = pts[src];
-    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    double x, y, z;
+    posed_point(T, p, x, y, z);
     bool reject = false;
     for (uint32_t j = 0; j < cnt && !reject; j++) {
       const double dx = P[3 * j] - x, dy = P[3 * j + 1] - y, dz = P[3 * j + 2] - z;
@@ -412,25 +269,16 @@ __global__ void fvm_update_kernel(
       for (int a = 0; a < 3; a++) N[a] = T.r[3 * a] * q.x + T.r[3 * a + 1] * q.y + T.r[3 * a + 2] * q.z;
     }
     if constexpr (COV) {
-      double* C6 = fcov64 + (static_cast<size_t>(v) * kFlatCap + cnt) * 6;
       const Cov8 q = cov[src];
-      const double Cm[3][3] = {{q.xx, q.xy, q.xz}, {q.xy, q.yy, q.yz}, {q.xz, q.yz, q.zz}};
-      double RC[3][3];
-      for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
-      int k = 0;
-      for (int a = 0; a < 3; a++)
-        for (int b = a; b < 3; b++) C6[k++] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+      posed_cov(T, q, fcov64 + (static_cast<size_t>(v) * kFlatCap + cnt) * 6);
     }
     cnt++;
   }
   counts[v] = cnt;
   lru[v] = lru_counter;
   if (is_new) {
-    coords[3 * v + 0] = static_cast<int>(key & 0x1fffffu) - (1 << 20);
-    coords[3 * v + 1] = static_cast<int>((key >> 21) & 0x1fffffu) - (1 << 20);
-    coords[3 * v + 2] = static_cast<int>((key >> 42) & 0x1fffffu) - (1 << 20);
-    ivm_hash_insert(hkeys, hvals, hmask, key, v);
+    voxel_key_coords(key, coords + 3 * v);
+    voxel_hash_insert(hkeys, hvals, hmask, key, v);
   }
 }
 
@@ -473,16 +321,8 @@ __global__ void fvm_export_kernel(uint32_t n, const uint32_t* __restrict__ count
     nrm[t] = make_float4(static_cast<float>(q[0]), static_cast<float>(q[1]), static_cast<float>(q[2]), 0.f);
   }
   if constexpr (COV) {
-    Cov8 o;
     const double* c = fcov64 + 6 * static_cast<size_t>(t);
-    o.xx = static_cast<float>(c[0]);
-    o.xy = static_cast<float>(c[1]);
-    o.xz = static_cast<float>(c[2]);
-    o.yy = static_cast<float>(c[3]);
-    o.yz = static_cast<float>(c[4]);
-    o.zz = static_cast<float>(c[5]);
-    o.pad0 = o.pad1 = 0.f;
-    cov[t] = o;
+    cov[t] = cov8_of(c[0], c[1], c[2], c[3], c[4], c[5]);
   }
 }
 
@@ -566,10 +406,7 @@ int ivm_lru_sweep(sga_context* ctx, sga_index* idx) {
     SGA_TRY(keep.alloc(nv));
     SGA_TRY(pos.alloc(nv));
     hipLaunchKernelGGL(ivm_keep_kernel, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, idx->vlru.p, idx->lru_horizon, idx->lru_counter, keep.p);
-    size_t tb = 0;
-    SGA_HIP(rocprim::exclusive_scan(nullptr, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
-    SGA_TRY(ensure_temp(ctx, tb));
-    SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, keep.p, pos.p, 0u, nv, rocprim::plus<uint32_t>(), ctx->stream));
+    SGA_TRY(exclusive_scan(ctx, keep.p, pos.p, nv));
     uint32_t last_keep = 0, last_pos = 0;
     SGA_HIP(hipMemcpyAsync(&last_keep, keep.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
     SGA_HIP(hipMemcpyAsync(&last_pos, pos.p + (nv - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -611,104 +448,87 @@ int ivm_lru_sweep(sga_context* ctx, sga_index* idx) {
   return SGA_OK;
 }
 
-// `table1`: [members][ranges: 6 ints per member][counters: 2 per member][ticket][prefix of the key grid: count + 1], written in pinned
-// memory, one copy command
-int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, IvmForestChain& ch) {
-  const size_t count = plan.forest.size(), N = plan.points;
+// `table1`: [members][ranges: 6 ints per member][counters: 2 per member][ticket][prefix of the key grid: count + 1]
+int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, VoxelForestChain& ch) {
+  const size_t count = plan.forest.size();
   if (count == 0) return SGA_OK;
-  ch.member_bits = plan.member_bits;
-  SGA_TRY(ch.keys.alloc(N));
-  SGA_TRY(ch.keys_sorted.alloc(N));
-  SGA_TRY(ch.vals.alloc(N));
-  SGA_TRY(ch.order.alloc(N));
-  SGA_TRY(ch.flags.alloc(N));
-  SGA_TRY(ch.seg_id.alloc(N));
-  SGA_TRY(ch.seg_start.alloc(N));
-  SGA_TRY(ch.seg_vid.alloc(N));
-  SGA_TRY(ch.rank_keys.alloc(N));
-  SGA_TRY(ch.seg_ids.alloc(N));
-  std::vector<IvmMember> members(count);
-  std::vector<uint32_t> prefix(count + 1, 0u);
-  const size_t member_words = count * (sizeof(IvmMember) / 8), range_words = 3 * count, counter_words = count, prefix_words = (prefix.size() + 1) / 2;
+  const size_t member_words = count * (sizeof(IvmMember) / 8), range_words = 3 * count, counter_words = count, prefix_words = (count + 2) / 2;
   const size_t words = member_words + range_words + counter_words + 1 + prefix_words;
-  SGA_TRY(ch.table1.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memset(host, 0, words * 8);
-  int* host_range = reinterpret_cast<int*>(host + member_words);
-  uint32_t off = 0;
-  for (size_t j = 0; j < count; j++) {
-    const size_t k = plan.forest[j];
-    const sga_cloud* c = clouds[k];
-    const sga_index* idx = maps[k];
-    IvmMember& g = members[j];
-    std::memset(&g, 0, sizeof(g));
-    g.pts = c->pts.p;
-    g.T = insert_pose(T ? T + 16 * k : nullptr, c->origin);
-    g.inv_leaf = 1.0 / idx->leaf;
-    g.hkeys = idx->hkeys.p;
-    g.hvals = idx->hvals.p;
-    g.range = reinterpret_cast<int*>(ch.table1.p + member_words) + 6 * j;
-    g.counters = reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words) + 2 * j;
-    g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
-    g.hmask = idx->n > 0 ? idx->hmask : 0u;
-    g.n = static_cast<uint32_t>(c->n);
-    g.off = off;
-    off += g.n;
-    for (int a = 0; a < 3; a++) host_range[6 * j + a] = INT_MAX, host_range[6 * j + 3 + a] = INT_MIN;
-    prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
-  }
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words + range_words + counter_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
-  ivm_forest_count_launch();
-  SGA_HIP(hipMemcpyAsync(ch.table1.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
-  const IvmMember* d_members = reinterpret_cast<const IvmMember*>(ch.table1.p);
-  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(ch.table1.p + member_words + range_words + counter_words + 1);
+  const uint32_t n32 = static_cast<uint32_t>(plan.points);
+  const IvmMember* d_members = nullptr;
+  SGA_TRY(voxel_forest_runs(ctx, ch, plan.points, plan.member_bits, plan.end_bit, ivm_forest_count_launch, [&]() -> int {
+    SGA_TRY(ch.seg_vid.alloc(plan.points));
+    std::vector<IvmMember> members(count);
+    std::vector<uint32_t> prefix(count + 1, 0u);
+    SGA_TRY(ch.table1.alloc(words));
+    SGA_TRY(upload_table(ctx, ch.table1.p, words, [&](unsigned long long* host) {
+      std::memset(host, 0, words * 8);
+      int* host_range = reinterpret_cast<int*>(host + member_words);
+      uint32_t off = 0;
+      for (size_t j = 0; j < count; j++) {
+        const size_t k = plan.forest[j];
+        const sga_cloud* c = clouds[k];
+        const sga_index* idx = maps[k];
+        IvmMember& g = members[j];
+        std::memset(&g, 0, sizeof(g));
+        g.pts = c->pts.p;
+        g.T = insert_pose(T ? T + 16 * k : nullptr, c->origin);
+        g.inv_leaf = 1.0 / idx->leaf;
+        g.hkeys = idx->hkeys.p;
+        g.hvals = idx->hvals.p;
+        g.range = reinterpret_cast<int*>(ch.table1.p + member_words) + 6 * j;
+        g.counters = reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words) + 2 * j;
+        g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
+        g.hmask = idx->n > 0 ? idx->hmask : 0u;
+        g.n = static_cast<uint32_t>(c->n);
+        g.off = off;
+        off += g.n;
+        for (int a = 0; a < 3; a++) host_range[6 * j + a] = INT_MAX, host_range[6 * j + 3 + a] = INT_MIN;
+        prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
+      }
+      std::memcpy(host, members.data(), member_words * 8);
+      std::memcpy(host + member_words + range_words + counter_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
+      ivm_forest_count_launch();
+    }));
+    d_members = reinterpret_cast<const IvmMember*>(ch.table1.p);
+    ivm_forest_count_launch();
+    hipLaunchKernelGGL(ivm_keys_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, reinterpret_cast<const uint32_t*>(ch.table1.p + member_words + range_words + counter_words + 1), static_cast<int>(count), ch.keys.p,
+                       ch.vals.p);
+    SGA_HIP(hipGetLastError());
+    return SGA_OK;
+  }));
   const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words + counter_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
-  const uint32_t n32 = static_cast<uint32_t>(N);
-  const dim3 grid((n32 + 255u) / 256u), block(256);
   ivm_forest_count_launch();
-  hipLaunchKernelGGL(ivm_keys_forest_kernel, dim3(prefix[count]), block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.keys.p, ch.vals.p);
-  SGA_HIP(hipGetLastError());
-  ivm_forest_count_launch();
-  SGA_TRY(sort_pairs(ctx, ch.keys.p, ch.keys_sorted.p, ch.vals.p, ch.order.p, N, 0, static_cast<unsigned>(plan.end_bit)));
-  ivm_forest_count_launch();
-  hipLaunchKernelGGL(ivm_heads_forest_kernel, grid, block, 0, ctx->stream, ch.keys_sorted.p, n32, ch.flags.p);
-  SGA_HIP(hipGetLastError());
-  ivm_forest_count_launch();
-  size_t tb = 0;
-  SGA_HIP(rocprim::exclusive_scan(nullptr, tb, ch.flags.p, ch.seg_id.p, 0u, N, rocprim::plus<uint32_t>(), ctx->stream));
-  SGA_TRY(ensure_temp(ctx, tb));
-  SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb, ch.flags.p, ch.seg_id.p, 0u, N, rocprim::plus<uint32_t>(), ctx->stream));
-  ivm_forest_count_launch();
-  hipLaunchKernelGGL(ivm_starts_forest_kernel, grid, block, 0, ctx->stream, d_members, ch.keys_sorted.p, ch.flags.p, ch.seg_id.p, ch.order.p, n32, ch.seg_start.p, ch.seg_vid.p, ch.rank_keys.p, ch.seg_ids.p, hand);
+  hipLaunchKernelGGL(ivm_starts_forest_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, ctx->stream, d_members, ch.keys_sorted.p, ch.flags.p, ch.seg_id.p, ch.order.p, n32, ch.seg_start.p, ch.seg_vid.p, ch.rank_keys.p, ch.seg_ids.p, hand);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
 }
 
-// `table2`: [members][prefix of the update grid: count + 1].  One sort of all runs of the chain under the rank key — the members' new
-// voxels in creation order, member after member, then every existing voxel's run in run order — and the assign + update launch
-int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& members, size_t runs, uint32_t total_new, size_t members_in_chain, IvmForestChain& ch) {
+// [entries][prefix of the launch's grid: count + 1]: the table of the update launch and of the export launch
+template <typename Entry>
+static int upload_entries(sga_context* ctx, DevBuf<unsigned long long>& table, const std::vector<Entry>& entries, const std::vector<uint32_t>& prefix) {
+  const size_t entry_words = entries.size() * (sizeof(Entry) / 8), words = entry_words + (prefix.size() + 1) / 2;
+  SGA_TRY(table.alloc(words));
+  return upload_table(ctx, table.p, words, [&](unsigned long long* host) {
+    std::memset(host, 0, words * 8);
+    std::memcpy(host, entries.data(), entry_words * 8);
+    std::memcpy(host + entry_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+    ivm_forest_count_launch();
+  });
+}
+
+// `table2`.  One sort of all runs of the chain under the rank key — the members' new voxels in creation order, member after member, then
+// every existing voxel's run in run order — and the assign + update launch
+int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& members, size_t runs, uint32_t total_new, size_t members_in_chain, VoxelForestChain& ch) {
   const size_t count = members.size();
   if (count == 0 || runs == 0) return SGA_OK;
   std::vector<uint32_t> prefix(count + 1, 0u);
   for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (members[j].nseg + 127u) / 128u;
   if (prefix[count] == 0) return SGA_OK;
-  const size_t member_words = count * (sizeof(IvmUpdate) / 8), words = member_words + (count + 2) / 2;
-  SGA_TRY(ch.table2.alloc(words));
+  const size_t member_words = count * (sizeof(IvmUpdate) / 8);
   SGA_TRY(ch.rank_keys_sorted.alloc(runs));
   SGA_TRY(ch.seg_by_rank.alloc(runs));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memset(host, 0, words * 8);
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-  ivm_forest_count_launch();
-  SGA_HIP(hipMemcpyAsync(ch.table2.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
+  SGA_TRY(upload_entries(ctx, ch.table2, members, prefix));
   int rank_member_bits = 0;  // member numbers 0 .. members_in_chain (the last one: the runs of existing voxels)
   while ((1ull << rank_member_bits) < members_in_chain + 1) rank_member_bits++;
   ivm_forest_count_launch();
@@ -720,23 +540,14 @@ int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& me
   return SGA_OK;
 }
 
-// `table3`: [maps][prefix of the export grid: count + 1]: the fp32 records of every map of the call in one launch
-int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& maps, IvmForestChain& ch) {
+// `table3`: the fp32 records of every map of the call in one launch
+int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& maps, VoxelForestChain& ch) {
   const size_t count = maps.size();
   if (count == 0) return SGA_OK;
   std::vector<uint32_t> prefix(count + 1, 0u);
   for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (maps[j].n + 255u) / 256u;
-  const size_t map_words = count * (sizeof(IvmExport) / 8), words = map_words + (count + 2) / 2;
-  SGA_TRY(ch.table3.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memset(host, 0, words * 8);
-  std::memcpy(host, maps.data(), map_words * 8);
-  std::memcpy(host + map_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-  ivm_forest_count_launch();
-  SGA_HIP(hipMemcpyAsync(ch.table3.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
+  const size_t map_words = count * (sizeof(IvmExport) / 8);
+  SGA_TRY(upload_entries(ctx, ch.table3, maps, prefix));
   ivm_forest_count_launch();
   hipLaunchKernelGGL(ivm_export_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, reinterpret_cast<const IvmExport*>(ch.table3.p), reinterpret_cast<const uint32_t*>(ch.table3.p + map_words), static_cast<int>(count));
   SGA_HIP(hipGetLastError());
@@ -1013,11 +824,8 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
     SGA_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys_sorted.p, vals.p, order.p, n, 0, 64, ctx->stream));
     SGA_TRY(ensure_temp(ctx, tb));
     SGA_HIP(rocprim::radix_sort_pairs(ctx->d_temp.p, tb, keys.p, keys_sorted.p, vals.p, order.p, n, 0, 64, ctx->stream));
-    hipLaunchKernelGGL(ivm_heads_kernel, grid, block, 0, ctx->stream, keys_sorted.p, n, flags.p);
-    size_t tb2 = 0;
-    SGA_HIP(rocprim::exclusive_scan(nullptr, tb2, flags.p, seg_id.p, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-    SGA_TRY(ensure_temp(ctx, tb2));
-    SGA_HIP(rocprim::exclusive_scan(ctx->d_temp.p, tb2, flags.p, seg_id.p, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+    segment_heads(ctx, keys_sorted.p, n, flags.p);
+    SGA_TRY(exclusive_scan(ctx, flags.p, seg_id.p, n));
     uint32_t last_flag = 0, last_seg = 0;
     SGA_HIP(hipMemcpyAsync(&last_flag, flags.p + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
     SGA_HIP(hipMemcpyAsync(&last_seg, seg_id.p + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
