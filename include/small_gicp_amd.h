@@ -122,6 +122,29 @@ int sga_cloud_slice(sga_context* ctx, const sga_cloud* cloud, size_t first, size
  * more in all.  sga_cloud_transform is the merge of one member. */
 int sga_cloud_merge(sga_context* ctx, const sga_cloud* const* clouds, const double* T /* count x 16 column-major, or NULL: identities */, size_t count, const double origin[3] /* or NULL */, sga_cloud** out);
 int sga_cloud_transform(sga_context* ctx, const sga_cloud* cloud, const double T[16], const double origin[3], sga_cloud** out);
+/* Raw sweeps deskewed on the device: per-point motion compensation ahead of the voxel grid.  A spinning LiDAR
+ * measures every point from the pose the sensor has at that instant; with the sensor pose T0 exp(s xi) at time s (xi: the motion per unit
+ * of time, sga_se3_exp's convention, rotation first), a point P measured at s_i in the sensor frame of that instant is, in the sensor
+ * frame at ref_time,
+ *   P' = exp(a_i xi) P,   a_i = double(s_i) - ref_time   (a_i xi componentwise).
+ * times[k][i] is the time of point i of clouds[k] in the cloud's storage order (the caller's order; the unit is the caller's, normally 0 =
+ * the sweep's start and 1 = its end).  With o the cloud's origin and r a record (P = r + o), (R_i, t_i) = exp(a_i xi) evaluated in double
+ * WITHOUT cancellation for every angle (sin, 2 sin^2(phi/2) and a series for phi - sin phi; csrc/lie.hpp) — a_i runs through 0 —, the
+ * output record is fl32(R_i r + (R_i o + t_i - o)) ((R_i - I) o formed from its own terms), normals become fl32(R_i n) and covariances
+ * the six entries of fl32(R_i C R_i^T): evaluated in double from the fp32 records and rounded once, as in sga_cloud_merge.  out[k] keeps
+ * clouds[k]'s origin and attributes; the index word of a point is its position.  xi = 0, or s_i == ref_time, reproduces the record
+ * exactly.  A non-finite time gives a non-finite point, which takes no part in the bounding box; nothing on the host reads the times.
+ * One table copy and ONE launch whatever count is.  A blocking context keeps the box of the records with every out[k] (its one wait);
+ * a stream-ordered context waits for nothing and its clouds carry no box.  An empty member yields an empty cloud without attributes;
+ * count == 0 is SGA_OK without device work.  Refusals (SGA_ERR_INVALID, every out[k] = NULL as on every failure) — before any handle is
+ * read: NULL arguments (clouds[k] / times[k] named by number), a non-finite twist entry or reference time (named by number), more than
+ * 2^15 members; then: a cloud of another device, times in device memory (they go through sga_cloud_deskew_device).
+ * sga_cloud_deskew is the batch of one.  sga_cloud_deskew_device takes the times from device memory of the context's device (float or
+ * double, cols = 1, any stride >= 1: a column of a wider array), checked against its allocation, and orders user_stream as
+ * sga_cloud_create_device does (flags: SGA_IO_NO_ORDER); host memory is refused (it goes through sga_cloud_deskew). */
+int sga_cloud_deskew_batch(sga_context* ctx, const sga_cloud* const* clouds, const float* const* times, const double* twists /* count x 6 */, const double* ref_times /* count, or NULL: 1.0 each */,
+                           size_t count, sga_cloud** out /* count */);
+int sga_cloud_deskew(sga_context* ctx, const sga_cloud* cloud, const float* times, const double twist[6], double ref_time, sga_cloud** out);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);
@@ -170,6 +193,8 @@ int sga_cloud_create_device(sga_context* ctx, const sga_device_array* points, co
  * the caller's frame — the origin is added in double, the sum rounded to dtype —, normals 3 per row, covariances 6, 9 (the symmetric
  * 3x3) or 16 (4x4, fourth row and column zero) per row.  Elements of a row past its cols are left untouched. */
 int sga_cloud_export_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* points, const sga_device_array* normals, const sga_device_array* covs, void* user_stream, int flags);
+/* sga_cloud_deskew with the times in device memory (above: "Raw sweeps deskewed on the device") */
+int sga_cloud_deskew_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* times /* float | double, cols 1, any stride */, const double twist[6], double ref_time, void* user_stream, int flags, sga_cloud** out);
 /* sga_index_knn for m queries in device memory (float or double rows; the search runs on fl32(double(q) - origin of the index), computed
  * by a kernel): d_idx m*k int64 and d_sq_dist m*k floats, device memory of the caller's.  kd-trees, Gaussian and flat voxel maps, with
  * the kernels, k limits and messages of the host call; a projective index is SGA_ERR_UNSUPPORTED, and the double distances of
@@ -557,8 +582,10 @@ typedef int (*sga_linearize_fn)(void* user, const double T[16], double H[36], do
 typedef int (*sga_error_fn)(void* user, const double T[16], double* e);
 int sga_optimize(const sga_registration_setting* setting, const double init_T[16], sga_linearize_fn linearize, sga_error_fn error, void* user, sga_result* out);
 
-/* util/lie.hpp:77-96 se3_exp (host). */
+/* util/lie.hpp:77-96 se3_exp (host), and its inverse for rotation angles below pi; twist = [rx ry rz tx ty tz].  Both are evaluated
+ * without cancellation at small angles (csrc/lie.hpp; the optimizer multiplies by the reference's own expressions, as before). */
 void sga_se3_exp(const double twist[6], double T[16]);
+void sga_se3_log(const double T[16], double twist[6]);
 
 #ifdef __cplusplus
 }

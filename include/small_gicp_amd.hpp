@@ -77,6 +77,19 @@ struct Isometry3d {
 #endif
 };
 
+/// The pose of a twist [rx ry rz tx ty tz] (sga_se3_exp) and the twist of a pose whose rotation angle is below pi (sga_se3_log): host
+/// functions, evaluated without cancellation at small angles.
+inline Isometry3d se3_exp(const std::array<double, 6>& twist) {
+  Isometry3d T;
+  sga_se3_exp(twist.data(), T.m.data());
+  return T;
+}
+inline std::array<double, 6> se3_log(const Isometry3d& T) {
+  std::array<double, 6> twist{};
+  sga_se3_log(T.data(), twist.data());
+  return twist;
+}
+
 /// One context (GPU + stream) per device, shared by the objects of this header.
 inline sga_context* default_context(int device = 0) {
   static std::array<sga_context*, 16> ctxs{};
@@ -142,6 +155,21 @@ struct PointCloud {
   Ptr transformed(const Isometry3d& T, const double* origin = nullptr) const {
     sga_cloud* made = nullptr;
     check(sga_cloud_transform(ctx, h, T.data(), origin, &made), "sga_cloud_transform");
+    return std::make_shared<PointCloud>(made, ctx);
+  }
+
+  /// This raw sweep with the sensor's motion undone, as a new cloud on the device (sga_cloud_deskew): point i, measured at times[i] in the
+  /// sensor frame of that instant, becomes exp((times[i] - ref_time) twist) p_i; twist = the motion per unit of time (se3_log of the
+  /// sweep's relative pose when the times run from 0 to 1).  times: size() values in host memory, the cloud's order.
+  Ptr deskewed(const float* times, const std::array<double, 6>& twist, double ref_time = 1.0) const {
+    sga_cloud* made = nullptr;
+    check(sga_cloud_deskew(ctx, h, times, twist.data(), ref_time, &made), "sga_cloud_deskew");
+    return std::make_shared<PointCloud>(made, ctx);
+  }
+  /// The same with the times in device memory of the context's device (sga_cloud_deskew_device: float or double, cols = 1, any stride).
+  Ptr deskewed(const sga_device_array& times, const std::array<double, 6>& twist, double ref_time = 1.0, void* stream = nullptr, int flags = 0) const {
+    sga_cloud* made = nullptr;
+    check(sga_cloud_deskew_device(ctx, h, &times, twist.data(), ref_time, stream, flags, &made), "sga_cloud_deskew_device");
     return std::make_shared<PointCloud>(made, ctx);
   }
 
@@ -729,6 +757,24 @@ inline PointCloud::Ptr merge_clouds(sga_context* ctx, const std::vector<std::sha
   sga_cloud* made = nullptr;
   check(sga_cloud_merge(ctx, cs.data(), Ts.empty() ? nullptr : T16.data(), cs.size(), origin, &made), "sga_cloud_merge");
   return std::make_shared<PointCloud>(made, ctx);
+}
+
+/// sga_cloud_deskew_batch: PointCloud::deskewed for B sweeps by one table copy and one launch whatever B is.  times[k]: clouds[k]->size()
+/// values; twists[k]: member k's motion per unit of time; ref_times empty: 1.0 each.
+inline std::vector<PointCloud::Ptr> deskew_clouds(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds, const std::vector<const float*>& times, const std::vector<std::array<double, 6>>& twists,
+                                                  const std::vector<double>& ref_times = {}) {
+  if (times.size() != clouds.size() || twists.size() != clouds.size() || (!ref_times.empty() && ref_times.size() != clouds.size())) throw std::runtime_error("deskew_clouds: as many times, twists and reference times as clouds");
+  std::vector<const sga_cloud*> cs;
+  std::vector<double> xi;
+  for (size_t k = 0; k < clouds.size(); k++) {
+    cs.push_back(clouds[k]->h);
+    xi.insert(xi.end(), twists[k].begin(), twists[k].end());
+  }
+  std::vector<sga_cloud*> made(clouds.size(), nullptr);
+  check(sga_cloud_deskew_batch(ctx, cs.data(), times.data(), xi.data(), ref_times.empty() ? nullptr : ref_times.data(), cs.size(), made.data()), "sga_cloud_deskew_batch");
+  std::vector<PointCloud::Ptr> out;
+  for (sga_cloud* h : made) out.push_back(std::make_shared<PointCloud>(h, ctx));
+  return out;
 }
 
 /// The problems of create_problems: ordinary sga_problem handles (sga_linearize, sga_align_problem, sga_batch_create, ...), destroyed with the set

@@ -98,6 +98,10 @@ SYMBOLS = [
     ("sga_cloud_merge", C.c_int, [_vp, _pvp, _dp, C.c_size_t, _dp, _pvp]),
     ("sga_cloud_transform", C.c_int, [_vp, _vp, _dp, _dp, _pvp]),
     ("sga_debug_cloud_merge_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_cloud_deskew_batch", C.c_int, [_vp, _pvp, _pvp, _dp, _dp, C.c_size_t, _pvp]),
+    ("sga_cloud_deskew", C.c_int, [_vp, _vp, _fp, _dp, C.c_double, _pvp]),
+    ("sga_cloud_deskew_device", C.c_int, [_vp, _vp, C.POINTER(DeviceArray), _dp, C.c_double, _vp, C.c_int, _pvp]),
+    ("sga_debug_cloud_deskew_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),
@@ -231,6 +235,7 @@ SYMBOLS = [
     ("sga_optimize_batch", C.c_int, [C.POINTER(RegistrationSettingC), C.c_size_t, _dp, BATCH_LINEARIZE_FN, BATCH_ERROR_FN, _vp, C.POINTER(ResultC)]),
     ("sga_optimize", C.c_int, [C.POINTER(RegistrationSettingC), _dp, LINEARIZE_FN, ERROR_FN, _vp, C.POINTER(ResultC)]),
     ("sga_se3_exp", None, [_dp, _dp]),
+    ("sga_se3_log", None, [_dp, _dp]),
 ]
 
 _LIB = None

@@ -278,6 +278,25 @@ class PointCloud:
         """A new cloud holding this one's points, normals and covariances posed by T (4x4; sga_cloud_transform): merge_clouds of one member."""
         return merge_clouds([self], [T], origin)
 
+    def deskewed(self, times, twist, ref_time=1.0, stream=None):
+        """This raw sweep with the sensor's motion undone, as a new cloud (sga_cloud_deskew): point i, measured at
+        times[i] in the sensor frame of that instant, becomes exp((times[i] - ref_time) twist) p_i — the sensor frame at ref_time.  twist:
+        the motion per unit of time, [rx ry rz tx ty tz] (se3_log of the sweep's relative pose when the times run from 0 to 1).  times: a
+        numpy array (N,), or a torch tensor on the cloud's device — float32 or float64, 1-D with any stride, e.g. a column scan[:, 4] —
+        which the device reads where it is (sga_cloud_deskew_device; stream: the hipStream_t it was produced on, default torch's current
+        stream).  Normals and covariances are rotated along; the cloud keeps its origin."""
+        xi = np.ascontiguousarray(np.asarray(twist, dtype=np.float64).reshape(6))
+        h = C.c_void_p()
+        if isinstance(times, np.ndarray) or not type(times).__module__.startswith("torch"):
+            t = np.ascontiguousarray(np.asarray(times, dtype=np.float32).reshape(-1))
+            if len(t) != self.size():
+                raise ValueError(f"{len(t)} times for a cloud of {self.size()} points")
+            check(load().sga_cloud_deskew(self.ctx.h, self.h, _fp(t), _dp(xi), float(ref_time), C.byref(h)))
+        else:
+            ta = _torch_times(times, self.size(), self.ctx)
+            check(load().sga_cloud_deskew_device(self.ctx.h, self.h, C.byref(ta), _dp(xi), float(ref_time), C.c_void_p(_torch_stream(self.ctx, stream)), 0, C.byref(h)))
+        return PointCloud(ctx=self.ctx, _handle=h)
+
     def empty(self):
         return self.size() == 0
 
@@ -1244,6 +1263,28 @@ def _torch_rows(t, what, ctx, cols_allowed):
     return _device_array(t.data_ptr(), _IO_DTYPES[name], cols, stride if t.shape[0] > 1 else cols), t.shape[0]
 
 
+def _torch_times(t, n, ctx):
+    """A tensor of n times -> sga_device_array: 1-D (or (N,1)), float32 / float64, any stride, on the context's device"""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("times must be a numpy array or a torch.Tensor")
+    if t.dim() == 2 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError(f"times of shape {tuple(t.shape)} for a cloud of {n} points")
+    name = str(t.dtype).replace("torch.", "")
+    if name not in _IO_DTYPES:
+        raise ValueError(f"times must be float32 or float64, not {t.dtype}")
+    if n > 1 and t.stride(0) < 1:
+        raise ValueError(f"times: stride {t.stride(0)} (an expanded or reversed view)")
+    if not t.is_cuda:
+        raise ValueError("times is a CPU tensor: hand it over as a numpy array (times.numpy())")
+    if t.device.index != int(ctx.device):
+        raise ValueError(f"times lives on {t.device}, the context on cuda:{ctx.device}")
+    return _device_array(t.data_ptr(), _IO_DTYPES[name], 1, t.stride(0) if n > 1 else 1)
+
+
 def _torch_stream(ctx, stream):
     import torch
 
@@ -1576,6 +1617,60 @@ def merge_clouds(clouds, Ts=None, origin=None, ctx=None):
     h = C.c_void_p()
     check(load().sga_cloud_merge(ctx.h, hs, None if t16 is None else _dp(t16), len(clouds), _dp(o), C.byref(h)))
     return PointCloud(ctx=ctx, _handle=h)
+
+
+def se3_exp(twist):
+    """sga_se3_exp: the 4x4 pose of a twist [rx ry rz tx ty tz] (rotation first), evaluated without cancellation at small angles."""
+    xi = np.ascontiguousarray(np.asarray(twist, dtype=np.float64).reshape(6))
+    T = np.empty(16)
+    load().sga_se3_exp(_dp(xi), _dp(T))
+    return T.reshape(4, 4).T.copy()
+
+
+def se3_log(T):
+    """sga_se3_log: the twist whose se3_exp is the rigid transform T (rotation angle below pi)."""
+    t16 = _T16(T)
+    xi = np.empty(6)
+    load().sga_se3_log(_dp(t16), _dp(xi))
+    return xi
+
+
+def deskew_clouds(clouds, times, twists, ref_times=None, ctx=None):
+    """sga_cloud_deskew_batch: PointCloud.deskewed for B sweeps — times[k] a numpy array of clouds[k].size() values, twists (B, 6),
+    ref_times (B,) or None (1.0 each) — by one table copy and one launch, whatever B is.  Returns the B deskewed clouds.  The members may
+    belong to several contexts of one device; ctx: the context the call runs on (default: the first cloud's)."""
+    clouds = list(clouds)
+    for c in clouds:
+        if not isinstance(c, PointCloud):
+            raise TypeError("deskew_clouds takes PointCloud objects")
+    B = len(clouds)
+    times = list(times)
+    if len(times) != B:
+        raise ValueError(f"{len(times)} time arrays for {B} clouds")
+    if B == 0:
+        return []  # (count == 0 is no device work: no context is needed)
+    ts = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(-1)) for t in times]
+    for k, (c, t) in enumerate(zip(clouds, ts)):
+        if len(t) != c.size():
+            raise ValueError(f"times[{k}]: {len(t)} times for a cloud of {c.size()} points")
+    xi = np.ascontiguousarray(np.asarray(twists, dtype=np.float64).reshape(B, 6))
+    rt = None if ref_times is None else np.ascontiguousarray(np.asarray(ref_times, dtype=np.float64).reshape(B))
+    ctx = ctx or clouds[0].ctx
+    hs = (C.c_void_p * B)(*[c.h.value for c in clouds])
+    tp = (C.c_void_p * B)(*[t.ctypes.data if len(t) else C.addressof(_NO_TIMES) for t in ts])
+    out = (C.c_void_p * B)()
+    check(load().sga_cloud_deskew_batch(ctx.h, hs, tp, _dp(xi), _dp(rt), B, out))
+    return [PointCloud(ctx=ctx, _handle=C.c_void_p(out[k])) for k in range(B)]
+
+
+_NO_TIMES = C.c_float()  # what an empty member's times point at (never read)
+
+
+def cloud_deskew_launches():
+    """Diagnostics (sga_debug_cloud_deskew_launches): table copies and kernels enqueued so far by PointCloud.deskewed / deskew_clouds."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_deskew_launches(C.byref(v)))
+    return v.value
 
 
 def cloud_merge_launches():

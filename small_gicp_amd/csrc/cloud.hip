@@ -1,8 +1,10 @@
 // Clouds: every sga_cloud_* entry point.  Host arrays (pageable through the context's pinned staging ring, pinned ones read in place)
 // and device arrays of the caller's become the 16 / 16 / 32-byte device records through ONE pack kernel, and
-// leave through ONE unpack kernel; slices, downloads and the small getters; posed clouds joined into one.
+// leave through ONE unpack kernel; slices, downloads and the small getters; posed clouds joined into one; sweeps
+// deskewed with a pose per point.
 #include "device_io.hpp"
 #include "forest.hpp"
+#include "lie.hpp"
 #include "voxel_steps.hpp"
 #include "notes.hpp"
 
@@ -28,11 +30,10 @@ __host__ __device__ inline double box_dec64(unsigned long long e) {
   return d;
 }
 
-// box_reduce_publish for doubles: d_box64 = {min x y z, max x y z (encoded), arrival counter, 0}, identity values and counter 0 between
-// launches; the last workgroup writes the six words into payload words 1..6 of the note, restores the accumulator and publishes.
-__device__ __forceinline__ void box64_reduce_publish(double lo[3], double hi[3], unsigned long long* __restrict__ d_box64, unsigned long long* __restrict__ slot, unsigned long long seq) {
+// The box of a workgroup's threads (lo = +inf / hi = -inf for none) joined into acc = {min x y z, max x y z (encoded), ...} with six
+// atomics; on return they have been issued and fenced (agent scope) and the workgroup has met.  Called by all threads.
+__device__ __forceinline__ void box64_reduce_block(double lo[3], double hi[3], unsigned long long* __restrict__ acc) {
   __shared__ double sh_box[kIoBlock / 64][6];
-  __shared__ bool sh_last;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
 #pragma unroll
@@ -55,12 +56,19 @@ __device__ __forceinline__ void box64_reduce_publish(double lo[3], double hi[3],
     double v = sh_box[0][k];
     for (int w = 1; w < kIoBlock / 64; w++) v = k < 3 ? fmin(v, sh_box[w][k]) : fmax(v, sh_box[w][k]);
     if (k < 3)
-      atomicMin(&d_box64[k], box_enc64(v));
+      atomicMin(&acc[k], box_enc64(v));
     else
-      atomicMax(&d_box64[k], box_enc64(v));
+      atomicMax(&acc[k], box_enc64(v));
   }
   __threadfence();
   __syncthreads();
+}
+
+// box_reduce_publish for doubles: d_box64 = {min x y z, max x y z (encoded), arrival counter, 0}, identity values and counter 0 between
+// launches; the last workgroup writes the six words into payload words 1..6 of the note, restores the accumulator and publishes.
+__device__ __forceinline__ void box64_reduce_publish(double lo[3], double hi[3], unsigned long long* __restrict__ d_box64, unsigned long long* __restrict__ slot, unsigned long long seq) {
+  __shared__ bool sh_last;
+  box64_reduce_block(lo, hi, d_box64);
   if (threadIdx.x == 0) sh_last = __hip_atomic_fetch_add(&d_box64[6], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
   __syncthreads();
   if (!sh_last) return;  // workgroup-uniform
@@ -220,6 +228,34 @@ __global__ void slice_cloud_kernel(const float4* __restrict__ pts, const float4*
   if (cov) ocov[i] = cov[first + i];
 }
 
+// What a pose does to one record, stated once for merge_cloud_kernel and deskew_cloud_kernel: the point R r + t (posed_point,
+// voxel_steps.hpp), the normal R n and the covariance R C R^T are evaluated in double from the fp32 records, with the insert kernels'
+// expressions (voxelmap.hip: fvm_update_kernel, ivm_update_kernel), and rounded once.
+__device__ __forceinline__ float4 posed_normal_record(const Pose12& T, const float4 q) {
+  double N[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) N[a] = T.r[3 * a] * q.x + T.r[3 * a + 1] * q.y + T.r[3 * a + 2] * q.z;
+  return make_float4(static_cast<float>(N[0]), static_cast<float>(N[1]), static_cast<float>(N[2]), 0.f);
+}
+__device__ __forceinline__ void posed_cov_record(const Pose12& T, const Cov8* __restrict__ in, Cov8* __restrict__ out) {
+  const float4* cin = reinterpret_cast<const float4*>(in);
+  const float4 c0 = cin[0], c1 = cin[1];  // xx xy xz yy | yz zz 0 0
+  const double Cm[3][3] = {{c0.x, c0.y, c0.z}, {c0.y, c0.w, c1.x}, {c0.z, c1.x, c1.y}};
+  double RC[3][3], C6[6];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = a; b < 3; b++) C6[k++] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
+  float4* cout = reinterpret_cast<float4*>(out);
+  cout[0] = make_float4(static_cast<float>(C6[0]), static_cast<float>(C6[1]), static_cast<float>(C6[2]), static_cast<float>(C6[3]));
+  cout[1] = make_float4(static_cast<float>(C6[4]), static_cast<float>(C6[5]), 0.f, 0.f);
+}
+
 // One member of a merge (read with scalar loads): its records, its pose with the offset between the two device
 // frames folded in — t = (R o_m + t_m) - o, formed on the host in double — and its stretch of the output.
 struct MergeMember {
@@ -232,8 +268,7 @@ struct MergeMember {
 static_assert(sizeof(MergeMember) % 8 == 0, "the table is copied in 8-byte words");
 
 // Posed clouds -> one cloud: workgroup b moves 256 points of the member m with prefix[m] <= b < prefix[m + 1] to their place in the
-// concatenation.  Points R r + t, normals R n and covariances R C R^T are evaluated in double from the fp32 records, with the insert
-// kernels' expressions (voxelmap.hip: fvm_update_kernel, ivm_update_kernel), and rounded once; w is the point's index in the output.  box != null: the
+// concatenation, each record posed by the member's pose (above); w is the point's index in the output.  box != null: the
 // bounding box of the posed points that are finite, taken BEFORE the rounding (which is monotone: the rounded box bounds the records
 // exactly), leaves as a note in payload words 1..6 (box64_reduce_publish).
 __global__ __launch_bounds__(kIoBlock) void merge_cloud_kernel(const MergeMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov,
@@ -246,40 +281,69 @@ __global__ __launch_bounds__(kIoBlock) void merge_cloud_kernel(const MergeMember
   if (i < g.n) {
     const Pose12& T = g.T;
     const uint32_t j = g.off + i;
-    const float4 p = g.pts[i];
-    const double x = T.r[0] * p.x + T.r[1] * p.y + T.r[2] * p.z + T.t[0];
-    const double y = T.r[3] * p.x + T.r[4] * p.y + T.r[5] * p.z + T.t[1];
-    const double z = T.r[6] * p.x + T.r[7] * p.y + T.r[8] * p.z + T.t[2];
+    double x, y, z;
+    posed_point(T, g.pts[i], x, y, z);
     opts[j] = make_float4(static_cast<float>(x), static_cast<float>(y), static_cast<float>(z), __uint_as_float(j));
     if (x - x == 0.0 && y - y == 0.0 && z - z == 0.0) lo[0] = hi[0] = x, lo[1] = hi[1] = y, lo[2] = hi[2] = z;  // a non-finite point stays out of the box
-    if (onrm != nullptr) {
-      const float4 q = g.nrm[i];
-      double N[3];
-#pragma unroll
-      for (int a = 0; a < 3; a++) N[a] = T.r[3 * a] * q.x + T.r[3 * a + 1] * q.y + T.r[3 * a + 2] * q.z;
-      onrm[j] = make_float4(static_cast<float>(N[0]), static_cast<float>(N[1]), static_cast<float>(N[2]), 0.f);
-    }
-    if (ocov != nullptr) {
-      const float4* cin = reinterpret_cast<const float4*>(g.cov + i);
-      const float4 c0 = cin[0], c1 = cin[1];  // xx xy xz yy | yz zz 0 0
-      const double Cm[3][3] = {{c0.x, c0.y, c0.z}, {c0.y, c0.w, c1.x}, {c0.z, c1.x, c1.y}};
-      double RC[3][3], C6[6];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) RC[a][b] = T.r[3 * a] * Cm[0][b] + T.r[3 * a + 1] * Cm[1][b] + T.r[3 * a + 2] * Cm[2][b];
-      int k = 0;
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = a; b < 3; b++) C6[k++] = RC[a][0] * T.r[3 * b] + RC[a][1] * T.r[3 * b + 1] + RC[a][2] * T.r[3 * b + 2];
-      float4* cout = reinterpret_cast<float4*>(ocov + j);
-      cout[0] = make_float4(static_cast<float>(C6[0]), static_cast<float>(C6[1]), static_cast<float>(C6[2]), static_cast<float>(C6[3]));
-      cout[1] = make_float4(static_cast<float>(C6[4]), static_cast<float>(C6[5]), 0.f, 0.f);
-    }
+    if (onrm != nullptr) onrm[j] = posed_normal_record(T, g.nrm[i]);
+    if (ocov != nullptr) posed_cov_record(T, g.cov + i, ocov + j);
   }
   if (box == nullptr) return;  // (uniform)
   box64_reduce_publish(lo, hi, box, note_slot, seq);
+}
+
+// One member of a deskew (read with scalar loads): its records and where they go, its times, what its twist
+// and its origin contribute to every point's pose (lie.hpp), and where its box is reduced and handed over.
+struct DeskewMember {
+  const float4* pts;
+  const float4* nrm;  // or null
+  const Cov8* cov;
+  float4* opts;
+  float4* onrm;
+  Cov8* ocov;
+  const void* times;         // float or double (tf64), tstride elements apart: device memory, or pinned host memory by its device address
+  unsigned long long* acc;   // {min x y z, max x y z (encoded), arrival counter, 0} in the call's table, identity values and 0 at the start; null: no box
+  unsigned long long* slot;  // six words of the context's box block (pinned, device-mapped)
+  double ref_time;
+  TwistConst c;
+  uint32_t n, blocks;
+  int tstride, tf64;
+};
+static_assert(sizeof(DeskewMember) % 8 == 0, "the table is copied in 8-byte words");
+
+// Sweeps -> sweeps as seen from the sensor frame at ref_time: workgroup b takes 256 points of the member m with prefix[m] <= b <
+// prefix[m + 1]; point i gets the pose exp((s_i - ref_time) xi) — in double, from the member's constants, with no cancellation for any
+// angle (lie.hpp) — and is posed as a member of a merge is.  w is the index.  A non-finite time makes every entry of the pose a NaN.
+// g.acc != null: the box of the member's finite unrounded points is joined in its accumulator; the member's last workgroup writes it into
+// the member's words of the box block, and the last member to arrive publishes the call's sequence number (forest_box_arrive).
+__global__ __launch_bounds__(kIoBlock) void deskew_cloud_kernel(const DeskewMember* __restrict__ members, const uint32_t* __restrict__ prefix_g, int count, const ForestBoxes hand) {
+  __shared__ bool sh_last;
+  const uint32_t* prefix = uniform_const(prefix_g);
+  const int m = forest_member_of(prefix, count, blockIdx.x);
+  const DeskewMember& g = *uniform_const(members + m);
+  const uint32_t i = (blockIdx.x - prefix[m]) * static_cast<uint32_t>(kIoBlock) + threadIdx.x;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  if (i < g.n) {
+    const size_t ti = static_cast<size_t>(i) * static_cast<size_t>(g.tstride);
+    const double s = g.tf64 ? static_cast<const double*>(g.times)[ti] : static_cast<double>(static_cast<const float*>(g.times)[ti]);
+    Pose12 T;
+    twist_pose(g.c, s - g.ref_time, T.r, T.t);
+    double x, y, z;
+    posed_point(T, g.pts[i], x, y, z);
+    g.opts[i] = make_float4(static_cast<float>(x), static_cast<float>(y), static_cast<float>(z), __uint_as_float(i));
+    if (x - x == 0.0 && y - y == 0.0 && z - z == 0.0) lo[0] = hi[0] = x, lo[1] = hi[1] = y, lo[2] = hi[2] = z;  // a non-finite point stays out of the box
+    if (g.onrm != nullptr) g.onrm[i] = posed_normal_record(T, g.nrm[i]);
+    if (g.ocov != nullptr) posed_cov_record(T, g.cov + i, g.ocov + i);
+  }
+  if (g.acc == nullptr) return;  // (uniform: a call has boxes for all members or for none)
+  box64_reduce_block(lo, hi, g.acc);
+  if (threadIdx.x == 0) sh_last = __hip_atomic_fetch_add(&g.acc[6], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == g.blocks - 1u;
+  __syncthreads();
+  if (!sh_last) return;  // workgroup-uniform
+  if (threadIdx.x < 6) g.slot[threadIdx.x] = __hip_atomic_load(&g.acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) forest_box_arrive(hand);
 }
 
 namespace {
@@ -712,6 +776,157 @@ static void host_bbox(const S* xyz, size_t n, size_t stride, double lo[3], doubl
     }
 }
 
+// ---- sga_cloud_deskew ------------------------------------------------------------------------------------------
+static std::atomic<unsigned long long> g_deskew_launches{0};
+
+// `count` sweeps, each point of member k posed by exp((s - ref_time_k) xi_k): one table — [members][prefix of the grid][box accumulators]
+// [ticket] — copied with one command, and ONE launch over the concatenation.  The times come from host arrays (times != null: all members'
+// in ONE slot of the staging ring, which the kernel reads by its device address) or, for a single member, from a device array (dtimes).
+// A blocking context waits for the members' boxes (the context's box block: its one wait); a stream-ordered one waits for nothing.
+static int cloud_deskew(sga_context* ctx, const sga_cloud* const* clouds, const float* const* times, const sga_device_array* dtimes, const double* twists, const double* ref_times, size_t count, void* user_stream, int flags, sga_cloud** out) {
+  for (size_t k = 0; out != nullptr && k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  if (!ctx || (count > 0 && (!out || !clouds || (!times && !dtimes) || !twists))) return fail(SGA_ERR_INVALID, "null argument");
+  if (count > kMergeMaxMembers) return fail(SGA_ERR_INVALID, "too many members (%zu; limit %zu)", count, kMergeMaxMembers);
+  for (size_t k = 0; k < count; k++) {
+    if (!clouds[k]) return fail(SGA_ERR_INVALID, "null argument: clouds[%zu] is NULL", k);
+    if (times != nullptr && !times[k]) return fail(SGA_ERR_INVALID, "null argument: times[%zu] is NULL", k);
+  }
+  for (size_t k = 0; k < count; k++) {
+    for (int e = 0; e < 6; e++)
+      if (!(twists[6 * k + e] - twists[6 * k + e] == 0.0)) return fail(SGA_ERR_INVALID, "twist %zu has a non-finite entry", k);
+    if (ref_times != nullptr && !(ref_times[k] - ref_times[k] == 0.0)) return fail(SGA_ERR_INVALID, "reference time %zu is not finite", k);
+  }
+  if (count == 0) return SGA_OK;
+  // ---- (from here on the handles are read)
+  std::vector<size_t> live;  // empty members take no workgroups
+  size_t total = 0, blocks = 0;
+  for (size_t k = 0; k < count; k++) {
+    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
+    if (clouds[k]->n == 0) continue;
+    live.push_back(k);
+    total += clouds[k]->n;
+    blocks += (clouds[k]->n + kIoBlock - 1) / kIoBlock;
+  }
+  if (blocks >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many points in all (%zu)", total);
+  if (!live.empty()) SGA_HIP(hipSetDevice(ctx->device));
+  for (size_t k : live) {
+    if (times != nullptr) {
+      bool on_device = false;
+      (void)pinned_device_view(times[k], clouds[k]->n * sizeof(float), &on_device);
+      if (on_device) return fail(SGA_ERR_INVALID, "times[%zu] is device memory: times that live on the device go through sga_cloud_deskew_device", k);
+    } else {
+      const size_t elem = dtimes->dtype == SGA_F64 ? 8 : 4;
+      size_t span = 0;  // the last element read ends here: a column of a wider array need not own the rest of its last row
+      if (__builtin_mul_overflow(clouds[k]->n - 1, static_cast<size_t>(dtimes->stride) * elem, &span) || __builtin_add_overflow(span, elem, &span))
+        return fail(SGA_ERR_INVALID, "times: %zu rows of stride %d overflow the address space", clouds[k]->n, dtimes->stride);
+      SGA_TRY(check_device_range(ctx, dtimes->data, span, elem, "times", "sga_cloud_deskew"));
+    }
+  }
+  StreamScope stream_scope(ctx->stream);
+  std::vector<std::unique_ptr<sga_cloud>> made(count);
+  for (size_t k = 0; k < count; k++) {
+    const sga_cloud* in = clouds[k];
+    std::unique_ptr<sga_cloud> c(new sga_cloud);
+    c->device = ctx->device;
+    c->n = in->n;
+    for (int a = 0; a < 3; a++) c->origin[a] = in->origin[a];  // a sweep moves by metres: it stays in its frame
+    if (in->n > 0) {  // (an empty member: an empty cloud without attributes)
+      c->has_normals = in->has_normals;
+      c->has_covs = in->has_covs;
+      SGA_TRY(c->pts.alloc(in->n));
+      if (in->has_normals) SGA_TRY(c->nrm.alloc(in->n));
+      if (in->has_covs) SGA_TRY(c->cov.alloc(in->n));
+    }
+    made[k] = std::move(c);
+  }
+  auto hand_over = [&]() {
+    for (size_t k = 0; k < count; k++) out[k] = made[k].release();
+    return SGA_OK;
+  };
+  if (live.empty()) return hand_over();
+  const size_t L = live.size();
+  const bool want_box = !ctx->stream_ordered;
+  for (size_t k : live) SGA_TRY(wait_ready(ctx, clouds[k]->ready));  // made by another context in stream-ordered mode (common.hpp: Ready)
+  // ---- host times: all members' in one slot of the staging ring
+  sga_context::StageSlot* tslot = nullptr;
+  if (times != nullptr) {
+    SGA_TRY(stage_acquire(ctx, total * sizeof(float), &tslot));
+    size_t off = 0;
+    for (size_t k : live) {
+      std::memcpy(static_cast<float*>(tslot->host) + off, times[k], clouds[k]->n * sizeof(float));
+      off += clouds[k]->n;
+    }
+  }
+  // ---- the table
+  const size_t member_words = L * (sizeof(DeskewMember) / 8), prefix_words = (L + 2) / 2, acc_words = want_box ? 8 * L : 0;
+  const size_t words = member_words + prefix_words + acc_words + 1;
+  DevBuf<unsigned long long> table;  // lives to the end of the call (then: the stream's free list)
+  SGA_TRY(table.alloc(words));
+  ForestBoxes hand{nullptr, 0u, nullptr, 0ull};
+  if (want_box) {
+    SGA_TRY(forest_box_block(ctx, 2 * L));  // eight words per member behind the block's four
+    hand.ticket = reinterpret_cast<unsigned*>(table.p + member_words + prefix_words + acc_words);
+    hand.total = static_cast<unsigned>(L);
+    hand.seq_word = ctx->h_forest_dev;
+    hand.seq = ++ctx->forest_seq;
+  }
+  std::vector<DeskewMember> members(L);
+  std::vector<uint32_t> prefix(L + 1, 0u);
+  size_t toff = 0;
+  for (size_t j = 0; j < L; j++) {
+    const size_t k = live[j];
+    const sga_cloud* in = clouds[k];
+    DeskewMember& g = members[j];
+    std::memset(&g, 0, sizeof(g));
+    g.pts = in->pts.p, g.nrm = in->has_normals ? in->nrm.p : nullptr, g.cov = in->has_covs ? in->cov.p : nullptr;
+    g.opts = made[k]->pts.p, g.onrm = made[k]->nrm.p, g.ocov = made[k]->cov.p;
+    if (times != nullptr) {
+      g.times = static_cast<const float*>(tslot->dev) + toff, g.tstride = 1, g.tf64 = 0;
+      toff += in->n;
+    } else {
+      g.times = dtimes->data, g.tstride = dtimes->stride, g.tf64 = dtimes->dtype == SGA_F64 ? 1 : 0;
+    }
+    if (want_box) g.acc = table.p + member_words + prefix_words + 8 * j, g.slot = ctx->h_forest_dev + 4 + 8 * j;
+    g.ref_time = ref_times ? ref_times[k] : 1.0;
+    g.c = twist_const(twists + 6 * k, in->origin);
+    g.n = static_cast<uint32_t>(in->n);
+    g.blocks = (g.n + kIoBlock - 1u) / kIoBlock;
+    prefix[j + 1] = prefix[j] + g.blocks;
+  }
+  IoOrder ord;
+  if (dtimes != nullptr) SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
+    std::memset(host, 0, words * 8);
+    std::memcpy(host, members.data(), member_words * 8);
+    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
+    for (size_t w = 0; w < acc_words; w++) {
+      const size_t e = w % 8;
+      host[member_words + prefix_words + w] = e < 3 ? box_enc64(INFINITY) : e < 6 ? box_enc64(-INFINITY) : 0ull;
+    }
+    g_deskew_launches.fetch_add(1, std::memory_order_relaxed);
+  }));
+  g_deskew_launches.fetch_add(1, std::memory_order_relaxed);
+  hipLaunchKernelGGL(deskew_cloud_kernel, dim3(prefix[L]), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<const DeskewMember*>(table.p), reinterpret_cast<const uint32_t*>(table.p + member_words), static_cast<int>(L), hand);
+  SGA_HIP(hipGetLastError());
+  if (tslot != nullptr && ctx->stream_ordered) SGA_TRY(stage_release(ctx, tslot));  // (a blocking context: the wait below shows that the kernel is over)
+  if (want_box) {
+    const int rc = forest_boxes_wait(ctx, hand.seq, "boxes of a deskew");
+    if (rc != SGA_OK) {
+      (void)hipStreamSynchronize(ctx->stream);  // nothing of this call stays in flight
+      (void)hipGetLastError();
+      return rc;
+    }
+    for (size_t j = 0; j < L; j++) {
+      double lo[3], hi[3];
+      for (int a = 0; a < 3; a++) lo[a] = box_dec64(ctx->h_forest[4 + 8 * j + a]), hi[a] = box_dec64(ctx->h_forest[4 + 8 * j + 3 + a]);
+      cloud_set_box(made[live[j]].get(), lo, hi, true, false);  // the rounding is monotone: the rounded box of the unrounded records is the box of the records
+    }
+  }
+  if (dtimes != nullptr) SGA_TRY(io_end(ctx, ord));
+  for (size_t k : live) SGA_TRY(mark_ready(ctx, made[k]->ready));
+  return hand_over();
+}
+
 namespace sga {
 // absolute fp32 coordinates, recentred about a GIVEN origin (multi.hip: the shards of one source share a device frame)
 int cloud_create_f32_about(sga_context* ctx, const float* xyz, const float* normals, const float* cov6, size_t n, const double origin[3], sga_cloud** out) {
@@ -828,6 +1043,30 @@ int sga_cloud_slice(sga_context* ctx, const sga_cloud* cloud, size_t first, size
 int sga_cloud_merge(sga_context* ctx, const sga_cloud* const* clouds, const double* T, size_t count, const double origin[3], sga_cloud** out) { return cloud_merge(ctx, clouds, T, count, origin, out); }
 
 int sga_cloud_transform(sga_context* ctx, const sga_cloud* cloud, const double T[16], const double origin[3], sga_cloud** out) { return cloud_merge(ctx, &cloud, T, 1, origin, out); }
+
+// Sweeps deskewed on the device: every point posed by exp((its time - ref_time) twist), DESIGN.md section 3.19
+int sga_cloud_deskew_batch(sga_context* ctx, const sga_cloud* const* clouds, const float* const* times, const double* twists, const double* ref_times, size_t count, sga_cloud** out) {
+  return cloud_deskew(ctx, clouds, times, nullptr, twists, ref_times, count, nullptr, 0, out);
+}
+
+int sga_cloud_deskew(sga_context* ctx, const sga_cloud* cloud, const float* times, const double twist[6], double ref_time, sga_cloud** out) {
+  if (!out) return fail(SGA_ERR_INVALID, "null argument");
+  return cloud_deskew(ctx, &cloud, &times, nullptr, twist, &ref_time, 1, nullptr, 0, out);
+}
+
+int sga_cloud_deskew_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* times, const double twist[6], double ref_time, void* user_stream, int flags, sga_cloud** out) {
+  if (out) *out = nullptr;
+  if (!out || !times) return fail(SGA_ERR_INVALID, "null argument");
+  if (times->dtype != SGA_F32 && times->dtype != SGA_F64) return fail(SGA_ERR_INVALID, "times: dtype %d is neither SGA_F32 nor SGA_F64", times->dtype);
+  if (times->cols != 1 || times->stride < 1) return fail(SGA_ERR_INVALID, "times: cols = %d, stride = %d (one time per row, rows one element or more apart)", times->cols, times->stride);
+  return cloud_deskew(ctx, &cloud, nullptr, times, twist, &ref_time, 1, user_stream, flags, out);
+}
+
+int sga_debug_cloud_deskew_launches(unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_deskew_launches.load(std::memory_order_relaxed);
+  return SGA_OK;
+}
 
 int sga_debug_cloud_merge_launches(unsigned long long* launches) {
   if (!launches) return fail(SGA_ERR_INVALID, "null argument");

@@ -10,6 +10,7 @@
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "lie.hpp"
 
 namespace sga {
 
@@ -393,9 +394,50 @@ void sga_registration_setting_default(sga_registration_setting* s) {
   for (int i = 0; i < 6; i++) s->restrict_dof_mask[i] = 1.0;
 }
 
+// The public exponential and its inverse are evaluated without cancellation (lie.hpp).  The optimizer keeps
+// se3_exp above — the reference's expressions, whose (1 - cos) / theta^2 loses digits at small angles — so that a registration's poses
+// stay the reference's.
 void sga_se3_exp(const double twist[6], double T[16]) {
-  const M4 m = se3_exp(twist);
-  memcpy(T, m.a, sizeof(m.a));
+  static const double zero[3] = {0, 0, 0};
+  const TwistConst c = twist_const(twist, zero);
+  double r[9], t[3];
+  twist_pose(c, 1.0, r, t);
+  for (int col = 0; col < 4; col++)
+    for (int row = 0; row < 4; row++) T[4 * col + row] = row == 3 ? (col == 3 ? 1.0 : 0.0) : col == 3 ? t[row] : r[3 * row + col];
+}
+
+// T (a rigid transform with rotation angle theta < pi) -> the twist whose exponential it is.  omega = (theta / sin theta) w with
+// w = vee(R - R^T) / 2 and theta = atan2(|w|, (tr R - 1) / 2): a quotient of two accurate numbers, or the series of asin(s) / s below
+// s = 0.01; what is lost towards pi is what R itself no longer holds, a factor 1 / (pi - theta).  v solves V v = t with
+// V = I + (1 - cos) / theta K + (theta - sin) / theta K^2 from lie.hpp's coefficients; V's condition number is at most pi / 2.
+void sga_se3_log(const double T[16], double twist[6]) {
+  auto R = [&](int row, int col) { return T[4 * col + row]; };
+  const double w[3] = {0.5 * (R(2, 1) - R(1, 2)), 0.5 * (R(0, 2) - R(2, 0)), 0.5 * (R(1, 0) - R(0, 1))};
+  const double m = std::fmax(std::fabs(w[0]), std::fmax(std::fabs(w[1]), std::fabs(w[2])));
+  double s = 0.0;
+  if (m > 0.0) s = m * std::sqrt((w[0] / m) * (w[0] / m) + (w[1] / m) * (w[1] / m) + (w[2] / m) * (w[2] / m));
+  const double c = 0.5 * (R(0, 0) + R(1, 1) + R(2, 2) - 1.0);
+  const double q = s * s;
+  const double factor = (c > 0.0 && s < 1e-2) ? 1.0 + q * (1.0 / 6.0 + q * (3.0 / 40.0 + q * (15.0 / 336.0 + q * (105.0 / 3456.0)))) : std::atan2(s, c) / s;
+  double xi[6] = {factor * w[0], factor * w[1], factor * w[2], 0.0, 0.0, 0.0};
+  static const double zero[3] = {0, 0, 0};
+  const TwistConst k = twist_const(xi, zero);
+  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  if (k.theta > 0.0) {
+    const RotCoef f = rot_coef(k.theta);
+    const double b = f.c2 / k.theta, d = f.f3 / k.theta;
+    const double K[3][3] = {{0, -k.k[2], k.k[1]}, {k.k[2], 0, -k.k[0]}, {-k.k[1], k.k[0], 0}};
+    const double KK[3][3] = {{k.kk[0], k.kk[1], k.kk[2]}, {k.kk[1], k.kk[3], k.kk[4]}, {k.kk[2], k.kk[4], k.kk[5]}};
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) V[i][j] += b * K[i][j] + d * KK[i][j];
+  }
+  // v = adj(V) t / det V
+  const double A[3][3] = {{V[1][1] * V[2][2] - V[1][2] * V[2][1], V[0][2] * V[2][1] - V[0][1] * V[2][2], V[0][1] * V[1][2] - V[0][2] * V[1][1]},
+                          {V[1][2] * V[2][0] - V[1][0] * V[2][2], V[0][0] * V[2][2] - V[0][2] * V[2][0], V[0][2] * V[1][0] - V[0][0] * V[1][2]},
+                          {V[1][0] * V[2][1] - V[1][1] * V[2][0], V[0][1] * V[2][0] - V[0][0] * V[2][1], V[0][0] * V[1][1] - V[0][1] * V[1][0]}};
+  const double det = V[0][0] * A[0][0] + V[0][1] * A[1][0] + V[0][2] * A[2][0];
+  for (int i = 0; i < 3; i++) xi[3 + i] = (A[i][0] * T[12] + A[i][1] * T[13] + A[i][2] * T[14]) / det;
+  for (int i = 0; i < 6; i++) twist[i] = xi[i];
 }
 
 int sga_optimize(const sga_registration_setting* setting, const double init_T[16], sga_linearize_fn linearize, sga_error_fn error, void* user, sga_result* out) {

@@ -36,6 +36,7 @@ class OnlineOdometry:
         self._prev_mode = self.ctx.set_stream_ordered(True)
         self.target = None  # (cloud, tree)
         self.T_world = np.eye(4)
+        self.motion = None  # the last registration's relative pose: the constant-velocity guess a raw sweep is deskewed with
         self.reg_ms = []
         self.total_ms = []
         self.iterations = []
@@ -52,10 +53,19 @@ class OnlineOdometry:
         except Exception:  # noqa: BLE001
             pass
 
-    def estimate(self, points):
-        """points: (N,3|4) float32 in the sensor frame. Returns T_world_sensor of this scan."""
+    def estimate(self, points, times=None):
+        """points: (N,3|4) float32 in the sensor frame. Returns T_world_sensor of this scan.
+        times: None — the scan is a rigid snapshot — or the time of every point within its sweep, 0 = start .. 1 = end (numpy (N,), or a
+        torch tensor on the context's device): the points are a RAW sweep, each in the sensor frame of its own instant, and are deskewed on
+        the device ahead of the voxel grid (PointCloud.deskewed) to the sweep's end under constant velocity — the twist is se3_log of the
+        previous frame's relative motion.  The first frame, which has no motion before it, is taken as it is; so is the second when it is
+        registered (two sweeps skewed alike still give their relative motion), but it becomes the third frame's target deskewed by the
+        motion it has just yielded: a deskewed scan is never registered against a skewed one."""
         t0 = time.perf_counter()
         raw = api.PointCloud(points, ctx=self.ctx)
+        bootstrap = times is not None and self.motion is None and self.target is not None  # the first registration of a sequence of sweeps
+        if times is not None and self.motion is not None:
+            raw = raw.deskewed(times, api.se3_log(self.motion), 1.0)
         cloud = api.voxelgrid_sampling(raw, self.res)
         self.ctx.synchronize()
         t1 = time.perf_counter()
@@ -71,7 +81,12 @@ class OnlineOdometry:
                 src = cloud.slice(lo, hi - lo)
             res = api.Problem(tgt_tree, src, np.eye(4)).align(self.setting, np.eye(4))
             self.T_world = self.T_world @ res.T_target_source
+            self.motion = res.T_target_source
             self.iterations.append(res.iterations + 1)
+            if bootstrap:  # once per sequence: this scan again, deskewed, as the next frame's target
+                cloud = api.voxelgrid_sampling(raw.deskewed(times, api.se3_log(self.motion), 1.0), self.res)
+                tree = api.KdTree(cloud)
+                api.estimate_covariances(cloud, tree, self.k)
         self.ctx.synchronize()
         t2 = time.perf_counter()
         self.target = (cloud, tree)
@@ -382,27 +397,34 @@ class PipelinedOdometry:
         return poses, wall, iters
 
 
-def run_synthetic(num_frames=20, pinned=False, **kw):
+def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, **kw):
     """Drive OnlineOdometry over the frozen KITTI-shaped synthetic sequence (small_gicp_amd.synthetic.kitti_like_scan).
     pinned: the scans are held in pinned host memory (api.pinned_copy) before the timed loop, like a driver that reads its scans into
     memory from sga_host_alloc — the reference's benchmark holds them in host memory too (benchmark/benchmark_odom.hpp:36-47); the upload
-    then has no CPU pass."""
+    then has no CPU pass.
+    sweeps: the scans are RAW sweeps of a spinning sensor (synthetic.kitti_like_sweep of frames 1 .. num_frames: every column measured
+    from the pose of its own instant) and are handed to the estimator with their times, which deskews them on the device; times=False
+    withholds the times, so the skewed sweeps are registered as if they were snapshots (what the deskew is compared against)."""
     from . import synthetic
 
     odom = OnlineOdometry(**kw)
     est, gt, sizes = [], [], []
     # every scan is in host memory before the loop starts, as in the reference's driver (benchmark/benchmark_odom.hpp:36-47; the generator
     # is ~50 ms of host work per scan: run between the frames it would leave the GPU idle and clocked down)
-    scans, T0 = [], None
+    scans, stamps, T0 = [], [], None
     for f in range(num_frames):
-        pts, Tws = synthetic.kitti_like_scan(f)
+        if sweeps:
+            pts, ts, Tws = synthetic.kitti_like_sweep(f + 1)[:3]
+            stamps.append(ts if times else None)
+        else:
+            pts, Tws = synthetic.kitti_like_scan(f)
         scans.append(api.pinned_copy(pts[:, :3], np.float32) if pinned else np.ascontiguousarray(pts[:, :3], dtype=np.float32))
         if T0 is None:
             T0 = Tws
         sizes.append(len(pts))
         gt.append(np.linalg.inv(T0) @ Tws)
-    for pts in scans:
-        est.append(odom.estimate(pts))
+    for f, pts in enumerate(scans):
+        est.append(odom.estimate(pts, stamps[f]) if sweeps else odom.estimate(pts))
     # relative pose error per frame pair (what scan-to-scan registration controls)
     rpe_t, rpe_r = [], []
     for i in range(1, num_frames):
@@ -421,6 +443,9 @@ def run_synthetic(num_frames=20, pinned=False, **kw):
         "mean_iterations": float(np.mean(odom.iterations)) if odom.iterations else 0.0,
         "rpe_trans_m_mean": float(np.mean(rpe_t)) if rpe_t else 0.0,
         "rpe_rot_rad_mean": float(np.mean(rpe_r)) if rpe_r else 0.0,
+        "rpe_trans_m": rpe_t,
+        "ate_trans_m_max": max(float(np.linalg.norm(e[:3, 3] - g[:3, 3])) for e, g in zip(est, gt)),
+        "sweeps": bool(sweeps),
         "estimated": est,
         "ground_truth": gt,
     }

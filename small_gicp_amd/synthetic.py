@@ -60,18 +60,19 @@ def registration_pair(n, target_seed=1, source_seed=2):
     return target, source, T
 
 
-def kitti_like_scan(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
-    """C5: one ~130k-return scan of the scene from a sensor 1.8 m above ground moving 1 m/frame with 1 deg/frame yaw.
-    Rays are cast against the ground plane and the 30 walls analytically; returns beyond 80 m or closer than 3 m are dropped.
-    Returns (points in the sensor frame float32 (N,3), T_world_sensor)."""
+def _walls(layout_seed):
     lay = np.random.default_rng(layout_seed)
     nwalls = 30
     centers = lay.uniform(-45, 45, size=(nwalls, 2))
     lengths = lay.uniform(2, 20, size=nwalls)
     heights = lay.uniform(2, 10, size=nwalls)
     along_x = lay.integers(0, 2, size=nwalls).astype(bool)
+    return centers, lengths, heights, along_x
+
+
+def _sensor_pose(frame):
+    """T_world_sensor of a frame: 1.8 m above ground, 1 m/frame on a gentle arc starting near the scene centre, 1 deg/frame yaw"""
     yaw = np.deg2rad(1.0 * frame)
-    # drive on a gentle arc starting near the scene centre
     pos = np.array([-30.0, -20.0, 1.8])
     for f in range(frame):
         a = np.deg2rad(1.0 * f)
@@ -79,30 +80,79 @@ def kitti_like_scan(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02,
     Tws = np.eye(4)
     Tws[:3, :3] = _rot([0, 0, 1], yaw)
     Tws[:3, 3] = pos
+    return Tws
+
+
+def _ring_directions(n_rings, n_az):
+    """unit rays of the sensor frame, ring-major: ray ring * n_az + column"""
     el = np.deg2rad(np.linspace(-24.8, 2.0, n_rings))
     az = np.linspace(-np.pi, np.pi, n_az, endpoint=False)
     EL, AZ = np.meshgrid(el, az, indexing="ij")
-    d_s = np.stack([np.cos(EL) * np.cos(AZ), np.cos(EL) * np.sin(AZ), np.sin(EL)], axis=-1).reshape(-1, 3)
-    d = d_s @ Tws[:3, :3].T
-    o = pos
+    return np.stack([np.cos(EL) * np.cos(AZ), np.cos(EL) * np.sin(AZ), np.sin(EL)], axis=-1).reshape(-1, 3)
+
+
+def _cast(o, d, layout):
+    """Rays o + t d (o: one origin (3,) or one per ray (N,3); d (N,3), world frame) against the ground plane and the walls, analytically:
+    (range of the nearest hit or inf, the surface it belongs to: -1 ground, else the wall number)"""
+    centers, lengths, heights, along_x = layout
     t_best = np.full(len(d), np.inf)
+    surface = np.full(len(d), -1)
     # ground z = 0
     with np.errstate(divide="ignore", invalid="ignore"):
-        tg = -o[2] / d[:, 2]
+        tg = -o[..., 2] / d[:, 2]
         hit = o + tg[:, None] * d
     ok = (tg > 0) & np.isfinite(tg)
     ok &= (np.abs(hit[:, 0]) <= 50) & (np.abs(hit[:, 1]) <= 50)
     t_best = np.where(ok, tg, t_best)
-    for w in range(nwalls):
+    for w in range(len(lengths)):
         ax = 1 if along_x[w] else 0  # wall plane is constant in this axis
         other = 1 - ax
         with np.errstate(divide="ignore", invalid="ignore"):
-            tw = (centers[w, ax] - o[ax]) / d[:, ax]
+            tw = (centers[w, ax] - o[..., ax]) / d[:, ax]
             hitw = o + tw[:, None] * d
         okw = (tw > 0) & np.isfinite(tw) & (np.abs(hitw[:, other] - centers[w, other]) <= 0.5 * lengths[w]) & (hitw[:, 2] >= 0) & (hitw[:, 2] <= heights[w])
-        t_best = np.where(okw & (tw < t_best), tw, t_best)
+        nearer = okw & (tw < t_best)
+        t_best = np.where(nearer, tw, t_best)
+        surface = np.where(nearer, w, surface)
+    return t_best, surface
+
+
+def kitti_like_scan(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
+    """C5: one ~130k-return scan of the scene from a sensor 1.8 m above ground moving 1 m/frame with 1 deg/frame yaw.
+    Rays are cast against the ground plane and the 30 walls analytically; returns beyond 80 m or closer than 3 m are dropped.
+    Returns (points in the sensor frame float32 (N,3), T_world_sensor)."""
+    Tws = _sensor_pose(frame)
+    d_s = _ring_directions(n_rings, n_az)
+    d = d_s @ Tws[:3, :3].T
+    t_best, _ = _cast(Tws[:3, 3], d, _walls(layout_seed))
     keep = np.isfinite(t_best) & (t_best >= 3.0) & (t_best <= 80.0)
     rng = np.random.default_rng(seed + frame)
     r = t_best[keep] + rng.normal(0, noise, keep.sum())
     pts = d_s[keep] * r[:, None]
     return np.ascontiguousarray(pts, dtype=np.float32), Tws
+
+
+def kitti_like_sweep(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
+    """The scan of kitti_like_scan(frame) as a spinning sensor delivers it: RAW, every azimuth column cast from the pose the sensor has at
+    its own firing time.  The sweep starts at the pose of frame - 1 and ends at the pose of `frame` (frame >= 1); with
+    xi = se3_log(T(frame - 1)^-1 T(frame)), column c fires at s = float32((c + 0.5) / n_az) from T(frame - 1) exp(s xi).
+    Returns (points in the sensor frame AT FIRING TIME float32 (N,3), times float32 (N,), T_world_sensor at the sweep's end, xi (6,),
+    surface (N,): the surface each return hit, -1 = ground, else the wall number).  Deskewed with xi to ref_time = 1 — p' =
+    exp((s - 1) xi) p — the points are what a rigid snapshot at T_world_sensor would have measured."""
+    from .api import se3_exp, se3_log
+
+    if int(frame) < 1:
+        raise ValueError("kitti_like_sweep: a sweep ends at its frame and starts at the one before, so frame >= 1")
+    T0, T1 = _sensor_pose(frame - 1), _sensor_pose(frame)
+    xi = se3_log(np.linalg.inv(T0) @ T1)
+    s_col = ((np.arange(n_az) + 0.5) / n_az).astype(np.float32)
+    T_col = np.stack([T0 @ se3_exp(float(s) * xi) for s in s_col])  # (n_az, 4, 4)
+    d_s = _ring_directions(n_rings, n_az)
+    col = np.tile(np.arange(n_az), n_rings)
+    d = np.einsum("nij,nj->ni", T_col[col, :3, :3], d_s)
+    t_best, surface = _cast(T_col[col, :3, 3], d, _walls(layout_seed))
+    keep = np.isfinite(t_best) & (t_best >= 3.0) & (t_best <= 80.0)
+    rng = np.random.default_rng(seed + frame)
+    r = t_best[keep] + rng.normal(0, noise, keep.sum())
+    pts = d_s[keep] * r[:, None]
+    return np.ascontiguousarray(pts, dtype=np.float32), np.ascontiguousarray(s_col[col][keep]), T1, xi, surface[keep]
