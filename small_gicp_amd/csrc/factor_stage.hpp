@@ -265,7 +265,7 @@ __device__ __forceinline__ void linearize_group(const LinParams<Real>& p0, int f
     } else if constexpr (TARGET == 1) {
       if (act[u]) {
         if (p.vox.offsets == 1)  // (wave-uniform) the default: the query's own voxel, no distance to compare
-          jn[u] = voxel_lookup(p.vox, static_cast<float>(Q[u][0]), static_cast<float>(Q[u][1]), static_cast<float>(Q[u][2]));
+          jn[u] = voxel_lookup<Real>(p.vox, Q[u][0], Q[u][1], Q[u][2]);
         else
           jn[u] = voxel_nearest<Real>(p.vox, p.tgt_pts, Q[u][0], Q[u][1], Q[u][2]);
       }

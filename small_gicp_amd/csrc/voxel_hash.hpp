@@ -37,8 +37,10 @@ __device__ __forceinline__ int fast_floor_d(double x) {
   return n - (x < static_cast<double>(n));
 }
 
-// returns voxel id or -1
-__device__ __forceinline__ int voxel_lookup(const VoxelView& v, float qx, float qy, float qz) {
+// returns voxel id or -1.  The query in the arithmetic of the pass (Real): fp64 passes floor the DOUBLE query, as the reference does — a
+// query just below a voxel face whose fp32 rounding lies on the face belongs to the lower voxel.
+template <typename Real>
+__device__ __forceinline__ int voxel_lookup(const VoxelView& v, Real qx, Real qy, Real qz) {
   const int cx = fast_floor_d((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
   const int cy = fast_floor_d((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
   const int cz = fast_floor_d((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
