@@ -19,13 +19,18 @@
 namespace sga {
 int build_cell_grid(sga_context* ctx, sga_index* idx);  // cell_grid.hip
 
-namespace {
-std::atomic<unsigned long long> g_forest_launches{0}, g_grid_forest_launches{0}, g_vox_forest_launches{0}, g_ivm_forest_launches{0};
-}  // namespace
+static std::atomic<unsigned long long> g_launches[static_cast<int>(Chain::kCount)];
+void count_launch(Chain chain) { g_launches[static_cast<int>(chain)].fetch_add(1, std::memory_order_relaxed); }
+int report_launches(Chain chain, unsigned long long* launches) {
+  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
+  *launches = g_launches[static_cast<int>(chain)].load(std::memory_order_relaxed);
+  return SGA_OK;
+}
 
-// the context's box block with room for `members` slots (grow-only; no call is in flight: every call waits for its boxes)
-int forest_box_block(sga_context* ctx, size_t members) {
-  const size_t need = 4 * members + 4;
+// the context's box block grows to the call's need (grow-only; no call is in flight: every call waits for its boxes)
+int forest_call_begin(sga_context* ctx, size_t members, size_t stride, unsigned long long* seq) {
+  const size_t need = 4 + stride * members;
+  *seq = ++ctx->forest_seq;
   if (ctx->forest_words >= need) return SGA_OK;
   if (ctx->h_forest) (void)hipHostFree(ctx->h_forest);
   ctx->h_forest = ctx->h_forest_dev = nullptr;
@@ -42,10 +47,18 @@ int forest_box_block(sga_context* ctx, size_t members) {
   return SGA_OK;
 }
 
-// the ONE wait of a forest call: all boxes (run counts) are there once the block shows the call's sequence number (wait_published, context.hip)
-int forest_boxes_wait(sga_context* ctx, unsigned long long seq, const char* what) {
-  const int rc = wait_published(ctx, ctx->h_forest, seq);
-  return rc == kNotPublished ? fail(SGA_ERR_HIP, "the %s were not published by the device", what) : rc;
+// all slots are written once the block shows the call's sequence number (wait_published, context.hip)
+int forest_call_wait(sga_context* ctx, int enqueued, unsigned long long seq, const char* what) {
+  int rc = enqueued;
+  if (rc == SGA_OK) {
+    rc = wait_published(ctx, ctx->h_forest, seq);
+    if (rc == kNotPublished) rc = fail(SGA_ERR_HIP, "the %s were not published by the device", what);
+  }
+  if (rc != SGA_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+  }
+  return rc;
 }
 
 namespace {
@@ -56,15 +69,8 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
   for (size_t k = 0; k < count; k++) {
     const sga_cloud* cloud = clouds[k];
     if (cloud->n == 0 || cloud->n > kForestMaxPoints) continue;  // the empty index below / the lone path
-    std::unique_ptr<sga_index> idx(new sga_index);  // as sga_index_build_kdtree sets it up
-    idx->kind = SGA_INDEX_KDTREE;
-    idx->device = ctx->device;
-    idx->n = cloud->n;
-    for (int a = 0; a < 3; a++) idx->origin[a] = cloud->origin[a];
-    idx->has_normals = cloud->has_normals;
-    idx->has_covs = cloud->has_covs;
     SGA_TRY(wait_ready(ctx, cloud->ready));
-    made[k] = std::move(idx);
+    made[k] = kd_index_new(ctx, cloud);
     forest.push_back(k);
     forest_points += cloud->n;
   }
@@ -74,7 +80,7 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
   if (!forest.empty()) {
     // ---- every allocation of every member, then the launches
     SGA_TRY(perms.alloc(2 * forest_points));
-    SGA_TRY(forest_box_block(ctx, forest.size()));
+    SGA_TRY(forest_call_begin(ctx, forest.size(), kSlotWords, &seq));
     std::vector<ForestTree> trees(forest.size());
     size_t at = 0;
     for (size_t j = 0; j < forest.size(); j++) {
@@ -86,12 +92,7 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
       idx->kd_depth = D;
       SGA_TRY(idx->kd_nodes.alloc(1ull << D));
       SGA_TRY(idx->kd_nodes4.alloc(kd_pair_count(D)));
-      SGA_TRY(idx->kd_pts.alloc(n + kKdLeafMax));
-      if (cloud->has_normals) SGA_TRY(idx->nrm.alloc(n));
-      if (cloud->has_covs) SGA_TRY(idx->cov.alloc(n));
-      SGA_TRY(idx->kd_boxes.alloc(4ull << D));
-      SGA_TRY(idx->kd_groups.alloc(8ull << (D - (D < 2 ? D : 2))));
-      SGA_TRY(idx->kd_leaf.alloc(8ull << D));
+      SGA_TRY(kd_index_alloc(idx, cloud, D));
       ForestTree& t = trees[j];
       std::memset(&t, 0, sizeof(t));
       t.pts = cloud->pts.p;
@@ -111,22 +112,16 @@ int build_kdtrees(sga_context* ctx, const sga_cloud* const* clouds, size_t count
       t.late_seq = late_note_begin(ctx->device, &t.late_slot);  // the length scale travels as a late note per index, as in the lone build
       idx->spacing = 0.0;
       idx->spacing_seq = t.late_seq;
-      t.box_slot = ctx->h_forest_dev + 4 + 4 * j;
+      t.box_slot = forest_slot_dev(ctx, j);
       t.n = static_cast<uint32_t>(n);
       t.D = D;
       t.dA = dA;
     }
-    seq = ++ctx->forest_seq;
-    if (const int rc = forest_build(ctx, trees, ctx->h_forest_dev, seq, table); rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // root levels already enqueued write into the box block: nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
     // ---- the one wait: the boxes of all members
-    SGA_TRY(forest_boxes_wait(ctx, seq, "boxes of a batched kd-tree build"));
+    SGA_TRY(forest_call_wait(ctx, forest_build(ctx, trees, ctx->h_forest_dev, seq, table), seq, "boxes of a batched kd-tree build"));
     for (size_t j = 0; j < forest.size(); j++) {
       sga_index* idx = made[forest[j]].get();
-      box_note_decode(ctx->h_forest + 4 + 4 * j + 1, idx->bbox_lo, idx->bbox_hi);
+      box_note_decode(forest_slot_host(ctx, j) + kSlotBox, idx->bbox_lo, idx->bbox_hi);
       for (int a = 0; a < 3; a++)
         if (!std::isfinite(idx->bbox_lo[a]) || !std::isfinite(idx->bbox_hi[a])) return fail(SGA_ERR_INVALID, "target cloud %zu contains non-finite coordinates", forest[j]);
     }
@@ -163,16 +158,11 @@ int voxelgrid_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t cou
       SGA_TRY(res->pts.alloc(clouds[plan.forest[j]]->n));  // room for one voxel per point: the centroid kernel runs before the host knows the count
       out[j] = res->pts.p;
     }
-    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
-    const unsigned long long seq = ++ctx->forest_seq;
-    if (const int rc = grid_forest_enqueue(ctx, clouds, leaf, plan, out.data(), seq); rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block and the outputs: nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
+    unsigned long long seq = 0;
+    SGA_TRY(forest_call_begin(ctx, plan.forest.size(), kSlotWords, &seq));
     // ---- the one wait: the voxel counts of all forest members
-    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel grid"));
-    for (size_t j = 0; j < plan.forest.size(); j++) made[plan.forest[j]]->n = static_cast<size_t>(ctx->h_forest[4 + 4 * j + 1]);
+    SGA_TRY(forest_call_wait(ctx, grid_forest_enqueue(ctx, clouds, leaf, plan, out.data(), seq), seq, "voxel counts of a batched voxel grid"));
+    for (size_t j = 0; j < plan.forest.size(); j++) made[plan.forest[j]]->n = static_cast<size_t>(forest_slot_host(ctx, j)[kSlotRuns]);
   }
   // ---- the other members through the lone routine, one after the other: no box, more than 262144 points, past the forest's caps
   for (size_t k : plan.lone) {
@@ -218,25 +208,9 @@ int voxelmaps_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t cou
   std::vector<size_t> built;       // their positions in the call
   auto add_member = [&](size_t k, uint32_t nvox, uint32_t off, uint32_t run0) -> int {
     const sga_cloud* cloud = clouds[k];
-    std::unique_ptr<sga_index> idx(new sga_index);  // as sga_index_build_gaussian_voxelmap sets it up
-    idx->kind = SGA_INDEX_VOXELMAP;
-    idx->device = ctx->device;
-    idx->leaf = leaf;
-    idx->has_covs = true;
-    idx->has_normals = false;
-    for (int a = 0; a < 3; a++) idx->origin[a] = cloud->origin[a];
-    idx->n = nvox;
-    uint32_t hsize = 16;
-    while (hsize < 2 * static_cast<uint64_t>(nvox)) hsize <<= 1;
-    idx->hmask = hsize - 1;
-    SGA_TRY(idx->hkeys.alloc(hsize));
-    SGA_TRY(idx->hvals.alloc(hsize));
-    if (nvox > 0) {
-      SGA_TRY(idx->pts.alloc(nvox));
-      SGA_TRY(idx->cov.alloc(nvox));
-      SGA_TRY(idx->vcoords.alloc(static_cast<size_t>(nvox) * 3));
-      SGA_TRY(idx->vcounts.alloc(nvox));
-    }
+    std::unique_ptr<sga_index> idx;
+    SGA_TRY(gaussian_map_new(ctx, cloud, leaf, nvox, idx));
+    SGA_TRY(gaussian_map_alloc_voxels(idx.get()));
     VoxMember g;
     std::memset(&g, 0, sizeof(g));
     g.pts = cloud->pts.p;
@@ -260,19 +234,14 @@ int voxelmaps_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t cou
   };
   size_t runs = 0;
   if (!plan.forest.empty()) {
-    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
-    const unsigned long long seq = ++ctx->forest_seq;
-    if (const int rc = vox_forest_enqueue_runs(ctx, clouds, leaf, plan, seq, ch); rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block: nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
+    unsigned long long seq = 0;
+    SGA_TRY(forest_call_begin(ctx, plan.forest.size(), kSlotWords, &seq));
     // ---- the one wait: the voxel counts and overflow words of all members of the chain
-    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel-map build"));
+    SGA_TRY(forest_call_wait(ctx, vox_forest_enqueue_runs(ctx, clouds, leaf, plan, seq, ch), seq, "voxel counts of a batched voxel-map build"));
     uint32_t off = 0;
     for (size_t j = 0; j < plan.forest.size(); j++) {
       const size_t k = plan.forest[j];
-      const unsigned long long nvox = ctx->h_forest[4 + 4 * j + 1], overflow = ctx->h_forest[4 + 4 * j + 2];
+      const unsigned long long nvox = forest_slot_host(ctx, j)[kSlotRuns], overflow = forest_slot_host(ctx, j)[kSlotOverflow];
       if (nvox > clouds[k]->n) return fail(SGA_ERR_HIP, "the device reported %llu voxels for the %zu points of cloud %zu", nvox, clouds[k]->n, k);
       if (overflow)
         lone.push_back(k);  // two voxels of the member may have shared a key: what the chain made of it is dropped
@@ -325,25 +294,21 @@ int insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* cons
   std::vector<size_t> own;  // the maps whose counter, sweep and export are this call's: the chain's members that did not overflow, and the empty ones
   if (!plan.forest.empty()) {
     const size_t B = plan.forest.size();
-    SGA_TRY(forest_box_block(ctx, B));
-    const unsigned long long seq = ++ctx->forest_seq;
-    if (const int rc = ivm_forest_enqueue_runs(ctx, maps, clouds, T, plan, seq, ch); rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block: nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
+    unsigned long long seq = 0;
+    SGA_TRY(forest_call_begin(ctx, B, kSlotWords, &seq));
     // ---- the one wait: run counts, overflow words and new-voxel counts of all members of the chain
-    SGA_TRY(forest_boxes_wait(ctx, seq, "voxel counts of a batched voxel-map insert"));
+    SGA_TRY(forest_call_wait(ctx, ivm_forest_enqueue_runs(ctx, maps, clouds, T, plan, seq, ch), seq, "voxel counts of a batched voxel-map insert"));
     std::vector<uint32_t> nseg(B), n_new(B);
     std::vector<bool> overflow(B);
     size_t runs = 0, total_new = 0;
     for (size_t j = 0; j < B; j++) {
       const size_t k = plan.forest[j];
-      const unsigned long long s = ctx->h_forest[4 + 4 * j + 1], w = ctx->h_forest[4 + 4 * j + 3];
+      const unsigned long long* slot = forest_slot_host(ctx, j);
+      const unsigned long long s = slot[kSlotRuns], w = slot[kSlotNewVoxels];
       if (s > clouds[k]->n || w > s) return fail(SGA_ERR_HIP, "the device reported %llu voxels (%llu new) for the %zu points of cloud %zu", s, w, clouds[k]->n, k);
       nseg[j] = static_cast<uint32_t>(s);
       n_new[j] = static_cast<uint32_t>(w);
-      overflow[j] = ctx->h_forest[4 + 4 * j + 2] != 0;
+      overflow[j] = slot[kSlotOverflow] != 0;
       runs += s;
       total_new += w;
       if (!overflow[j] && maps[k]->n + w >= (1ull << 31)) return fail(SGA_ERR_INVALID, "voxel map too large (member %zu)", k);
@@ -433,27 +398,15 @@ int insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* cons
 }
 }  // namespace
 
-void forest_count_launch() { g_forest_launches.fetch_add(1, std::memory_order_relaxed); }
-void grid_forest_count_launch() { g_grid_forest_launches.fetch_add(1, std::memory_order_relaxed); }
-void vox_forest_count_launch() { g_vox_forest_launches.fetch_add(1, std::memory_order_relaxed); }
-void ivm_forest_count_launch() { g_ivm_forest_launches.fetch_add(1, std::memory_order_relaxed); }
 }  // namespace sga
 
 using namespace sga;
 
 extern "C" {
 
-int sga_debug_forest_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_forest_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_forest_launches(unsigned long long* launches) { return report_launches(Chain::Forest, launches); }
 
-int sga_debug_voxelgrid_batch_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_grid_forest_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_voxelgrid_batch_launches(unsigned long long* launches) { return report_launches(Chain::Grid, launches); }
 
 int sga_debug_voxelgrid_batch_plan(const sga_cloud* const* clouds, size_t count, double leaf, int out[6]) {
   if (!out || (count > 0 && !clouds)) return fail(SGA_ERR_INVALID, "null argument");
@@ -471,22 +424,24 @@ int sga_debug_voxelgrid_batch_plan(const sga_cloud* const* clouds, size_t count,
 
 int sga_voxelgrid_sampling_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, sga_cloud** out) {
   if (count == 0) return SGA_OK;
-  if (out)
-    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  null_out(out, count);
   if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
   SGA_TRY(voxelgrid_batch_check(clouds, count, leaf));
   for (size_t k = 0; k < count; k++)
     if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
   SGA_ENTER(ctx);
-  std::vector<std::unique_ptr<sga_cloud>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
-  SGA_TRY(voxelgrid_batch(ctx, clouds, count, leaf, made));
-  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
-  return SGA_OK;
+  return build_into(out, [&](std::vector<std::unique_ptr<sga_cloud>>& made) { return voxelgrid_batch(ctx, clouds, count, leaf, made); });
 }
 
-int sga_debug_voxelmap_batch_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_vox_forest_launches.load(std::memory_order_relaxed);
+int sga_debug_voxelmap_batch_launches(unsigned long long* launches) { return report_launches(Chain::VoxBuild, launches); }
+
+static int report_plan(const VoxForestPlan& P, int out[6]) {
+  out[0] = static_cast<int>(P.forest.size());
+  out[1] = static_cast<int>(P.lone.size());
+  out[2] = static_cast<int>(P.empty.size());
+  out[3] = P.member_bits;
+  out[4] = P.end_bit;
+  out[5] = static_cast<int>(P.points);
   return SGA_OK;
 }
 
@@ -494,49 +449,27 @@ int sga_debug_voxelmap_batch_plan(const sga_cloud* const* clouds, size_t count, 
   if (!out || (count > 0 && !clouds)) return fail(SGA_ERR_INVALID, "null argument");
   for (int k = 0; k < 6; k++) out[k] = 0;
   SGA_TRY(voxelmaps_batch_check(clouds, count, leaf));
-  const VoxForestPlan P = vox_forest_plan(clouds, count);
-  out[0] = static_cast<int>(P.forest.size());
-  out[1] = static_cast<int>(P.lone.size());
-  out[2] = static_cast<int>(P.empty.size());
-  out[3] = P.member_bits;
-  out[4] = P.end_bit;
-  out[5] = static_cast<int>(P.points);
-  return SGA_OK;
+  return report_plan(vox_forest_plan(clouds, count), out);
 }
 
 int sga_index_build_gaussian_voxelmap_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, double leaf, sga_index** out) {
   if (count == 0) return SGA_OK;
-  if (out)
-    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  null_out(out, count);
   if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
   SGA_TRY(voxelmaps_batch_check(clouds, count, leaf));
   for (size_t k = 0; k < count; k++)
     if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
   SGA_ENTER(ctx);
-  std::vector<std::unique_ptr<sga_index>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
-  SGA_TRY(voxelmaps_batch(ctx, clouds, count, leaf, made));
-  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
-  return SGA_OK;
+  return build_into(out, [&](std::vector<std::unique_ptr<sga_index>>& made) { return voxelmaps_batch(ctx, clouds, count, leaf, made); });
 }
 
-int sga_debug_voxelmap_insert_batch_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_ivm_forest_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_voxelmap_insert_batch_launches(unsigned long long* launches) { return report_launches(Chain::IvmInsert, launches); }
 
 int sga_debug_voxelmap_insert_batch_plan(sga_index* const* maps, const sga_cloud* const* clouds, size_t count, int out[6]) {
   if (!out || (count > 0 && (!maps || !clouds))) return fail(SGA_ERR_INVALID, "null argument");
   for (int k = 0; k < 6; k++) out[k] = 0;
   SGA_TRY(insert_batch_check(maps, clouds, count));
-  const IvmForestPlan P = ivm_forest_plan(maps, clouds, count);
-  out[0] = static_cast<int>(P.forest.size());
-  out[1] = static_cast<int>(P.lone.size());
-  out[2] = static_cast<int>(P.empty.size());
-  out[3] = P.member_bits;
-  out[4] = P.end_bit;
-  out[5] = static_cast<int>(P.points);
-  return SGA_OK;
+  return report_plan(ivm_forest_plan(maps, clouds, count), out);
 }
 
 int sga_voxelmap_insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, size_t count) {
@@ -551,18 +484,14 @@ int sga_voxelmap_insert_batch(sga_context* ctx, sga_index* const* maps, const sg
 
 int sga_index_build_kdtree_batch(sga_context* ctx, const sga_cloud* const* clouds, size_t count, sga_index** out) {
   if (count == 0) return SGA_OK;
-  if (out)
-    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  null_out(out, count);
   if (!ctx || !clouds || !out) return fail(SGA_ERR_INVALID, "null argument");
   for (size_t k = 0; k < count; k++) {
     if (!clouds[k]) return fail(SGA_ERR_INVALID, "clouds[%zu] is NULL", k);
     if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
   }
   SGA_ENTER(ctx);
-  std::vector<std::unique_ptr<sga_index>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
-  SGA_TRY(build_kdtrees(ctx, clouds, count, made));
-  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
-  return SGA_OK;
+  return build_into(out, [&](std::vector<std::unique_ptr<sga_index>>& made) { return build_kdtrees(ctx, clouds, count, made); });
 }
 
 int sga_estimate_normals_covariances_batch(sga_context* ctx, sga_cloud* const* clouds, sga_index* const* indices, size_t count, int k, int flags) {

@@ -448,7 +448,6 @@ void cloud_set_box(sga_cloud* c, const double lo[3], const double hi[3], bool re
 }
 
 // ---- sga_cloud_merge -----------------------------------------------------------------------------------------
-std::atomic<unsigned long long> g_merge_launches{0};
 constexpr size_t kMergeMaxMembers = 1u << 15;
 
 // Member m's pose for an output frame at `o`: R as given (column-major T16, null: the identity), t = c - o with c = R o_m + t_m the
@@ -467,8 +466,7 @@ Pose12 merge_pose(const double* T16, const double o_m[3], const double o[3]) {
   return T;
 }
 
-// One pass over the non-empty members `live`: the table ([members][prefix of the grid: live + 1 words of 32 bits], written in the
-// staging ring, one copy command) and ONE launch over the concatenation.  want_box: the box of the finite posed points, relative to o,
+// One pass over the non-empty members `live`: the table ([members][prefix of the grid: live + 1]) and ONE launch over the concatenation.  want_box: the box of the finite posed points, relative to o,
 // arrives as a note the call waits for (lo > hi: no finite point).
 int merge_pass(sga_context* ctx, const sga_cloud* const* clouds, const double* T, const std::vector<size_t>& live, const double o[3], sga_cloud* c, bool want_box, DevBuf<unsigned long long>& table, double lo[3], double hi[3]) {
   const size_t count = live.size();
@@ -488,19 +486,14 @@ int merge_pass(sga_context* ctx, const sga_cloud* const* clouds, const double* T
     off += g.n;
     prefix[j + 1] = prefix[j] + (g.n + kIoBlock - 1u) / kIoBlock;
   }
-  const size_t member_words = count * (sizeof(MergeMember) / 8), words = member_words + (prefix.size() + 1) / 2;
-  SGA_TRY(table.alloc(words));
-  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
-    host[words - 1] = 0ull;
-    std::memcpy(host, members.data(), member_words * 8);
-    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-    g_merge_launches.fetch_add(1, std::memory_order_relaxed);
-  }));
+  const uint32_t* d_prefix = nullptr;
+  count_launch(Chain::Merge);
+  SGA_TRY(upload_entries(ctx, table, members, prefix, &d_prefix));
   unsigned long long* note = nullptr;
   const unsigned long long seq = want_box ? note_begin(ctx, &note) : 0ull;
-  g_merge_launches.fetch_add(1, std::memory_order_relaxed);
-  hipLaunchKernelGGL(merge_cloud_kernel, dim3(prefix[count]), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<const MergeMember*>(table.p), reinterpret_cast<const uint32_t*>(table.p + member_words), static_cast<int>(count), c->pts.p,
-                     c->nrm.p, c->cov.p, want_box ? ctx->d_box64.p : nullptr, note, seq);
+  count_launch(Chain::Merge);
+  hipLaunchKernelGGL(merge_cloud_kernel, dim3(prefix[count]), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<const MergeMember*>(table.p), d_prefix, static_cast<int>(count), c->pts.p, c->nrm.p, c->cov.p,
+                     want_box ? ctx->d_box64.p : nullptr, note, seq);
   SGA_HIP(hipGetLastError());
   if (want_box) {
     unsigned long long payload[kNoteWords - 1];
@@ -777,14 +770,12 @@ static void host_bbox(const S* xyz, size_t n, size_t stride, double lo[3], doubl
 }
 
 // ---- sga_cloud_deskew ------------------------------------------------------------------------------------------
-static std::atomic<unsigned long long> g_deskew_launches{0};
-
-// `count` sweeps, each point of member k posed by exp((s - ref_time_k) xi_k): one table — [members][prefix of the grid][box accumulators]
-// [ticket] — copied with one command, and ONE launch over the concatenation.  The times come from host arrays (times != null: all members'
+// `count` sweeps, each point of member k posed by exp((s - ref_time_k) xi_k): one table — [members][prefix of the grid][box accumulators:
+// 8 words per member][ticket] — and ONE launch over the concatenation.  The times come from host arrays (times != null: all members'
 // in ONE slot of the staging ring, which the kernel reads by its device address) or, for a single member, from a device array (dtimes).
 // A blocking context waits for the members' boxes (the context's box block: its one wait); a stream-ordered one waits for nothing.
 static int cloud_deskew(sga_context* ctx, const sga_cloud* const* clouds, const float* const* times, const sga_device_array* dtimes, const double* twists, const double* ref_times, size_t count, void* user_stream, int flags, sga_cloud** out) {
-  for (size_t k = 0; out != nullptr && k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  null_out(out, count);
   if (!ctx || (count > 0 && (!out || !clouds || (!times && !dtimes) || !twists))) return fail(SGA_ERR_INVALID, "null argument");
   if (count > kMergeMaxMembers) return fail(SGA_ERR_INVALID, "too many members (%zu; limit %zu)", count, kMergeMaxMembers);
   for (size_t k = 0; k < count; k++) {
@@ -858,17 +849,19 @@ static int cloud_deskew(sga_context* ctx, const sga_cloud* const* clouds, const 
     }
   }
   // ---- the table
-  const size_t member_words = L * (sizeof(DeskewMember) / 8), prefix_words = (L + 2) / 2, acc_words = want_box ? 8 * L : 0;
-  const size_t words = member_words + prefix_words + acc_words + 1;
+  TableLayout lay;
+  const auto s_members = lay.add<DeskewMember>(L);
+  const auto s_prefix = lay.add_prefixes(1, L);
+  const auto s_acc = lay.add<unsigned long long>(want_box ? 8 * L : 0);
+  const auto s_ticket = lay.add<unsigned>(1);
   DevBuf<unsigned long long> table;  // lives to the end of the call (then: the stream's free list)
-  SGA_TRY(table.alloc(words));
+  SGA_TRY(table.alloc(lay.words()));
   ForestBoxes hand{nullptr, 0u, nullptr, 0ull};
   if (want_box) {
-    SGA_TRY(forest_box_block(ctx, 2 * L));  // eight words per member behind the block's four
-    hand.ticket = reinterpret_cast<unsigned*>(table.p + member_words + prefix_words + acc_words);
+    SGA_TRY(forest_call_begin(ctx, L, kDeskewSlotWords, &hand.seq));
+    hand.ticket = lay.at(s_ticket, table.p);
     hand.total = static_cast<unsigned>(L);
     hand.seq_word = ctx->h_forest_dev;
-    hand.seq = ++ctx->forest_seq;
   }
   std::vector<DeskewMember> members(L);
   std::vector<uint32_t> prefix(L + 1, 0u);
@@ -886,7 +879,7 @@ static int cloud_deskew(sga_context* ctx, const sga_cloud* const* clouds, const 
     } else {
       g.times = dtimes->data, g.tstride = dtimes->stride, g.tf64 = dtimes->dtype == SGA_F64 ? 1 : 0;
     }
-    if (want_box) g.acc = table.p + member_words + prefix_words + 8 * j, g.slot = ctx->h_forest_dev + 4 + 8 * j;
+    if (want_box) g.acc = lay.at(s_acc, table.p) + 8 * j, g.slot = forest_slot_dev(ctx, j, kDeskewSlotWords);
     g.ref_time = ref_times ? ref_times[k] : 1.0;
     g.c = twist_const(twists + 6 * k, in->origin);
     g.n = static_cast<uint32_t>(in->n);
@@ -895,30 +888,28 @@ static int cloud_deskew(sga_context* ctx, const sga_cloud* const* clouds, const 
   }
   IoOrder ord;
   if (dtimes != nullptr) SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
-  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
-    std::memset(host, 0, words * 8);
-    std::memcpy(host, members.data(), member_words * 8);
-    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-    for (size_t w = 0; w < acc_words; w++) {
-      const size_t e = w % 8;
-      host[member_words + prefix_words + w] = e < 3 ? box_enc64(INFINITY) : e < 6 ? box_enc64(-INFINITY) : 0ull;
-    }
-    g_deskew_launches.fetch_add(1, std::memory_order_relaxed);
-  }));
-  g_deskew_launches.fetch_add(1, std::memory_order_relaxed);
-  hipLaunchKernelGGL(deskew_cloud_kernel, dim3(prefix[L]), dim3(kIoBlock), 0, ctx->stream, reinterpret_cast<const DeskewMember*>(table.p), reinterpret_cast<const uint32_t*>(table.p + member_words), static_cast<int>(L), hand);
-  SGA_HIP(hipGetLastError());
-  if (tslot != nullptr && ctx->stream_ordered) SGA_TRY(stage_release(ctx, tslot));  // (a blocking context: the wait below shows that the kernel is over)
-  if (want_box) {
-    const int rc = forest_boxes_wait(ctx, hand.seq, "boxes of a deskew");
-    if (rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
+  auto enqueue = [&]() -> int {
+    count_launch(Chain::Deskew);
+    SGA_TRY(upload_table(ctx, table.p, lay.words(), [&](unsigned long long* host) {
+      lay.put(s_members, host, members.data());
+      lay.put(s_prefix, host, prefix.data());
+      for (size_t w = 0; w < s_acc.count; w++)
+        if (w % 8 < 6) lay.at(s_acc, host)[w] = box_enc64(w % 8 < 3 ? INFINITY : -INFINITY);
+    }));
+    count_launch(Chain::Deskew);
+    hipLaunchKernelGGL(deskew_cloud_kernel, dim3(prefix[L]), dim3(kIoBlock), 0, ctx->stream, lay.at(s_members, table.p), lay.at(s_prefix, table.p), static_cast<int>(L), hand);
+    SGA_HIP(hipGetLastError());
+    return SGA_OK;
+  };
+  if (!want_box) {  // a stream-ordered context waits for nothing
+    SGA_TRY(enqueue());
+    if (tslot != nullptr) SGA_TRY(stage_release(ctx, tslot));
+  } else {  // (a blocking context: the wait shows that the kernel is over)
+    SGA_TRY(forest_call_wait(ctx, enqueue(), hand.seq, "boxes of a deskew"));
     for (size_t j = 0; j < L; j++) {
+      const unsigned long long* slot = forest_slot_host(ctx, j, kDeskewSlotWords);
       double lo[3], hi[3];
-      for (int a = 0; a < 3; a++) lo[a] = box_dec64(ctx->h_forest[4 + 8 * j + a]), hi[a] = box_dec64(ctx->h_forest[4 + 8 * j + 3 + a]);
+      for (int a = 0; a < 3; a++) lo[a] = box_dec64(slot[kDeskewSlotLo + a]), hi[a] = box_dec64(slot[kDeskewSlotHi + a]);
       cloud_set_box(made[live[j]].get(), lo, hi, true, false);  // the rounding is monotone: the rounded box of the unrounded records is the box of the records
     }
   }
@@ -1062,17 +1053,9 @@ int sga_cloud_deskew_device(sga_context* ctx, const sga_cloud* cloud, const sga_
   return cloud_deskew(ctx, &cloud, nullptr, times, twist, &ref_time, 1, user_stream, flags, out);
 }
 
-int sga_debug_cloud_deskew_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_deskew_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_cloud_deskew_launches(unsigned long long* launches) { return report_launches(Chain::Deskew, launches); }
 
-int sga_debug_cloud_merge_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_merge_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_cloud_merge_launches(unsigned long long* launches) { return report_launches(Chain::Merge, launches); }
 
 int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]) {
   if (!cloud || !has_box || !lo || !hi) return fail(SGA_ERR_INVALID, "null argument");

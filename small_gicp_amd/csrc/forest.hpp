@@ -1,12 +1,17 @@
-// Batched preprocessing (batch_preprocess.hip): the kd-trees and the covariances of B small clouds in one chain
-// of launches.  A call writes ONE table into pinned memory and copies it to the device with one command; the batched kernels
-// (index_build.hip, preprocess.hip: beside the lone kernels whose bodies they share) read what the lone kernel receives as its arguments
-// from the table entry of their tree, with scalar loads (uniform_const).
+// The batched chains: one call serves B members through one chain of launches and one host wait.  Shared here:
+//   * the table: laid out once (forest_table.hpp), filled in a zeroed slot of the pinned staging ring and copied to the device with one
+//     command (upload_table: the only way a table reaches the device); the batched kernels — beside the lone kernels whose bodies they
+//     share — read what the lone kernel receives as its arguments from their member's entry, with scalar loads (uniform_const);
+//   * the box block: pinned, device-mapped words of the context; word 0 receives the call's sequence number once every member has
+//     written its slot (forest_slot_dev / forest_slot_host, the kSlot constants);
+//   * the call (forest_call_begin, the chain's enqueue, forest_call_wait: the ONE host wait) and the launch counters (Chain).
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "common.hpp"
 #include "device_math.hpp"
+#include "forest_table.hpp"
 #include "kd_search.hpp"
 #include "uniform.hpp"
 
@@ -77,17 +82,65 @@ __device__ __forceinline__ int forest_member_of(const uint32_t* prefix, int coun
   return lo;
 }
 
-// A call's table on its way to the device: a slot of the context's pinned staging ring is acquired, `fill` writes the `words` 8-byte
-// words of the table into it, ONE copy command carries them to `dst`, and the slot is released behind the copy.
+// A call's table on its way to the device: a slot of the staging ring is acquired and zeroed, `fill` writes what is not zero of the
+// table's `words` 8-byte words, ONE copy command carries them to `dst`, the slot is released behind it.  (Counts nothing: Chain.)
 template <typename Fill>
 int upload_table(sga_context* ctx, unsigned long long* dst, size_t words, Fill&& fill) {
   sga_context::StageSlot* slot = nullptr;
   SGA_TRY(stage_acquire(ctx, words * 8, &slot));
   unsigned long long* host = static_cast<unsigned long long*>(slot->host);
+  std::memset(host, 0, words * 8);
   fill(host);
   SGA_HIP(hipMemcpyAsync(dst, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
   return stage_release(ctx, slot);
 }
+// The table of a launch that needs no more than [entries][prefix of its grids: count + 1 each]; *d_prefix: the prefixes on the device
+template <typename Entry>
+int upload_entries(sga_context* ctx, DevBuf<unsigned long long>& table, const std::vector<Entry>& entries, const std::vector<uint32_t>& prefix, const uint32_t** d_prefix) {
+  TableLayout L;
+  const auto members = L.add<Entry>(entries.size());
+  const auto grids = L.add_prefixes(prefix.size() / (entries.size() + 1), entries.size());
+  SGA_TRY(table.alloc(L.words()));
+  *d_prefix = L.at(grids, table.p);
+  return upload_table(ctx, table.p, L.words(), [&](unsigned long long* host) {
+    L.put(members, host, entries.data());
+    L.put(grids, host, prefix.data());
+  });
+}
+
+// ---- the box block and the call ---------------------------------------------------------------------------------------------------------
+// Member j's slot: `stride` words from word 4 + stride * j of the block, as the device addresses it and as the host reads it
+constexpr size_t kSlotWords = 4, kDeskewSlotWords = 8;
+inline unsigned long long* forest_slot_dev(const sga_context* ctx, size_t j, size_t stride = kSlotWords) { return ctx->h_forest_dev + 4 + stride * j; }
+inline const unsigned long long* forest_slot_host(const sga_context* ctx, size_t j, size_t stride = kSlotWords) { return ctx->h_forest + 4 + stride * j; }
+// what the words of a slot hold
+constexpr int kSlotBox = 1;                                          // kd forest, problem creation: words 1..3, the box (box_note_decode)
+constexpr int kSlotRuns = 1, kSlotOverflow = 2, kSlotNewVoxels = 3;  // grid forest: runs; map build: runs, overflow; insert: all three
+constexpr int kDeskewSlotLo = 0, kDeskewSlotHi = 3;                  // deskew (kDeskewSlotWords): the box, three words each (box_dec64)
+// batch_preprocess.hip.  A call begins: the box block has room for `members` slots of `stride` words, *seq is the call's sequence number
+int forest_call_begin(sga_context* ctx, size_t members, size_t stride, unsigned long long* seq);
+// ... and, its chain enqueued with status `enqueued`, waits until the block shows `seq`.  A failed enqueue and a failed wait (`what`
+// did not arrive) drain the stream: kernels already enqueued write into the block and the members' arrays, nothing stays in flight.
+int forest_call_wait(sga_context* ctx, int enqueued, unsigned long long seq, const char* what);
+
+// An entry point that makes one object per member: a failure leaves every out[k] NULL and destroys what was made inside the entry point
+template <typename T>
+void null_out(T** out, size_t count) {
+  for (size_t k = 0; out != nullptr && k < count; k++) out[k] = nullptr;
+}
+template <typename T, typename Build>
+int build_into(T** out, Build&& build) {
+  std::vector<std::unique_ptr<T>> made;
+  SGA_TRY(build(made));
+  for (size_t k = 0; k < made.size(); k++) out[k] = made[k].release();
+  return SGA_OK;
+}
+
+// ---- the launch counters (diagnostics: the sga_debug_*_launches entry points) --------------------------------------------------------------
+// What a chain counts is its own rule: Forest (kd, features) and Grid count kernels and sorts, the others their table copies as well
+enum class Chain { Forest, Grid, VoxBuild, IvmInsert, Problem, Merge, Deskew, kCount };
+void count_launch(Chain chain);                                  // batch_preprocess.hip
+int report_launches(Chain chain, unsigned long long* launches);  // the body of an sga_debug_*_launches entry point
 
 // index_build.hip: the build of all `trees` (every field but spacing_acc filled in by the caller) enqueued on the context's stream;
 // `table` (device memory: the trees, the launches' member lists, the accumulators) must live until the kernels have run
@@ -97,9 +150,9 @@ int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, in
 void forest_tree_shape(size_t n, int* D, int* dA);  // index_build.hip: depth and first LDS level of a cloud of 1 <= n <= kForestMaxPoints points
 int features_check_k(int k);     // preprocess.hip: SGA_OK, or the lone estimation's error for a num_neighbors outside its range
 long long knn_wave_max_points();  // preprocess.hip: g_knn_wave_max
-void forest_count_launch();       // batch_preprocess.hip: every kernel the two entry points enqueue (sga_debug_forest_launches)
-int forest_box_block(sga_context* ctx, size_t members);  // batch_preprocess.hip: the context's box block with room for `members` slots
-int forest_boxes_wait(sga_context* ctx, unsigned long long seq, const char* what);  // the ONE wait of a forest call: the block shows `seq`
+// index_build.hip, for the lone build and the forest: the header of a kd index over `cloud`; the six arrays behind its nodes (kd_pts .. kd_leaf)
+std::unique_ptr<sga_index> kd_index_new(const sga_context* ctx, const sga_cloud* cloud);
+int kd_index_alloc(sga_index* idx, const sga_cloud* cloud, int D);
 
 // ---- the grid forest: sga_voxelgrid_sampling for B clouds in one chain of launches --------------------------
 // What the host decides about a batched voxel-grid call before it launches anything (preprocess.hip: grid_forest_plan);
@@ -118,9 +171,8 @@ struct GridForestPlan {
 };
 GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, double leaf);
 // preprocess.hip: keys, sort, runs, centroids of the plan's forest members enqueued on the context's stream; out[j]: the records of forest
-// member j (room for the member's point count); member j's run count arrives in word 4 j + 5 of the context's box block, then `seq` in word 0
+// member j (room for the member's point count); member j's run count arrives in word kSlotRuns of its slot of the box block, then `seq` in word 0
 int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq);
-void grid_forest_count_launch();  // batch_preprocess.hip: every kernel and sort of grid_forest_enqueue (sga_debug_voxelgrid_batch_launches)
 // ---- the voxel forests (DESIGN.md sections 3.14 and 3.15): sga_index_build_gaussian_voxelmap for B clouds, sga_voxelmap_insert for B
 // (Gaussian map, cloud, pose) triples, each in one chain of launches.  The sort key, the tables and the stages: voxel_steps.hpp.
 constexpr size_t kVoxForestMaxMember = 262144;    // points of a member of the chain (2^18: a run's first point takes 18 bits of the rank key)

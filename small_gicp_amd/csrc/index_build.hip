@@ -902,6 +902,26 @@ static int split_class(size_t seg_max) {
   return c;
 }
 
+std::unique_ptr<sga_index> kd_index_new(const sga_context* ctx, const sga_cloud* cloud) {
+  std::unique_ptr<sga_index> idx(new sga_index);
+  idx->kind = SGA_INDEX_KDTREE;
+  idx->device = ctx->device;
+  idx->n = cloud->n;
+  for (int k = 0; k < 3; k++) idx->origin[k] = cloud->origin[k];  // the tree lives in its cloud's device frame (common.hpp)
+  idx->has_normals = cloud->has_normals;
+  idx->has_covs = cloud->has_covs;
+  return idx;
+}
+int kd_index_alloc(sga_index* idx, const sga_cloud* cloud, int D) {
+  const size_t n = cloud->n;
+  SGA_TRY(idx->kd_pts.alloc(n + kKdLeafMax));  // + one leaf of points at infinity: leaf scans read 8 slots unconditionally
+  if (cloud->has_normals) SGA_TRY(idx->nrm.alloc(n));
+  if (cloud->has_covs) SGA_TRY(idx->cov.alloc(n));
+  SGA_TRY(idx->kd_boxes.alloc(4ull << D));
+  SGA_TRY(idx->kd_groups.alloc(8ull << (D - (D < 2 ? D : 2))));
+  return idx->kd_leaf.alloc(8ull << D);
+}
+
 // box_seq: the note (notes.hpp) that carries the cloud's bounding box to the host — from the first split level when there is one (it takes
 // the box of its segment, the whole cloud, anyway), else from bbox_note_kernel
 static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx, unsigned long long* box_seq) {
@@ -1016,12 +1036,7 @@ static int build_kdtree(sga_context* ctx, const sga_cloud* cloud, sga_index* idx
     std::swap(cur, nxt);
   }
   SGA_HIP(hipGetLastError());
-  SGA_TRY(idx->kd_pts.alloc(n + kKdLeafMax));  // + one leaf of points at infinity: leaf scans read 8 slots unconditionally
-  if (cloud->has_normals) SGA_TRY(idx->nrm.alloc(n));
-  if (cloud->has_covs) SGA_TRY(idx->cov.alloc(n));
-  SGA_TRY(idx->kd_boxes.alloc(4ull << D));
-  SGA_TRY(idx->kd_groups.alloc(8ull << (D - (D < 2 ? D : 2))));
-  SGA_TRY(idx->kd_leaf.alloc(8ull << D));
+  SGA_TRY(kd_index_alloc(idx, cloud, D));
   unsigned long long* late_slot = nullptr;
   const unsigned long long spacing_seq = late_note_begin(ctx->device, &late_slot);  // the target's length scale arrives whenever the tail kernel has run: nobody waits for it
   idx->spacing = 0.0;
@@ -1139,25 +1154,27 @@ int forest_build(sga_context* ctx, std::vector<ForestTree>& trees, unsigned long
   for (int a = 0; a <= max_dA; a++) add_step(2, a, 0, [&](const ForestTree& t) { return t.dA == a && t.dA < t.D; });
   for (int D = 0; D <= max_D; D++) add_step(3, D, 0, [&](const ForestTree& t) { return t.D == D; });
   for (int D = 9; D <= max_D; D++) add_step(4, D, 0, [&](const ForestTree& t) { return t.D == D; });
-  // ---- one table: [trees][accumulators of the tails: 4 words per tree][ticket][member lists], written in pinned memory, one copy command
-  const size_t tree_words = count * (sizeof(ForestTree) / 8), acc_words = 4 * count, list_words = (members.size() + 1) / 2;
-  const size_t words = tree_words + acc_words + 1 + list_words;
-  SGA_TRY(table.alloc(words));
-  for (size_t k = 0; k < count; k++) trees[k].spacing_acc = table.p + tree_words + 4 * k;
-  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
-    std::memcpy(host, trees.data(), tree_words * 8);
-    std::memset(host + tree_words, 0, (acc_words + 1 + list_words) * 8);
-    std::memcpy(host + tree_words + acc_words + 1, members.data(), members.size() * sizeof(uint32_t));
+  // ---- the table: [trees][accumulators of the tails: 4 words per tree][ticket][member lists]
+  TableLayout L;
+  const auto s_trees = L.add<ForestTree>(count);
+  const auto s_acc = L.add<unsigned long long>(4 * count);
+  const auto s_ticket = L.add<unsigned>(1);
+  const auto s_lists = L.add<uint32_t>(members.size());
+  SGA_TRY(table.alloc(L.words()));
+  for (size_t k = 0; k < count; k++) trees[k].spacing_acc = L.at(s_acc, table.p) + 4 * k;
+  SGA_TRY(upload_table(ctx, table.p, L.words(), [&](unsigned long long* host) {
+    L.put(s_trees, host, trees.data());
+    L.put(s_lists, host, members.data());
   }));
-  const ForestTree* d_trees = reinterpret_cast<const ForestTree*>(table.p);
-  const uint32_t* d_members = reinterpret_cast<const uint32_t*>(table.p + tree_words + acc_words + 1);
-  const ForestBoxes hand{reinterpret_cast<unsigned*>(table.p + tree_words + acc_words), static_cast<unsigned>(count), box_seq_word, box_seq};
+  const ForestTree* d_trees = L.at(s_trees, table.p);
+  const uint32_t* d_members = L.at(s_lists, table.p);
+  const ForestBoxes hand{L.at(s_ticket, table.p), static_cast<unsigned>(count), box_seq_word, box_seq};
   constexpr uint32_t kMaxGridY = 65535;  // the trees of a step are blockIdx.y: longer member lists go out in pieces
   for (const Step& whole : steps)
     for (uint32_t off = 0; off < whole.num; off += kMaxGridY) {
     const Step s{whole.kind, whole.arg, whole.cls, whole.first + off, std::min(kMaxGridY, whole.num - off)};
     const uint32_t* list = d_members + s.first;
-    forest_count_launch();
+    count_launch(Chain::Forest);
     switch (s.kind) {
       case 0: hipLaunchKernelGGL(kd_forest_root_kernel, dim3(s.num), dim3(kSplitFinish), 0, ctx->stream, d_trees, list, hand); break;
       case 1: {
@@ -1218,13 +1235,7 @@ int sga_index_build_kdtree(sga_context* ctx, const sga_cloud* target, sga_index*
   *out = nullptr;
   SGA_ENTER(ctx);
   const size_t n = target->n;
-  std::unique_ptr<sga_index> idx(new sga_index);
-  idx->kind = SGA_INDEX_KDTREE;
-  idx->device = ctx->device;
-  idx->n = n;
-  for (int k = 0; k < 3; k++) idx->origin[k] = target->origin[k];  // the tree lives in its cloud's device frame (common.hpp)
-  idx->has_normals = target->has_normals;
-  idx->has_covs = target->has_covs;
+  std::unique_ptr<sga_index> idx = kd_index_new(ctx, target);
   SGA_TRY(wait_ready(ctx, target->ready));  // attributes estimated on another context in stream-ordered mode
   if (n > 0) {
     // the bounding box travels to the host as a note (notes.hpp) while the build behind it is being enqueued

@@ -598,7 +598,7 @@ int features_check_k(int k) {
 }
 
 // knn_wave_kernel + features_from_list_kernel for all members (every one of 1 <= n <= g_knn_wave_max points, k <= 64) in two launches;
-// `table`: [members][prefix of the search grid: count + 1][prefix of the feature grid: count + 1], written in pinned memory, one copy command
+// `table`: [members][prefix of the search grid: count + 1][prefix of the feature grid: count + 1]
 static_assert(sizeof(ForestFeat) % 8 == 0, "table entries are copied as 8-byte words");
 int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, int k, int flags, DevBuf<unsigned long long>& table) {
   const size_t count = members.size();
@@ -608,17 +608,12 @@ int forest_features(sga_context* ctx, const std::vector<ForestFeat>& members, in
     prefix[m + 1] = prefix[m] + members[m].g.n;
     prefix[count + 1 + m + 1] = prefix[count + 1 + m] + (members[m].g.n + kFeatBlock - 1) / kFeatBlock;
   }
-  const size_t member_words = count * (sizeof(ForestFeat) / 8), words = member_words + (count + 1);
-  SGA_TRY(table.alloc(words));
-  SGA_TRY(upload_table(ctx, table.p, words, [&](unsigned long long* host) {
-    std::memcpy(host, members.data(), member_words * 8);
-    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-  }));
+  const uint32_t* d_prefix = nullptr;
+  SGA_TRY(upload_entries(ctx, table, members, prefix, &d_prefix));
   const ForestFeat* d_members = reinterpret_cast<const ForestFeat*>(table.p);
-  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(table.p + member_words);
-  forest_count_launch();
+  count_launch(Chain::Forest);
   hipLaunchKernelGGL(knn_wave_forest_kernel, dim3(prefix[count]), dim3(64), 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), k);
-  forest_count_launch();
+  count_launch(Chain::Forest);
   hipLaunchKernelGGL(features_from_list_forest_kernel, dim3(prefix[2 * count + 1]), dim3(kFeatBlock), 0, ctx->stream, d_members, d_prefix + count + 1, static_cast<int>(count), k, flags);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
@@ -755,15 +750,15 @@ int grid_forest_launch(sga_context* ctx, const GridMember* d_members, const uint
   SGA_TRY(seg_start.alloc(points));
   const int B = static_cast<int>(count);
   const uint32_t *key_blocks = prefix.data(), *tiles = key_blocks + count + 1, *mean_blocks = tiles + count + 1;
-  grid_forest_count_launch();
+  count_launch(Chain::Grid);
   hipLaunchKernelGGL((downsample_keys_forest_kernel<Key>), dim3(key_blocks[count]), dim3(256), 0, ctx->stream, d_members, d_prefix, B, 1.0 / leaf, keys.p, vals.p);
   SGA_HIP(hipGetLastError());
-  grid_forest_count_launch();
+  count_launch(Chain::Grid);
   SGA_TRY(sort_pairs(ctx, keys.p, keys_sorted.p, vals.p, order.p, points, 0, std::min<unsigned>(end_bit, 8 * sizeof(Key))));
-  grid_forest_count_launch();
+  count_launch(Chain::Grid);
   hipLaunchKernelGGL((ds_segments_forest_kernel<Key>), dim3(tiles[count]), dim3(kSegThreads), 0, ctx->stream, d_members, d_prefix + count + 1, B, keys_sorted.p, ctx->vg_status.p, epoch, seg_start.p, hand);
   SGA_HIP(hipGetLastError());
-  grid_forest_count_launch();
+  count_launch(Chain::Grid);
   hipLaunchKernelGGL(ds_mean_forest_kernel, dim3(mean_blocks[count]), dim3(256), 0, ctx->stream, d_members, d_prefix + 2 * (count + 1), B, seg_start.p, order.p);
   SGA_HIP(hipGetLastError());
   return SGA_OK;  // (the buffers go to the stream's free list: reused only behind these kernels)
@@ -795,22 +790,19 @@ GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, do
   return P;
 }
 
-// `table`: [members][scratch: 4 x uint32 per member][ticket][prefix of the key grid, of the tiles, of the centroid grid: count + 1 each],
-// written in pinned memory, one copy command
+// `table`: [members][scratch: 4 x uint32 per member][ticket][prefix of the key grid, of the tiles, of the centroid grid: count + 1 each]
 int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq) {
   const size_t count = plan.forest.size();
   if (count == 0) return SGA_OK;
   std::vector<GridMember> members(count);
   std::vector<uint32_t> prefix(3 * (count + 1), 0u);
-  const size_t member_words = count * (sizeof(GridMember) / 8), scratch_words = 2 * count, prefix_words = (prefix.size() + 1) / 2;
-  const size_t words = member_words + scratch_words + 1 + prefix_words;
+  TableLayout L;
+  const auto s_members = L.add<GridMember>(count);
+  const auto s_scratch = L.add<uint32_t>(4 * count);
+  const auto s_ticket = L.add<unsigned>(1);
+  const auto s_prefix = L.add_prefixes(3, count);
   DevBuf<unsigned long long> table;
-  SGA_TRY(table.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memset(host, 0, words * 8);
-  uint32_t* host_scratch = reinterpret_cast<uint32_t*>(host + member_words);
+  SGA_TRY(table.alloc(L.words()));
   uint32_t off = 0;
   for (size_t j = 0; j < count; j++) {
     const sga_cloud* c = clouds[plan.forest[j]];
@@ -820,8 +812,8 @@ int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double
     std::memset(&g, 0, sizeof(g));
     g.pts = c->pts.p;
     g.out = out[j];
-    g.scratch = reinterpret_cast<uint32_t*>(table.p + member_words) + 4 * j;
-    g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
+    g.scratch = L.at(s_scratch, table.p) + 4 * j;
+    g.count_slot = forest_slot_dev(ctx, j);
     g.ox = c->origin[0], g.oy = c->origin[1], g.oz = c->origin[2];
     g.tag = plan.W < 64 ? static_cast<unsigned long long>(j) << plan.W : 0ull;  // (W = 64: one member, number 0)
     g.bad = g.tag | (1ull << vp.L.total);
@@ -829,20 +821,20 @@ int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double
     g.n = n;
     g.off = off;
     off += n;
-    host_scratch[4 * j + 2] = n;  // valid points: lowered by the first dropped point the runs kernel meets
     prefix[j + 1] = prefix[j] + (n + 255u) / 256u;
     prefix[count + 1 + j + 1] = prefix[count + 1 + j] + vp.tiles;
     prefix[2 * (count + 1) + j + 1] = prefix[2 * (count + 1) + j] + (n * 8u + 255u) / 256u;
   }
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words + scratch_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
-  SGA_HIP(hipMemcpyAsync(table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
+  SGA_TRY(upload_table(ctx, table.p, L.words(), [&](unsigned long long* host) {
+    L.put(s_members, host, members.data());
+    L.put(s_prefix, host, prefix.data());
+    for (size_t j = 0; j < count; j++) L.at(s_scratch, host)[4 * j + 2] = members[j].n;  // valid points: lowered by the first dropped point the runs kernel meets
+  }));
   unsigned epoch = 0;
   SGA_TRY(voxelgrid_status(ctx, prefix[2 * count + 1], &epoch));
-  const GridMember* d_members = reinterpret_cast<const GridMember*>(table.p);
-  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(table.p + member_words + scratch_words + 1);
-  const ForestBoxes hand{reinterpret_cast<unsigned*>(table.p + member_words + scratch_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  const GridMember* d_members = L.at(s_members, table.p);
+  const uint32_t* d_prefix = L.at(s_prefix, table.p);
+  const ForestBoxes hand{L.at(s_ticket, table.p), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
   const unsigned end_bit = static_cast<unsigned>(plan.W + plan.member_bits);
   return plan.key_bytes == 4 ? grid_forest_launch<uint32_t>(ctx, d_members, d_prefix, prefix, count, plan.points, leaf, end_bit, epoch, hand)
                              : grid_forest_launch<unsigned long long>(ctx, d_members, d_prefix, prefix, count, plan.points, leaf, end_bit, epoch, hand);

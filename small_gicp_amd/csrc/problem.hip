@@ -491,9 +491,6 @@ int sga_problem_create(sga_context* ctx, const sga_index* target, const sga_clou
 
 // ---- sga_problem_create for every member ------------------------------------------------------------------------
 namespace {
-std::atomic<unsigned long long> g_problem_forest_launches{0};
-void problem_forest_count_launch() { g_problem_forest_launches.fetch_add(1, std::memory_order_relaxed); }
-
 // the argument checks of sga_problem_create_batch and of its plan that need no context (status and message as the lone call's, naming the member)
 int problem_batch_check(const sga_index* const* targets, const sga_cloud* const* sources, size_t count) {
   for (size_t k = 0; k < count; k++) {
@@ -504,8 +501,8 @@ int problem_batch_check(const sga_index* const* targets, const sga_cloud* const*
 }
 
 // The chain of the plan's members enqueued on the context's stream: the table ([members][boxes: 6 ints per member][done: one counter per
-// member][ticket][prefix of the grid: count + 1], written in pinned memory, one copy command), the keys launch, ONE stable sort of the
-// concatenation and the finish launch.  Member j's box arrives in words 4 j + 5 .. 4 j + 7 of the context's box block, then `seq` in word 0.
+// member][ticket][prefix of the grid: count + 1]), the keys launch, ONE stable sort of the concatenation and the finish launch.  Member j's
+// box arrives in words kSlotBox .. kSlotBox + 2 of its slot of the context's box block, then `seq` in word 0.
 struct ProblemForestChain {
   DevBuf<ProblemKey> recs, recs_sorted;
   DevBuf<unsigned long long> table;
@@ -517,14 +514,13 @@ int problem_forest_enqueue(sga_context* ctx, const sga_index* const* targets, co
   SGA_TRY(ch.recs_sorted.alloc(N));
   std::vector<ProblemMember> members(count);
   std::vector<uint32_t> prefix(count + 1, 0u);
-  const size_t member_words = count * (sizeof(ProblemMember) / 8), box_words = 3 * count, done_words = (count + 1) / 2, prefix_words = (prefix.size() + 1) / 2;
-  const size_t words = member_words + box_words + done_words + 1 + prefix_words;
-  SGA_TRY(ch.table.alloc(words));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, words * 8, &slot));
-  unsigned long long* host = static_cast<unsigned long long*>(slot->host);
-  std::memset(host, 0, words * 8);
-  int* host_box = reinterpret_cast<int*>(host + member_words);
+  TableLayout L;
+  const auto s_members = L.add<ProblemMember>(count);
+  const auto s_box = L.add<int>(6 * count);
+  const auto s_done = L.add<unsigned>(count);
+  const auto s_ticket = L.add<unsigned>(1);
+  const auto s_prefix = L.add_prefixes(1, count);
+  SGA_TRY(ch.table.alloc(L.words()));
   uint32_t off = 0;
   for (size_t j = 0; j < count; j++) {
     const size_t k = plan.forest[j];
@@ -547,33 +543,34 @@ int problem_forest_enqueue(sga_context* ctx, const sga_index* const* targets, co
     if (g.use_kd) g.kd = make_kd_view(target);
     g.T = rigid_from_colmajor<float>(T);
     source_key_cells(target, &g.ox, &g.oy, &g.oz, &g.inv);
-    g.box = reinterpret_cast<int*>(ch.table.p + member_words) + 6 * j;
-    g.done = reinterpret_cast<unsigned*>(ch.table.p + member_words + box_words) + j;
-    g.box_slot = ctx->h_forest_dev + 4 + 4 * j;
+    g.box = L.at(s_box, ch.table.p) + 6 * j;
+    g.done = L.at(s_done, ch.table.p) + j;
+    g.box_slot = forest_slot_dev(ctx, j);
     g.n = static_cast<uint32_t>(source->n);
     g.off = off;
     off += g.n;
-    for (int a = 0; a < 3; a++) host_box[6 * j + a] = kBoxEncPosInf, host_box[6 * j + 3 + a] = kBoxEncNegInf;
     prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
   }
-  std::memcpy(host, members.data(), member_words * 8);
-  std::memcpy(host + member_words + box_words + done_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
-  problem_forest_count_launch();
-  SGA_HIP(hipMemcpyAsync(ch.table.p, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
-  SGA_TRY(stage_release(ctx, slot));
-  const ProblemMember* d_members = reinterpret_cast<const ProblemMember*>(ch.table.p);
-  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(ch.table.p + member_words + box_words + done_words + 1);
-  const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table.p + member_words + box_words + done_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  count_launch(Chain::Problem);
+  SGA_TRY(upload_table(ctx, ch.table.p, L.words(), [&](unsigned long long* host) {
+    L.put(s_members, host, members.data());
+    L.put(s_prefix, host, prefix.data());
+    for (size_t j = 0; j < count; j++)
+      for (int a = 0; a < 3; a++) L.at(s_box, host)[6 * j + a] = kBoxEncPosInf, L.at(s_box, host)[6 * j + 3 + a] = kBoxEncNegInf;
+  }));
+  const ProblemMember* d_members = L.at(s_members, ch.table.p);
+  const uint32_t* d_prefix = L.at(s_prefix, ch.table.p);
+  const ForestBoxes hand{L.at(s_ticket, ch.table.p), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
   const dim3 grid(prefix[count]), block(256);
-  problem_forest_count_launch();
+  count_launch(Chain::Problem);
   hipLaunchKernelGGL(problem_keys_forest_kernel, grid, block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.recs.p);
   SGA_HIP(hipGetLastError());
-  problem_forest_count_launch();
+  count_launch(Chain::Problem);
   size_t tb = 0;
   SGA_HIP(rocprim::merge_sort(nullptr, tb, ch.recs.p, ch.recs_sorted.p, N, ProblemKeyLess(), ctx->stream));
   SGA_TRY(ensure_temp(ctx, tb));
   SGA_HIP(rocprim::merge_sort(ctx->d_temp.p, tb, ch.recs.p, ch.recs_sorted.p, N, ProblemKeyLess(), ctx->stream));
-  problem_forest_count_launch();
+  count_launch(Chain::Problem);
   hipLaunchKernelGGL(problem_finish_forest_kernel, grid, block, 0, ctx->stream, d_members, d_prefix, static_cast<int>(count), ch.recs_sorted.p, hand);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
@@ -595,18 +592,13 @@ int problems_batch(sga_context* ctx, const sga_index* const* targets, const sga_
       made[k] = problem_new(ctx, targets[k], sources[k]);
       SGA_TRY(problem_alloc_state(ctx, made[k].get(), sources[k]->n, sources[k]->has_covs, /*own_arrays=*/true, /*init_state=*/false));
     }
-    SGA_TRY(forest_box_block(ctx, plan.forest.size()));
-    const unsigned long long seq = ++ctx->forest_seq;
-    if (const int rc = problem_forest_enqueue(ctx, targets, sources, init_T, plan, made, seq, ch); rc != SGA_OK) {
-      (void)hipStreamSynchronize(ctx->stream);  // kernels already enqueued write into the box block and the members' arrays: nothing of this call stays in flight
-      (void)hipGetLastError();
-      return rc;
-    }
+    unsigned long long seq = 0;
+    SGA_TRY(forest_call_begin(ctx, plan.forest.size(), kSlotWords, &seq));
     // ---- the one wait: the boxes of all members
-    SGA_TRY(forest_boxes_wait(ctx, seq, "boxes of a batched problem creation"));
+    SGA_TRY(forest_call_wait(ctx, problem_forest_enqueue(ctx, targets, sources, init_T, plan, made, seq, ch), seq, "boxes of a batched problem creation"));
     for (size_t j = 0; j < plan.forest.size(); j++) {
       sga_problem* pb = made[plan.forest[j]].get();
-      box_note_decode(ctx->h_forest + 4 + 4 * j + 1, pb->bbox_lo, pb->bbox_hi);
+      box_note_decode(forest_slot_host(ctx, j) + kSlotBox, pb->bbox_lo, pb->bbox_hi);
       for (int a = 0; a < 3; a++)
         if (!std::isfinite(pb->bbox_lo[a]) || !std::isfinite(pb->bbox_hi[a])) return fail(SGA_ERR_INVALID, "source cloud contains non-finite coordinates (problem %zu)", plan.forest[j]);
     }
@@ -623,11 +615,7 @@ int problems_batch(sga_context* ctx, const sga_index* const* targets, const sga_
 }
 }  // namespace
 
-int sga_debug_problem_batch_launches(unsigned long long* launches) {
-  if (!launches) return fail(SGA_ERR_INVALID, "null argument");
-  *launches = g_problem_forest_launches.load(std::memory_order_relaxed);
-  return SGA_OK;
-}
+int sga_debug_problem_batch_launches(unsigned long long* launches) { return report_launches(Chain::Problem, launches); }
 
 int sga_debug_problem_batch_plan(const sga_index* const* targets, const sga_cloud* const* sources, size_t count, int out[4]) {
   if (!out || (count > 0 && (!targets || !sources))) return fail(SGA_ERR_INVALID, "null argument");
@@ -643,17 +631,13 @@ int sga_debug_problem_batch_plan(const sga_index* const* targets, const sga_clou
 
 int sga_problem_create_batch(sga_context* ctx, const sga_index* const* targets, const sga_cloud* const* sources, const double* init_T, size_t count, sga_problem** out) {
   if (count == 0) return SGA_OK;
-  if (out)
-    for (size_t k = 0; k < count; k++) out[k] = nullptr;  // on any failure every out[k] is NULL
+  null_out(out, count);
   if (!ctx || !targets || !sources || !out) return fail(SGA_ERR_INVALID, "null argument");
   SGA_TRY(problem_batch_check(targets, sources, count));
   for (size_t k = 0; k < count; k++)
     if (targets[k]->device != ctx->device || sources[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "target/source live on another device (problem %zu)", k);
   SGA_ENTER(ctx);
-  std::vector<std::unique_ptr<sga_problem>> made;  // (a failure destroys what was made, inside the entry point: the blocks go to the stream's free list)
-  SGA_TRY(problems_batch(ctx, targets, sources, init_T, count, made));
-  for (size_t k = 0; k < count; k++) out[k] = made[k].release();
-  return SGA_OK;
+  return build_into(out, [&](std::vector<std::unique_ptr<sga_problem>>& made) { return problems_batch(ctx, targets, sources, init_T, count, made); });
 }
 
 int sga_problem_destroy(sga_problem* problem) {

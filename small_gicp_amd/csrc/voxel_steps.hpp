@@ -203,8 +203,13 @@ struct VoxelForestChain {
 };
 // The part of the runs stage that the two forests share, on the context's stream: the scratch of `points` points, then `keys_stage` —
 // the forest's own table and keys launch, which fills ch.keys / ch.vals — then the sort under `end_bit` bits, the heads and the scan
-// (ch.keys_sorted, ch.order, ch.flags, ch.seg_id).  Every command counts through `count_launch`.
-int voxel_forest_runs(sga_context* ctx, VoxelForestChain& ch, size_t points, int member_bits, int end_bit, void (*count_launch)(), const std::function<int()>& keys_stage);
+// (ch.keys_sorted, ch.order, ch.flags, ch.seg_id).  Every command counts for `chain`.
+int voxel_forest_runs(sga_context* ctx, VoxelForestChain& ch, size_t points, int member_bits, int end_bit, Chain chain, const std::function<int()>& keys_stage);
+// the ranges section of a table as the host writes it: the identity of min / max, {min x, y, z, max x, y, z} per member
+inline void voxel_range_identity(int* range, size_t count) {
+  for (size_t j = 0; j < count; j++)
+    for (int a = 0; a < 3; a++) range[6 * j + a] = INT_MAX, range[6 * j + 3 + a] = INT_MIN;
+}
 
 // One member of the build chain (read with scalar loads).  The first block is what voxel_keys_kernel receives, used by the stage before the
 // host's wait; the second is what voxel_finalize_kernel receives, known once the host has the voxel counts and filled in for the stage
@@ -225,12 +230,15 @@ struct VoxMember {
   uint32_t hmask, nvox;
   uint32_t run0, pad;              // the member's first run among the runs of the whole chain
 };
-// voxelmap_build.hip: keys, sort, runs of the plan's chain enqueued on the context's stream; member j's voxel count arrives in word 4 j + 5 of
-// the context's box block, its overflow word in word 4 j + 6, then `seq` in word 0
+// voxelmap_build.hip: keys, sort, runs of the plan's chain enqueued on the context's stream; member j's voxel count arrives in word kSlotRuns
+// of its slot of the context's box block, its overflow word in word kSlotOverflow, then `seq` in word 0
 int vox_forest_enqueue_runs(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const VoxForestPlan& plan, unsigned long long seq, VoxelForestChain& ch);
 // the ranks' sort over `runs` runs, the clearing of every member's hash table and the finalize launch (members: second block filled in)
 int vox_forest_enqueue_finalize(sga_context* ctx, const std::vector<VoxMember>& members, size_t runs, double leaf, VoxelForestChain& ch);
-void vox_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the two (sga_debug_voxelmap_batch_launches)
+// the header and the hash table of a Gaussian map of `nvox` voxels over `cloud`, then its per-voxel arrays: what the lone build and the
+// chain make of (cloud, leaf, nvox), each at the point where it allocates
+int gaussian_map_new(sga_context* ctx, const sga_cloud* cloud, double leaf, uint32_t nvox, std::unique_ptr<sga_index>& idx);
+int gaussian_map_alloc_voxels(sga_index* idx);
 
 // One member of the insert chain before the host's wait (table 1, read with scalar loads): what ivm_keys_kernel and ivm_lookup_kernel receive
 struct IvmMember {
@@ -273,7 +281,7 @@ struct IvmExport {
   uint32_t n, pad;
 };
 // voxelmap.hip.  Keys, sort, heads, scan, starts + lookup of the plan's chain: member j's run count, overflow word and new-voxel count
-// arrive in words 4 j + 5 .. 4 j + 7 of the context's box block, then `seq` in word 0
+// arrive in words kSlotRuns, kSlotOverflow, kSlotNewVoxels of its slot of the context's box block, then `seq` in word 0
 int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, VoxelForestChain& ch);
 // the ranks' sort over `runs` runs (`total_new` of them new voxels) of `members_in_chain` members and the assign + update launch (members: the
 // ones that did not overflow)
@@ -281,6 +289,5 @@ int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& me
 int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& maps, VoxelForestChain& ch);
 int ivm_reserve(sga_context* ctx, sga_index* idx, size_t n_total);  // the per-voxel arrays and the table for n_total voxels, under sga_voxelmap_insert's conditions
 int ivm_lru_sweep(sga_context* ctx, sga_index* idx);                // the sweep of sga_voxelmap_insert (incremental_voxelmap.hpp:76-88) when the map's counter says it is due
-void ivm_forest_count_launch();  // batch_preprocess.hip: every kernel, sort, scan and copy command of the chain (sga_debug_voxelmap_insert_batch_launches)
 
 }  // namespace sga

@@ -452,69 +452,57 @@ int ivm_lru_sweep(sga_context* ctx, sga_index* idx) {
 int ivm_forest_enqueue_runs(sga_context* ctx, sga_index* const* maps, const sga_cloud* const* clouds, const double* T, const IvmForestPlan& plan, unsigned long long seq, VoxelForestChain& ch) {
   const size_t count = plan.forest.size();
   if (count == 0) return SGA_OK;
-  const size_t member_words = count * (sizeof(IvmMember) / 8), range_words = 3 * count, counter_words = count, prefix_words = (count + 2) / 2;
-  const size_t words = member_words + range_words + counter_words + 1 + prefix_words;
+  TableLayout L;
+  const auto s_members = L.add<IvmMember>(count);
+  const auto s_range = L.add<int>(6 * count);
+  const auto s_counters = L.add<unsigned>(2 * count);
+  const auto s_ticket = L.add<unsigned>(1);
+  const auto s_prefix = L.add_prefixes(1, count);
   const uint32_t n32 = static_cast<uint32_t>(plan.points);
   const IvmMember* d_members = nullptr;
-  SGA_TRY(voxel_forest_runs(ctx, ch, plan.points, plan.member_bits, plan.end_bit, ivm_forest_count_launch, [&]() -> int {
+  SGA_TRY(voxel_forest_runs(ctx, ch, plan.points, plan.member_bits, plan.end_bit, Chain::IvmInsert, [&]() -> int {
     SGA_TRY(ch.seg_vid.alloc(plan.points));
     std::vector<IvmMember> members(count);
     std::vector<uint32_t> prefix(count + 1, 0u);
-    SGA_TRY(ch.table1.alloc(words));
-    SGA_TRY(upload_table(ctx, ch.table1.p, words, [&](unsigned long long* host) {
-      std::memset(host, 0, words * 8);
-      int* host_range = reinterpret_cast<int*>(host + member_words);
-      uint32_t off = 0;
-      for (size_t j = 0; j < count; j++) {
-        const size_t k = plan.forest[j];
-        const sga_cloud* c = clouds[k];
-        const sga_index* idx = maps[k];
-        IvmMember& g = members[j];
-        std::memset(&g, 0, sizeof(g));
-        g.pts = c->pts.p;
-        g.T = insert_pose(T ? T + 16 * k : nullptr, c->origin);
-        g.inv_leaf = 1.0 / idx->leaf;
-        g.hkeys = idx->hkeys.p;
-        g.hvals = idx->hvals.p;
-        g.range = reinterpret_cast<int*>(ch.table1.p + member_words) + 6 * j;
-        g.counters = reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words) + 2 * j;
-        g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
-        g.hmask = idx->n > 0 ? idx->hmask : 0u;
-        g.n = static_cast<uint32_t>(c->n);
-        g.off = off;
-        off += g.n;
-        for (int a = 0; a < 3; a++) host_range[6 * j + a] = INT_MAX, host_range[6 * j + 3 + a] = INT_MIN;
-        prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
-      }
-      std::memcpy(host, members.data(), member_words * 8);
-      std::memcpy(host + member_words + range_words + counter_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
-      ivm_forest_count_launch();
+    SGA_TRY(ch.table1.alloc(L.words()));
+    uint32_t off = 0;
+    for (size_t j = 0; j < count; j++) {
+      const size_t k = plan.forest[j];
+      const sga_cloud* c = clouds[k];
+      const sga_index* idx = maps[k];
+      IvmMember& g = members[j];
+      std::memset(&g, 0, sizeof(g));
+      g.pts = c->pts.p;
+      g.T = insert_pose(T ? T + 16 * k : nullptr, c->origin);
+      g.inv_leaf = 1.0 / idx->leaf;
+      g.hkeys = idx->hkeys.p;
+      g.hvals = idx->hvals.p;
+      g.range = L.at(s_range, ch.table1.p) + 6 * j;
+      g.counters = L.at(s_counters, ch.table1.p) + 2 * j;
+      g.count_slot = forest_slot_dev(ctx, j);
+      g.hmask = idx->n > 0 ? idx->hmask : 0u;
+      g.n = static_cast<uint32_t>(c->n);
+      g.off = off;
+      off += g.n;
+      prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
+    }
+    count_launch(Chain::IvmInsert);
+    SGA_TRY(upload_table(ctx, ch.table1.p, L.words(), [&](unsigned long long* host) {
+      L.put(s_members, host, members.data());
+      L.put(s_prefix, host, prefix.data());
+      voxel_range_identity(L.at(s_range, host), count);
     }));
-    d_members = reinterpret_cast<const IvmMember*>(ch.table1.p);
-    ivm_forest_count_launch();
-    hipLaunchKernelGGL(ivm_keys_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, reinterpret_cast<const uint32_t*>(ch.table1.p + member_words + range_words + counter_words + 1), static_cast<int>(count), ch.keys.p,
-                       ch.vals.p);
+    d_members = L.at(s_members, ch.table1.p);
+    count_launch(Chain::IvmInsert);
+    hipLaunchKernelGGL(ivm_keys_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, L.at(s_prefix, ch.table1.p), static_cast<int>(count), ch.keys.p, ch.vals.p);
     SGA_HIP(hipGetLastError());
     return SGA_OK;
   }));
-  const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words + counter_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
-  ivm_forest_count_launch();
+  const ForestBoxes hand{L.at(s_ticket, ch.table1.p), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  count_launch(Chain::IvmInsert);
   hipLaunchKernelGGL(ivm_starts_forest_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, ctx->stream, d_members, ch.keys_sorted.p, ch.flags.p, ch.seg_id.p, ch.order.p, n32, ch.seg_start.p, ch.seg_vid.p, ch.rank_keys.p, ch.seg_ids.p, hand);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
-}
-
-// [entries][prefix of the launch's grid: count + 1]: the table of the update launch and of the export launch
-template <typename Entry>
-static int upload_entries(sga_context* ctx, DevBuf<unsigned long long>& table, const std::vector<Entry>& entries, const std::vector<uint32_t>& prefix) {
-  const size_t entry_words = entries.size() * (sizeof(Entry) / 8), words = entry_words + (prefix.size() + 1) / 2;
-  SGA_TRY(table.alloc(words));
-  return upload_table(ctx, table.p, words, [&](unsigned long long* host) {
-    std::memset(host, 0, words * 8);
-    std::memcpy(host, entries.data(), entry_words * 8);
-    std::memcpy(host + entry_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-    ivm_forest_count_launch();
-  });
 }
 
 // `table2`.  One sort of all runs of the chain under the rank key — the members' new voxels in creation order, member after member, then
@@ -525,16 +513,17 @@ int ivm_forest_enqueue_update(sga_context* ctx, const std::vector<IvmUpdate>& me
   std::vector<uint32_t> prefix(count + 1, 0u);
   for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (members[j].nseg + 127u) / 128u;
   if (prefix[count] == 0) return SGA_OK;
-  const size_t member_words = count * (sizeof(IvmUpdate) / 8);
   SGA_TRY(ch.rank_keys_sorted.alloc(runs));
   SGA_TRY(ch.seg_by_rank.alloc(runs));
-  SGA_TRY(upload_entries(ctx, ch.table2, members, prefix));
+  const uint32_t* d_prefix = nullptr;
+  count_launch(Chain::IvmInsert);
+  SGA_TRY(upload_entries(ctx, ch.table2, members, prefix, &d_prefix));
   int rank_member_bits = 0;  // member numbers 0 .. members_in_chain (the last one: the runs of existing voxels)
   while ((1ull << rank_member_bits) < members_in_chain + 1) rank_member_bits++;
-  ivm_forest_count_launch();
+  count_launch(Chain::IvmInsert);
   SGA_TRY(sort_pairs(ctx, ch.rank_keys.p, ch.rank_keys_sorted.p, ch.seg_ids.p, ch.seg_by_rank.p, runs, 0, static_cast<unsigned>(kVoxRankMemberShift + rank_member_bits)));
-  ivm_forest_count_launch();
-  hipLaunchKernelGGL(ivm_update_forest_kernel, dim3(prefix[count]), dim3(128), 0, ctx->stream, reinterpret_cast<const IvmUpdate*>(ch.table2.p), reinterpret_cast<const uint32_t*>(ch.table2.p + member_words), static_cast<int>(count),
+  count_launch(Chain::IvmInsert);
+  hipLaunchKernelGGL(ivm_update_forest_kernel, dim3(prefix[count]), dim3(128), 0, ctx->stream, reinterpret_cast<const IvmUpdate*>(ch.table2.p), d_prefix, static_cast<int>(count),
                      total_new, ch.seg_by_rank.p, ch.seg_start.p, ch.seg_vid.p, ch.keys_sorted.p, ch.order.p);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
@@ -546,10 +535,11 @@ int ivm_forest_enqueue_export(sga_context* ctx, const std::vector<IvmExport>& ma
   if (count == 0) return SGA_OK;
   std::vector<uint32_t> prefix(count + 1, 0u);
   for (size_t j = 0; j < count; j++) prefix[j + 1] = prefix[j] + (maps[j].n + 255u) / 256u;
-  const size_t map_words = count * (sizeof(IvmExport) / 8);
-  SGA_TRY(upload_entries(ctx, ch.table3, maps, prefix));
-  ivm_forest_count_launch();
-  hipLaunchKernelGGL(ivm_export_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, reinterpret_cast<const IvmExport*>(ch.table3.p), reinterpret_cast<const uint32_t*>(ch.table3.p + map_words), static_cast<int>(count));
+  const uint32_t* d_prefix = nullptr;
+  count_launch(Chain::IvmInsert);
+  SGA_TRY(upload_entries(ctx, ch.table3, maps, prefix, &d_prefix));
+  count_launch(Chain::IvmInsert);
+  hipLaunchKernelGGL(ivm_export_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, reinterpret_cast<const IvmExport*>(ch.table3.p), d_prefix, static_cast<int>(count));
   SGA_HIP(hipGetLastError());
   return SGA_OK;
 }

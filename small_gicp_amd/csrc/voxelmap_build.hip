@@ -173,7 +173,7 @@ __global__ __launch_bounds__(128) void voxel_finalize_forest_kernel(const VoxMem
   }
 }
 
-int voxel_forest_runs(sga_context* ctx, VoxelForestChain& ch, size_t points, int member_bits, int end_bit, void (*count_launch)(), const std::function<int()>& keys_stage) {
+int voxel_forest_runs(sga_context* ctx, VoxelForestChain& ch, size_t points, int member_bits, int end_bit, Chain chain, const std::function<int()>& keys_stage) {
   ch.member_bits = member_bits;
   SGA_TRY(ch.keys.alloc(points));
   SGA_TRY(ch.keys_sorted.alloc(points));
@@ -185,59 +185,82 @@ int voxel_forest_runs(sga_context* ctx, VoxelForestChain& ch, size_t points, int
   SGA_TRY(ch.rank_keys.alloc(points));
   SGA_TRY(ch.seg_ids.alloc(points));
   SGA_TRY(keys_stage());
-  count_launch();
+  count_launch(chain);
   SGA_TRY(sort_pairs(ctx, ch.keys.p, ch.keys_sorted.p, ch.vals.p, ch.order.p, points, 0, static_cast<unsigned>(end_bit)));
-  count_launch();
+  count_launch(chain);
   segment_heads_forest(ctx, ch.keys_sorted.p, static_cast<uint32_t>(points), ch.flags.p);
   SGA_HIP(hipGetLastError());
-  count_launch();
+  count_launch(chain);
   return exclusive_scan(ctx, ch.flags.p, ch.seg_id.p, points);
+}
+
+int gaussian_map_new(sga_context* ctx, const sga_cloud* cloud, double leaf, uint32_t nvox, std::unique_ptr<sga_index>& idx) {
+  idx.reset(new sga_index);
+  idx->kind = SGA_INDEX_VOXELMAP;
+  idx->device = ctx->device;
+  idx->leaf = leaf;
+  idx->has_covs = true;
+  idx->has_normals = false;
+  for (int k = 0; k < 3; k++) idx->origin[k] = cloud->origin[k];  // the means are averages of the cloud's device-frame records
+  idx->n = nvox;
+  uint32_t hsize = 16;
+  while (hsize < 2 * static_cast<uint64_t>(nvox)) hsize <<= 1;
+  idx->hmask = hsize - 1;
+  SGA_TRY(idx->hkeys.alloc(hsize));
+  return idx->hvals.alloc(hsize);
+}
+int gaussian_map_alloc_voxels(sga_index* idx) {
+  if (idx->n == 0) return SGA_OK;
+  SGA_TRY(idx->pts.alloc(idx->n));
+  SGA_TRY(idx->cov.alloc(idx->n));
+  SGA_TRY(idx->vcoords.alloc(idx->n * 3));
+  return idx->vcounts.alloc(idx->n);
 }
 
 // `table1`: [members][ranges: 6 ints per member][ticket][prefix of the key grid: count + 1]
 int vox_forest_enqueue_runs(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const VoxForestPlan& plan, unsigned long long seq, VoxelForestChain& ch) {
   const size_t count = plan.forest.size();
   if (count == 0) return SGA_OK;
-  const size_t member_words = count * (sizeof(VoxMember) / 8), range_words = 3 * count, prefix_words = (count + 2) / 2;
-  const size_t words = member_words + range_words + 1 + prefix_words;
+  TableLayout L;
+  const auto s_members = L.add<VoxMember>(count);
+  const auto s_range = L.add<int>(6 * count);
+  const auto s_ticket = L.add<unsigned>(1);
+  const auto s_prefix = L.add_prefixes(1, count);
   const uint32_t n32 = static_cast<uint32_t>(plan.points);
   const VoxMember* d_members = nullptr;
-  SGA_TRY(voxel_forest_runs(ctx, ch, plan.points, plan.member_bits, plan.end_bit, vox_forest_count_launch, [&]() -> int {
+  SGA_TRY(voxel_forest_runs(ctx, ch, plan.points, plan.member_bits, plan.end_bit, Chain::VoxBuild, [&]() -> int {
     std::vector<VoxMember> members(count);
     std::vector<uint32_t> prefix(count + 1, 0u);
-    SGA_TRY(ch.table1.alloc(words));
-    SGA_TRY(upload_table(ctx, ch.table1.p, words, [&](unsigned long long* host) {
-      std::memset(host, 0, words * 8);
-      int* host_range = reinterpret_cast<int*>(host + member_words);
-      uint32_t off = 0;
-      for (size_t j = 0; j < count; j++) {
-        const sga_cloud* c = clouds[plan.forest[j]];
-        VoxMember& g = members[j];
-        std::memset(&g, 0, sizeof(g));
-        g.pts = c->pts.p;
-        g.cov = c->cov.p;
-        g.ox = c->origin[0], g.oy = c->origin[1], g.oz = c->origin[2];
-        g.range = reinterpret_cast<int*>(ch.table1.p + member_words) + 6 * j;
-        g.count_slot = ctx->h_forest_dev + 4 + 4 * j;
-        g.n = static_cast<uint32_t>(c->n);
-        g.off = off;
-        off += g.n;
-        for (int a = 0; a < 3; a++) host_range[6 * j + a] = INT_MAX, host_range[6 * j + 3 + a] = INT_MIN;
-        prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
-      }
-      std::memcpy(host, members.data(), member_words * 8);
-      std::memcpy(host + member_words + range_words + 1, prefix.data(), prefix.size() * sizeof(uint32_t));
-      vox_forest_count_launch();
+    SGA_TRY(ch.table1.alloc(L.words()));
+    uint32_t off = 0;
+    for (size_t j = 0; j < count; j++) {
+      const sga_cloud* c = clouds[plan.forest[j]];
+      VoxMember& g = members[j];
+      std::memset(&g, 0, sizeof(g));
+      g.pts = c->pts.p;
+      g.cov = c->cov.p;
+      g.ox = c->origin[0], g.oy = c->origin[1], g.oz = c->origin[2];
+      g.range = L.at(s_range, ch.table1.p) + 6 * j;
+      g.count_slot = forest_slot_dev(ctx, j);
+      g.n = static_cast<uint32_t>(c->n);
+      g.off = off;
+      off += g.n;
+      prefix[j + 1] = prefix[j] + (g.n + 255u) / 256u;
+    }
+    count_launch(Chain::VoxBuild);
+    SGA_TRY(upload_table(ctx, ch.table1.p, L.words(), [&](unsigned long long* host) {
+      L.put(s_members, host, members.data());
+      L.put(s_prefix, host, prefix.data());
+      voxel_range_identity(L.at(s_range, host), count);
     }));
-    d_members = reinterpret_cast<const VoxMember*>(ch.table1.p);
-    vox_forest_count_launch();
-    hipLaunchKernelGGL(voxel_keys_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, reinterpret_cast<const uint32_t*>(ch.table1.p + member_words + range_words + 1), static_cast<int>(count), 1.0 / leaf, ch.keys.p,
-                       ch.vals.p);
+    d_members = L.at(s_members, ch.table1.p);
+    count_launch(Chain::VoxBuild);
+    hipLaunchKernelGGL(voxel_keys_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, L.at(s_prefix, ch.table1.p), static_cast<int>(count), 1.0 / leaf, ch.keys.p, ch.vals.p);
     SGA_HIP(hipGetLastError());
     return SGA_OK;
   }));
-  const ForestBoxes hand{reinterpret_cast<unsigned*>(ch.table1.p + member_words + range_words), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
-  vox_forest_count_launch();
+  const ForestBoxes hand{L.at(s_ticket, ch.table1.p), static_cast<unsigned>(count), ctx->h_forest_dev, seq};
+  count_launch(Chain::VoxBuild);
   hipLaunchKernelGGL(segment_starts_forest_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, ctx->stream, d_members, ch.keys_sorted.p, ch.flags.p, ch.seg_id.p, ch.order.p, n32, ch.seg_start.p, ch.rank_keys.p, ch.seg_ids.p, hand);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
@@ -252,25 +275,20 @@ int vox_forest_enqueue_finalize(sga_context* ctx, const std::vector<VoxMember>& 
     prefix[j + 1] = prefix[j] + (members[j].hmask + 256u) / 256u;
     prefix[count + 1 + j + 1] = prefix[count + 1 + j] + (members[j].nvox + 127u) / 128u;
   }
-  const size_t member_words = count * (sizeof(VoxMember) / 8), words = member_words + (count + 1);
-  SGA_TRY(ch.table2.alloc(words));
-  SGA_TRY(upload_table(ctx, ch.table2.p, words, [&](unsigned long long* host) {
-    std::memcpy(host, members.data(), member_words * 8);
-    std::memcpy(host + member_words, prefix.data(), prefix.size() * sizeof(uint32_t));
-    vox_forest_count_launch();
-  }));
+  const uint32_t* d_prefix = nullptr;
+  count_launch(Chain::VoxBuild);
+  SGA_TRY(upload_entries(ctx, ch.table2, members, prefix, &d_prefix));
   const VoxMember* d_members = reinterpret_cast<const VoxMember*>(ch.table2.p);
-  const uint32_t* d_prefix = reinterpret_cast<const uint32_t*>(ch.table2.p + member_words);
-  vox_forest_count_launch();
+  count_launch(Chain::VoxBuild);
   hipLaunchKernelGGL(voxel_clear_forest_kernel, dim3(prefix[count]), dim3(256), 0, ctx->stream, d_members, d_prefix, static_cast<int>(count));
   SGA_HIP(hipGetLastError());
   if (runs == 0 || prefix[2 * count + 1] == 0) return SGA_OK;  // (every map of the call is empty)
   // voxel id = rank of the voxel's first inserted point within its member: one sort of all runs under (member, index of the first point)
   SGA_TRY(ch.rank_keys_sorted.alloc(runs));
   SGA_TRY(ch.seg_by_rank.alloc(runs));
-  vox_forest_count_launch();
+  count_launch(Chain::VoxBuild);
   SGA_TRY(sort_pairs(ctx, ch.rank_keys.p, ch.rank_keys_sorted.p, ch.seg_ids.p, ch.seg_by_rank.p, runs, 0, static_cast<unsigned>(kVoxRankMemberShift + ch.member_bits)));
-  vox_forest_count_launch();
+  count_launch(Chain::VoxBuild);
   hipLaunchKernelGGL(voxel_finalize_forest_kernel, dim3(prefix[2 * count + 1]), dim3(128), 0, ctx->stream, d_members, d_prefix + count + 1, static_cast<int>(count), 1.0 / leaf, ch.seg_by_rank.p, ch.seg_start.p, ch.keys_sorted.p, ch.order.p);
   SGA_HIP(hipGetLastError());
   return SGA_OK;
@@ -290,13 +308,6 @@ int sga_index_build_gaussian_voxelmap(sga_context* ctx, const sga_cloud* cloud, 
   *out = nullptr;
   SGA_ENTER(ctx);
   const size_t n = cloud->n;
-  std::unique_ptr<sga_index> idx(new sga_index);
-  idx->kind = SGA_INDEX_VOXELMAP;
-  idx->device = ctx->device;
-  idx->leaf = leaf;
-  idx->has_covs = true;
-  idx->has_normals = false;
-  for (int k = 0; k < 3; k++) idx->origin[k] = cloud->origin[k];  // the means are averages of the cloud's device-frame records
   SGA_TRY(wait_ready(ctx, cloud->ready));
   uint32_t nvox = 0;
   DevBuf<unsigned long long> keys, keys_sorted;
@@ -324,14 +335,10 @@ int sga_index_build_gaussian_voxelmap(sga_context* ctx, const sga_cloud* cloud, 
     SGA_HIP(hipStreamSynchronize(ctx->stream));
     nvox = last_seg + last_flag;
   }
-  idx->n = nvox;
-  uint32_t hsize = 16;
-  while (hsize < 2 * static_cast<uint64_t>(nvox)) hsize <<= 1;
-  idx->hmask = hsize - 1;
-  SGA_TRY(idx->hkeys.alloc(hsize));
-  SGA_TRY(idx->hvals.alloc(hsize));
-  SGA_HIP(hipMemsetAsync(idx->hkeys.p, 0xff, hsize * sizeof(unsigned long long), ctx->stream));
-  SGA_HIP(hipMemsetAsync(idx->hvals.p, 0, hsize * sizeof(uint32_t), ctx->stream));
+  std::unique_ptr<sga_index> idx;
+  SGA_TRY(gaussian_map_new(ctx, cloud, leaf, nvox, idx));
+  SGA_HIP(hipMemsetAsync(idx->hkeys.p, 0xff, idx->hkeys.n * sizeof(unsigned long long), ctx->stream));
+  SGA_HIP(hipMemsetAsync(idx->hvals.p, 0, idx->hvals.n * sizeof(uint32_t), ctx->stream));
   if (nvox > 0) {
     SGA_TRY(seg_start.alloc(nvox));
     SGA_TRY(seg_first.alloc(nvox));
@@ -344,10 +351,7 @@ int sga_index_build_gaussian_voxelmap(sga_context* ctx, const sga_cloud* cloud, 
     SGA_HIP(rocprim::radix_sort_pairs(nullptr, tb, seg_first.p, seg_first_sorted.p, seg_ids.p, seg_by_rank.p, nvox, 0, 32, ctx->stream));
     SGA_TRY(ensure_temp(ctx, tb));
     SGA_HIP(rocprim::radix_sort_pairs(ctx->d_temp.p, tb, seg_first.p, seg_first_sorted.p, seg_ids.p, seg_by_rank.p, nvox, 0, 32, ctx->stream));
-    SGA_TRY(idx->pts.alloc(nvox));
-    SGA_TRY(idx->cov.alloc(nvox));
-    SGA_TRY(idx->vcoords.alloc(static_cast<size_t>(nvox) * 3));
-    SGA_TRY(idx->vcounts.alloc(nvox));
+    SGA_TRY(gaussian_map_alloc_voxels(idx.get()));
     hipLaunchKernelGGL(
       voxel_finalize_kernel, dim3((nvox + 127) / 128), dim3(128), 0, ctx->stream, seg_by_rank.p, nvox, seg_start.p, static_cast<uint32_t>(n_valid), keys_sorted.p, order.p, cloud->pts.p, cloud->cov.p, idx->pts.p, idx->cov.p,
       idx->vcoords.p, idx->vcounts.p, idx->hkeys.p, idx->hvals.p, idx->hmask);
