@@ -145,6 +145,42 @@ int sga_cloud_transform(sga_context* ctx, const sga_cloud* cloud, const double T
 int sga_cloud_deskew_batch(sga_context* ctx, const sga_cloud* const* clouds, const float* const* times, const double* twists /* count x 6 */, const double* ref_times /* count, or NULL: 1.0 each */,
                            size_t count, sga_cloud** out /* count */);
 int sga_cloud_deskew(sga_context* ctx, const sga_cloud* cloud, const float* times, const double twist[6], double ref_time, sga_cloud** out);
+/* Clouds cropped on the device: the returns nobody wants — the ego vehicle, near-field clutter, far noise, non-finite returns, what lies
+ * outside a radius of a submap — dropped ahead of the deskew and the voxel grid, the survivors compacted in their order (DESIGN.md
+ * section 3.20).  ONE predicate, evaluated in double from the fp32 record r and the cloud's origin o:
+ *   range:  x_a = double(r_a) + (o_a - center_a) (the bracket formed once on the host), d2 = x . x; keep iff
+ *           min_range^2 <= d2 && d2 <= max_range^2 (the squares formed on the host; no square root is taken);
+ *   box:    y_a = double(r_a) + o_a, inside iff box_lo_a <= y_a && y_a <= box_hi_a on all three axes; box_mode 1 keeps the points inside,
+ *           2 the finite points NOT inside (an ego-vehicle box: points on the closed boundary are dropped), 0 makes no box test;
+ *   a record with a non-finite coordinate is dropped in every mode: the default crop (sga_crop_default: center 0, ranges 0 and +inf, no
+ *   box) is "remove the non-finite points".
+ * A point is kept when it passes the range test and the box test.  out[k] keeps clouds[k]'s origin; its record j is input record
+ * kept[j] bit for bit in x, y, z, normal and covariance, its index word is j, kept[] ascending (the compaction is stable); out[k] carries the bounding
+ * box of its records.  kept[k] (optional, room for clouds[k]'s size): the indices kept, the first size-of-out[k] entries written —
+ * what a caller needs to keep its times, intensities, rings or labels aligned.  A member of which nothing is kept, and an empty
+ * member, yield an empty cloud without attributes.  One table copy and ONE launch whatever count is, and one host wait — on a
+ * stream-ordered context too: the sizes have to reach the host.  The arrays of out[k] have room for clouds[k]'s size.
+ * count == 0 is SGA_OK before anything is looked at.  Refusals (SGA_ERR_INVALID, every out[k] = NULL as on every failure) — before any
+ * handle is read: NULL arguments (clouds[k] named by number); more than 2^15 members; of crops[k], named by number: min_range negative or
+ * NaN, max_range NaN, min_range > max_range, a non-finite center, box_mode outside 0..2, and with box_mode != 0 a NaN bound or
+ * box_lo > box_hi (infinite bounds are fine) — then: a cloud of another device, 2^31 tiles of 2048 points or more in all.
+ * sga_cloud_crop is the batch of one. */
+typedef struct sga_crop {
+  double center[3];            /* caller's frame; ranges are measured from here */
+  double min_range, max_range; /* keep min_range^2 <= d2 <= max_range^2 */
+  double box_lo[3], box_hi[3]; /* caller's frame, closed interval per axis */
+  int box_mode;                /* 0: no box test, 1: keep inside, 2: keep outside */
+  int pad;
+} sga_crop;
+void sga_crop_default(sga_crop* crop);
+int sga_cloud_crop_batch(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop* crops /* count */, int64_t* const* kept /* count, or NULL; entries may be NULL */, size_t count,
+                         sga_cloud** out /* count */);
+int sga_cloud_crop(sga_context* ctx, const sga_cloud* cloud, const sga_crop* crop, int64_t* kept /* or NULL */, sga_cloud** out);
+/* A new cloud whose record j is record indices[j] of `cloud` — points, normals and covariances bit for bit, the index word j, the origin
+ * kept — by ONE launch: a gather (the reference's random_sampling, util/downsampling.hpp, is the host's choice of indices followed by
+ * this).  Repeats are allowed and the order is as given; m == 0 yields an empty cloud without attributes.  The indices are checked on
+ * the host — an index outside [0, size) is SGA_ERR_INVALID and named by its position — and reach the device through the staging ring. */
+int sga_cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t m, sga_cloud** out);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);
@@ -195,6 +231,10 @@ int sga_cloud_create_device(sga_context* ctx, const sga_device_array* points, co
 int sga_cloud_export_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* points, const sga_device_array* normals, const sga_device_array* covs, void* user_stream, int flags);
 /* sga_cloud_deskew with the times in device memory (above: "Raw sweeps deskewed on the device") */
 int sga_cloud_deskew_device(sga_context* ctx, const sga_cloud* cloud, const sga_device_array* times /* float | double, cols 1, any stride */, const double twist[6], double ref_time, void* user_stream, int flags, sga_cloud** out);
+/* sga_cloud_crop with the indices kept written to device memory: d_kept (or NULL) is device memory of the context's device with room for
+ * the cloud's size in int64, checked against its allocation; the first size-of-*out entries are written.  user_stream is ordered as
+ * sga_cloud_create_device orders it (flags: SGA_IO_NO_ORDER). */
+int sga_cloud_crop_device(sga_context* ctx, const sga_cloud* cloud, const sga_crop* crop, int64_t* d_kept, void* user_stream, int flags, sga_cloud** out);
 /* sga_index_knn for m queries in device memory (float or double rows; the search runs on fl32(double(q) - origin of the index), computed
  * by a kernel): d_idx m*k int64 and d_sq_dist m*k floats, device memory of the caller's.  kd-trees, Gaussian and flat voxel maps, with
  * the kernels, k limits and messages of the host call; a projective index is SGA_ERR_UNSUPPORTED, and the double distances of

@@ -98,6 +98,26 @@ inline sga_context* default_context(int device = 0) {
   return ctxs[device];
 }
 
+/// The predicate of PointCloud::cropped / crop_clouds (sga_crop with its defaults: every finite point is kept).  A point p of the caller's
+/// frame is kept when it is finite, min_range <= |p - center| <= max_range, and — box_mode 1 — it lies inside the closed box [box_lo,
+/// box_hi] or — box_mode 2, an ego-vehicle box — it does not.
+struct Crop : sga_crop {
+  Crop() { sga_crop_default(this); }
+  Crop(double min_r, double max_r) {
+    sga_crop_default(this);
+    min_range = min_r, max_range = max_r;
+  }
+  Crop& box(const std::array<double, 3>& lo, const std::array<double, 3>& hi, int mode = 1) {
+    for (int a = 0; a < 3; a++) box_lo[a] = lo[a], box_hi[a] = hi[a];
+    box_mode = mode;
+    return *this;
+  }
+  Crop& about(const std::array<double, 3>& c) {
+    for (int a = 0; a < 3; a++) center[a] = c[a];
+    return *this;
+  }
+};
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -170,6 +190,24 @@ struct PointCloud {
   Ptr deskewed(const sga_device_array& times, const std::array<double, 6>& twist, double ref_time = 1.0, void* stream = nullptr, int flags = 0) const {
     sga_cloud* made = nullptr;
     check(sga_cloud_deskew_device(ctx, h, &times, twist.data(), ref_time, stream, flags, &made), "sga_cloud_deskew_device");
+    return std::make_shared<PointCloud>(made, ctx);
+  }
+
+  /// This cloud without the points the crop drops, as a new cloud on the device (sga_cloud_crop): the order, the normals, the covariances
+  /// and the origin are kept.  kept (optional): receives the indices kept, ascending — what keeps a sweep's times aligned.
+  Ptr cropped(const Crop& crop, std::vector<int64_t>* kept = nullptr) const {
+    sga_cloud* made = nullptr;
+    if (kept) kept->resize(size());
+    check(sga_cloud_crop(ctx, h, &crop, kept && !kept->empty() ? kept->data() : nullptr, &made), "sga_cloud_crop");
+    Ptr out = std::make_shared<PointCloud>(made, ctx);
+    if (kept) kept->resize(out->size());
+    return out;
+  }
+  /// A new cloud whose point j is this cloud's point indices[j] with its normal and covariance (sga_cloud_select: one launch); repeats
+  /// are allowed, the order is as given.
+  Ptr selected(const std::vector<int64_t>& indices) const {
+    sga_cloud* made = nullptr;
+    check(sga_cloud_select(ctx, h, indices.data(), indices.size(), &made), "sga_cloud_select");
     return std::make_shared<PointCloud>(made, ctx);
   }
 
@@ -774,6 +812,31 @@ inline std::vector<PointCloud::Ptr> deskew_clouds(sga_context* ctx, const std::v
   check(sga_cloud_deskew_batch(ctx, cs.data(), times.data(), xi.data(), ref_times.empty() ? nullptr : ref_times.data(), cs.size(), made.data()), "sga_cloud_deskew_batch");
   std::vector<PointCloud::Ptr> out;
   for (sga_cloud* h : made) out.push_back(std::make_shared<PointCloud>(h, ctx));
+  return out;
+}
+
+/// sga_cloud_crop_batch: PointCloud::cropped for B clouds, each under its own crop, by one table copy and one launch whatever B is.
+/// kept (optional): kept->at(k) receives the indices kept of clouds[k].
+inline std::vector<PointCloud::Ptr> crop_clouds(sga_context* ctx, const std::vector<std::shared_ptr<const PointCloud>>& clouds, const std::vector<Crop>& crops, std::vector<std::vector<int64_t>>* kept = nullptr) {
+  if (crops.size() != clouds.size()) throw std::runtime_error("crop_clouds: as many crops as clouds");
+  std::vector<const sga_cloud*> cs;
+  std::vector<sga_crop> cr(crops.begin(), crops.end());
+  std::vector<int64_t*> kp(clouds.size(), nullptr);
+  if (kept) kept->assign(clouds.size(), {});
+  for (size_t k = 0; k < clouds.size(); k++) {
+    cs.push_back(clouds[k]->h);
+    if (kept) {
+      (*kept)[k].resize(clouds[k]->size());
+      kp[k] = (*kept)[k].empty() ? nullptr : (*kept)[k].data();
+    }
+  }
+  std::vector<sga_cloud*> made(clouds.size(), nullptr);
+  check(sga_cloud_crop_batch(ctx, cs.data(), cr.data(), kept ? kp.data() : nullptr, cs.size(), made.data()), "sga_cloud_crop_batch");
+  std::vector<PointCloud::Ptr> out;
+  for (size_t k = 0; k < made.size(); k++) {
+    out.push_back(std::make_shared<PointCloud>(made[k], ctx));
+    if (kept) (*kept)[k].resize(out[k]->size());
+  }
   return out;
 }
 

@@ -70,6 +70,12 @@ class DeviceArray(C.Structure):
     _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("cols", C.c_int), ("stride", C.c_int)]
 
 
+class Crop(C.Structure):
+    """sga_crop: the predicate of sga_cloud_crop (center, min_range, max_range, box_lo, box_hi, box_mode 0 none | 1 inside | 2 outside)."""
+
+    _fields_ = [("center", C.c_double * 3), ("min_range", C.c_double), ("max_range", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("box_mode", C.c_int), ("pad", C.c_int)]
+
+
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
@@ -102,6 +108,12 @@ SYMBOLS = [
     ("sga_cloud_deskew", C.c_int, [_vp, _vp, _fp, _dp, C.c_double, _pvp]),
     ("sga_cloud_deskew_device", C.c_int, [_vp, _vp, C.POINTER(DeviceArray), _dp, C.c_double, _vp, C.c_int, _pvp]),
     ("sga_debug_cloud_deskew_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_crop_default", None, [C.POINTER(Crop)]),
+    ("sga_cloud_crop_batch", C.c_int, [_vp, _pvp, C.POINTER(Crop), _pvp, C.c_size_t, _pvp]),
+    ("sga_cloud_crop", C.c_int, [_vp, _vp, C.POINTER(Crop), C.POINTER(C.c_int64), _pvp]),
+    ("sga_cloud_crop_device", C.c_int, [_vp, _vp, C.POINTER(Crop), _vp, _vp, C.c_int, _pvp]),
+    ("sga_cloud_select", C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_size_t, _pvp]),
+    ("sga_debug_cloud_crop_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),

@@ -297,6 +297,42 @@ class PointCloud:
             check(load().sga_cloud_deskew_device(self.ctx.h, self.h, C.byref(ta), _dp(xi), float(ref_time), C.c_void_p(_torch_stream(self.ctx, stream)), 0, C.byref(h)))
         return PointCloud(ctx=self.ctx, _handle=h)
 
+    def cropped(self, min_range=0.0, max_range=np.inf, center=None, box=None, box_mode="inside", return_kept=False, stream=None):
+        """This cloud without the returns nobody wants, as a new cloud (sga_cloud_crop): a point p (caller's
+        frame) is kept when it is finite, min_range <= |p - center| <= max_range (center None: the origin of the caller's frame) and —
+        box = (lo, hi), closed per axis — it lies inside the box (box_mode "inside") or not inside it ("outside": an ego-vehicle box).
+        The defaults keep every finite point.  The order of the points, their normals and covariances and the cloud's origin are kept.
+        return_kept: also the indices kept, ascending — (cloud, kept) — so that times, intensities or labels follow: a numpy int64
+        array, or, when stream is given (a torch.cuda.Stream or a hipStream_t the caller works on: sga_cloud_crop_device), a torch int64
+        tensor on the cloud's device that never touches the host."""
+        cr = _crop(min_range, max_range, center, box, box_mode)
+        n = self.size()
+        h = C.c_void_p()
+        if stream is None:
+            kept = np.empty(n, np.int64) if return_kept else None
+            check(load().sga_cloud_crop(self.ctx.h, self.h, C.byref(cr), None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
+            out = PointCloud(ctx=self.ctx, _handle=h)
+            return (out, kept[: out.size()].copy()) if return_kept else out
+        import torch
+
+        dev = torch.device("cuda", int(self.ctx.device))
+        s = _torch_stream(self.ctx, stream)
+        kept = None
+        if return_kept:
+            with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)):  # (allocated on `stream`: torch's allocator orders its reuse behind it)
+                kept = torch.empty((n,), dtype=torch.int64, device=dev)
+        check(load().sga_cloud_crop_device(self.ctx.h, self.h, C.byref(cr), C.c_void_p(kept.data_ptr() if kept is not None and n > 0 else None), C.c_void_p(s), 0, C.byref(h)))
+        out = PointCloud(ctx=self.ctx, _handle=h)
+        return (out, kept[: out.size()]) if return_kept else out
+
+    def selected(self, indices):
+        """A new cloud whose point j is this cloud's point indices[j], with its normal and covariance (sga_cloud_select: one launch).
+        Repeats are allowed, the order is as given, the origin is kept; an index outside [0, size) is refused and named by its position."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        h = C.c_void_p()
+        check(load().sga_cloud_select(self.ctx.h, self.h, idx.ctypes.data_as(C.POINTER(C.c_int64)), len(idx), C.byref(h)))
+        return PointCloud(ctx=self.ctx, _handle=h)
+
     def empty(self):
         return self.size() == 0
 
@@ -1664,6 +1700,83 @@ def deskew_clouds(clouds, times, twists, ref_times=None, ctx=None):
 
 
 _NO_TIMES = C.c_float()  # what an empty member's times point at (never read)
+
+
+_BOX_MODES = {"inside": 1, "outside": 2}
+
+
+def _crop(min_range=0.0, max_range=np.inf, center=None, box=None, box_mode="inside"):
+    """The sga_crop of PointCloud.cropped's arguments (an sga_crop is passed through).  The library judges the values."""
+    if isinstance(min_range, _lib.Crop):
+        return min_range
+    cr = _lib.Crop()
+    load().sga_crop_default(C.byref(cr))
+    cr.min_range, cr.max_range = float(min_range), float(max_range)
+    if center is not None:
+        cr.center[:] = [float(v) for v in np.asarray(center, dtype=np.float64).reshape(3)]
+    if box is not None:
+        if box_mode not in _BOX_MODES:
+            raise ValueError('box_mode must be "inside" or "outside"')
+        lo, hi = box
+        cr.box_lo[:] = [float(v) for v in np.asarray(lo, dtype=np.float64).reshape(3)]
+        cr.box_hi[:] = [float(v) for v in np.asarray(hi, dtype=np.float64).reshape(3)]
+        cr.box_mode = _BOX_MODES[box_mode]
+    return cr
+
+
+def crop_clouds(clouds, crops, return_kept=False, ctx=None):
+    """sga_cloud_crop_batch: PointCloud.cropped for B clouds — crops[k] a dict of cropped()'s keyword arguments (min_range, max_range,
+    center, box, box_mode), or one dict for all — by one table copy and one launch, whatever B is.  Returns the B cropped clouds, or
+    (clouds, kept) with kept[k] the numpy int64 indices kept of clouds[k].  The members may belong to several contexts of one device;
+    ctx: the context the call runs on (default: the first cloud's)."""
+    clouds = list(clouds)
+    for c in clouds:
+        if not isinstance(c, PointCloud):
+            raise TypeError("crop_clouds takes PointCloud objects")
+    B = len(clouds)
+    crops = [crops] * B if isinstance(crops, (dict, _lib.Crop)) else list(crops)
+    if len(crops) != B:
+        raise ValueError(f"{len(crops)} crops for {B} clouds")
+    if B == 0:
+        return ([], []) if return_kept else []  # (count == 0 is no device work: no context is needed)
+    cs = (_lib.Crop * B)(*[c if isinstance(c, _lib.Crop) else _crop(**c) for c in crops])
+    ctx = ctx or clouds[0].ctx
+    hs = (C.c_void_p * B)(*[c.h.value for c in clouds])
+    kept = [np.empty(c.size(), np.int64) for c in clouds] if return_kept else None
+    kp = None if kept is None else (C.c_void_p * B)(*[k.ctypes.data if len(k) else None for k in kept])
+    out = (C.c_void_p * B)()
+    check(load().sga_cloud_crop_batch(ctx.h, hs, cs, kp, B, out))
+    res = [PointCloud(ctx=ctx, _handle=C.c_void_p(out[k])) for k in range(B)]
+    return (res, [kept[k][: res[k].size()].copy() for k in range(B)]) if return_kept else res
+
+
+def random_sampling_indices(n, num_samples, seed=None):
+    """The choice behind random_sampling: num_samples distinct indices of range(n) in ascending order (util/downsampling.hpp: std::sample
+    keeps the input's order), the same for the same seed; every index when num_samples >= n.  Pure host code."""
+    n, num_samples = int(n), int(num_samples)
+    if num_samples < 0:
+        raise ValueError("num_samples must not be negative")
+    if num_samples >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=num_samples, replace=False)).astype(np.int64)
+
+
+def random_sampling(points, num_samples, seed=None):
+    """util/downsampling.hpp random_sampling: num_samples points of the cloud chosen at random, in the input's order, with their normals
+    and covariances — the host picks the indices (random_sampling_indices), one PointCloud.selected follows.  num_samples >= size: the
+    cloud as it is."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    n = cloud.size()
+    if int(num_samples) >= n:
+        return cloud
+    return cloud.selected(random_sampling_indices(n, num_samples, seed))
+
+
+def cloud_crop_launches():
+    """Diagnostics (sga_debug_cloud_crop_launches): table copies and kernels enqueued so far by PointCloud.cropped / crop_clouds."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_crop_launches(C.byref(v)))
+    return v.value
 
 
 def cloud_deskew_launches():

@@ -727,7 +727,10 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
   return SGA_OK;
 }
 
-// the status words of ds_segments_kernel for a launch of `tiles` workgroups, and the launch's epoch (voxelgrid_run's rule: grow-only; a
+}  // namespace
+
+namespace sga {
+// (forest.hpp) the status words of ds_segments_kernel for a launch of `tiles` workgroups, and the launch's epoch (voxelgrid_run's rule: grow-only; a
 // fresh or zeroed array reads "nothing yet" for every epoch > 0; the epochs end at 2^30 - 1)
 int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch) {
   if (ctx->vg_status.n < tiles || ctx->vg_epoch >= (1u << 30) - 1u) {
@@ -738,6 +741,9 @@ int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch) {
   *epoch = ++ctx->vg_epoch;
   return SGA_OK;
 }
+}  // namespace sga
+
+namespace {
 
 template <typename Key>
 int grid_forest_launch(sga_context* ctx, const GridMember* d_members, const uint32_t* d_prefix, const std::vector<uint32_t>& prefix, size_t count, size_t points, double leaf, unsigned end_bit, unsigned epoch, const ForestBoxes& hand) {

@@ -22,8 +22,11 @@ class OnlineOdometry:
     and the context's RCCL communicator (Context.comm_init) sums the shards' systems once per linearization / error pass, so every rank
     computes the same pose."""
 
-    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None):
+    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None):
         self.shard = shard
+        # min_range / max_range (metres from the sensor; None: no bound): when either is given, every scan is cropped on the device ahead of
+        # the deskew (PointCloud.cropped), non-finite returns included, and a sweep's times follow the points kept.  Both None: no crop call.
+        self.crop = None if min_range is None and max_range is None else (0.0 if min_range is None else float(min_range), np.inf if max_range is None else float(max_range))
         self.res = downsampling_resolution
         self.k = num_neighbors
         self.setting = api.make_setting("GICP", max_correspondence_distance=max_correspondence_distance)
@@ -63,6 +66,8 @@ class OnlineOdometry:
         motion it has just yielded: a deskewed scan is never registered against a skewed one."""
         t0 = time.perf_counter()
         raw = api.PointCloud(points, ctx=self.ctx)
+        if self.crop is not None:
+            raw, times = self._cropped(raw, times)
         bootstrap = times is not None and self.motion is None and self.target is not None  # the first registration of a sequence of sweeps
         if times is not None and self.motion is not None:
             raw = raw.deskewed(times, api.se3_log(self.motion), 1.0)
@@ -93,6 +98,21 @@ class OnlineOdometry:
         self.reg_ms.append(1e3 * (t2 - t1))
         self.total_ms.append(1e3 * (t2 - t0))
         return self.T_world.copy()
+
+
+    def _cropped(self, raw, times):
+        """The raw cloud within the estimator's ranges, and the times of the points kept (numpy times: numpy indices; a torch tensor on
+        the device: the indices stay there)."""
+        lo, hi = self.crop
+        if times is None:
+            return raw.cropped(lo, hi), None
+        if isinstance(times, np.ndarray) or not type(times).__module__.startswith("torch"):
+            raw, kept = raw.cropped(lo, hi, return_kept=True)
+            return raw, np.asarray(times).reshape(-1)[kept]
+        import torch
+
+        raw, kept = raw.cropped(lo, hi, return_kept=True, stream=torch.cuda.current_stream(int(self.ctx.device)))
+        return raw, times.reshape(-1)[kept]
 
 
 class ModelOdometry:
@@ -397,17 +417,18 @@ class PipelinedOdometry:
         return poses, wall, iters
 
 
-def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, **kw):
+def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_range=None, max_range=None, **kw):
     """Drive OnlineOdometry over the frozen KITTI-shaped synthetic sequence (small_gicp_amd.synthetic.kitti_like_scan).
     pinned: the scans are held in pinned host memory (api.pinned_copy) before the timed loop, like a driver that reads its scans into
     memory from sga_host_alloc — the reference's benchmark holds them in host memory too (benchmark/benchmark_odom.hpp:36-47); the upload
     then has no CPU pass.
     sweeps: the scans are RAW sweeps of a spinning sensor (synthetic.kitti_like_sweep of frames 1 .. num_frames: every column measured
     from the pose of its own instant) and are handed to the estimator with their times, which deskews them on the device; times=False
-    withholds the times, so the skewed sweeps are registered as if they were snapshots (what the deskew is compared against)."""
+    withholds the times, so the skewed sweeps are registered as if they were snapshots (what the deskew is compared against).
+    min_range / max_range: the estimator crops every scan to these ranges on the device first (OnlineOdometry); both None: no crop."""
     from . import synthetic
 
-    odom = OnlineOdometry(**kw)
+    odom = OnlineOdometry(min_range=min_range, max_range=max_range, **kw)
     est, gt, sizes = [], [], []
     # every scan is in host memory before the loop starts, as in the reference's driver (benchmark/benchmark_odom.hpp:36-47; the generator
     # is ~50 ms of host work per scan: run between the frames it would leave the GPU idle and clocked down)
