@@ -370,12 +370,7 @@ int insert_batch(sga_context* ctx, sga_index* const* maps, const sga_cloud* cons
     const sga_index* idx = maps[own[i]];
     const sga_cloud* cloud = clouds[own[i]];
     double* o = origins.data() + 3 * i;
-    for (int a = 0; a < 3; a++) o[a] = idx->origin[a];
-    if (cloud->n > 0) {  // the device frame of the records follows the inserted scan, as in the lone call
-      const Pose12 P = insert_pose(T ? T + 16 * own[i] : nullptr, cloud->origin);
-      const double lo[3] = {P.t[0], P.t[1], P.t[2]};
-      choose_origin(lo, lo, o);
-    }
+    map_origin_after_insert(insert_pose(T ? T + 16 * own[i] : nullptr, cloud->origin), cloud->n, 1.0 / idx->leaf, idx->origin, o);  // as in the lone call
     if (idx->n == 0) continue;
     IvmExport e;
     std::memset(&e, 0, sizeof(e));

@@ -288,9 +288,9 @@ __global__ void voxel_knn_kernel(
     idx[j] = -1;
     d2[j] = INFINITY;
   }
-  const int cx = fast_floor_d((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
-  const int cy = fast_floor_d((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
-  const int cz = fast_floor_d((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
+  const int cx = query_coord((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
+  const int cy = query_coord((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
+  const int cz = query_coord((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
   int found = 0;
   auto push = [&](long long index, float d) {
     if (d > max_sq || d >= d2[k - 1]) return;

@@ -37,14 +37,31 @@ __device__ __forceinline__ int fast_floor_d(double x) {
   return n - (x < static_cast<double>(n));
 }
 
+// ---- which coordinates the key holds: stated once, for the maps' contents (voxel_steps.hpp) and for the searches below ------------------------
+// voxel_key keeps 21 bits per axis: the coordinates c with |c| < 2^20.  Whether u = x / leaf has such a coordinate is decided ON THE DOUBLE,
+// before the conversion to int: floor(u) > -2^20 <=> u >= -(2^20 - 1), floor(u) < 2^20 <=> u < 2^20.  False for a NaN — the conversion makes
+// 0 of it, a voxel beside the origin —, for +-inf and for everything the conversion saturates: u in [-2^31, -2^31 + 1) floors to INT_MIN,
+// whose absolute value is undefined and in practice negative, so that a test |c| >= 2^20 on the int let it pass and the key's mask sent it
+// to coordinate 0.
+__host__ __device__ __forceinline__ bool voxel_coord_in_range(double u) { return u >= -1048575.0 && u < 1048576.0; }
+// an int coordinate known to lie within +-(2^21 + 1): a query's voxel (query_coord) plus a search offset
+__device__ __forceinline__ bool voxel_coord_in_range(int c) { return c > -(1 << 20) && c < (1 << 20); }
+// The voxel coordinate of a query at u = x / leaf.  A query up to one voxel outside the range still reaches a voxel inside it through a search
+// offset, so the coordinate is needed beyond the range: u is clamped to +-2^21 first (a NaN fails the first comparison and becomes
+// -2^21) — out of range under every offset, never saturated, and c + offset cannot overflow.
+__device__ __forceinline__ int query_coord(double u) {
+  const double w = u >= -2097152.0 ? (u <= 2097152.0 ? u : 2097152.0) : -2097152.0;
+  return fast_floor_d(w);
+}
+
 // returns voxel id or -1.  The query in the arithmetic of the pass (Real): fp64 passes floor the DOUBLE query, as the reference does — a
 // query just below a voxel face whose fp32 rounding lies on the face belongs to the lower voxel.
 template <typename Real>
 __device__ __forceinline__ int voxel_lookup(const VoxelView& v, Real qx, Real qy, Real qz) {
-  const int cx = fast_floor_d((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
-  const int cy = fast_floor_d((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
-  const int cz = fast_floor_d((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
-  if (abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20)) return -1;
+  const int cx = query_coord((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
+  const int cy = query_coord((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
+  const int cz = query_coord((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
+  if (!(voxel_coord_in_range(cx) && voxel_coord_in_range(cy) && voxel_coord_in_range(cz))) return -1;
   const unsigned long long key = voxel_key(cx, cy, cz);
   uint32_t slot = voxel_hash(key) & v.hmask;
   for (uint32_t probe = 0; probe <= v.hmask; ++probe) {
@@ -66,14 +83,14 @@ __device__ __forceinline__ int voxel_lookup(const VoxelView& v, Real qx, Real qy
 // Returns the voxel id or -1.  Distances between the fp32 records the device holds, evaluated in Real.
 template <typename Real>
 __device__ __forceinline__ int voxel_nearest(const VoxelView& v, const float4* __restrict__ means, Real qx, Real qy, Real qz) {
-  const int cx = fast_floor_d((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
-  const int cy = fast_floor_d((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
-  const int cz = fast_floor_d((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
+  const int cx = query_coord((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
+  const int cy = query_coord((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
+  const int cz = query_coord((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
   Real best = static_cast<Real>(INFINITY);
   int j = -1;
   auto offer = [&](int ox, int oy, int oz) {
     const int x = cx + ox, y = cy + oy, z = cz + oz;
-    if (abs(x) >= (1 << 20) || abs(y) >= (1 << 20) || abs(z) >= (1 << 20)) return;
+    if (!(voxel_coord_in_range(x) && voxel_coord_in_range(y) && voxel_coord_in_range(z))) return;
     const unsigned long long key = voxel_key(x, y, z);
     uint32_t slot = voxel_hash(key) & v.hmask;
     int vox = -1;
@@ -125,7 +142,7 @@ struct FlatView {
 };
 
 __device__ __forceinline__ int flat_voxel_at(const FlatView& v, int cx, int cy, int cz) {
-  if (abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20)) return -1;
+  if (!(voxel_coord_in_range(cx) && voxel_coord_in_range(cy) && voxel_coord_in_range(cz))) return -1;
   const unsigned long long key = voxel_key(cx, cy, cz);
   uint32_t slot = voxel_hash(key) & v.hmask;
   for (uint32_t probe = 0; probe <= v.hmask; ++probe) {
@@ -140,9 +157,9 @@ __device__ __forceinline__ int flat_voxel_at(const FlatView& v, int cx, int cy, 
 // returns the slot (voxel * kFlatCap + i) of the nearest stored point or -1; t = that point
 template <typename Real>
 __device__ __forceinline__ int flat_nearest(const FlatView& v, const float4* __restrict__ pts, Real qx, Real qy, Real qz, float4& t) {
-  const int cx = fast_floor_d((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
-  const int cy = fast_floor_d((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
-  const int cz = fast_floor_d((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
+  const int cx = query_coord((static_cast<double>(qx) + v.org[0]) * v.inv_leaf);
+  const int cy = query_coord((static_cast<double>(qy) + v.org[1]) * v.inv_leaf);
+  const int cz = query_coord((static_cast<double>(qz) + v.org[2]) * v.inv_leaf);
   Real best = static_cast<Real>(INFINITY);
   int j = -1;
   auto scan = [&](int ox, int oy, int oz) {

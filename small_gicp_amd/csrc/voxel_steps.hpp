@@ -48,20 +48,32 @@ __device__ __forceinline__ void posed_cov(const Pose12& T, const Cov8 q, double 
 }
 
 // ---- voxel coordinates: true = the point is dropped -----------------------------------------------------------------------------------------
-// a coordinate that voxel_key (21 bits per axis) cannot hold
-__device__ __forceinline__ bool voxel_out_of_range(int cx, int cy, int cz) { return abs(cx) >= (1 << 20) || abs(cy) >= (1 << 20) || abs(cz) >= (1 << 20); }
-// incremental maps: fast_floor(T p / leaf) in double; a point beyond the key's range or with a NaN coordinate is dropped
+// (ux, uy, uz) = x / leaf: a point with a coordinate that voxel_key cannot hold, a NaN or an infinity among them, is dropped — decided on
+// the doubles (voxel_coord_in_range, voxel_hash.hpp); the ints of a dropped point mean nothing
+__device__ __forceinline__ bool voxel_coords(double ux, double uy, double uz, int& cx, int& cy, int& cz) {
+  cx = fast_floor_d(ux), cy = fast_floor_d(uy), cz = fast_floor_d(uz);
+  return !(voxel_coord_in_range(ux) && voxel_coord_in_range(uy) && voxel_coord_in_range(uz));
+}
+// incremental maps: fast_floor(T p / leaf) in double
 __device__ __forceinline__ bool insert_coords(const Pose12& T, const float4 p, double inv_leaf, int& cx, int& cy, int& cz) {
   double x, y, z;
   posed_point(T, p, x, y, z);
-  cx = fast_floor_d(x * inv_leaf), cy = fast_floor_d(y * inv_leaf), cz = fast_floor_d(z * inv_leaf);
-  return voxel_out_of_range(cx, cy, cz) || !(x == x) || !(y == y) || !(z == z);
+  return voxel_coords(x * inv_leaf, y * inv_leaf, z * inv_leaf, cx, cy, cz);
 }
 // one-shot maps; (ox, oy, oz): origin of the cloud's device frame — voxel coordinates are those of the CALLER's frame
-// (incremental_voxelmap.hpp:60).  A point beyond the key's range is dropped.
+// (incremental_voxelmap.hpp:60)
 __device__ __forceinline__ bool build_coords(const float4 p, double ox, double oy, double oz, double inv_leaf, int& cx, int& cy, int& cz) {
-  cx = fast_floor_d((static_cast<double>(p.x) + ox) * inv_leaf), cy = fast_floor_d((static_cast<double>(p.y) + oy) * inv_leaf), cz = fast_floor_d((static_cast<double>(p.z) + oz) * inv_leaf);
-  return voxel_out_of_range(cx, cy, cz);
+  return voxel_coords((static_cast<double>(p.x) + ox) * inv_leaf, (static_cast<double>(p.y) + oy) * inv_leaf, (static_cast<double>(p.z) + oz) * inv_leaf, cx, cy, cz);
+}
+// The device frame of an incremental map's fp32 records follows the inserted scan: its origin becomes the quantised position of the posed
+// cloud frame (T.t = R o_c + t) — unless the cloud is empty, or that position is one the map holds no voxel at (beyond the key's range:
+// every point near it is dropped; records relative to it would lose the map's precision for nothing), where the map keeps its frame.
+inline void map_origin_after_insert(const Pose12& T, size_t n, double inv_leaf, const double old_origin[3], double origin[3]) {
+  for (int k = 0; k < 3; k++) origin[k] = old_origin[k];
+  if (n == 0) return;
+  for (int k = 0; k < 3; k++)
+    if (!voxel_coord_in_range(T.t[k] * inv_leaf)) return;
+  choose_origin(T.t, T.t, origin);
 }
 // the coordinates a voxel_key was made of
 __device__ __forceinline__ void voxel_key_coords(unsigned long long key, int* __restrict__ xyz) {

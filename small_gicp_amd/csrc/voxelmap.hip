@@ -790,11 +790,8 @@ int sga_voxelmap_insert(sga_context* ctx, sga_index* idx, const sga_cloud* cloud
   // moved origin of the cloud's frame, quantised), so a map that walks kilometres (scan-to-model odometry) keeps sub-millimetre records.
   // (the new origin is committed only where the records are exported below — an insert that fails on the way leaves the map's
   // fp32 records AND the origin they are relative to as they were)
-  double new_origin[3] = {idx->origin[0], idx->origin[1], idx->origin[2]};
-  if (cloud->n > 0) {
-    const double lo[3] = {T.t[0], T.t[1], T.t[2]};
-    choose_origin(lo, lo, new_origin);
-  }
+  double new_origin[3];
+  map_origin_after_insert(T, cloud->n, 1.0 / idx->leaf, idx->origin, new_origin);
   const size_t n = cloud->n;
   const uint32_t n_old = static_cast<uint32_t>(idx->n);
   if (n > 0) {

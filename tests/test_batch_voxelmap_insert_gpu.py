@@ -6,9 +6,7 @@ download() (coordinates, fp32 means and covariances, counts), size(), sga_index_
 (queries: the round's points in the map's frame plus a handful far outside).  No tolerance appears except in the oracle case, which uses
 the assertions and the 2e-7 bounds of tests/test_gpu_parity.py::test_incremental_voxelmap_matches_oracle.  LRU stamps and the insert
 counter are observed through the sweeps: a member whose counter or stamps were off would sweep in another round or drop other voxels.
-The shapes are the smallest at which each mechanism of the chain can fail.
-
-(This file has not run on an MI355X yet.)"""
+The shapes are the smallest at which each mechanism of the chain can fail."""
 import ctypes as C
 import os
 import subprocess
