@@ -181,6 +181,42 @@ int sga_cloud_crop(sga_context* ctx, const sga_cloud* cloud, const sga_crop* cro
  * this).  Repeats are allowed and the order is as given; m == 0 yields an empty cloud without attributes.  The indices are checked on
  * the host — an index outside [0, size) is SGA_ERR_INVALID and named by its position — and reach the device through the staging ring. */
 int sga_cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t m, sga_cloud** out);
+/* Outliers removed on the device: isolated returns — rain, dust, multipath, mixed pixels at depth edges — dropped from a cloud by the
+ * distances to its own nearest neighbours, the survivors compacted in their order.  For a cloud of n points,
+ * the point itself counts as its own nearest record at distance 0: s_i(j) is the j-th smallest Euclidean distance from point i to the
+ * records of the cloud, s_i(0) = 0 — the filters depend on multisets of distances only, never on how ties are broken.
+ *   mode 0, statistical (k, std_mul): d_i = (s_i(0) + ... + s_i(k')) / k' with k' = min(k, n - 1) (n = 1: d_0 = 0); mean = sum d_i / n;
+ *           stddev = sqrt(sum (d_i - mean)^2 / (n - 1)), 0 for n < 2; threshold = mean + std_mul * stddev; keep iff d_i <= threshold.
+ *   mode 1, radius (k = the least number of neighbours, radius): keep iff point i has at least k other records within radius, i.e. iff
+ *           s_i(k) <= radius; d_i = s_i(k), +inf when n <= k (such a point is removed).
+ * Distances are the fp32 squared distances of the kd search, square-rooted and summed in double; mean, stddev and threshold are formed
+ * in double on the device in an order that depends on nothing but n (no floating-point atomics): two calls on the same cloud give the
+ * same bits.  kdtree: a kd-tree over THIS cloud — checked as sga_estimate_normals_covariances checks it: kind, size, the origin of the
+ * device frame — or NULL: a temporary one is built.  *out is what sga_cloud_crop hands back: an ordinary cloud that keeps the input's
+ * order, origin, normals and covariances bit for bit, its index word the new position, its box the box of its own records; nothing
+ * kept, or an empty input, yields an empty cloud without attributes (and zeroed stats for an empty input).  kept (or NULL; room for n):
+ * the indices kept, ascending, the first size-of-*out entries written.  stat (or NULL; room for n): d_i in the cloud's order.  stats
+ * (or NULL): mean, stddev and threshold of the d_i (radius mode: threshold = radius; mean and stddev are those of the s_i(k)) and the
+ * number kept.  With a caller's tree the call enqueues at most four commands whatever n is — the statistic, the threshold, the
+ * compaction's table copy, the compaction — and waits once, for the count and the box, on a stream-ordered context too.
+ * A cloud with a non-finite coordinate has no kd-tree (the build refuses it: "contains non-finite coordinates", which a temporary build
+ * reports from here): crop first, sga_cloud_crop's default removes such points.  Refusals (SGA_ERR_INVALID, *out = NULL as on every
+ * failure) — before any handle is read: NULL ctx, cloud, filter or out; mode other than 0 or 1; k outside [1, 63] (the point and its k
+ * neighbours fill the 64 lanes of a wave); in mode 0 a std_mul that is not finite and >= 0; in mode 1 a radius that is not finite and
+ * > 0 — then: a cloud of another device, a tree of another kind, size or device frame, 2^31 points or more. */
+typedef struct sga_outlier_filter {
+  int mode; /* 0 statistical, 1 radius */
+  int k;    /* neighbours: averaged over (mode 0), required within radius (mode 1) */
+  double std_mul;
+  double radius;
+} sga_outlier_filter;
+typedef struct sga_outlier_stats {
+  double mean, stddev, threshold; /* radius mode: threshold = radius, mean / stddev still reported */
+  size_t kept;
+} sga_outlier_stats;
+void sga_outlier_filter_default(sga_outlier_filter* filter); /* statistical, k = 10, std_mul = 1.0 */
+int sga_cloud_remove_outliers(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_outlier_filter* filter, int64_t* kept /* n, or NULL */,
+                              double* stat /* n: d_i in the cloud's order, or NULL */, sga_outlier_stats* stats /* or NULL */, sga_cloud** out);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

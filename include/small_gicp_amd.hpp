@@ -118,6 +118,23 @@ struct Crop : sga_crop {
   }
 };
 
+/// The filter of PointCloud::without_outliers (sga_outlier_filter with its defaults: statistical, k = 10, std_mul = 1).  Statistical: a
+/// point is kept when the mean distance to its k nearest neighbours is at most mean + std_mul * stddev of that figure over the cloud;
+/// radius: when at least k other points lie within `radius`.
+struct OutlierFilter : sga_outlier_filter {
+  OutlierFilter() { sga_outlier_filter_default(this); }
+  static OutlierFilter statistical(int k_ = 10, double std_mul_ = 1.0) {
+    OutlierFilter f;
+    f.k = k_, f.std_mul = std_mul_;
+    return f;
+  }
+  static OutlierFilter within_radius(int min_neighbors, double radius_) {
+    OutlierFilter f;
+    f.mode = 1, f.k = min_neighbors, f.radius = radius_;
+    return f;
+  }
+};
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -199,6 +216,19 @@ struct PointCloud {
     sga_cloud* made = nullptr;
     if (kept) kept->resize(size());
     check(sga_cloud_crop(ctx, h, &crop, kept && !kept->empty() ? kept->data() : nullptr, &made), "sga_cloud_crop");
+    Ptr out = std::make_shared<PointCloud>(made, ctx);
+    if (kept) kept->resize(out->size());
+    return out;
+  }
+  /// This cloud without its isolated returns, as a new cloud on the device (sga_cloud_remove_outliers): the order, the normals, the
+  /// covariances and the origin are kept.  kdtree: the handle of the KdTree over this cloud (KdTree::h), or null: a temporary one is
+  /// built.  kept / stat / stats (optional): the indices kept, ascending; the statistic of every point in this cloud's order; its mean,
+  /// stddev and threshold.  A cloud with a non-finite coordinate is refused: crop first.
+  Ptr without_outliers(const OutlierFilter& filter = OutlierFilter(), const sga_index* kdtree = nullptr, std::vector<int64_t>* kept = nullptr, std::vector<double>* stat = nullptr, sga_outlier_stats* stats = nullptr) const {
+    sga_cloud* made = nullptr;
+    if (kept) kept->resize(size());
+    if (stat) stat->resize(size());
+    check(sga_cloud_remove_outliers(ctx, h, kdtree, &filter, kept && !kept->empty() ? kept->data() : nullptr, stat && !stat->empty() ? stat->data() : nullptr, stats, &made), "sga_cloud_remove_outliers");
     Ptr out = std::make_shared<PointCloud>(made, ctx);
     if (kept) kept->resize(out->size());
     return out;

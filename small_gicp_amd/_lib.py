@@ -76,6 +76,18 @@ class Crop(C.Structure):
     _fields_ = [("center", C.c_double * 3), ("min_range", C.c_double), ("max_range", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("box_mode", C.c_int), ("pad", C.c_int)]
 
 
+class OutlierFilter(C.Structure):
+    """sga_outlier_filter: mode 0 statistical (k, std_mul) | 1 radius (k neighbours within radius)."""
+
+    _fields_ = [("mode", C.c_int), ("k", C.c_int), ("std_mul", C.c_double), ("radius", C.c_double)]
+
+
+class OutlierStats(C.Structure):
+    """sga_outlier_stats: mean, stddev and threshold of the per-point statistic, and the number of points kept."""
+
+    _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kept", C.c_size_t)]
+
+
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
@@ -114,6 +126,9 @@ SYMBOLS = [
     ("sga_cloud_crop_device", C.c_int, [_vp, _vp, C.POINTER(Crop), _vp, _vp, C.c_int, _pvp]),
     ("sga_cloud_select", C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_size_t, _pvp]),
     ("sga_debug_cloud_crop_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_outlier_filter_default", None, [C.POINTER(OutlierFilter)]),
+    ("sga_cloud_remove_outliers", C.c_int, [_vp, _vp, _vp, C.POINTER(OutlierFilter), C.POINTER(C.c_int64), _dp, C.POINTER(OutlierStats), _pvp]),
+    ("sga_debug_cloud_outliers_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),

@@ -325,6 +325,30 @@ class PointCloud:
         out = PointCloud(ctx=self.ctx, _handle=h)
         return (out, kept[: out.size()]) if return_kept else out
 
+    def without_outliers(self, k=10, std_mul=1.0, radius=None, tree=None, return_kept=False, return_stats=False):
+        """This cloud without its isolated returns, as a new cloud (sga_cloud_remove_outliers).  Statistical
+        mode (radius None): a point is kept when the mean distance to its k nearest neighbours is at most mean + std_mul * stddev of
+        that figure over the cloud.  Radius mode (radius given): a point is kept when at least k other points lie within radius.
+        tree: the KdTree over this cloud (None: a temporary one is built).  The order of the points, their normals and covariances and
+        the cloud's origin are kept.  A cloud with a non-finite coordinate is refused: crop first (cropped() removes such points).
+        return_kept: also the indices kept (numpy int64, ascending); return_stats: also a dict with the per-point statistic "stat"
+        (numpy float64, this cloud's order), "mean", "stddev", "threshold" and "kept" — (cloud[, kept][, stats])."""
+        f = _outlier_filter(k, std_mul, radius)
+        n = self.size()
+        kept = np.empty(n, np.int64) if return_kept else None
+        stat = np.empty(n, np.float64) if return_stats else None
+        st = _lib.OutlierStats() if return_stats else None
+        h = C.c_void_p()
+        check(load().sga_cloud_remove_outliers(self.ctx.h, self.h, None if tree is None else tree.h, C.byref(f), None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               None if stat is None else _dp(stat), None if st is None else C.byref(st), C.byref(h)))
+        out = PointCloud(ctx=self.ctx, _handle=h)
+        res = [out]
+        if return_kept:
+            res.append(kept[: out.size()].copy())
+        if return_stats:
+            res.append({"stat": stat, "mean": st.mean, "stddev": st.stddev, "threshold": st.threshold, "kept": int(st.kept)})
+        return res[0] if len(res) == 1 else tuple(res)
+
     def selected(self, indices):
         """A new cloud whose point j is this cloud's point indices[j], with its normal and covariance (sga_cloud_select: one launch).
         Repeats are allowed, the order is as given, the origin is kept; an index outside [0, size) is refused and named by its position."""
@@ -1722,6 +1746,34 @@ def _crop(min_range=0.0, max_range=np.inf, center=None, box=None, box_mode="insi
         cr.box_hi[:] = [float(v) for v in np.asarray(hi, dtype=np.float64).reshape(3)]
         cr.box_mode = _BOX_MODES[box_mode]
     return cr
+
+
+def _outlier_filter(k=10, std_mul=1.0, radius=None):
+    """The sga_outlier_filter of PointCloud.without_outliers' arguments (one is passed through).  The library judges the values."""
+    if isinstance(k, _lib.OutlierFilter):
+        return k
+    f = _lib.OutlierFilter()
+    load().sga_outlier_filter_default(C.byref(f))
+    f.k = int(k)
+    if radius is None:
+        f.std_mul = float(std_mul)
+    else:
+        f.mode, f.radius = 1, float(radius)
+    return f
+
+
+def remove_outliers(points, k=10, std_mul=1.0, radius=None, tree=None, return_kept=False, return_stats=False):
+    """PointCloud.without_outliers of a PointCloud or of an (N,3|4) array (uploaded first)."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    return cloud.without_outliers(k, std_mul, radius, tree, return_kept, return_stats)
+
+
+def cloud_outliers_launches():
+    """Diagnostics (sga_debug_cloud_outliers_launches): commands enqueued so far by PointCloud.without_outliers (the statistic, the
+    threshold, the compaction's table copy, the compaction; a temporary tree's build is not counted)."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_outliers_launches(C.byref(v)))
+    return v.value
 
 
 def crop_clouds(clouds, crops, return_kept=False, ctx=None):

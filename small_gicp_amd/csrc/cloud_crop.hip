@@ -28,6 +28,8 @@ struct CropMember {
   long long* kept64;         // ... or device memory of the caller's; or null
   unsigned long long* acc;   // {min x y z, max x y z (encoded), ticket, finished} in the call's table: identity values and zeros at the start
   unsigned long long* slot;  // eight words of the context's box block (pinned, device-mapped): the count, the box
+  const double* stat;        // the statistic predicate (sga_cloud_remove_outliers, cloud_outliers.hip): one value per point, in the cloud's
+  const double* limit;       // order, and the limit they are held against — device memory written by earlier launches; or both null
   double d[3];               // o - center
   double o[3];
   double r2min, r2max;
@@ -90,7 +92,9 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
   uint32_t wave_total = 0;
 #pragma unroll
   for (int j = 0; j < kCropItems; j++) {
-    kept[j] = __ballot(first + 64u * j < g.n && crop_keeps(g, p[j]));
+    bool keep = first + 64u * j < g.n && crop_keeps(g, p[j]);
+    if (g.stat != nullptr) keep = keep && g.stat[first + 64u * j] <= *g.limit;  // (uniform; read only where the point exists and passes)
+    kept[j] = __ballot(keep);
     wave_total += static_cast<uint32_t>(__popcll(kept[j]));
   }
   if (lane == 0) sh_wave[wave] = wave_total;
@@ -227,7 +231,10 @@ int crop_check(const sga_crop& c, size_t k) {
 // and ONE launch over the members' tiles.  The indices kept leave as uint32 through ONE slot of the staging ring, which the kernel writes
 // by its device address and the host widens after the wait (kept), or as int64 into device memory of the caller's (d_kept, one member).
 // The call waits for the members' counts and boxes (the context's box block: its one wait), on a stream-ordered context too.
-int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop* crops, int64_t* const* kept, int64_t* d_kept, bool device_form, size_t count, void* user_stream, int flags, sga_cloud** out) {
+// stat (one member only): the statistic predicate on top of the crop's, its launches counted under Chain::Outliers.
+int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop* crops, int64_t* const* kept, int64_t* d_kept, bool device_form, size_t count, void* user_stream, int flags, sga_cloud** out,
+               const CropStat* stat = nullptr) {
+  const Chain chain = stat != nullptr ? Chain::Outliers : Chain::Crop;
   if (count == 0) return SGA_OK;
   null_out(out, count);
   if (!ctx || !out || !clouds || !crops) return fail(SGA_ERR_INVALID, "null argument");
@@ -286,6 +293,7 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
   const auto s_prefix = lay.add_prefixes(1, L);
   const auto s_acc = lay.add<unsigned long long>(8 * L);
   const auto s_ticket = lay.add<unsigned>(1);
+  const auto s_limit = lay.add<double>(stat != nullptr ? 1 : 0);  // the limit of a statistic predicate that no launch computes
   DevBuf<unsigned long long> table;  // lives to the end of the call (then: the stream's free list)
   SGA_TRY(table.alloc(lay.words()));
   ForestBoxes hand{nullptr, 0u, nullptr, 0ull};
@@ -323,19 +331,21 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
     g.n = static_cast<uint32_t>(in->n);
     g.tiles = (g.n + kCropTile - 1u) / kCropTile;
     g.box_mode = cr.box_mode;
+    if (stat != nullptr) g.stat = stat->d, g.limit = stat->limit != nullptr ? stat->limit : lay.at(s_limit, table.p);
     prefix[j + 1] = prefix[j] + g.tiles;
   }
   IoOrder ord;
   if (device_form) SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
   auto enqueue = [&]() -> int {
-    count_launch(Chain::Crop);
+    count_launch(chain);
     SGA_TRY(upload_table(ctx, table.p, lay.words(), [&](unsigned long long* host) {
       lay.put(s_members, host, members.data());
       lay.put(s_prefix, host, prefix.data());
       for (size_t w = 0; w < s_acc.count; w++)
         if (w % 8 < 6) lay.at(s_acc, host)[w] = box_enc64(w % 8 < 3 ? INFINITY : -INFINITY);
+      if (stat != nullptr) *lay.at(s_limit, host) = stat->limit_value;
     }));
-    count_launch(Chain::Crop);
+    count_launch(chain);
     hipLaunchKernelGGL(crop_cloud_kernel, dim3(prefix[L]), dim3(kCropThreads), 0, ctx->stream, lay.at(s_members, table.p), lay.at(s_prefix, table.p), static_cast<int>(L), ctx->vg_status.p, epoch, hand);
     SGA_HIP(hipGetLastError());
     return SGA_OK;
@@ -401,6 +411,13 @@ int cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indice
 }
 
 }  // namespace
+
+int cloud_crop_stat(sga_context* ctx, const sga_cloud* cloud, const CropStat& stat, int64_t* kept, sga_cloud** out) {
+  sga_crop all;  // every finite point passes the crop's own predicate
+  sga_crop_default(&all);
+  return cloud_crop(ctx, &cloud, &all, &kept, nullptr, false, 1, nullptr, 0, out, &stat);
+}
+
 }  // namespace sga
 
 using namespace sga;

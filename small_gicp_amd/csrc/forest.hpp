@@ -139,7 +139,7 @@ int build_into(T** out, Build&& build) {
 
 // ---- the launch counters (diagnostics: the sga_debug_*_launches entry points) --------------------------------------------------------------
 // What a chain counts is its own rule: Forest (kd, features) and Grid count kernels and sorts, the others their table copies as well
-enum class Chain { Forest, Grid, VoxBuild, IvmInsert, Problem, Merge, Deskew, Crop, kCount };
+enum class Chain { Forest, Grid, VoxBuild, IvmInsert, Problem, Merge, Deskew, Crop, Outliers, kCount };
 void count_launch(Chain chain);                                  // batch_preprocess.hip
 int report_launches(Chain chain, unsigned long long* launches);  // the body of an sga_debug_*_launches entry point
 
@@ -178,6 +178,16 @@ int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double
 // with room for a launch of `tiles` workgroups, and that launch's epoch.  Words of earlier launches carry an older epoch and read as
 // "nothing yet": nothing is cleared between launches.  Shared by the voxel grid's runs kernels and the crop (cloud_crop.hip).
 int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch);
+// cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip): the crop's compaction — its table, its ONE
+// launch, its one wait, its output cloud — over the points i of `cloud` with d[i] <= the limit.  d (the cloud's size, the cloud's order)
+// and limit are device memory that launches enqueued earlier on the context's stream write; limit == nullptr: limit_value travels in the
+// call's table.  The table copy and the launch are counted under Chain::Outliers.
+struct CropStat {
+  const double* d;
+  const double* limit;
+  double limit_value;
+};
+int cloud_crop_stat(sga_context* ctx, const sga_cloud* cloud, const CropStat& stat, int64_t* kept /* or null */, sga_cloud** out);
 // ---- the voxel forests (DESIGN.md sections 3.14 and 3.15): sga_index_build_gaussian_voxelmap for B clouds, sga_voxelmap_insert for B
 // (Gaussian map, cloud, pose) triples, each in one chain of launches.  The sort key, the tables and the stages: voxel_steps.hpp.
 constexpr size_t kVoxForestMaxMember = 262144;    // points of a member of the chain (2^18: a run's first point takes 18 bits of the rank key)

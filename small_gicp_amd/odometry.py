@@ -22,8 +22,12 @@ class OnlineOdometry:
     and the context's RCCL communicator (Context.comm_init) sums the shards' systems once per linearization / error pass, so every rank
     computes the same pose."""
 
-    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None):
+    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None, outlier_k=None, outlier_std_mul=1.0):
         self.shard = shard
+        # outlier_k (None: off, the default): every downsampled scan loses its isolated returns on the device (PointCloud.without_outliers:
+        # the mean distance to outlier_k neighbours above mean + outlier_std_mul * stddev) after the voxel grid and before the kd-tree and
+        # the covariances.  None: no such call is made.
+        self.outlier = None if outlier_k is None else (int(outlier_k), float(outlier_std_mul))
         # min_range / max_range (metres from the sensor; None: no bound): when either is given, every scan is cropped on the device ahead of
         # the deskew (PointCloud.cropped), non-finite returns included, and a sweep's times follow the points kept.  Both None: no crop call.
         self.crop = None if min_range is None and max_range is None else (0.0 if min_range is None else float(min_range), np.inf if max_range is None else float(max_range))
@@ -71,7 +75,7 @@ class OnlineOdometry:
         bootstrap = times is not None and self.motion is None and self.target is not None  # the first registration of a sequence of sweeps
         if times is not None and self.motion is not None:
             raw = raw.deskewed(times, api.se3_log(self.motion), 1.0)
-        cloud = api.voxelgrid_sampling(raw, self.res)
+        cloud = self._downsampled(raw)
         self.ctx.synchronize()
         t1 = time.perf_counter()
         tree = api.KdTree(cloud)
@@ -89,7 +93,7 @@ class OnlineOdometry:
             self.motion = res.T_target_source
             self.iterations.append(res.iterations + 1)
             if bootstrap:  # once per sequence: this scan again, deskewed, as the next frame's target
-                cloud = api.voxelgrid_sampling(raw.deskewed(times, api.se3_log(self.motion), 1.0), self.res)
+                cloud = self._downsampled(raw.deskewed(times, api.se3_log(self.motion), 1.0))
                 tree = api.KdTree(cloud)
                 api.estimate_covariances(cloud, tree, self.k)
         self.ctx.synchronize()
@@ -99,6 +103,14 @@ class OnlineOdometry:
         self.total_ms.append(1e3 * (t2 - t0))
         return self.T_world.copy()
 
+
+    def _downsampled(self, raw):
+        """The voxel grid of the raw cloud and, when outlier_k is given, that cloud without its isolated returns (a temporary tree: the
+        scan's own tree is built over what is left)."""
+        cloud = api.voxelgrid_sampling(raw, self.res)
+        if self.outlier is not None:
+            cloud = cloud.without_outliers(self.outlier[0], self.outlier[1])
+        return cloud
 
     def _cropped(self, raw, times):
         """The raw cloud within the estimator's ranges, and the times of the points kept (numpy times: numpy indices; a torch tensor on
@@ -417,7 +429,7 @@ class PipelinedOdometry:
         return poses, wall, iters
 
 
-def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_range=None, max_range=None, **kw):
+def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_range=None, max_range=None, outliers=False, outlier_share=0.01, **kw):
     """Drive OnlineOdometry over the frozen KITTI-shaped synthetic sequence (small_gicp_amd.synthetic.kitti_like_scan).
     pinned: the scans are held in pinned host memory (api.pinned_copy) before the timed loop, like a driver that reads its scans into
     memory from sga_host_alloc — the reference's benchmark holds them in host memory too (benchmark/benchmark_odom.hpp:36-47); the upload
@@ -425,7 +437,9 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
     sweeps: the scans are RAW sweeps of a spinning sensor (synthetic.kitti_like_sweep of frames 1 .. num_frames: every column measured
     from the pose of its own instant) and are handed to the estimator with their times, which deskews them on the device; times=False
     withholds the times, so the skewed sweeps are registered as if they were snapshots (what the deskew is compared against).
-    min_range / max_range: the estimator crops every scan to these ranges on the device first (OnlineOdometry); both None: no crop."""
+    min_range / max_range: the estimator crops every scan to these ranges on the device first (OnlineOdometry); both None: no crop.
+    outliers: outlier_share of every scan's returns (1 % by default) are replaced by isolated returns along their own rays
+    (synthetic.with_isolated_returns, seeded by the frame); outlier_k= / outlier_std_mul= (OnlineOdometry) remove them on the device."""
     from . import synthetic
 
     odom = OnlineOdometry(min_range=min_range, max_range=max_range, **kw)
@@ -439,6 +453,8 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
             stamps.append(ts if times else None)
         else:
             pts, Tws = synthetic.kitti_like_scan(f)
+        if outliers:
+            pts = synthetic.with_isolated_returns(pts, outlier_share, seed=4242 + f)[0]
         scans.append(api.pinned_copy(pts[:, :3], np.float32) if pinned else np.ascontiguousarray(pts[:, :3], dtype=np.float32))
         if T0 is None:
             T0 = Tws

@@ -156,3 +156,19 @@ def kitti_like_sweep(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02
     r = t_best[keep] + rng.normal(0, noise, keep.sum())
     pts = d_s[keep] * r[:, None]
     return np.ascontiguousarray(pts, dtype=np.float32), np.ascontiguousarray(s_col[col][keep]), T1, xi, surface[keep]
+
+
+def with_isolated_returns(points, share=0.01, seed=4242, min_range=5.0, max_range=60.0):
+    """The scan with isolated returns scattered into it — rain, dust, multipath: round(share * N) of its points (chosen from `seed`) are
+    replaced by returns along their own rays at a range uniform in [min_range, max_range] m, i.e. somewhere in the free space in front
+    of (or behind) the surface the ray hit.  The number and the order of the points are kept, so times and rings still line up.
+    Returns (points float32 (N,3), indices of the replaced points, ascending)."""
+    pts = np.array(points, dtype=np.float32)[:, :3].copy()
+    n = len(pts)
+    m = int(round(share * n))
+    rng = np.random.default_rng(seed)
+    idx = np.sort(rng.choice(n, size=m, replace=False)).astype(np.int64)
+    d = pts[idx].astype(np.float64)
+    d /= np.maximum(np.linalg.norm(d, axis=1), 1e-9)[:, None]
+    pts[idx] = (d * rng.uniform(min_range, max_range, m)[:, None]).astype(np.float32)
+    return np.ascontiguousarray(pts), idx
