@@ -1,8 +1,9 @@
 // Clouds cropped and gathered on the device: sga_cloud_crop / _batch / _device — range and box filters with a
-// stable compaction, one table and ONE launch for B members — and sga_cloud_select, a gather by host indices.
+// stable compaction, one table and ONE launch for B members — and the gather behind sga_cloud_select (indices) and sga_cloud_slice (a range).
 #include "cloud_box.hpp"
 #include "device_io.hpp"
 #include "forest.hpp"
+#include "lookback.hpp"
 
 #include <cmath>
 #include <memory>
@@ -13,7 +14,6 @@ namespace {
 constexpr int kCropThreads = 256, kCropItems = 8, kCropTile = kCropThreads * kCropItems;
 static_assert(kCropThreads == kIoBlock, "box64_reduce_block reduces the waves of a 256-thread workgroup");
 constexpr unsigned kCropSpinLimit = 1u << 22;  // polls of one look-back window before a workgroup gives up (seconds: the call then fails)
-constexpr size_t kCropMaxMembers = 1u << 15;
 
 // One member of a crop (read with scalar loads): its records and where the kept ones go, the predicate's constants — formed on the host
 // in double —, its words of the call's table and its slot of the box block.
@@ -26,8 +26,8 @@ struct CropMember {
   Cov8* ocov;
   uint32_t* kept32;          // the indices kept: a stretch of a slot of the staging ring, by its device address; or null
   long long* kept64;         // ... or device memory of the caller's; or null
-  unsigned long long* acc;   // {min x y z, max x y z (encoded), ticket, finished} in the call's table: identity values and zeros at the start
-  unsigned long long* slot;  // eight words of the context's box block (pinned, device-mapped): the count, the box
+  unsigned long long* acc;   // {min x y z, max x y z (encoded), ticket, finished} in the call's table (cloud_box.hpp: MemberBoxes)
+  unsigned long long* slot;  // its slot of the context's box block (pinned, device-mapped): the count, the box
   const double* stat;        // the statistic predicate (sga_cloud_remove_outliers, cloud_outliers.hip): one value per point, in the cloud's
   const double* limit;       // order, and the limit they are held against — device memory written by earlier launches; or both null
   double d[3];               // o - center
@@ -51,6 +51,19 @@ __device__ __forceinline__ bool crop_keeps(const CropMember& g, const float4 p) 
     keep = keep && (inside == (g.box_mode == 1));
   }
   return keep;
+}
+
+// Record i, whose point is p, becomes record r: the point with the index word r, then normal and covariance (two float4) where the output keeps them.
+__device__ __forceinline__ void copy_record(const float4 p, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, uint32_t i, float4* __restrict__ opts, float4* __restrict__ onrm, Cov8* __restrict__ ocov, uint32_t r) {
+  opts[r] = make_float4(p.x, p.y, p.z, __uint_as_float(r));
+  if (onrm != nullptr) onrm[r] = nrm[i];
+  if (ocov != nullptr) {
+    const float4* cin = reinterpret_cast<const float4*>(cov + i);
+    float4* cout = reinterpret_cast<float4*>(ocov + r);
+    const float4 c0 = cin[0], c1 = cin[1];
+    cout[0] = c0;
+    cout[1] = c1;
+  }
 }
 
 }  // namespace
@@ -105,21 +118,20 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
     if (w < wave) wave_base += sh_wave[w];
     total += sh_wave[w];
   }
-  const unsigned long long tag = static_cast<unsigned long long>(epoch) << 34;
-  constexpr unsigned long long kAgg = 1ull << 32, kPrefix = 2ull << 32;
+  const unsigned long long tag = static_cast<unsigned long long>(epoch) << kLookEpochShift;
   bool gave_up = false;  // (wave 0, uniform)
   if (wave == 0) {
     uint32_t excl = 0;
     if (tile > 0) {
-      if (lane == 0) __hip_atomic_store(&status[tile], tag | kAgg | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) __hip_atomic_store(&status[tile], tag | kLookAgg | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       int look = static_cast<int>(tile) - 1;
       for (;;) {
         const int j = look - lane;
         unsigned long long w;
         unsigned polls = 0;
         for (;;) {
-          w = j >= 0 ? __hip_atomic_load(&status[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : (tag | kPrefix);
-          if (__ballot((w >> 34) != (tag >> 34)) == 0ull) break;  // every predecessor of this window has published
+          w = j >= 0 ? __hip_atomic_load(&status[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : (tag | kLookPrefix);
+          if (__ballot((w >> kLookEpochShift) != (tag >> kLookEpochShift)) == 0ull) break;  // every predecessor of this window has published
           if (++polls >= kCropSpinLimit) {
             gave_up = true;
             break;
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
           __builtin_amdgcn_s_sleep(2);
         }
         if (gave_up) break;
-        const unsigned long long prefixes = __ballot((w & kPrefix) != 0ull);
+        const unsigned long long prefixes = __ballot((w & kLookPrefix) != 0ull);
         const int stop = prefixes != 0ull ? __ffsll(static_cast<long long>(prefixes)) - 1 : 63;  // nearest predecessor holding an inclusive prefix
         uint32_t v = lane <= stop ? static_cast<uint32_t>(w) : 0u;
 #pragma unroll
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
       }
     }
     if (lane == 0) {
-      __hip_atomic_store(&status[tile], tag | kPrefix | (excl + total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&status[tile], tag | kLookPrefix | (excl + total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       sh_excl = excl;  // (after a give-up: below the true prefix — every write stays inside the member's arrays)
     }
   }
@@ -151,15 +163,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
     if ((mask >> lane) & 1ull) {
       const uint32_t i = first + 64u * j;
       const uint32_t r = dst + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-      g.opts[r] = make_float4(p[j].x, p[j].y, p[j].z, __uint_as_float(r));
-      if (g.onrm != nullptr) g.onrm[r] = g.nrm[i];
-      if (g.ocov != nullptr) {
-        const float4* cin = reinterpret_cast<const float4*>(g.cov + i);
-        float4* cout = reinterpret_cast<float4*>(g.ocov + r);
-        const float4 c0 = cin[0], c1 = cin[1];
-        cout[0] = c0;
-        cout[1] = c1;
-      }
+      copy_record(p[j], g.nrm, g.cov, i, g.opts, g.onrm, g.ocov, r);
       if (g.kept32 != nullptr) g.kept32[r] = i;
       if (g.kept64 != nullptr) g.kept64[r] = static_cast<long long>(i);
       const double x = p[j].x, y = p[j].y, z = p[j].z;
@@ -178,34 +182,24 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
   }
   __syncthreads();
   if (!sh_last) return;  // workgroup-uniform
-  if (threadIdx.x < 6) g.slot[kCropSlotLo + threadIdx.x] = __hip_atomic_load(&g.acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x < 6) g.slot[kBoxSlotLo + threadIdx.x] = __hip_atomic_load(&g.acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (threadIdx.x == 0) {
     // every tile has finished: the last tile's word holds its inclusive prefix, the member's count
     const unsigned long long w = __hip_atomic_load(&status[g.tiles - 1u], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    g.slot[kCropSlotCount] = sh_failed ? ~0ull : (w & 0xffffffffull);
+    g.slot[kBoxSlotCount] = sh_failed ? ~0ull : (w & 0xffffffffull);
   }
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) forest_box_arrive(hand);
 }
 
-// out record j = in record idx[j], the index word j
-__global__ __launch_bounds__(256) void select_cloud_kernel(const float4* __restrict__ pts, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, const uint32_t* __restrict__ idx, uint32_t m, float4* __restrict__ opts,
+// out record j = in record idx[j] (select), or first + j when idx is null (slice); the index word j
+__global__ __launch_bounds__(256) void gather_cloud_kernel(const float4* __restrict__ pts, const float4* __restrict__ nrm, const Cov8* __restrict__ cov, const uint32_t* __restrict__ idx, uint32_t first, uint32_t m, float4* __restrict__ opts,
                                                            float4* __restrict__ onrm, Cov8* __restrict__ ocov) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= m) return;
-  const uint32_t i = idx[j];
-  float4 p = pts[i];
-  p.w = __uint_as_float(j);
-  opts[j] = p;
-  if (nrm != nullptr) onrm[j] = nrm[i];
-  if (cov != nullptr) {
-    const float4* cin = reinterpret_cast<const float4*>(cov + i);
-    float4* cout = reinterpret_cast<float4*>(ocov + j);
-    const float4 c0 = cin[0], c1 = cin[1];
-    cout[0] = c0;
-    cout[1] = c1;
-  }
+  const uint32_t i = idx != nullptr ? idx[j] : first + j;
+  copy_record(pts[i], nrm, cov, i, opts, onrm, ocov, j);
 }
 
 namespace {
@@ -227,6 +221,24 @@ int crop_check(const sga_crop& c, size_t k) {
   return SGA_OK;
 }
 
+// What the records of `in` and the crop `cr` alone decide of a member's entry: the inputs, the predicate's constants, the tiles.
+CropMember crop_member(const sga_cloud* in, const sga_crop& cr) {
+  CropMember g;
+  std::memset(&g, 0, sizeof(g));
+  g.pts = in->pts.p, g.nrm = in->has_normals ? in->nrm.p : nullptr, g.cov = in->has_covs ? in->cov.p : nullptr;
+  for (int a = 0; a < 3; a++) {
+    g.d[a] = in->origin[a] - cr.center[a];
+    g.o[a] = in->origin[a];
+    g.blo[a] = cr.box_lo[a], g.bhi[a] = cr.box_hi[a];
+  }
+  g.r2min = cr.min_range * cr.min_range;
+  g.r2max = cr.max_range * cr.max_range;
+  g.n = static_cast<uint32_t>(in->n);
+  g.tiles = (g.n + kCropTile - 1u) / kCropTile;
+  g.box_mode = cr.box_mode;
+  return g;
+}
+
 // `count` clouds, each cropped by its own predicate: one table — [members][prefix of the grid][accumulators: 8 words per member][ticket] —
 // and ONE launch over the members' tiles.  The indices kept leave as uint32 through ONE slot of the staging ring, which the kernel writes
 // by its device address and the host widens after the wait (kept), or as int64 into device memory of the caller's (d_kept, one member).
@@ -238,99 +250,48 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
   if (count == 0) return SGA_OK;
   null_out(out, count);
   if (!ctx || !out || !clouds || !crops) return fail(SGA_ERR_INVALID, "null argument");
-  if (count > kCropMaxMembers) return fail(SGA_ERR_INVALID, "too many members (%zu; limit %zu)", count, kCropMaxMembers);
-  for (size_t k = 0; k < count; k++)
-    if (!clouds[k]) return fail(SGA_ERR_INVALID, "null argument: clouds[%zu] is NULL", k);
+  SGA_TRY(cloud_members_args(clouds, count));
   for (size_t k = 0; k < count; k++) SGA_TRY(crop_check(crops[k], k));
   // ---- (from here on the handles are read)
-  std::vector<size_t> live;  // empty members take no workgroups
-  size_t tiles = 0, kept_words = 0;
-  for (size_t k = 0; k < count; k++) {
-    if (clouds[k]->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud %zu lives on another device", k);
-    if (clouds[k]->n == 0) continue;
-    live.push_back(k);
-    tiles += (clouds[k]->n + kCropTile - 1) / kCropTile;
+  CloudMembers mem;
+  SGA_TRY(cloud_members(ctx, clouds, count, kCropTile, &mem));
+  const std::vector<size_t>& live = mem.live;
+  size_t kept_words = 0;
+  for (size_t k : live)
     if (kept != nullptr && kept[k] != nullptr) kept_words += clouds[k]->n;
-  }
-  if (tiles >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many points in all (%zu tiles of %d; limit 2^31-1)", tiles, kCropTile);
+  if (mem.blocks >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many points in all (%zu tiles of %d; limit 2^31-1)", mem.blocks, kCropTile);
   if (!live.empty()) SGA_HIP(hipSetDevice(ctx->device));
   if (d_kept != nullptr && !live.empty()) SGA_TRY(check_device_range(ctx, d_kept, clouds[0]->n * sizeof(int64_t), sizeof(int64_t), "d_kept", "sga_cloud_crop"));
   StreamScope stream_scope(ctx->stream);
-  // The output arrays have room for the input: the count is known only once the kernel has run, and the kernel writes in the same pass
-  // (the voxel grid's speculative path does the same; a shrinking copy would be a second launch).
-  std::vector<std::unique_ptr<sga_cloud>> made(count);
-  auto empty_like = [&](const sga_cloud* in) {
-    std::unique_ptr<sga_cloud> c(new sga_cloud);
-    c->device = ctx->device;
-    for (int a = 0; a < 3; a++) c->origin[a] = in->origin[a];
-    return c;
-  };
-  for (size_t k = 0; k < count; k++) {
-    const sga_cloud* in = clouds[k];
-    made[k] = empty_like(in);  // (an empty member: an empty cloud without attributes)
-    if (in->n == 0) continue;
-    sga_cloud* c = made[k].get();
-    c->has_normals = in->has_normals;
-    c->has_covs = in->has_covs;
-    SGA_TRY(c->pts.alloc(in->n));
-    if (in->has_normals) SGA_TRY(c->nrm.alloc(in->n));
-    if (in->has_covs) SGA_TRY(c->cov.alloc(in->n));
-  }
-  auto hand_over = [&]() {
-    for (size_t k = 0; k < count; k++) out[k] = made[k].release();
-    return SGA_OK;
-  };
-  if (live.empty()) return hand_over();
+  std::vector<std::unique_ptr<sga_cloud>> made(count);  // with room for the input: the count is known only once the kernel has run
+  for (size_t k = 0; k < count; k++) SGA_TRY(cloud_make_like(ctx, clouds[k], clouds[k]->n, &made[k]));
+  if (live.empty()) return hand_over(made, out);
   const size_t L = live.size();
   for (size_t k : live) SGA_TRY(wait_ready(ctx, clouds[k]->ready));  // made by another context in stream-ordered mode (common.hpp: Ready)
   sga_context::StageSlot* kslot = nullptr;
   if (kept_words > 0) SGA_TRY(stage_acquire(ctx, kept_words * sizeof(uint32_t), &kslot));
   unsigned epoch = 0;
-  SGA_TRY(voxelgrid_status(ctx, static_cast<uint32_t>(tiles), &epoch));
+  SGA_TRY(voxelgrid_status(ctx, static_cast<uint32_t>(mem.blocks), &epoch));
   // ---- the table
   TableLayout lay;
   const auto s_members = lay.add<CropMember>(L);
   const auto s_prefix = lay.add_prefixes(1, L);
-  const auto s_acc = lay.add<unsigned long long>(8 * L);
-  const auto s_ticket = lay.add<unsigned>(1);
+  MemberBoxes boxes;
+  boxes.add(lay, L);
   const auto s_limit = lay.add<double>(stat != nullptr ? 1 : 0);  // the limit of a statistic predicate that no launch computes
-  DevBuf<unsigned long long> table;  // lives to the end of the call (then: the stream's free list)
-  SGA_TRY(table.alloc(lay.words()));
-  ForestBoxes hand{nullptr, 0u, nullptr, 0ull};
-  SGA_TRY(forest_call_begin(ctx, L, kCropSlotWords, &hand.seq));
-  hand.ticket = lay.at(s_ticket, table.p);
-  hand.total = static_cast<unsigned>(L);
-  hand.seq_word = ctx->h_forest_dev;
+  DevBuf<unsigned long long> table;
+  ForestBoxes hand;
+  SGA_TRY(boxes.begin(ctx, lay, table, &hand));
   std::vector<CropMember> members(L);
   std::vector<uint32_t> prefix(L + 1, 0u);
-  std::vector<size_t> koff(L, 0);
   size_t kat = 0;
   for (size_t j = 0; j < L; j++) {
     const size_t k = live[j];
-    const sga_cloud* in = clouds[k];
-    const sga_crop& cr = crops[k];
-    CropMember& g = members[j];
-    std::memset(&g, 0, sizeof(g));
-    g.pts = in->pts.p, g.nrm = in->has_normals ? in->nrm.p : nullptr, g.cov = in->has_covs ? in->cov.p : nullptr;
+    CropMember& g = members[j] = crop_member(clouds[k], crops[k]);
     g.opts = made[k]->pts.p, g.onrm = made[k]->nrm.p, g.ocov = made[k]->cov.p;
-    if (kept != nullptr && kept[k] != nullptr) {
-      koff[j] = kat;
-      g.kept32 = static_cast<uint32_t*>(kslot->dev) + kat;
-      kat += in->n;
-    }
+    if (kept != nullptr && kept[k] != nullptr) g.kept32 = static_cast<uint32_t*>(kslot->dev) + kat, kat += g.n;
     g.kept64 = reinterpret_cast<long long*>(d_kept);
-    g.acc = lay.at(s_acc, table.p) + 8 * j;
-    g.slot = forest_slot_dev(ctx, j, kCropSlotWords);
-    for (int a = 0; a < 3; a++) {
-      g.d[a] = in->origin[a] - cr.center[a];
-      g.o[a] = in->origin[a];
-      g.blo[a] = cr.box_lo[a], g.bhi[a] = cr.box_hi[a];
-    }
-    g.r2min = cr.min_range * cr.min_range;
-    g.r2max = cr.max_range * cr.max_range;
-    g.n = static_cast<uint32_t>(in->n);
-    g.tiles = (g.n + kCropTile - 1u) / kCropTile;
-    g.box_mode = cr.box_mode;
+    g.acc = lay.at(boxes.acc, table.p) + 8 * j, g.slot = forest_slot_dev(ctx, j, kBoxSlotWords);
     if (stat != nullptr) g.stat = stat->d, g.limit = stat->limit != nullptr ? stat->limit : lay.at(s_limit, table.p);
     prefix[j + 1] = prefix[j] + g.tiles;
   }
@@ -341,8 +302,7 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
     SGA_TRY(upload_table(ctx, table.p, lay.words(), [&](unsigned long long* host) {
       lay.put(s_members, host, members.data());
       lay.put(s_prefix, host, prefix.data());
-      for (size_t w = 0; w < s_acc.count; w++)
-        if (w % 8 < 6) lay.at(s_acc, host)[w] = box_enc64(w % 8 < 3 ? INFINITY : -INFINITY);
+      boxes.init(host);
       if (stat != nullptr) *lay.at(s_limit, host) = stat->limit_value;
     }));
     count_launch(chain);
@@ -352,60 +312,46 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
   };
   SGA_TRY(forest_call_wait(ctx, enqueue(), hand.seq, "counts of a crop"));  // (the wait shows that every workgroup has written what it writes)
   if (device_form) SGA_TRY(io_end(ctx, ord));
+  kat = 0;
   for (size_t j = 0; j < L; j++) {
     const size_t k = live[j];
-    const unsigned long long* slot = forest_slot_host(ctx, j, kCropSlotWords);
-    const unsigned long long m = slot[kCropSlotCount];
+    const uint32_t* src = kept != nullptr && kept[k] != nullptr ? static_cast<const uint32_t*>(kslot->host) + kat : nullptr;  // as the kernel was told
+    if (src != nullptr) kat += clouds[k]->n;
+    const unsigned long long m = forest_slot_host(ctx, j, kBoxSlotWords)[kBoxSlotCount];
     if (m == ~0ull) return fail(SGA_ERR_HIP, "the crop of cloud %zu gave up waiting for a predecessor tile", k);
     if (m > clouds[k]->n) return fail(SGA_ERR_HIP, "the device reported %llu points kept of the %zu of cloud %zu", m, clouds[k]->n, k);
     if (m == 0) {
-      made[k] = empty_like(clouds[k]);  // nothing kept: an empty cloud without attributes
+      SGA_TRY(cloud_make_like(ctx, clouds[k], 0, &made[k]));  // nothing kept: an empty cloud without attributes
       continue;
     }
     made[k]->n = static_cast<size_t>(m);
-    double lo[3], hi[3];
-    for (int a = 0; a < 3; a++) lo[a] = box_dec64(slot[kCropSlotLo + a]), hi[a] = box_dec64(slot[kCropSlotHi + a]);
-    cloud_set_box(made[k].get(), lo, hi, true, false);  // the box of the records themselves
-    if (kept != nullptr && kept[k] != nullptr) {
-      const uint32_t* src = static_cast<const uint32_t*>(kslot->host) + koff[j];
-      for (size_t i = 0; i < m; i++) kept[k][i] = static_cast<int64_t>(src[i]);
-    }
+    boxes.read(ctx, j, made[k].get());
+    for (size_t i = 0; src != nullptr && i < m; i++) kept[k][i] = static_cast<int64_t>(src[i]);
   }
   for (size_t k : live) SGA_TRY(mark_ready(ctx, made[k]->ready));
-  return hand_over();
+  return hand_over(made, out);
 }
 
-int cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t m, sga_cloud** out) {
-  if (out) *out = nullptr;
-  if (!ctx || !cloud || !out || (m > 0 && !indices)) return fail(SGA_ERR_INVALID, "null argument");
-  if (m >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many indices (%zu; limit 2^31-1)", m);
-  if (cloud->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
-  for (size_t j = 0; j < m; j++)
-    if (indices[j] < 0 || static_cast<unsigned long long>(indices[j]) >= cloud->n) return fail(SGA_ERR_INVALID, "indices[%zu] = %lld is outside a cloud of %zu points", j, static_cast<long long>(indices[j]), cloud->n);
-  SGA_ENTER(ctx);
-  std::unique_ptr<sga_cloud> c(new sga_cloud);
-  c->device = ctx->device;
-  c->n = m;
-  for (int a = 0; a < 3; a++) c->origin[a] = cloud->origin[a];
-  if (m == 0) {  // an empty cloud without attributes
-    *out = c.release();
-    return SGA_OK;
+// The m records indices[j] of `cloud` (select), or first .. first + m - 1 when indices is null (slice), as a cloud in its cloud's device frame:
+// ONE launch, none for m == 0, no host wait (the indices' slot of the staging ring is reused only behind the kernel), no box.  m == 0: an
+// empty cloud without attributes, unless keep_flags (a slice keeps its cloud's).  The caller has checked the arguments and entered the context.
+int cloud_gather(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t first, size_t m, bool keep_flags, sga_cloud** out) {
+  std::unique_ptr<sga_cloud> c;
+  SGA_TRY(cloud_make(ctx, cloud->origin, m, (m > 0 || keep_flags) && cloud->has_normals, (m > 0 || keep_flags) && cloud->has_covs, &c));
+  if (m > 0) {
+    SGA_TRY(wait_ready(ctx, cloud->ready));
+    sga_context::StageSlot* slot = nullptr;
+    if (indices != nullptr) {
+      SGA_TRY(stage_acquire(ctx, m * sizeof(uint32_t), &slot));
+      uint32_t* host = static_cast<uint32_t*>(slot->host);
+      for (size_t j = 0; j < m; j++) host[j] = static_cast<uint32_t>(indices[j]);
+    }
+    hipLaunchKernelGGL(gather_cloud_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, cloud->pts.p, cloud->nrm.p, cloud->cov.p, slot != nullptr ? static_cast<const uint32_t*>(slot->dev) : nullptr, static_cast<uint32_t>(first),
+                       static_cast<uint32_t>(m), c->pts.p, c->nrm.p, c->cov.p);
+    SGA_HIP(hipGetLastError());
+    if (slot != nullptr) SGA_TRY(stage_release(ctx, slot));
+    SGA_TRY(mark_ready(ctx, c->ready));
   }
-  c->has_normals = cloud->has_normals;
-  c->has_covs = cloud->has_covs;
-  SGA_TRY(c->pts.alloc(m));
-  if (cloud->has_normals) SGA_TRY(c->nrm.alloc(m));
-  if (cloud->has_covs) SGA_TRY(c->cov.alloc(m));
-  SGA_TRY(wait_ready(ctx, cloud->ready));
-  sga_context::StageSlot* slot = nullptr;
-  SGA_TRY(stage_acquire(ctx, m * sizeof(uint32_t), &slot));
-  uint32_t* host = static_cast<uint32_t*>(slot->host);
-  for (size_t j = 0; j < m; j++) host[j] = static_cast<uint32_t>(indices[j]);
-  hipLaunchKernelGGL(select_cloud_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, cloud->pts.p, cloud->has_normals ? cloud->nrm.p : nullptr, cloud->has_covs ? cloud->cov.p : nullptr, static_cast<const uint32_t*>(slot->dev),
-                     static_cast<uint32_t>(m), c->pts.p, c->nrm.p, c->cov.p);
-  SGA_HIP(hipGetLastError());
-  SGA_TRY(stage_release(ctx, slot));  // (the slot is reused only after the event behind the kernel: no wait here, as in sga_cloud_slice)
-  SGA_TRY(mark_ready(ctx, c->ready));
   *out = c.release();
   return SGA_OK;
 }
@@ -444,7 +390,25 @@ int sga_cloud_crop_device(sga_context* ctx, const sga_cloud* cloud, const sga_cr
   return cloud_crop(ctx, &cloud, crop, nullptr, d_kept, true, 1, user_stream, flags, out);
 }
 
-int sga_cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t m, sga_cloud** out) { return cloud_select(ctx, cloud, indices, m, out); }
+int sga_cloud_select(sga_context* ctx, const sga_cloud* cloud, const int64_t* indices, size_t m, sga_cloud** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !cloud || !out || (m > 0 && !indices)) return fail(SGA_ERR_INVALID, "null argument");
+  if (m >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many indices (%zu; limit 2^31-1)", m);
+  if (cloud->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
+  for (size_t j = 0; j < m; j++)
+    if (indices[j] < 0 || static_cast<unsigned long long>(indices[j]) >= cloud->n) return fail(SGA_ERR_INVALID, "indices[%zu] = %lld is outside a cloud of %zu points", j, static_cast<long long>(indices[j]), cloud->n);
+  SGA_ENTER(ctx);
+  return cloud_gather(ctx, cloud, indices, 0, m, false, out);
+}
+
+int sga_cloud_slice(sga_context* ctx, const sga_cloud* cloud, size_t first, size_t count, sga_cloud** out) {
+  if (!ctx || !cloud || !out) return fail(SGA_ERR_INVALID, "null argument");
+  if (first > cloud->n || count > cloud->n - first) return fail(SGA_ERR_INVALID, "slice [%zu, %zu) outside a cloud of %zu points", first, first + count, cloud->n);
+  if (cloud->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
+  *out = nullptr;
+  SGA_ENTER(ctx);
+  return cloud_gather(ctx, cloud, nullptr, first, count, true, out);  // (shards of one registration share their cloud's device frame)
+}
 
 int sga_debug_cloud_crop_launches(unsigned long long* launches) { return report_launches(Chain::Crop, launches); }
 

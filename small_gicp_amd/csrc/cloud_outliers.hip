@@ -1,7 +1,8 @@
 // Outliers removed on the device: sga_cloud_remove_outliers — the mean distance to the k nearest neighbours
 // (statistical mode) or the distance to the k-th (radius mode) of every point from the exact k-NN of the cloud's own kd-tree, a threshold
-// formed in double on the device, and the crop's stable compaction over the points within it (cloud_crop.hip: cloud_crop_stat).  No host
-// wait but the crop's.
+// formed in double on the device, and the crop's stable compaction over the points within it (cloud_crop.hip: cloud_crop_stat,
+// cloud_ops.hpp).  No host wait but the crop's.
+#include "cloud_ops.hpp"
 #include "forest.hpp"
 #include "knn_wave.hpp"
 

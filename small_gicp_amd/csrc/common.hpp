@@ -115,7 +115,7 @@ struct sga_context {
   sga::DevBuf<unsigned> d_ticket; // arrival counter of the reduction kernel (reduce_rows.hpp), zero between launches
   double* h_accum = nullptr;      // pinned + device-mapped: [0, 128) a result, word 128 = sequence number of the last published result
   double* h_accum_dev = nullptr;  // device address of h_accum
-  // pinned, device-mapped staging ring for uploads from pageable memory (cloud.hip): the pack kernel reads a slot over PCIe while
+  // pinned, device-mapped staging ring for uploads from pageable memory (cloud_io.hip): the pack kernel reads a slot over PCIe while
   // the host fills the next one; a slot is reused once the event recorded behind its reader has completed
   struct StageSlot {
     void* host = nullptr;
@@ -158,7 +158,7 @@ struct sga_context {
   uint64_t comm_calls = 0;
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // sga_debug_timer_*: GPU time between two points of the stream
   hipEvent_t ev_aux = nullptr;   // small read-backs that must not wait for the work enqueued behind them (stream-ordered mode)
-  // device_io.hpp: the two events that order a caller's stream against the context's (made on first use), and (cloud.hip) the 64-bit
+  // device_io.hpp: the two events that order a caller's stream against the context's (made on first use), and (cloud_io.hip) the 64-bit
   // accumulator of a double cloud's bounding box {min x y z, max x y z (ordered encoding), arrival counter, 0}: identity values between launches
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
   sga::DevBuf<unsigned long long> d_box64;
@@ -181,7 +181,7 @@ struct sga_context {
   bool sharded() const { return comm != nullptr || comm_fn != nullptr; }
 };
 
-// cloud.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
+// cloud_io.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
 // the event that stage_release records behind its reader has completed.
 int stage_acquire(sga_context* ctx, size_t bytes, sga_context::StageSlot** out);
 int stage_release(sga_context* ctx, sga_context::StageSlot* slot);
@@ -190,9 +190,11 @@ int stage_release(sga_context* ctx, sga_context::StageSlot* slot);
 // estimation returns while its kernels are still in flight on the producing context's stream.  The object remembers that stream and an
 // event recorded behind the work; an entry point that consumes the object on ANOTHER stream first makes its stream wait for the event
 // (sga::wait_ready), so outputs never race with a half-built input whichever context consumes them.  (Same stream: stream order suffices.)
-// Producers that return early in stream-ordered mode: sga_index_build_kdtree, sga_estimate_normals_covariances, sga_index_clone; every
-// entry point that takes a cloud or an index waits (problem creation, index build, estimation, refresh, voxel grid, voxel-map insert, kNN,
-// downloads, clone).  All other producers (voxel grid, voxel-map insert / build, uploads) synchronise their stream before they return.
+// Producers that may return early in stream-ordered mode, and mark what they made (sga::mark_ready): sga_index_build_kdtree,
+// sga_estimate_normals_covariances, sga_index_clone, and every producer of a cloud — the uploads (host arrays, sga_cloud_create_device),
+// slice, select, merge / transform, deskew, crop and outlier removal.  Every entry point that takes a cloud or an index waits (problem
+// creation, index build, estimation, refresh, voxel grid, voxel-map insert, kNN, downloads, clone, and the cloud operations above).  The
+// other producers (voxel grid, voxel-map insert / build) synchronise their stream before they return.
 namespace sga {
 struct Ready {
   hipEvent_t event = nullptr;

@@ -1,6 +1,6 @@
 // Device-resident clouds, queries and results: what the entry points that take their data from, and leave their
 // results in, device memory of the context's device have in common (device_io.hpp) — sga_cloud_create_device, sga_cloud_export_device
-// (cloud.hip), sga_index_knn_device, sga_problem_get_factors_device (problem.hip).  Nothing of the caller's data touches the host; the
+// (cloud_io.hip), sga_index_knn_device, sga_problem_get_factors_device (problem.hip).  Nothing of the caller's data touches the host; the
 // caller's stream and the context's are ordered by two events (io_begin / io_end), never by a host wait.  Every caller pointer is checked
 // against the allocation it lies in before a kernel is given it: a wrong row count must be an error code, not a fault on a device other
 // people are using.

@@ -1,4 +1,4 @@
-// What the entry points that read or write caller memory on the device share (cloud.hip, problem.hip; defined in device_io.hip): the
+// What the entry points that read or write caller memory on the device share (cloud_io.hip, cloud_pose.hip, cloud_crop.hip, problem.hip; defined in device_io.hip): the
 // checks of a caller's pointers, the ordering of a caller's stream against the context's, and the strided row loads of their kernels.
 #pragma once
 #include "common.hpp"

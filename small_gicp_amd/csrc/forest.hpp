@@ -110,14 +110,12 @@ int upload_entries(sga_context* ctx, DevBuf<unsigned long long>& table, const st
 
 // ---- the box block and the call ---------------------------------------------------------------------------------------------------------
 // Member j's slot: `stride` words from word 4 + stride * j of the block, as the device addresses it and as the host reads it
-constexpr size_t kSlotWords = 4, kDeskewSlotWords = 8, kCropSlotWords = 8;
+constexpr size_t kSlotWords = 4;  // (deskew and crop: kBoxSlotWords, cloud_ops.hpp)
 inline unsigned long long* forest_slot_dev(const sga_context* ctx, size_t j, size_t stride = kSlotWords) { return ctx->h_forest_dev + 4 + stride * j; }
 inline const unsigned long long* forest_slot_host(const sga_context* ctx, size_t j, size_t stride = kSlotWords) { return ctx->h_forest + 4 + stride * j; }
 // what the words of a slot hold
 constexpr int kSlotBox = 1;                                          // kd forest, problem creation: words 1..3, the box (box_note_decode)
 constexpr int kSlotRuns = 1, kSlotOverflow = 2, kSlotNewVoxels = 3;  // grid forest: runs; map build: runs, overflow; insert: all three
-constexpr int kDeskewSlotLo = 0, kDeskewSlotHi = 3;                  // deskew (kDeskewSlotWords): the box, three words each (box_dec64)
-constexpr int kCropSlotCount = 0, kCropSlotLo = 1, kCropSlotHi = 4;  // crop (kCropSlotWords): the points kept, then the box of the kept records
 // batch_preprocess.hip.  A call begins: the box block has room for `members` slots of `stride` words, *seq is the call's sequence number
 int forest_call_begin(sga_context* ctx, size_t members, size_t stride, unsigned long long* seq);
 // ... and, its chain enqueued with status `enqueued`, waits until the block shows `seq`.  A failed enqueue and a failed wait (`what`
@@ -174,20 +172,6 @@ GridForestPlan grid_forest_plan(const sga_cloud* const* clouds, size_t count, do
 // preprocess.hip: keys, sort, runs, centroids of the plan's forest members enqueued on the context's stream; out[j]: the records of forest
 // member j (room for the member's point count); member j's run count arrives in word kSlotRuns of its slot of the box block, then `seq` in word 0
 int grid_forest_enqueue(sga_context* ctx, const sga_cloud* const* clouds, double leaf, const GridForestPlan& plan, float4* const* out, unsigned long long seq);
-// preprocess.hip: the context's look-back status words (ctx->vg_status: one word per tile, {epoch : 30, state : 2, value : 32}; grow-only)
-// with room for a launch of `tiles` workgroups, and that launch's epoch.  Words of earlier launches carry an older epoch and read as
-// "nothing yet": nothing is cleared between launches.  Shared by the voxel grid's runs kernels and the crop (cloud_crop.hip).
-int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch);
-// cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip): the crop's compaction — its table, its ONE
-// launch, its one wait, its output cloud — over the points i of `cloud` with d[i] <= the limit.  d (the cloud's size, the cloud's order)
-// and limit are device memory that launches enqueued earlier on the context's stream write; limit == nullptr: limit_value travels in the
-// call's table.  The table copy and the launch are counted under Chain::Outliers.
-struct CropStat {
-  const double* d;
-  const double* limit;
-  double limit_value;
-};
-int cloud_crop_stat(sga_context* ctx, const sga_cloud* cloud, const CropStat& stat, int64_t* kept /* or null */, sga_cloud** out);
 // ---- the voxel forests (DESIGN.md sections 3.14 and 3.15): sga_index_build_gaussian_voxelmap for B clouds, sga_voxelmap_insert for B
 // (Gaussian map, cloud, pose) triples, each in one chain of launches.  The sort key, the tables and the stages: voxel_steps.hpp.
 constexpr size_t kVoxForestMaxMember = 262144;    // points of a member of the chain (2^18: a run's first point takes 18 bits of the rank key)

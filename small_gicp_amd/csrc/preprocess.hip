@@ -11,6 +11,7 @@
 #include "forest.hpp"
 #include "kd_search.hpp"
 #include "knn_wave.hpp"
+#include "lookback.hpp"
 #include "notes.hpp"
 #include "sort_util.hpp"
 
@@ -68,8 +69,7 @@ __global__ void downsample_keys_kernel(const float4* __restrict__ pts, uint32_t 
 // Sorted keys -> the start of every run (seg_start[r], r in ascending key order), the number of runs (scratch[1]) and of valid points
 // (scratch[2]); the number of runs also goes to the host as a note.  Single pass: a workgroup takes the next tile of 2048 keys (arrival
 // order = tile order, so a workgroup only ever waits for workgroups that are already running), counts its run heads, publishes the count
-// and looks back over its predecessors' published counts / prefixes 64 at a time (decoupled look-back).  status[]: one word per tile,
-// {epoch : 30, state : 2, value : 32}; words of earlier launches carry an older epoch and read as "nothing yet", so nothing is cleared.
+// and looks back over its predecessors' published counts / prefixes 64 at a time (decoupled look-back; lookback.hpp: the status words).
 constexpr int kSegThreads = 256, kSegItems = 8, kSegTile = kSegThreads * kSegItems;
 // (the body of ds_segments_kernel and of its batched form; num_tiles: the workgroups that share scratch[0] and status[]; done(runs) is
 // called by one thread of the last tile to be taken)
@@ -109,20 +109,19 @@ __device__ __forceinline__ void ds_segments_body(const Key* __restrict__ keys, u
     if (w < wave) wave_base += sh_wave[w];
     total += sh_wave[w];
   }
-  const unsigned long long tag = static_cast<unsigned long long>(epoch) << 34;
-  constexpr unsigned long long kAgg = 1ull << 32, kPrefix = 2ull << 32;
+  const unsigned long long tag = static_cast<unsigned long long>(epoch) << kLookEpochShift;
   if (wave == 0) {
     uint32_t excl = 0;
     if (tile > 0) {
-      if (lane == 0) __hip_atomic_store(&status[tile], tag | kAgg | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) __hip_atomic_store(&status[tile], tag | kLookAgg | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       int look = static_cast<int>(tile) - 1;
       for (;;) {
         const int j = look - lane;
         unsigned long long w;
         do {
-          w = j >= 0 ? __hip_atomic_load(&status[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : (tag | kPrefix);
-        } while (__ballot((w >> 34) != (tag >> 34)) != 0ull);  // every predecessor of this window has taken its tile: it publishes without waiting for anybody
-        const unsigned long long prefixes = __ballot((w & kPrefix) != 0ull);
+          w = j >= 0 ? __hip_atomic_load(&status[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : (tag | kLookPrefix);
+        } while (__ballot((w >> kLookEpochShift) != (tag >> kLookEpochShift)) != 0ull);  // every predecessor of this window has taken its tile: it publishes without waiting for anybody
+        const unsigned long long prefixes = __ballot((w & kLookPrefix) != 0ull);
         const int stop = prefixes != 0ull ? __ffsll(static_cast<long long>(prefixes)) - 1 : 63;  // nearest predecessor holding an inclusive prefix
         uint32_t v = lane <= stop ? static_cast<uint32_t>(w) : 0u;
 #pragma unroll
@@ -133,7 +132,7 @@ __device__ __forceinline__ void ds_segments_body(const Key* __restrict__ keys, u
       }
     }
     if (lane == 0) {
-      __hip_atomic_store(&status[tile], tag | kPrefix | (excl + total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&status[tile], tag | kLookPrefix | (excl + total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       sh_excl = excl;
     }
   }
@@ -730,7 +729,7 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
 }  // namespace
 
 namespace sga {
-// (forest.hpp) the status words of ds_segments_kernel for a launch of `tiles` workgroups, and the launch's epoch (voxelgrid_run's rule: grow-only; a
+// (lookback.hpp) the status words of ds_segments_kernel for a launch of `tiles` workgroups, and the launch's epoch (voxelgrid_run's rule: grow-only; a
 // fresh or zeroed array reads "nothing yet" for every epoch > 0; the epochs end at 2^30 - 1)
 int voxelgrid_status(sga_context* ctx, uint32_t tiles, unsigned* epoch) {
   if (ctx->vg_status.n < tiles || ctx->vg_epoch >= (1u << 30) - 1u) {

@@ -1,4 +1,4 @@
-"""Sweeps deskewed on the device (csrc/cloud.hip: sga_cloud_deskew / _batch / _device).
+"""Sweeps deskewed on the device (csrc/cloud_pose.hip: sga_cloud_deskew / _batch / _device).
 
 The reference is an fp64 restatement in this file, computed from the members' records, origins, times and twists, never the library.  For
 a member with twist xi = (w, v), origin o, reference time s0 and a point with record r and time s:  a = float64(s) - s0, theta = |w|,

@@ -1,4 +1,4 @@
-"""Posed clouds merged on the device (csrc/cloud.hip: sga_cloud_merge / sga_cloud_transform).
+"""Posed clouds merged on the device (csrc/cloud_pose.hip: sga_cloud_merge / sga_cloud_transform).
 
 The reference is an fp64 restatement in this file, computed from the members' records and origins, never the library: for member m with
 pose (R, t) and origin o_m, and the output's origin o,

@@ -1,4 +1,4 @@
-"""Every way of making and reading a cloud (csrc/cloud.hip) against a NumPy fp64 restatement written here.
+"""Every way of making and reading a cloud (csrc/cloud_io.hip; slices: csrc/cloud_crop.hip) against a NumPy fp64 restatement written here.
 
 The host and the device entry points share one pack and one unpack kernel, so "device equals host" (tests/test_device_io_gpu.py) compares
 a kernel with itself; this file says what the bytes must BE.  Every step is one correctly rounded IEEE operation (a widening, one

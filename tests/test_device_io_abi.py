@@ -1,4 +1,4 @@
-"""The boundary of the device-resident entry points (csrc/cloud.hip, problem.hip, device_io.hip) without a device: the four symbols
+"""The boundary of the device-resident entry points (csrc/cloud_io.hip, problem.hip, device_io.hip) without a device: the four symbols
 exist and are bound, the Python names are callable, an empty call is SGA_OK whatever else is passed, null arguments and a bad dtype /
 cols / stride are refused before any handle is read — the handles handed in are stand-ins at an address nothing is mapped at, so reading
 one would end the process — and from_torch refuses what it cannot take with ValueError before the library (or a context) is needed.

@@ -1,4 +1,4 @@
-"""Device-resident clouds, queries and results (csrc/cloud.hip, problem.hip, device_io.hip): torch tensors and device pointers in and out.
+"""Device-resident clouds, queries and results (csrc/cloud_io.hip, problem.hip, device_io.hip): torch tensors and device pointers in and out.
 
 Every comparison is BIT EQUALITY with the host entry point fed the same values — no tolerance anywhere: the device path computes
 fl32(double(x) - o), double(record) + o and plain casts, the host path the same expressions on the same values, and a bounding box is
