@@ -217,6 +217,51 @@ typedef struct sga_outlier_stats {
 void sga_outlier_filter_default(sga_outlier_filter* filter); /* statistical, k = 10, std_mul = 1.0 */
 int sga_cloud_remove_outliers(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_outlier_filter* filter, int64_t* kept /* n, or NULL */,
                               double* stat /* n: d_i in the cloud's order, or NULL */, sga_outlier_stats* stats /* or NULL */, sga_cloud** out);
+/* A posed cloud compared with a target on the device: how much of a scan the map already explains, and which points are new (DESIGN.md
+ * section 3.22) — the keyframe decision of a mapping loop, the fitness and inlier RMSE of a loop-closure candidate, "add only what the
+ * map does not hold yet", change detection.  For point i of `cloud` (fp32 record r_i in the device frame at origin o_c) and a target
+ * whose device frame is at o_t:  q_i = R r_i + (c - o_t) in double, c = R o_c + t (per row ((R0 o0 + R1 o1) + R2 o2) + t); T
+ * (column-major 4x4, maps the cloud into the target; NULL: the identity) gives R and t.
+ *   kd-tree target:   the exact nearest record of float(q_i) by the registration's 1-NN walk, searched within max_distance widened by
+ *                     |q_i - float(q_i)|; d_i is that record's distance measured again in double from q_i.
+ *   Gaussian map (one-shot or incremental) / flat map: the lookup of the registration over the map's own search offsets (1 / 7 / 27),
+ *                     the first of equal distances winning; d_i is the distance to the voxel's mean / to the stored point.
+ * Point i is MATCHED iff it has a winner and d_i <= max_distance.  It is unmatched when it has none, when the winner is farther, or
+ * when a coordinate of q_i is not finite; an unmatched point reports d_i = +inf and nearest -1.  An empty target (no points, no voxels)
+ * leaves every point unmatched.
+ * dist (or NULL; room for n): d_i in the cloud's order.  nearest (or NULL; room for n): the winner — the target point's ORIGINAL index
+ * (kd-tree), the voxel id (Gaussian map), voxel * 16 + slot (flat map: its position in sga_flatmap_download's arrays).  stats (or NULL):
+ * points = n, matched, fitness = matched / points (0 for an empty cloud), rmse = sqrt(sum d_i^2 / matched) and mean_distance over the
+ * matched (0 when there are none) — the sums formed in double on the device in an order that depends on nothing but n (no
+ * floating-point atomics): two calls give the same bits.
+ * params->keep: 0 — statistics only, out must be NULL; 1 / 2 — *out receives the matched / the unmatched points as an ordinary cloud, by
+ * the compaction of sga_cloud_crop: the input's order, origin, normals and covariances, record j of *out equal to input record kept[j] bit
+ * for bit, its index word j, its box the box of its own records; nothing kept, or an empty input, yields an empty cloud without
+ * attributes.  As in the crop the compaction keeps finite records only: a point with a non-finite coordinate counts in `points`, never in
+ * `matched`, and is in no output cloud, the unmatched one included.  kept (or NULL; room for n; only with keep != 0): the indices kept,
+ * ascending, the first size-of-*out entries written.
+ * Commands: a statistics-only call enqueues TWO — the distances, the sums — and waits once for the second; with an output cloud the
+ * compaction's table copy and launch follow (four in all) and the one wait is the compaction's, on a stream-ordered context too.  An
+ * empty cloud enqueues nothing and gives zero stats.  The cloud and the target may have been made on other contexts of the device that
+ * returned before their kernels had run: the call orders itself behind both.
+ * Refusals (SGA_ERR_INVALID, *out = NULL as on every failure) — before any handle is read: NULL ctx, cloud, target or params; keep
+ * outside 0..2; out given with keep == 0, or missing with keep != 0; kept given with keep == 0; max_distance NaN or <= 0 (+inf is
+ * allowed); a non-finite entry of T — then: a cloud or a target of another device, a projective target (SGA_ERR_UNSUPPORTED), 2^31
+ * points or more. */
+typedef struct sga_overlap {
+  double max_distance;
+  int keep; /* 0 none, 1 the matched, 2 the unmatched */
+  int reserved;
+} sga_overlap;
+typedef struct sga_overlap_stats {
+  size_t points, matched;
+  double fitness; /* matched / points, 0 for an empty cloud */
+  double rmse;    /* over the matched, 0 if none */
+  double mean_distance;
+} sga_overlap_stats;
+void sga_overlap_default(sga_overlap* p); /* max_distance 1.0, keep 0 */
+int sga_cloud_overlap(sga_context* ctx, const sga_cloud* cloud, const sga_index* target, const double T[16] /* or NULL */, const sga_overlap* params, double* dist /* n, or NULL */, int64_t* nearest /* n, or NULL */,
+                      int64_t* kept /* n, or NULL */, sga_overlap_stats* stats /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

@@ -135,6 +135,27 @@ struct OutlierFilter : sga_outlier_filter {
   }
 };
 
+/// What PointCloud::overlap asks for (sga_overlap with its defaults: max_distance 1, statistics only).  A point is matched when its
+/// nearest target record lies within max_distance; keep says which points the output cloud holds.
+struct Overlap {
+  enum Keep { None = 0, Matched = 1, Unmatched = 2 };
+  double max_distance = 1.0;
+  Keep keep = None;
+  Overlap() = default;
+  Overlap(double max_distance_, Keep keep_ = None) : max_distance(max_distance_), keep(keep_) {}
+};
+struct PointCloud;
+/// What PointCloud::overlap found: the statistics (points, matched, fitness = matched / points, rmse and mean_distance over the matched),
+/// the cloud of the matched or the unmatched points (null when keep is None) and — where asked for — the distance per point (+inf where
+/// unmatched), the winner per point (the target point's index, the voxel id, voxel * 16 + slot for a flat map; -1 where unmatched) and
+/// the indices of the output cloud's points, ascending.
+struct OverlapResult {
+  sga_overlap_stats stats{};
+  std::shared_ptr<PointCloud> cloud;
+  std::vector<double> dist;
+  std::vector<int64_t> nearest, kept;
+};
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -232,6 +253,28 @@ struct PointCloud {
     Ptr out = std::make_shared<PointCloud>(made, ctx);
     if (kept) kept->resize(out->size());
     return out;
+  }
+  /// How much of this cloud, posed by T (cloud -> target; null: the identity), the target already explains, and which points are new
+  /// (sga_cloud_overlap).  target: the handle of a KdTree, a GaussianVoxelMap or a flat map (their member h).  with_dist / with_nearest /
+  /// with_kept: also fill OverlapResult's per-point arrays (kept needs a keep other than None).
+  OverlapResult overlap(const sga_index* target, const Isometry3d* T = nullptr, const Overlap& what = Overlap(), bool with_dist = false, bool with_nearest = false, bool with_kept = false) const {
+    OverlapResult r;
+    sga_overlap p;
+    sga_overlap_default(&p);
+    p.max_distance = what.max_distance, p.keep = static_cast<int>(what.keep);
+    const size_t n = size();
+    if (with_dist) r.dist.resize(n);
+    if (with_nearest) r.nearest.resize(n);
+    if (with_kept) r.kept.resize(n);
+    sga_cloud* made = nullptr;
+    check(sga_cloud_overlap(ctx, h, target, T ? T->data() : nullptr, &p, r.dist.empty() ? nullptr : r.dist.data(), r.nearest.empty() ? nullptr : r.nearest.data(), r.kept.empty() ? nullptr : r.kept.data(), &r.stats,
+                            p.keep != 0 ? &made : nullptr),
+          "sga_cloud_overlap");
+    if (p.keep != 0) {
+      r.cloud = std::make_shared<PointCloud>(made, ctx);
+      r.kept.resize(with_kept ? r.cloud->size() : 0);
+    }
+    return r;
   }
   /// A new cloud whose point j is this cloud's point indices[j] with its normal and covariance (sga_cloud_select: one launch); repeats
   /// are allowed, the order is as given.

@@ -109,6 +109,10 @@ int sga_debug_cloud_crop_launches(unsigned long long* launches);
  * mode only when stats are asked for), the compaction's table copy and the compaction — at most four whatever the cloud's size.  The build
  * of a temporary tree is not counted here; an empty cloud enqueues nothing. */
 int sga_debug_cloud_outliers_launches(unsigned long long* launches);
+/* Launches enqueued so far, in this process, by sga_cloud_overlap: per call the distances and the sums — two for a statistics-only call —
+ * and, when a cloud is made, the compaction's table copy and the compaction: four, whatever the cloud's size and the kind of target.  An
+ * empty cloud enqueues nothing.  (The compaction of an overlap call is counted here, not by sga_debug_cloud_outliers_launches.) */
+int sga_debug_cloud_overlap_launches(unsigned long long* launches);
 /* The bounding box of its finite records (device frame) that a cloud carries, when its producer knew it (uploads, sga_cloud_merge; the
  * voxel grid sorts short keys with it): *has_box = 0 and zeros when it carries none. */
 int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]);

@@ -88,6 +88,18 @@ class OutlierStats(C.Structure):
     _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kept", C.c_size_t)]
 
 
+class OverlapParams(C.Structure):
+    """sga_overlap: max_distance, keep 0 none | 1 the matched | 2 the unmatched."""
+
+    _fields_ = [("max_distance", C.c_double), ("keep", C.c_int), ("reserved", C.c_int)]
+
+
+class OverlapStats(C.Structure):
+    """sga_overlap_stats: points, matched, fitness = matched / points, rmse and mean_distance over the matched."""
+
+    _fields_ = [("points", C.c_size_t), ("matched", C.c_size_t), ("fitness", C.c_double), ("rmse", C.c_double), ("mean_distance", C.c_double)]
+
+
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
@@ -129,6 +141,9 @@ SYMBOLS = [
     ("sga_outlier_filter_default", None, [C.POINTER(OutlierFilter)]),
     ("sga_cloud_remove_outliers", C.c_int, [_vp, _vp, _vp, C.POINTER(OutlierFilter), C.POINTER(C.c_int64), _dp, C.POINTER(OutlierStats), _pvp]),
     ("sga_debug_cloud_outliers_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_overlap_default", None, [C.POINTER(OverlapParams)]),
+    ("sga_cloud_overlap", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(OverlapParams), _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(OverlapStats), _pvp]),
+    ("sga_debug_cloud_overlap_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),

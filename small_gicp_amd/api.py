@@ -349,6 +349,41 @@ class PointCloud:
             res.append({"stat": stat, "mean": st.mean, "stddev": st.stddev, "threshold": st.threshold, "kept": int(st.kept)})
         return res[0] if len(res) == 1 else tuple(res)
 
+    def overlap(self, target, T=None, max_distance=1.0, keep=None, return_dist=False, return_nearest=False, return_kept=False, ctx=None):
+        """How much of this cloud, posed by T (4x4, cloud -> target; None: the identity), the target already explains, and which points
+        are new (sga_cloud_overlap).  target: a KdTree, a GaussianVoxelMap or a flat map.  A point is matched
+        when its nearest target record (kd-tree: the exact nearest point; maps: the lookup over the map's search offsets) lies within
+        max_distance.  Returns a dict — "points", "matched", "fitness" = matched / points, "rmse" and "mean_distance" over the matched —
+        followed, as requested and in this order, by the cloud of the matched or the unmatched points (keep="matched" | "unmatched":
+        this cloud's order, normals, covariances and origin; points with a non-finite coordinate are in neither), "dist" (numpy
+        float64: the distance per point, +inf where unmatched), "nearest" (numpy int64: the target point's index, the voxel id, or
+        voxel * 16 + slot for a flat map; -1 where unmatched) and "kept" (numpy int64: the indices of the output cloud's points,
+        ascending; needs keep).  ctx: the context the call runs on (default: this cloud's)."""
+        p = _overlap_params(max_distance, keep)
+        ctx = ctx or self.ctx
+        n = self.size()
+        t16 = None if T is None else _T16(T)
+        dist = np.empty(n, np.float64) if return_dist else None
+        nearest = np.empty(n, np.int64) if return_nearest else None
+        kept = np.empty(n, np.int64) if return_kept else None
+        st = _lib.OverlapStats()
+        h = C.c_void_p()
+        _i64 = C.POINTER(C.c_int64)
+        check(load().sga_cloud_overlap(ctx.h, self.h, target.h, _dp(t16), C.byref(p), _dp(dist), None if nearest is None else nearest.ctypes.data_as(_i64),
+                                       None if kept is None else kept.ctypes.data_as(_i64), C.byref(st), C.byref(h) if p.keep != 0 else None))
+        res = [{"points": int(st.points), "matched": int(st.matched), "fitness": st.fitness, "rmse": st.rmse, "mean_distance": st.mean_distance}]
+        out = None
+        if p.keep != 0:
+            out = PointCloud(ctx=ctx, _handle=h)
+            res.append(out)
+        if return_dist:
+            res.append(dist)
+        if return_nearest:
+            res.append(nearest)
+        if return_kept:
+            res.append(kept[: out.size()].copy())
+        return res[0] if len(res) == 1 else tuple(res)
+
     def selected(self, indices):
         """A new cloud whose point j is this cloud's point indices[j], with its normal and covariance (sga_cloud_select: one launch).
         Repeats are allowed, the order is as given, the origin is kept; an index outside [0, size) is refused and named by its position."""
@@ -1773,6 +1808,35 @@ def cloud_outliers_launches():
     threshold, the compaction's table copy, the compaction; a temporary tree's build is not counted)."""
     v = C.c_ulonglong()
     check(load().sga_debug_cloud_outliers_launches(C.byref(v)))
+    return v.value
+
+
+_OVERLAP_KEEP = {None: 0, "matched": 1, "unmatched": 2}
+
+
+def _overlap_params(max_distance=1.0, keep=None):
+    """The sga_overlap of PointCloud.overlap's arguments (one is passed through).  The library judges the values."""
+    if isinstance(max_distance, _lib.OverlapParams):
+        return max_distance
+    if keep not in _OVERLAP_KEEP:
+        raise ValueError('keep must be None, "matched" or "unmatched"')
+    p = _lib.OverlapParams()
+    load().sga_overlap_default(C.byref(p))
+    p.max_distance, p.keep = float(max_distance), _OVERLAP_KEEP[keep]
+    return p
+
+
+def cloud_overlap(points, target, T=None, max_distance=1.0, keep=None, return_dist=False, return_nearest=False, return_kept=False, ctx=None):
+    """PointCloud.overlap of a PointCloud or of an (N,3|4) array (uploaded first)."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    return cloud.overlap(target, T, max_distance, keep, return_dist, return_nearest, return_kept, ctx)
+
+
+def cloud_overlap_launches():
+    """Diagnostics (sga_debug_cloud_overlap_launches): commands enqueued so far by PointCloud.overlap (the distances and the sums; with
+    an output cloud also the compaction's table copy and the compaction)."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_overlap_launches(C.byref(v)))
     return v.value
 
 

@@ -243,10 +243,10 @@ CropMember crop_member(const sga_cloud* in, const sga_crop& cr) {
 // and ONE launch over the members' tiles.  The indices kept leave as uint32 through ONE slot of the staging ring, which the kernel writes
 // by its device address and the host widens after the wait (kept), or as int64 into device memory of the caller's (d_kept, one member).
 // The call waits for the members' counts and boxes (the context's box block: its one wait), on a stream-ordered context too.
-// stat (one member only): the statistic predicate on top of the crop's, its launches counted under Chain::Outliers.
+// stat (one member only): the statistic predicate on top of the crop's, its launches counted under the chain it names.
 int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop* crops, int64_t* const* kept, int64_t* d_kept, bool device_form, size_t count, void* user_stream, int flags, sga_cloud** out,
                const CropStat* stat = nullptr) {
-  const Chain chain = stat != nullptr ? Chain::Outliers : Chain::Crop;
+  const Chain chain = stat != nullptr ? stat->chain : Chain::Crop;
   if (count == 0) return SGA_OK;
   null_out(out, count);
   if (!ctx || !out || !clouds || !crops) return fail(SGA_ERR_INVALID, "null argument");

@@ -1,9 +1,10 @@
-// What the cloud translation units (cloud.hip, cloud_io.hip, cloud_pose.hip, cloud_crop.hip, cloud_outliers.hip) share on the host.
+// What the cloud translation units (cloud.hip, cloud_io.hip, cloud_pose.hip, cloud_crop.hip, cloud_outliers.hip, cloud_overlap.hip) share on the host.
 #pragma once
 #include <memory>
 #include <vector>
 
 #include "common.hpp"
+#include "forest.hpp"
 
 namespace sga {
 
@@ -45,14 +46,15 @@ int ensure_box64(sga_context* ctx);  // the context's 64-bit box accumulator (d_
 // address.  on_device (optional): set when p is device memory, which no host entry point takes
 const void* pinned_device_view(const void* p, size_t bytes, bool* on_device = nullptr);
 
-// ---- cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip) ---------------------------------------
+// ---- cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip) and sga_cloud_overlap (cloud_overlap.hip, 3.22) ----
 // The crop's compaction — its table, its ONE launch, its one wait, its output cloud — over the points i of `cloud` with d[i] <= the limit.
 // d (the cloud's size, the cloud's order) and limit are device memory that launches enqueued earlier on the context's stream write;
-// limit == nullptr: limit_value travels in the call's table.  The table copy and the launch are counted under Chain::Outliers.
+// limit == nullptr: limit_value travels in the call's table.  The table copy and the launch are counted under `chain`.
 struct CropStat {
   const double* d;
   const double* limit;
   double limit_value;
+  Chain chain = Chain::Outliers;
 };
 int cloud_crop_stat(sga_context* ctx, const sga_cloud* cloud, const CropStat& stat, int64_t* kept /* or null */, sga_cloud** out);
 

@@ -215,11 +215,18 @@ class SubmapOdometry:
     scans at their estimated world poses (api.merge_clouds: one launch, the covariances ride along rotated, nothing is estimated twice)
     and the KdTree over it; the scan is registered from the previous pose, as ModelOdometry does.  Per scan the preprocessing is
     OnlineOdometry's.  The driver names the submap's device-frame origin itself — the library's rule applied to the previous position —
-    so the stream-ordered context never waits for a bounding box."""
+    so the stream-ordered context never waits for a bounding box.
+    keyframe_overlap (None: off, the default — every scan joins the window): a registered scan joins the window only when the share of
+    its points that the submap already explains (PointCloud.overlap against the submap's tree at the new pose: the fitness within
+    overlap_distance, default the downsampling resolution) is BELOW keyframe_overlap; the first scan always joins.  fitness: the figure
+    of every registered scan; keyframes_added: the scans that joined."""
 
-    def __init__(self, window=5, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, record=False):
+    def __init__(self, window=5, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, record=False, keyframe_overlap=None, overlap_distance=None):
         if window < 1:
             raise ValueError("window must be at least 1")
+        self.keyframe_overlap = None if keyframe_overlap is None else float(keyframe_overlap)
+        self.overlap_distance = float(downsampling_resolution if overlap_distance is None else overlap_distance)
+        self.fitness, self.keyframes_added = [], 0
         self.window = window
         self.res = downsampling_resolution
         self.k = num_neighbors
@@ -260,6 +267,7 @@ class SubmapOdometry:
         t1 = time.perf_counter()
         tree = api.KdTree(cloud)
         api.estimate_covariances(cloud, tree, self.k)
+        joins = True
         if self.keyframes:
             submap = api.merge_clouds([c for c, _ in self.keyframes], [T for _, T in self.keyframes], origin=self._submap_origin(), ctx=self.ctx)
             target = api.KdTree(submap)
@@ -269,9 +277,14 @@ class SubmapOdometry:
             self.iterations.append(res.iterations + 1)
             if self.record:
                 self.records.append((submap, cloud, init, self.T_world.copy(), res.iterations + 1))
+            if self.keyframe_overlap is not None:
+                self.fitness.append(cloud.overlap(target, self.T_world, self.overlap_distance, ctx=self.ctx)["fitness"])
+                joins = self.fitness[-1] < self.keyframe_overlap
         self.ctx.synchronize()
         t2 = time.perf_counter()
-        self.keyframes = (self.keyframes + [(cloud, self.T_world.copy())])[-self.window :]
+        if joins:
+            self.keyframes = (self.keyframes + [(cloud, self.T_world.copy())])[-self.window :]
+            self.keyframes_added += 1
         self.reg_ms.append(1e3 * (t2 - t1))
         self.total_ms.append(1e3 * (t2 - t0))
         return self.T_world.copy()
@@ -279,7 +292,9 @@ class SubmapOdometry:
 
 def run_synthetic_submap(num_frames=20, window=5, **kw):
     """SubmapOdometry over the frozen synthetic sequence (keyword arguments go to SubmapOdometry); absolute trajectory error against the
-    generator's ground truth.  The return value has run_synthetic_model's shape (num_points: the last submap's size, in place of num_voxels)."""
+    generator's ground truth.  The return value has run_synthetic_model's shape (num_points: the last submap's size, in place of num_voxels),
+    with keyframes_added (the scans that joined the window) and fitness (the overlap figure of every registered scan; empty unless
+    keyframe_overlap is given)."""
     from . import synthetic
 
     odom = SubmapOdometry(window=window, **kw)
@@ -302,6 +317,8 @@ def run_synthetic_submap(num_frames=20, window=5, **kw):
         "mean_iterations": float(np.mean(odom.iterations)) if odom.iterations else 0.0,
         "ate_trans_m_max": max(ate),
         "num_points": sum(c.size() for c, _ in odom.keyframes),
+        "keyframes_added": odom.keyframes_added,
+        "fitness": list(odom.fitness),
         "estimated": est,
         "ground_truth": gt,
     }
