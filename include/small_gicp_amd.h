@@ -262,6 +262,60 @@ typedef struct sga_overlap_stats {
 void sga_overlap_default(sga_overlap* p); /* max_distance 1.0, keep 0 */
 int sga_cloud_overlap(sga_context* ctx, const sga_cloud* cloud, const sga_index* target, const double T[16] /* or NULL */, const sga_overlap* params, double* dist /* n, or NULL */, int64_t* nearest /* n, or NULL */,
                       int64_t* kept /* n, or NULL */, sga_overlap_stats* stats /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
+/* The free-space check of a mapping loop: which points of `map` does the posed `scan` see THROUGH — the ghost
+ * trails that moving objects leave in a submap — by a range image of the scan, on the device.
+ * Sensor frame: x forward, y left, z up (what a spinning lidar and KITTI deliver; NOT the camera convention of the projective search).
+ * Projection of a point s, every operation rounded, no product fused into a sum:  rho = sqrt((sx^2 + sy^2) + sz^2), az = atan2(sy, sx),
+ * el = asin(sz / rho), su = (az / (2 pi) + 0.5) * width, u = (int)su with u == width becoming 0 (azimuth +pi is the direction of -pi),
+ * sv = (fov_up - el) / (fov_up - fov_down) * height, v = floor(sv).  s is IN THE IMAGE iff rho > 0, everything is finite, 0 <= sv and
+ * v < height.
+ * Range image of `scan` (point = fp32 record + the cloud's origin, in double): a cell holds the least rho over the scan's returns that are
+ * finite, in the image and have rho >= min_range; an empty cell holds +inf.  Returns nearer than min_range are the ego vehicle: they
+ * would shadow everything behind them, and are left out.  max_range does not bound the scan's returns.
+ * Map point i (fp32 record r in the map's device frame at origin o_m), T (column-major 4x4, NULL: the identity) the pose registration
+ * returns — it maps the scan's sensor frame into the map's frame, T = [R t]:  w_k = (double)r_k + (o_m[k] - t[k]), the difference formed
+ * once on the host;  s = R^T w, per component ((R[0][k] w0 + R[1][k] w1) + R[2][k] w2);  rho_i = |s| as above.
+ * Window of (u, v): du in -window_h .. window_h, wrapping in azimuth; dv in -window_v .. window_v, rows outside the image skipped.  m_i
+ * and M_i are the least and the greatest finite cell of the window.  With tol_i = margin + margin_ratio * rho_i:
+ *   state 0  unobserved    s not finite, not in the image, rho_i < min_range, rho_i > max_range, or no return in the window
+ *   state 3  seen through  rho_i + tol_i < m_i: every return of the window lies behind the point
+ *   state 2  occluded      rho_i - tol_i > M_i: the point lies behind every return
+ *   state 1  consistent    everything else
+ * Clearance c_i = m_i - rho_i for the states 1 .. 3, NaN for state 0.  The rule reads only the multiset of ranges in a window: it depends
+ * on no order, and two calls give the same bytes.
+ * state / clearance (or NULL; room for n): per map point, the map's order.  range_image (or NULL; room for width * height): cell (u, v)
+ * at [v * width + u].  stats (or NULL): points = n and the four counts.  params->keep: 0 — no cloud, out must be NULL; 1 — *out
+ * receives the seen-through points; 2 — all the others (the cleaned map) — as an ordinary cloud, by the compaction of sga_cloud_crop:
+ * the map's order, origin, normals and covariances, record j of *out equal to map record kept[j] bit for bit, finite records only;
+ * nothing kept, or an empty map, yields an empty cloud without attributes.  A non-finite map record counts in `points` and in
+ * `unobserved` and is in no output cloud.  kept (or NULL; room for n; only with keep != 0): the indices kept, ascending, the first
+ * size-of-*out entries written.
+ * Commands: a statistics-only call enqueues FOUR — the fill that clears the image, the image, the states, the counts — THREE when the
+ * scan is empty (no image kernel: every point is unobserved), and waits once for the last; with an output cloud the compaction's table
+ * copy and launch follow (six / five in all) and the one wait is the compaction's.  An empty map enqueues nothing and gives zero stats
+ * and an empty cloud — unless range_image is asked for: then the image alone is built and handed back (the fill, the image, the export:
+ * three, two for an empty scan).  Both clouds may have been made on other contexts of the device that returned before their kernels
+ * had run: the call orders itself behind both.
+ * Refusals (SGA_ERR_INVALID, *out = NULL as on every failure, nothing enqueued) — before any handle is read: NULL ctx, map, scan or
+ * params; width or height below 1 or width * height above 2^24; fov_up or fov_down not finite, outside [-pi/2, pi/2], or fov_up <=
+ * fov_down; min_range not finite or < 0; max_range NaN or < min_range (+inf is allowed); margin or margin_ratio not finite or < 0;
+ * window_h or window_v outside [0, 16]; keep outside 0..2; out given with keep == 0, or missing with keep != 0; kept given with keep ==
+ * 0; a non-finite entry of T — then: a cloud of another device, 2^31 points or more in either cloud. */
+typedef struct sga_visibility {
+  int width, height;
+  double fov_up, fov_down;     /* radians */
+  double min_range, max_range; /* max_range may be +inf */
+  double margin, margin_ratio;
+  int window_h, window_v;
+  int keep; /* 0 none, 1 the seen-through, 2 all the others (the cleaned map) */
+  int reserved;
+} sga_visibility; /* 72 bytes */
+typedef struct sga_visibility_stats {
+  size_t points, unobserved, consistent, occluded, seen_through;
+} sga_visibility_stats; /* 40 bytes */
+void sga_visibility_default(sga_visibility* p); /* 1024 x 64, +3 / -25 degrees in radians, 0.5 / 60.0, 0.2 / 0.01, 1 / 1, keep 0 */
+int sga_cloud_visibility(sga_context* ctx, const sga_cloud* map, const sga_cloud* scan, const double T[16] /* or NULL */, const sga_visibility* params, uint8_t* state /* n, or NULL */, double* clearance /* n, or NULL */,
+                         double* range_image /* width * height, [v * width + u], or NULL */, int64_t* kept /* n, or NULL; only with keep != 0 */, sga_visibility_stats* stats /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

@@ -156,6 +156,28 @@ struct OverlapResult {
   std::vector<int64_t> nearest, kept;
 };
 
+/// What PointCloud::visibility asks for (sga_visibility with its defaults: 1024 x 64 over [-25, +3] degrees, ranges 0.5 .. 60 m, margin
+/// 0.2 m + 1 % of the range, window 1 x 1, statistics only).  keep says which points the output cloud holds.
+struct Visibility : sga_visibility {
+  enum Keep { None = 0, SeenThrough = 1, Rest = 2 };
+  enum State : uint8_t { Unobserved = 0, Consistent = 1, Occluded = 2, Seen = 3 };
+  Visibility() { sga_visibility_default(this); }
+  explicit Visibility(Keep keep_) {
+    sga_visibility_default(this);
+    keep = static_cast<int>(keep_);
+  }
+};
+/// What PointCloud::visibility found: the counts per state, the cloud of the seen-through points or of all the others (null when keep is
+/// None) and — where asked for — the state and the clearance per point (NaN where unobserved), the scan's range image ([v * width + u],
+/// +inf where empty) and the indices of the output cloud's points, ascending.
+struct VisibilityResult {
+  sga_visibility_stats stats{};
+  std::shared_ptr<PointCloud> cloud;
+  std::vector<uint8_t> state;
+  std::vector<double> clearance, range_image;
+  std::vector<int64_t> kept;
+};
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -271,6 +293,27 @@ struct PointCloud {
                             p.keep != 0 ? &made : nullptr),
           "sga_cloud_overlap");
     if (p.keep != 0) {
+      r.cloud = std::make_shared<PointCloud>(made, ctx);
+      r.kept.resize(with_kept ? r.cloud->size() : 0);
+    }
+    return r;
+  }
+  /// The free-space check with this cloud as the map (sga_cloud_visibility): which of its points does `scan`, posed by T (the scan's sensor
+  /// frame — x forward, y left, z up — into this cloud's frame; null: the identity), see through?  with_state / with_clearance /
+  /// with_image / with_kept: also fill VisibilityResult's arrays (kept needs a keep other than None).
+  VisibilityResult visibility(const PointCloud& scan, const Isometry3d* T = nullptr, const Visibility& what = Visibility(), bool with_state = false, bool with_clearance = false, bool with_image = false,
+                              bool with_kept = false) const {
+    VisibilityResult r;
+    const size_t n = size();
+    if (with_state) r.state.resize(n);
+    if (with_clearance) r.clearance.resize(n);
+    if (with_image) r.range_image.resize(static_cast<size_t>(what.width > 0 ? what.width : 0) * static_cast<size_t>(what.height > 0 ? what.height : 0));
+    if (with_kept) r.kept.resize(n);
+    sga_cloud* made = nullptr;
+    check(sga_cloud_visibility(ctx, h, scan.h, T ? T->data() : nullptr, &what, r.state.empty() ? nullptr : r.state.data(), r.clearance.empty() ? nullptr : r.clearance.data(),
+                               r.range_image.empty() ? nullptr : r.range_image.data(), r.kept.empty() ? nullptr : r.kept.data(), &r.stats, what.keep != 0 ? &made : nullptr),
+          "sga_cloud_visibility");
+    if (what.keep != 0) {
       r.cloud = std::make_shared<PointCloud>(made, ctx);
       r.kept.resize(with_kept ? r.cloud->size() : 0);
     }

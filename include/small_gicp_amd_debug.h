@@ -113,6 +113,11 @@ int sga_debug_cloud_outliers_launches(unsigned long long* launches);
  * and, when a cloud is made, the compaction's table copy and the compaction: four, whatever the cloud's size and the kind of target.  An
  * empty cloud enqueues nothing.  (The compaction of an overlap call is counted here, not by sga_debug_cloud_outliers_launches.) */
 int sga_debug_cloud_overlap_launches(unsigned long long* launches);
+/* Commands enqueued so far, in this process, by sga_cloud_visibility: per call the fill that clears the range image, the image kernel
+ * (none for an empty scan), the states and the counts — four for a statistics-only call, three with an empty scan — and, when a cloud is
+ * made, the compaction's table copy and the compaction: six / five.  An empty map enqueues nothing, unless the range image is asked for:
+ * then the fill, the image kernel (none for an empty scan) and the export, three / two. */
+int sga_debug_cloud_visibility_launches(unsigned long long* launches);
 /* The bounding box of its finite records (device frame) that a cloud carries, when its producer knew it (uploads, sga_cloud_merge; the
  * voxel grid sorts short keys with it): *has_box = 0 and zeros when it carries none. */
 int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]);

@@ -100,6 +100,20 @@ class OverlapStats(C.Structure):
     _fields_ = [("points", C.c_size_t), ("matched", C.c_size_t), ("fitness", C.c_double), ("rmse", C.c_double), ("mean_distance", C.c_double)]
 
 
+class VisibilityParams(C.Structure):
+    """sga_visibility: the range image (width x height over [fov_down, fov_up], radians), the ranges, the margin, the window, keep 0 none |
+    1 the seen-through | 2 all the others."""
+
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fov_up", C.c_double), ("fov_down", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("margin", C.c_double),
+                ("margin_ratio", C.c_double), ("window_h", C.c_int), ("window_v", C.c_int), ("keep", C.c_int), ("reserved", C.c_int)]
+
+
+class VisibilityStats(C.Structure):
+    """sga_visibility_stats: points and the number in each state."""
+
+    _fields_ = [("points", C.c_size_t), ("unobserved", C.c_size_t), ("consistent", C.c_size_t), ("occluded", C.c_size_t), ("seen_through", C.c_size_t)]
+
+
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
@@ -144,6 +158,9 @@ SYMBOLS = [
     ("sga_overlap_default", None, [C.POINTER(OverlapParams)]),
     ("sga_cloud_overlap", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(OverlapParams), _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(OverlapStats), _pvp]),
     ("sga_debug_cloud_overlap_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_visibility_default", None, [C.POINTER(VisibilityParams)]),
+    ("sga_cloud_visibility", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(VisibilityParams), C.POINTER(C.c_uint8), _dp, _dp, C.POINTER(C.c_int64), C.POINTER(VisibilityStats), _pvp]),
+    ("sga_debug_cloud_visibility_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),

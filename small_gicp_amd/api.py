@@ -384,6 +384,51 @@ class PointCloud:
             res.append(kept[: out.size()].copy())
         return res[0] if len(res) == 1 else tuple(res)
 
+    def visibility(self, scan, T=None, *, width=None, height=None, fov_up=None, fov_down=None, min_range=None, max_range=None, margin=None, margin_ratio=None, window_h=None, window_v=None, keep=None,
+                   return_state=False, return_clearance=False, return_image=False, return_kept=False, params=None, ctx=None):
+        """The free-space check with this cloud as the map (sga_cloud_visibility): which of its points does `scan`,
+        posed by T (4x4: the scan's sensor frame — x forward, y left, z up — into this cloud's frame; None: the identity), see through?
+        The scan's returns form a range image of width x height cells over [fov_down, fov_up] (radians) holding the least range from
+        min_range on; a map point is unobserved (state 0: out of the image, out of [min_range, max_range], no return in its window of
+        (2 window_h + 1) x (2 window_v + 1) cells), seen through (3: every return of the window lies more than margin + margin_ratio *
+        range behind it), occluded (2: it lies more than that behind every return) or consistent (1).  Returns a dict — "points",
+        "unobserved", "consistent", "occluded", "seen_through" — followed, as requested and in this order, by the cloud of the seen-through
+        points or of all the others (keep="seen_through" | "rest": this cloud's order, normals, covariances and origin; points with a
+        non-finite coordinate are in neither), "state" (numpy uint8), "clearance" (numpy float64: the window's least range minus the
+        point's, NaN where unobserved), "image" (numpy float64 (height, width), +inf where empty) and "kept" (numpy int64: the indices of
+        the output cloud's points, ascending; needs keep).  A parameter left at None takes the library's default (sga_visibility_default:
+        1024 x 64 over [-25, +3] degrees, ranges 0.5 .. 60 m, margin 0.2 m + 1 %, window 1 x 1).  params: a dict of the keyword arguments
+        above, in their place.  ctx: the context the call runs on (default: this cloud's)."""
+        given = dict(width=width, height=height, fov_up=fov_up, fov_down=fov_down, min_range=min_range, max_range=max_range, margin=margin, margin_ratio=margin_ratio, window_h=window_h, window_v=window_v)
+        given.update(params or {})
+        given = {name: value for name, value in given.items() if value is not None}
+        p = _visibility_params(keep=keep, **given)
+        ctx = ctx or self.ctx
+        n = self.size()
+        t16 = None if T is None else _T16(T)
+        state = np.empty(n, np.uint8) if return_state else None
+        clearance = np.empty(n, np.float64) if return_clearance else None
+        image = np.empty((p.height, p.width), np.float64) if return_image else None
+        kept = np.empty(n, np.int64) if return_kept else None
+        st = _lib.VisibilityStats()
+        h = C.c_void_p()
+        check(load().sga_cloud_visibility(ctx.h, self.h, scan.h, _dp(t16), C.byref(p), None if state is None else state.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(clearance), _dp(image),
+                                          None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st), C.byref(h) if p.keep != 0 else None))
+        res = [{"points": int(st.points), "unobserved": int(st.unobserved), "consistent": int(st.consistent), "occluded": int(st.occluded), "seen_through": int(st.seen_through)}]
+        out = None
+        if p.keep != 0:
+            out = PointCloud(ctx=ctx, _handle=h)
+            res.append(out)
+        if return_state:
+            res.append(state)
+        if return_clearance:
+            res.append(clearance)
+        if return_image:
+            res.append(image)
+        if return_kept:
+            res.append(kept[: out.size()].copy())
+        return res[0] if len(res) == 1 else tuple(res)
+
     def selected(self, indices):
         """A new cloud whose point j is this cloud's point indices[j], with its normal and covariance (sga_cloud_select: one launch).
         Repeats are allowed, the order is as given, the origin is kept; an index outside [0, size) is refused and named by its position."""
@@ -1837,6 +1882,38 @@ def cloud_overlap_launches():
     an output cloud also the compaction's table copy and the compaction)."""
     v = C.c_ulonglong()
     check(load().sga_debug_cloud_overlap_launches(C.byref(v)))
+    return v.value
+
+
+_VISIBILITY_KEEP = {None: 0, "seen_through": 1, "rest": 2}
+
+
+def _visibility_params(keep=None, **fields):
+    """The sga_visibility of PointCloud.visibility's keyword arguments over the library's defaults.  The library judges the values."""
+    if keep not in _VISIBILITY_KEEP:
+        raise ValueError('keep must be None, "seen_through" or "rest"')
+    p = _lib.VisibilityParams()
+    load().sga_visibility_default(C.byref(p))
+    for name, value in fields.items():
+        if name not in ("width", "height", "fov_up", "fov_down", "min_range", "max_range", "margin", "margin_ratio", "window_h", "window_v"):
+            raise TypeError("visibility has no parameter %r" % name)
+        setattr(p, name, int(value) if name in ("width", "height", "window_h", "window_v") else float(value))
+    p.keep = _VISIBILITY_KEEP[keep]
+    return p
+
+
+def cloud_visibility(map_points, scan_points, T=None, **kw):
+    """PointCloud.visibility of PointClouds or of (N,3|4) arrays (uploaded first): the map, the scan, the pose, the keyword arguments."""
+    cloud = map_points if isinstance(map_points, PointCloud) else PointCloud(map_points)
+    scan = scan_points if isinstance(scan_points, PointCloud) else PointCloud(scan_points)
+    return cloud.visibility(scan, T, **kw)
+
+
+def cloud_visibility_launches():
+    """Diagnostics (sga_debug_cloud_visibility_launches): commands enqueued so far by PointCloud.visibility (the fill, the image, the
+    states, the counts; with an output cloud also the compaction's table copy and the compaction)."""
+    v = C.c_ulonglong()
+    check(load().sga_debug_cloud_visibility_launches(C.byref(v)))
     return v.value
 
 

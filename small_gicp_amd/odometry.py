@@ -219,11 +219,19 @@ class SubmapOdometry:
     keyframe_overlap (None: off, the default — every scan joins the window): a registered scan joins the window only when the share of
     its points that the submap already explains (PointCloud.overlap against the submap's tree at the new pose: the fitness within
     overlap_distance, default the downsampling resolution) is BELOW keyframe_overlap; the first scan always joins.  fitness: the figure
-    of every registered scan; keyframes_added: the scans that joined."""
+    of every registered scan; keyframes_added: the scans that joined.
+    remove_seen_through (False: off, the default): once a scan is registered, every keyframe (cloud_k, T_k) of the window is replaced by
+    the points the RAW scan does not see through (PointCloud.visibility with keep="rest" and T = T_k^-1 T_world: the free-space check
+    that takes the trails of moving objects out of the submap); visibility: a dict of that call's keyword arguments (None: the
+    library's defaults).  removed_points: the points taken out, per registered scan."""
 
-    def __init__(self, window=5, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, record=False, keyframe_overlap=None, overlap_distance=None):
+    def __init__(self, window=5, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, record=False, keyframe_overlap=None, overlap_distance=None,
+                 remove_seen_through=False, visibility=None):
         if window < 1:
             raise ValueError("window must be at least 1")
+        self.remove_seen_through = bool(remove_seen_through)
+        self.visibility = dict(visibility or {})
+        self.removed_points = []
         self.keyframe_overlap = None if keyframe_overlap is None else float(keyframe_overlap)
         self.overlap_distance = float(downsampling_resolution if overlap_distance is None else overlap_distance)
         self.fitness, self.keyframes_added = [], 0
@@ -258,6 +266,16 @@ class SubmapOdometry:
         api.load().sga_choose_origin(api._dp(p), api._dp(p), api._dp(o))
         return o
 
+    def _remove_seen_through(self, raw):
+        """every keyframe of the window without the points that the raw scan, at the pose just found, sees through -> the points removed"""
+        removed = 0
+        for k, (cloud_k, T_k) in enumerate(self.keyframes):
+            _, rest = cloud_k.visibility(raw, np.linalg.inv(T_k) @ self.T_world, keep="rest", params=self.visibility, ctx=self.ctx)
+            if 0 < rest.size() < cloud_k.size():  # (a keyframe the scan would see through entirely is left alone: the pose is in doubt, not the map)
+                removed += cloud_k.size() - rest.size()
+                self.keyframes[k] = (rest, T_k)
+        return removed
+
     def estimate(self, points):
         """points: (N,3|4) float32 in the sensor frame. Returns T_world_sensor of this scan."""
         t0 = time.perf_counter()
@@ -280,6 +298,8 @@ class SubmapOdometry:
             if self.keyframe_overlap is not None:
                 self.fitness.append(cloud.overlap(target, self.T_world, self.overlap_distance, ctx=self.ctx)["fitness"])
                 joins = self.fitness[-1] < self.keyframe_overlap
+            if self.remove_seen_through:
+                self.removed_points.append(self._remove_seen_through(raw))
         self.ctx.synchronize()
         t2 = time.perf_counter()
         if joins:
@@ -290,23 +310,42 @@ class SubmapOdometry:
         return self.T_world.copy()
 
 
-def run_synthetic_submap(num_frames=20, window=5, **kw):
+def run_synthetic_submap(num_frames=20, window=5, mover=False, **kw):
     """SubmapOdometry over the frozen synthetic sequence (keyword arguments go to SubmapOdometry); absolute trajectory error against the
     generator's ground truth.  The return value has run_synthetic_model's shape (num_points: the last submap's size, in place of num_voxels),
     with keyframes_added (the scans that joined the window) and fitness (the overlap figure of every registered scan; empty unless
-    keyframe_overlap is given)."""
+    keyframe_overlap is given).  mover: every scan goes through synthetic.with_moving_sphere at synthetic.mover_centre(frame).
+    ghost_points (0 without a mover): the points of the final window, at their estimated poses, within 1.1 radii of the mover's centre at
+    an EARLIER frame and farther than that from its centre at the last one — the trail it left in the submap.  removed_points: what
+    remove_seen_through took out, per registered scan (empty when it is off); entered_points: the points that joined the window."""
     from . import synthetic
 
     odom = SubmapOdometry(window=window, **kw)
     est, gt = [], []
     T0 = None
+    entered, added = 0, 0
     for f in range(num_frames):
         pts, Tws = synthetic.kitti_like_scan(f)
+        if mover:
+            pts, _ = synthetic.with_moving_sphere(pts, Tws, synthetic.mover_centre(f))
         if T0 is None:
             T0 = Tws
         est.append(odom.estimate(pts))
         gt.append(np.linalg.inv(T0) @ Tws)
+        if odom.keyframes_added > added:  # the scan joined the window (it is checked against later scans only)
+            added = odom.keyframes_added
+            entered += odom.keyframes[-1][0].size()
     ate = [float(np.linalg.norm(e[:3, 3] - g[:3, 3])) for e, g in zip(est, gt)]
+    ghosts = 0
+    if mover:
+        radius, Ti = 1.1 * 1.0, np.linalg.inv(T0)
+        centres = [Ti[:3, :3] @ synthetic.mover_centre(f) + Ti[:3, 3] for f in range(num_frames)]  # in the frame of the first scan, as the estimates are
+        for c, T in odom.keyframes:
+            p = c.xyz().astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+            trail = np.zeros(len(p), bool)
+            for centre in centres[:-1]:
+                trail |= np.linalg.norm(p - centre, axis=1) <= radius
+            ghosts += int((trail & (np.linalg.norm(p - centres[-1], axis=1) > radius)).sum())
     skip = 2 if num_frames > 4 else 1  # (as run_synthetic: the first frames carry first-touch allocations)
     out = {
         "frames": num_frames,
@@ -319,6 +358,9 @@ def run_synthetic_submap(num_frames=20, window=5, **kw):
         "num_points": sum(c.size() for c, _ in odom.keyframes),
         "keyframes_added": odom.keyframes_added,
         "fitness": list(odom.fitness),
+        "ghost_points": ghosts,
+        "removed_points": list(odom.removed_points),
+        "entered_points": entered,
         "estimated": est,
         "ground_truth": gt,
     }

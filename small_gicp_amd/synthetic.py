@@ -172,3 +172,28 @@ def with_isolated_returns(points, share=0.01, seed=4242, min_range=5.0, max_rang
     d /= np.maximum(np.linalg.norm(d, axis=1), 1e-9)[:, None]
     pts[idx] = (d * rng.uniform(min_range, max_range, m)[:, None]).astype(np.float32)
     return np.ascontiguousarray(pts), idx
+
+
+def mover_centre(frame):
+    """The world position of the moving sphere of run_synthetic_submap(mover=True) at a frame: it crosses the road 12 m ahead of the first
+    sensor pose, 1 m above ground, at 1.5 m/frame."""
+    return _sensor_pose(0)[:3, 3] + np.array([12.0, -6.0 + 1.5 * frame, -0.8])
+
+
+def with_moving_sphere(points, T_world_sensor, centre_world, radius=1.0):
+    """The scan with a sphere standing in the scene — a moving object caught at one instant: every ray of the scan (sensor frame, from the
+    sensor's origin) that meets the sphere of `radius` around centre_world nearer than its own return is shortened to the sphere.  The
+    number and the order of the points are kept.  Returns (points float32 (N,3), mask (N,) bool of the changed returns)."""
+    pts = np.array(points, dtype=np.float32)[:, :3].copy()
+    T = np.asarray(T_world_sensor, dtype=np.float64)
+    c = T[:3, :3].T @ (np.asarray(centre_world, dtype=np.float64) - T[:3, 3])  # the centre in the sensor frame
+    p = pts.astype(np.float64)
+    r = np.linalg.norm(p, axis=1)
+    d = p / np.maximum(r, 1e-9)[:, None]
+    b = d @ c
+    disc = b * b - (c @ c - float(radius) ** 2)
+    with np.errstate(invalid="ignore"):
+        t = b - np.sqrt(disc)
+    hit = (disc >= 0) & (t > 0) & (t < r)
+    pts[hit] = (d[hit] * t[hit, None]).astype(np.float32)
+    return np.ascontiguousarray(pts), hit
