@@ -316,6 +316,77 @@ typedef struct sga_visibility_stats {
 void sga_visibility_default(sga_visibility* p); /* 1024 x 64, +3 / -25 degrees in radians, 0.5 / 60.0, 0.2 / 0.01, 1 / 1, keep 0 */
 int sga_cloud_visibility(sga_context* ctx, const sga_cloud* map, const sga_cloud* scan, const double T[16] /* or NULL */, const sga_visibility* params, uint8_t* state /* n, or NULL */, double* clearance /* n, or NULL */,
                          double* range_image /* width * height, [v * width + u], or NULL */, int64_t* kept /* n, or NULL; only with keep != 0 */, sga_visibility_stats* stats /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
+/* Global registration on the device: a pose from geometry alone — FPFH descriptors, nearest rows in feature
+ * space, RANSAC over the correspondences — for the initial guess every local registration needs.  Three calls, usable one by one.
+ * Everything is computed in double from the fp32 records, with integer atomics and fixed-order sums only: two calls give the same bytes.
+ *
+ * sga_features: n rows of dim floats on the device (1 <= dim <= 128).  sga_features_create uploads a caller's rows (row-major, n * dim;
+ * n == 0: an empty handle, rows may be NULL); sga_features_download writes n * dim floats.
+ *
+ * sga_cloud_fpfh: one 33-bin Fast Point Feature Histogram per point of a cloud WITH normals.  Neighbours of point i: its k' = min(k, n - 1)
+ * nearest other records of the exact k-NN of the cloud's kd-tree, in the search's order.  viewpoint (caller's frame; NULL: normals as
+ * stored): a normal is negated where n . (viewpoint - p) < 0 (nothing is written back).  Pair feature of (i, j), PCL's computePairFeatures:
+ * d = p_j - p_i, l = |d| (l == 0: pair skipped); a1 = n_i . d / l, a2 = n_j . d / l; if |a1| < |a2| the roles swap (n1 = n_j, n2 = n_i,
+ * d <- -d, phi = -a2), else n1 = n_i, n2 = n_j, phi = a1; v = (d / l) x n1 (|v| == 0: pair skipped), normalised; w = n1 x v; alpha = v . n2;
+ * theta = atan2(w . n2, n1 . n2).  Bins, each clamped to 0 .. 10: floor(11 (theta + pi) / (2 pi)), floor(11 (alpha + 1) / 2), floor(11 (phi
+ * + 1) / 2).  SPFH_i: the three 11-bin count histograms (theta, alpha, phi) over the pairs not skipped, scaled by 100 / (pairs counted);
+ * zero where nothing was counted.  FPFH_i = SPFH_i + (1 / k') sum_j w_ij SPFH_j, w_ij = 1 / |p_j - p_i|^2 (0 for coincident points), the
+ * sum in the list's order; each of the three sub-histograms is then rescaled to sum 100 (one that sums to 0 stays 0) and the result is
+ * rounded once to fp32.  n == 0: an empty handle, nothing launched; n == 1: one zero row (one fill).  kdtree: over THIS cloud, checked as
+ * sga_cloud_remove_outliers checks it, or NULL: a temporary one (a cloud with a non-finite coordinate has no kd-tree and is refused).
+ * Three launches, no host wait (a blocking context waits once for the last).
+ * Refusals (SGA_ERR_INVALID, *out = NULL) — before any handle is read: NULL ctx, cloud or out; k outside [2, 63]; a non-finite
+ * viewpoint — then: a cloud of another device or without normals, a tree of another kind, size or device frame, 2^31 / 33 points or more.
+ *
+ * sga_features_match: for every row of `source` the row of `target` (same dim) of least squared L2 distance, formed in double from the
+ * fp32 values, bins 0 .. dim - 1 summed in order; ties go to the lowest index.  mutual != 0: match[i] = j is kept only when the nearest
+ * source row of j is i, otherwise -1.  match (n): the winner or -1; dist (n, or NULL): the square root of the winning distance, +inf for
+ * -1; matched (or NULL): the number of entries that are not -1.  Two launches (three with mutual), one host wait; an empty source or
+ * target gives all -1 with nothing launched.  Refusals: NULL ctx, source, target or match; mutual other than 0 or 1 — then: another
+ * device, different dims, 2^31 rows or more.
+ *
+ * sga_ransac_correspondences: the rigid motion T (column-major 4x4, source -> target, caller's frames) that most of M index pairs
+ * (pairs[2 m] into source, pairs[2 m + 1] into target) agree on.  Points are record + origin in double.  Hypothesis h in [0, iterations)
+ * draws three distinct pairs with a counter-based generator: mix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  u_j = mix64(seed ^ mix64(4 h + j)), j = 0, 1, 2; idx(u, R) = ((u >> 32) * R) >> 32;
+ * i0 = idx(u0, M); i1 = idx(u1, M - 1), incremented if >= i0; i2 = idx(u2, M - 2), incremented if >= min(i0, i1), then again if >=
+ * max(i0, i1).  Edge test: for each of the three edges with lengths ls, lt the hypothesis is dropped unless min(ls, lt) >=
+ * edge_similarity * max(ls, lt) and min(ls, lt) >= min_edge.  Pose from triangle frames (a, b, c the triple's points): e1 = (b - a) /
+ * |b - a|, e3 = e1 x (c - a) normalised — dropped when |b - a| is 0 or |e1 x (c - a)| < 1e-9 |c - a| or is 0, in either cloud —, e2 = e3 x
+ * e1, F = [e1 e2 e3]; R = F_t F_s^T, t = centroid_t - R centroid_s.  Score: the number of the M pairs with |R p_s + t - p_t| <=
+ * max_distance.  Best: the greatest score, ties to the lowest h (one 64-bit integer atomic max: no arrival order enters).  Refit: over the
+ * best hypothesis' inliers the least-squares rotation (Horn's quaternion form, a Jacobi eigen-solver on the host) from fixed-order sums
+ * formed on the device; the hypothesis pose is kept (refit = 0) when fewer than 3 inliers remain or the cross-covariance has rank < 2.
+ * result: inliers and inlier_rmse are those of the best hypothesis.  M < 3, or no hypothesis passed the tests: SGA_OK, inliers = 0, T =
+ * identity.  Four commands (the pairs' points, the fill of the best word, the hypotheses, the refit sums), one host wait.
+ * Refusals — before any handle is read: NULL ctx, source, target, params, T or result, pairs NULL with M > 0; max_distance not finite
+ * or <= 0; iterations outside [1, 2^32); edge_similarity outside [0, 1]; min_edge not finite or < 0; M >= 2^31 — then: another device,
+ * an index outside either cloud (named by its position), before anything is enqueued. */
+typedef struct sga_features sga_features;
+int sga_features_create(sga_context* ctx, const float* rows, size_t n, int dim, sga_features** out);
+int sga_features_size(const sga_features* features, size_t* n, int* dim);
+int sga_features_download(sga_context* ctx, const sga_features* features, float* rows);
+int sga_features_destroy(sga_features* features);
+#define SGA_FPFH_DIM 33
+int sga_cloud_fpfh(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, int k, const double viewpoint[3] /* or NULL */, sga_features** out);
+int sga_features_match(sga_context* ctx, const sga_features* source, const sga_features* target, int mutual, int64_t* match /* n */, double* dist /* n, or NULL */, size_t* matched /* or NULL */);
+typedef struct sga_ransac {
+  double max_distance;     /* inlier bound, metres */
+  uint64_t iterations;     /* hypotheses, 1 .. 2^32 - 1 */
+  uint64_t seed;
+  double edge_similarity;  /* 0: off */
+  double min_edge;
+} sga_ransac; /* 40 bytes */
+typedef struct sga_ransac_result {
+  uint64_t inliers;
+  double inlier_rmse;
+  uint64_t best_hypothesis;
+  uint64_t scored; /* hypotheses that passed the edge and degeneracy tests */
+  int refit;       /* 1: T is the least-squares fit over the inliers, 0: the hypothesis pose (or the identity) */
+  int reserved;
+} sga_ransac_result; /* 40 bytes */
+void sga_ransac_default(sga_ransac* p); /* 1.0, 20000, 0, 0.9, 0.0 */
+int sga_ransac_correspondences(sga_context* ctx, const sga_cloud* source, const sga_cloud* target, const int64_t* pairs /* M x 2 */, size_t M, const sga_ransac* params, double T[16], sga_ransac_result* result);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

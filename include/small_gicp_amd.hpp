@@ -178,6 +178,66 @@ struct VisibilityResult {
   std::vector<int64_t> kept;
 };
 
+/// n rows of dim floats on the device (sga_features): the FPFH descriptors of PointCloud::fpfh, or a caller's own (1 <= dim <= 128).
+struct Features {
+  using Ptr = std::shared_ptr<Features>;
+  Features(sga_features* handle, sga_context* context) : ctx(context), h(handle) {}
+  /// rows: n * dim floats, row-major
+  Features(const float* rows, size_t n, int dim, sga_context* context = default_context()) : ctx(context) { check(sga_features_create(ctx, rows, n, dim, &h), "sga_features_create"); }
+  Features(const Features&) = delete;
+  Features& operator=(const Features&) = delete;
+  ~Features() { sga_features_destroy(h); }
+  size_t size() const {
+    size_t n = 0;
+    sga_features_size(h, &n, nullptr);
+    return n;
+  }
+  int dim() const {
+    int d = 0;
+    sga_features_size(h, nullptr, &d);
+    return d;
+  }
+  /// the rows on the host, row-major
+  std::vector<float> download() const {
+    std::vector<float> rows(size() * static_cast<size_t>(dim()));
+    check(sga_features_download(ctx, h, rows.empty() ? nullptr : rows.data()), "sga_features_download");
+    return rows;
+  }
+  sga_context* ctx = default_context();
+  sga_features* h = nullptr;
+};
+
+/// For every row of `source` the nearest row of `target` in squared L2 distance (sga_features_match; ties to the lowest index); mutual:
+/// only the pairs that are each other's nearest.  Returns the pairs (source row, target row), ascending in the source row; dist
+/// (optional): their distances.
+inline std::vector<std::array<int64_t, 2>> match_features(const Features& source, const Features& target, bool mutual = true, std::vector<double>* dist = nullptr) {
+  const size_t n = source.size();
+  std::vector<int64_t> match(n);
+  std::vector<double> d(dist ? n : 0);
+  size_t matched = 0;
+  int64_t none = -1;
+  check(sga_features_match(source.ctx, source.h, target.h, mutual ? 1 : 0, n > 0 ? match.data() : &none, d.empty() ? nullptr : d.data(), &matched), "sga_features_match");
+  std::vector<std::array<int64_t, 2>> pairs;
+  pairs.reserve(matched);
+  if (dist) dist->clear();
+  for (size_t i = 0; i < n; i++)
+    if (match[i] >= 0) {
+      pairs.push_back({static_cast<int64_t>(i), match[i]});
+      if (dist) dist->push_back(d[i]);
+    }
+  return pairs;
+}
+
+/// The parameters of ransac_correspondences (sga_ransac with its defaults: max_distance 1, 20000 hypotheses, seed 0, edge_similarity 0.9,
+/// min_edge 0) and what it found: the pose, source -> target, with the inliers and their RMSE under the best hypothesis, that hypothesis'
+/// number, the hypotheses that passed the edge and degeneracy tests, and whether the pose is the least-squares refit over the inliers.
+struct Ransac : sga_ransac {
+  Ransac() { sga_ransac_default(this); }
+};
+struct RansacResult : sga_ransac_result {
+  Isometry3d T_target_source;
+};
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -319,6 +379,14 @@ struct PointCloud {
     }
     return r;
   }
+  /// One 33-bin Fast Point Feature Histogram per point (sga_cloud_fpfh); the cloud needs normals.  kdtree: the handle of the KdTree over
+  /// this cloud, or null: a temporary one is built.  viewpoint (optional, the caller's frame): the normals are turned towards it for
+  /// the descriptor; nothing is written back.
+  Features::Ptr fpfh(const sga_index* kdtree = nullptr, int k = 20, const std::array<double, 3>* viewpoint = nullptr) const {
+    sga_features* made = nullptr;
+    check(sga_cloud_fpfh(ctx, h, kdtree, k, viewpoint ? viewpoint->data() : nullptr, &made), "sga_cloud_fpfh");
+    return std::make_shared<Features>(made, ctx);
+  }
   /// A new cloud whose point j is this cloud's point indices[j] with its normal and covariance (sga_cloud_select: one launch); repeats
   /// are allowed, the order is as given.
   Ptr selected(const std::vector<int64_t>& indices) const {
@@ -381,6 +449,15 @@ private:
   mutable std::vector<double> host_xyz;
   mutable std::vector<float> host_nrm, host_cov;
 };
+
+/// The rigid motion most of the index pairs (source point, target point) agree on (sga_ransac_correspondences): hypotheses from three
+/// pairs each, scored by the pairs within max_distance, the best refitted over its inliers.  Fewer than three pairs, or no hypothesis
+/// that passed the tests: inliers 0 and the identity.
+inline RansacResult ransac_correspondences(const PointCloud& source, const PointCloud& target, const std::vector<std::array<int64_t, 2>>& pairs, const Ransac& params = Ransac()) {
+  RansacResult r;
+  check(sga_ransac_correspondences(source.ctx, source.h, target.h, pairs.empty() ? nullptr : pairs.data()->data(), pairs.size(), &params, r.T_target_source.m.data(), &r), "sga_ransac_correspondences");
+  return r;
+}
 
 /// kNN for m queries in device memory against a kd-tree, a Gaussian or a flat voxel map (sga_index_knn_device): d_idx m*k int64 and
 /// d_sq_dist m*k floats are device memory of the caller's; -1 / inf = none.

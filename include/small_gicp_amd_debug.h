@@ -118,6 +118,20 @@ int sga_debug_cloud_overlap_launches(unsigned long long* launches);
  * made, the compaction's table copy and the compaction: six / five.  An empty map enqueues nothing, unless the range image is asked for:
  * then the fill, the image kernel (none for an empty scan) and the export, three / two. */
 int sga_debug_cloud_visibility_launches(unsigned long long* launches);
+/* Commands enqueued so far, in this process, by the three calls of the global registration (small_gicp_amd.h):
+ * sga_cloud_fpfh three per call (the neighbour lists, the SPFH counts, the FPFH rows; one fill for a cloud of one point, none for an empty one),
+ * sga_features_match two (three with mutual; none when either side is empty), sga_ransac_correspondences four (the pairs' points, the
+ * fill of the best word, the hypotheses, the refit sums; none for M < 3).  The build of a temporary tree is not counted. */
+int sga_debug_cloud_fpfh_launches(unsigned long long* launches);
+int sga_debug_features_match_launches(unsigned long long* launches);
+int sga_debug_ransac_launches(unsigned long long* launches);
+/* The host arithmetic of sga_ransac_correspondences, exposed so that it can be tested without a device.  draw: the three distinct pair
+ * numbers hypothesis h draws from M >= 3 pairs under `seed` (SGA_ERR_INVALID for M < 3 or M >= 2^31).  rigid_from_sums: the least-squares
+ * rigid motion of n point pairs from their plain sums — sum_s = sum p_s, sum_t = sum p_t, cross[3 r + c] = sum p_s[r] p_t[c] — by Horn's
+ * quaternion form over a Jacobi eigen-solver; T column-major 4x4.  Returns 1 and writes T, or 0 with T untouched when n < 3 or the
+ * centred cross-covariance has rank < 2 (its second singular value is below 1e-12 of the first). */
+int sga_debug_ransac_draw(uint64_t seed, uint64_t h, uint64_t M, uint64_t out[3]);
+int sga_debug_rigid_from_sums(uint64_t n, const double sum_s[3], const double sum_t[3], const double cross[9], double T[16]);
 /* The bounding box of its finite records (device frame) that a cloud carries, when its producer knew it (uploads, sga_cloud_merge; the
  * voxel grid sorts short keys with it): *has_box = 0 and zeros when it carries none. */
 int sga_debug_cloud_box(const sga_cloud* cloud, int* has_box, float lo[3], float hi[3]);

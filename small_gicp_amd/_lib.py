@@ -114,6 +114,19 @@ class VisibilityStats(C.Structure):
     _fields_ = [("points", C.c_size_t), ("unobserved", C.c_size_t), ("consistent", C.c_size_t), ("occluded", C.c_size_t), ("seen_through", C.c_size_t)]
 
 
+class Ransac(C.Structure):
+    """sga_ransac: max_distance, iterations (1 .. 2^32 - 1), seed, edge_similarity (0: off), min_edge."""
+
+    _fields_ = [("max_distance", C.c_double), ("iterations", C.c_uint64), ("seed", C.c_uint64), ("edge_similarity", C.c_double), ("min_edge", C.c_double)]
+
+
+class RansacResult(C.Structure):
+    """sga_ransac_result: inliers and inlier_rmse of the best hypothesis, its number, the hypotheses that passed the tests, refit 0 | 1."""
+
+    _fields_ = [("inliers", C.c_uint64), ("inlier_rmse", C.c_double), ("best_hypothesis", C.c_uint64), ("scored", C.c_uint64), ("refit", C.c_int), ("reserved", C.c_int)]
+
+
+FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
@@ -161,6 +174,19 @@ SYMBOLS = [
     ("sga_visibility_default", None, [C.POINTER(VisibilityParams)]),
     ("sga_cloud_visibility", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(VisibilityParams), C.POINTER(C.c_uint8), _dp, _dp, C.POINTER(C.c_int64), C.POINTER(VisibilityStats), _pvp]),
     ("sga_debug_cloud_visibility_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_features_create", C.c_int, [_vp, _fp, C.c_size_t, C.c_int, _pvp]),
+    ("sga_features_size", C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    ("sga_features_download", C.c_int, [_vp, _vp, _fp]),
+    ("sga_features_destroy", C.c_int, [_vp]),
+    ("sga_cloud_fpfh", C.c_int, [_vp, _vp, _vp, C.c_int, _dp, _pvp]),
+    ("sga_features_match", C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_size_t)]),
+    ("sga_ransac_default", None, [C.POINTER(Ransac)]),
+    ("sga_ransac_correspondences", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(Ransac), _dp, C.POINTER(RansacResult)]),
+    ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_ransac_draw", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("sga_debug_rigid_from_sums", C.c_int, [C.c_uint64, _dp, _dp, _dp, _dp]),
     ("sga_debug_cloud_box", C.c_int, [_vp, C.POINTER(C.c_int), _fp, _fp]),
     ("sga_cloud_destroy", C.c_int, [_vp]),
     ("sga_cloud_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),

@@ -349,6 +349,16 @@ class PointCloud:
             res.append({"stat": stat, "mean": st.mean, "stddev": st.stddev, "threshold": st.threshold, "kept": int(st.kept)})
         return res[0] if len(res) == 1 else tuple(res)
 
+    def fpfh(self, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
+        """One 33-bin Fast Point Feature Histogram per point, as Features on the device (sga_cloud_fpfh).  The
+        cloud needs normals.  tree: the KdTree over this cloud (None: a temporary one is built).  k: neighbours per point, 2 .. 63.
+        viewpoint: a point of the caller's frame the normals are turned towards for the descriptor (nothing is written back); None:
+        the normals as stored."""
+        vp = None if viewpoint is None else np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float64).reshape(3))
+        h = C.c_void_p()
+        check(load().sga_cloud_fpfh(self.ctx.h, self.h, None if tree is None else tree.h, int(k), _dp(vp), C.byref(h)))
+        return Features(ctx=self.ctx, _handle=h)
+
     def overlap(self, target, T=None, max_distance=1.0, keep=None, return_dist=False, return_nearest=False, return_kept=False, ctx=None):
         """How much of this cloud, posed by T (4x4, cloud -> target; None: the identity), the target already explains, and which points
         are new (sga_cloud_overlap).  target: a KdTree, a GaussianVoxelMap or a flat map.  A point is matched
@@ -1857,6 +1867,126 @@ def cloud_outliers_launches():
 
 
 _OVERLAP_KEEP = {None: 0, "matched": 1, "unmatched": 2}
+
+
+class Features:
+    """n rows of dim float32 values on the device (sga_features): FPFH descriptors (PointCloud.fpfh), or a caller's own."""
+
+    def __init__(self, ctx=None, _handle=None):
+        self.ctx = ctx or default_context()
+        self.h = _handle if _handle is not None else C.c_void_p()
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            load().sga_features_destroy(self.h)
+            self.h = C.c_void_p()
+
+    @staticmethod
+    def from_array(rows, ctx=None):
+        """Features from an (n, dim) array, 1 <= dim <= 128 (sga_features_create)."""
+        a = np.ascontiguousarray(np.asarray(rows), dtype=np.float32)
+        if a.ndim != 2:
+            raise ValueError("rows must be (n, dim)")
+        f = Features(ctx)
+        check(load().sga_features_create(f.ctx.h, _fp(a) if len(a) else None, a.shape[0], a.shape[1], C.byref(f.h)))
+        return f
+
+    def _shape(self):
+        n, d = C.c_size_t(), C.c_int()
+        check(load().sga_features_size(self.h, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    def size(self):
+        return self._shape()[0]
+
+    __len__ = size
+
+    @property
+    def dim(self):
+        return self._shape()[1]
+
+    def numpy(self):
+        n, d = self._shape()
+        out = np.empty((n, d), np.float32)
+        check(load().sga_features_download(self.ctx.h, self.h, _fp(out) if n else None))
+        return out
+
+
+def compute_fpfh(points, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
+    """PointCloud.fpfh of a PointCloud with normals."""
+    return points.fpfh(tree, k, viewpoint)
+
+
+def match_features(src, tgt, mutual=True, return_dist=False):
+    """For every row of src the nearest row of tgt in squared L2 distance (sga_features_match; ties to the lowest index); mutual: only the
+    pairs that are each other's nearest.  Returns the pairs, (M, 2) int64 (source row, target row), ascending in the source row
+    [, and the distances (M,) float64]."""
+    n = src.size()
+    match = np.empty(n, np.int64)
+    dist = np.empty(n, np.float64) if return_dist else None
+    cnt = C.c_size_t()
+    check(load().sga_features_match(src.ctx.h, src.h, tgt.h, 1 if mutual else 0, match.ctypes.data_as(C.POINTER(C.c_int64)), _dp(dist), C.byref(cnt)))
+    keep = np.nonzero(match >= 0)[0]
+    pairs = np.ascontiguousarray(np.stack([keep.astype(np.int64), match[keep]], axis=1))
+    return (pairs, dist[keep]) if return_dist else pairs
+
+
+def _ransac_params(**fields):
+    p = _lib.Ransac()
+    load().sga_ransac_default(C.byref(p))
+    for name, value in fields.items():
+        if value is not None:
+            setattr(p, name, value)
+    return p
+
+
+def ransac_correspondences(source, target, pairs, max_distance=None, iterations=None, seed=None, edge_similarity=None, min_edge=None):
+    """The rigid motion most of the index pairs (M, 2) (source point, target point) agree on (sga_ransac_correspondences; DESIGN.md
+    section 3.24); None: the library's default (1.0, 20000, 0, 0.9, 0.0).  Returns a dict: "T" (4x4, source -> target), "inliers",
+    "inlier_rmse", "best_hypothesis", "scored", "refit"."""
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    p = _ransac_params(max_distance=max_distance, iterations=None if iterations is None else int(iterations), seed=None if seed is None else int(seed), edge_similarity=edge_similarity, min_edge=min_edge)
+    T = np.empty(16)
+    r = _lib.RansacResult()
+    check(load().sga_ransac_correspondences(source.ctx.h, source.h, target.h, pr.ctypes.data_as(C.POINTER(C.c_int64)) if len(pr) else None, len(pr), C.byref(p), _dp(T), C.byref(r)))
+    return {"T": T.reshape(4, 4).T.copy(), "inliers": int(r.inliers), "inlier_rmse": r.inlier_rmse, "best_hypothesis": int(r.best_hypothesis), "scored": int(r.scored), "refit": int(r.refit)}
+
+
+def global_align(target_points, source_points, voxel_size, k=20, iterations=20000, seed=0, refine=True, setting=None, viewpoint=(0.0, 0.0, 0.0)):
+    """A pose from geometry alone, then the local registration from it: voxel grid at voxel_size, trees, normals
+    and covariances, FPFH with the viewpoint at each cloud's sensor origin (viewpoint, in each cloud's own frame; default (0, 0, 0)), mutual matching, RANSAC with max_distance = 1.5
+    voxel_size and min_edge = 2 voxel_size, and — refine — GICP (setting: a make_setting; default "GICP") from the coarse pose.
+    Returns (coarse, refined): the dict of ransac_correspondences with "pairs" added, and the RegistrationResult (None without refine)."""
+    tgt, ttree = preprocess_points(target_points, voxel_size, k)
+    src, stree = preprocess_points(source_points, voxel_size, k)
+    pairs = match_features(src.fpfh(stree, k, viewpoint), tgt.fpfh(ttree, k, viewpoint), mutual=True)
+    coarse = ransac_correspondences(src, tgt, pairs, max_distance=1.5 * voxel_size, iterations=iterations, seed=seed, min_edge=2.0 * voxel_size)
+    coarse["pairs"] = pairs
+    refined = None
+    if refine:
+        refined = Problem(ttree, src, coarse["T"]).align(setting or make_setting("GICP"), coarse["T"])
+    return coarse, refined
+
+
+def _launches(name):
+    v = C.c_ulonglong()
+    check(getattr(load(), name)(C.byref(v)))
+    return v.value
+
+
+def cloud_fpfh_launches():
+    """Diagnostics (sga_debug_cloud_fpfh_launches): commands enqueued so far by PointCloud.fpfh (three per call)."""
+    return _launches("sga_debug_cloud_fpfh_launches")
+
+
+def features_match_launches():
+    """Diagnostics (sga_debug_features_match_launches): commands enqueued so far by match_features (two per call, three with mutual)."""
+    return _launches("sga_debug_features_match_launches")
+
+
+def ransac_launches():
+    """Diagnostics (sga_debug_ransac_launches): commands enqueued so far by ransac_correspondences (four per call)."""
+    return _launches("sga_debug_ransac_launches")
 
 
 def _overlap_params(max_distance=1.0, keep=None):

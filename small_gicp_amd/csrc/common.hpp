@@ -243,6 +243,15 @@ struct sga_cloud {
   sga::DevBuf<sga::Cov8> cov;
 };
 
+// n rows of dim floats (global registration): FPFH descriptors, or a caller's own
+struct sga_features {
+  int device = 0;
+  mutable sga::Ready ready;
+  size_t n = 0;
+  int dim = 0;
+  sga::DevBuf<float> rows;  // row-major n x dim
+};
+
 enum { SGA_INDEX_KDTREE = 0, SGA_INDEX_VOXELMAP = 1, SGA_INDEX_FLATMAP = 2, SGA_INDEX_PROJECTIVE = 3 };
 constexpr int kFlatCap = 16;  // point slots per voxel of a flat map (max_num_points_in_cell <= 16)
 struct sga_index {

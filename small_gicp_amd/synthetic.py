@@ -50,6 +50,26 @@ def scene(n, seed, layout_seed=12345, noise=0.01):
     return np.ascontiguousarray(pts, dtype=np.float32)
 
 
+def bumpy_terrain(n, seed, layout_seed=2024, noise=0.01):
+    """A terrain with shape of its own — what descriptors need, and what the plane and the axis-aligned walls of scene() lack: 40
+    Gaussian bumps (centres uniform in +-20 m, heights uniform in [0.5, 3] m, widths uniform in [1, 4] m, all from
+    default_rng(layout_seed)); x and y uniform in +-20 m from default_rng(seed), z the sum of the bumps, N(0, noise) on all three axes;
+    float32.  Two calls with different `seed` resample the SAME surface."""
+    lay = np.random.default_rng(layout_seed)
+    centres = lay.uniform(-20, 20, size=(40, 2))
+    heights = lay.uniform(0.5, 3.0, size=40)
+    widths = lay.uniform(1.0, 4.0, size=40)
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-20, 20, n)
+    y = rng.uniform(-20, 20, n)
+    z = np.zeros(n)
+    for c, h, w in zip(centres, heights, widths):
+        z += h * np.exp(-((x - c[0]) ** 2 + (y - c[1]) ** 2) / (2.0 * w * w))
+    pts = np.stack([x, y, z], axis=1)
+    pts += rng.normal(0, noise, size=pts.shape)
+    return np.ascontiguousarray(pts, dtype=np.float32)
+
+
 def registration_pair(n, target_seed=1, source_seed=2):
     """(target, source, T_gt): independent resamples of one scene; the source is expressed in a frame displaced by T_gt^-1."""
     T = gt_transform()
