@@ -387,6 +387,63 @@ typedef struct sga_ransac_result {
 } sga_ransac_result; /* 40 bytes */
 void sga_ransac_default(sga_ransac* p); /* 1.0, 20000, 0, 0.9, 0.0 */
 int sga_ransac_correspondences(sga_context* ctx, const sga_cloud* source, const sga_cloud* target, const int64_t* pairs /* M x 2 */, size_t M, const sga_ransac* params, double T[16], sga_ransac_result* result);
+
+/* ---- place recognition: Scan Context (Kim & Kim, IROS 2018) and an exhaustive shift-aligned search ------------
+ * "Which of my earlier keyframes is this place, and how am I turned against it?"  A database keeps one descriptor per keyframe on the
+ * device; a query compares a scan with every candidate at every column shift.  All arithmetic is double from the fp32 records, with
+ * integer atomics and fixed-order sums only: two calls give the same bytes.  tests/place_ref.py restates the rule in numpy.
+ *
+ * Descriptor of a cloud under the parameters rings R, sectors S, max_range L, height and under center (the sensor's position in the cloud's
+ * own coordinates, caller's frame; NULL: zeros): a row-major R x S fp32 image D.  For each record, p = (record + origin) - center in
+ * double; a record with a non-finite component is skipped; rho = sqrt(px^2 + py^2), skipped if rho >= L; ring = min(floor(rho / L * R),
+ * R - 1); theta = atan2(py, px), plus 2 pi when negative (atan2(0, 0) = 0); sector = min(floor(theta / (2 pi) * S), S - 1); v =
+ * float32(max(pz + height, 0)); D[ring][sector] is the greatest v of its cell, 0 for an empty cell.
+ *
+ * Distance of a query image q to an entry c at shift s in [0, S): n_q[j] = sqrt(sum_r q[r][j]^2), rings ascending, likewise n_c; the
+ * column pair (j, (j + s) mod S) counts when both norms are > 0; d(s) = 1 - (1 / count) sum_j (sum_r q[r][j] c[r][(j + s) mod S]) /
+ * (n_q[j] n_c[(j + s) mod S]) over the counting pairs, in double; count == 0: d(s) = 1.  d = min_s d(s), ties to the lowest s.  (The
+ * device adds the terms of four fixed slices of j, each ascending, and the slices in order: a fixed order, within a few 2^-53 of the
+ * plain ascending sum.)  Meaning of the shift: if the query's sensor frame is the entry's turned by yaw about z (T_entry^-1 T_query =
+ * rotz(yaw)), the best shift is round(yaw / (2 pi / S)) mod S.
+ *
+ * Query: the candidates are the entries [first, first + count); the result is the k best (fewer when there are fewer candidates) by
+ * ascending (d, index), written to out[0 .. *found); all_dist / all_shift (count values each, or NULL): d and its shift for every
+ * candidate.  Zero candidates: *found = 0, nothing launched.
+ *
+ * The database grows by doubling from 64 entries (a device-to-device copy on the context's stream; earlier entries stay bytewise equal).
+ * Commands: sga_places_add three (the fill of the slot, the descriptor, the column norms; one fill for an empty cloud; plus one copy
+ * when the database grows), no host wait on a stream-ordered context (a blocking context waits once); sga_places_add_descriptor one;
+ * sga_places_query four by cloud (fill, descriptor, match, selection; three for an empty cloud), two by image, exactly one host wait;
+ * sga_cloud_scan_context three (fill, descriptor, the hand-over to the host; two for an empty cloud), one wait.
+ * Refusals (SGA_ERR_INVALID; outputs untouched) — before any handle is read: NULL arguments (center may be NULL); rings outside [1, 64],
+ * sectors outside [1, 256], rings * sectors > 4096, max_range not finite or <= 0, height not finite; a non-finite center; k outside
+ * [1, 32] — then, before anything is enqueued: a context, cloud or database of another device; first + count beyond the size; a host
+ * image with a non-finite or negative value (named by its position). */
+typedef struct sga_place_params {
+  int rings, sectors;
+  double max_range;
+  double height;
+} sga_place_params; /* 24 bytes */
+typedef struct sga_place_match {
+  int64_t index;
+  int32_t shift;
+  int32_t reserved;
+  double distance;
+} sga_place_match; /* 24 bytes */
+typedef struct sga_places sga_places;
+void sga_place_params_default(sga_place_params* p); /* 20, 60, 80.0, 2.0 */
+int sga_places_create(sga_context* ctx, const sga_place_params* params, sga_places** out);
+int sga_places_destroy(sga_places* db);
+int sga_places_size(const sga_places* db, size_t* n);
+int sga_places_params(const sga_places* db, sga_place_params* params);
+int sga_places_add(sga_context* ctx, sga_places* db, const sga_cloud* cloud, const double center[3] /* or NULL */, size_t* index);
+int sga_places_add_descriptor(sga_context* ctx, sga_places* db, const float* image /* R x S */, size_t* index);
+int sga_places_download(sga_context* ctx, const sga_places* db, size_t first, size_t count, float* images /* count x R x S */);
+int sga_cloud_scan_context(sga_context* ctx, const sga_cloud* cloud, const sga_place_params* params, const double center[3] /* or NULL */, float* image /* R x S */);
+int sga_places_query(sga_context* ctx, const sga_places* db, const sga_cloud* cloud, const double center[3] /* or NULL */, size_t first, size_t count, int k, sga_place_match* out /* k */, size_t* found,
+                     double* all_dist /* count, or NULL */, int32_t* all_shift /* count, or NULL */);
+int sga_places_query_descriptor(sga_context* ctx, const sga_places* db, const float* image /* R x S */, size_t first, size_t count, int k, sga_place_match* out /* k */, size_t* found, double* all_dist /* count, or NULL */,
+                                int32_t* all_shift /* count, or NULL */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

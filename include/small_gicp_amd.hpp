@@ -238,6 +238,13 @@ struct RansacResult : sga_ransac_result {
   Isometry3d T_target_source;
 };
 
+/// The parameters of a Scan Context descriptor (sga_place_params with its defaults: 20 rings x 60 sectors out to 80 m, heights
+/// measured from 2 m below the sensor) and one result of a query: the entry, its best column shift, its distance.
+struct PlaceParams : sga_place_params {
+  PlaceParams() { sga_place_params_default(this); }
+};
+using PlaceMatch = sga_place_match;
+
 /// points/point_cloud.hpp:15-71 — device-resident; host copies on demand (points(i) etc. read a cached download).
 struct PointCloud {
   using Ptr = std::shared_ptr<PointCloud>;
@@ -387,6 +394,13 @@ struct PointCloud {
     check(sga_cloud_fpfh(ctx, h, kdtree, k, viewpoint ? viewpoint->data() : nullptr, &made), "sga_cloud_fpfh");
     return std::make_shared<Features>(made, ctx);
   }
+  /// The Scan Context descriptor of this cloud (sga_cloud_scan_context): rings x sectors floats, row-major.  center (optional): the
+  /// sensor's position in the cloud's coordinates.
+  std::vector<float> scan_context(const PlaceParams& params = PlaceParams(), const std::array<double, 3>* center = nullptr) const {
+    std::vector<float> image(params.rings > 0 && params.sectors > 0 ? static_cast<size_t>(params.rings) * static_cast<size_t>(params.sectors) : 1);
+    check(sga_cloud_scan_context(ctx, h, &params, center ? center->data() : nullptr, image.data()), "sga_cloud_scan_context");
+    return image;
+  }
   /// A new cloud whose point j is this cloud's point indices[j] with its normal and covariance (sga_cloud_select: one launch); repeats
   /// are allowed, the order is as given.
   Ptr selected(const std::vector<int64_t>& indices) const {
@@ -448,6 +462,75 @@ private:
   mutable bool host_valid = false;
   mutable std::vector<double> host_xyz;
   mutable std::vector<float> host_nrm, host_cov;
+};
+
+/// Place recognition (sga_places_*): the Scan Context descriptors of keyframes on the device, searched exhaustively at every column
+/// shift.  add() forms a descriptor on the device, where it stays; query() returns the k nearest entries by ascending (distance, index),
+/// each with the shift that aligns it: the yaw between the two visits is shift * 2 pi / sectors.
+struct Places {
+  explicit Places(const PlaceParams& params_ = PlaceParams(), sga_context* context = default_context()) : ctx(context), params(params_) { check(sga_places_create(ctx, &params, &h), "sga_places_create"); }
+  Places(const Places&) = delete;
+  Places& operator=(const Places&) = delete;
+  ~Places() { sga_places_destroy(h); }
+  size_t size() const {
+    size_t n = 0;
+    sga_places_size(h, &n);
+    return n;
+  }
+  size_t cells() const { return static_cast<size_t>(params.rings) * static_cast<size_t>(params.sectors); }
+  /// the descriptor of `cloud` becomes the next entry; returns its index
+  size_t add(const PointCloud& cloud, const std::array<double, 3>* center = nullptr) {
+    size_t index = 0;
+    check(sga_places_add(ctx, h, cloud.h, center ? center->data() : nullptr, &index), "sga_places_add");
+    return index;
+  }
+  /// an image of rings x sectors finite values >= 0 becomes the next entry
+  size_t add_descriptor(const std::vector<float>& image) {
+    if (image.size() != cells()) throw std::runtime_error("Places::add_descriptor: the image must hold rings x sectors values");
+    size_t index = 0;
+    check(sga_places_add_descriptor(ctx, h, image.data(), &index), "sga_places_add_descriptor");
+    return index;
+  }
+  /// the images of the entries [first, first + count), row-major
+  std::vector<float> download(size_t first, size_t count) const {
+    std::vector<float> images(count * cells());
+    check(sga_places_download(ctx, h, first, count, images.empty() ? nullptr : images.data()), "sga_places_download");
+    return images;
+  }
+  /// the k best of the entries [first, first + count) (count == SIZE_MAX: to the end) for a cloud ...
+  std::vector<PlaceMatch> query(const PointCloud& cloud, int k = 1, size_t first = 0, size_t count = SIZE_MAX, const std::array<double, 3>* center = nullptr) const {
+    std::vector<PlaceMatch> out(k > 0 ? static_cast<size_t>(k) : 1);
+    size_t found = 0;
+    check(sga_places_query(ctx, h, cloud.h, center ? center->data() : nullptr, first, span(first, count), k, out.data(), &found, nullptr, nullptr), "sga_places_query");
+    out.resize(found);
+    return out;
+  }
+  /// ... or for an image
+  std::vector<PlaceMatch> query(const std::vector<float>& image, int k = 1, size_t first = 0, size_t count = SIZE_MAX) const {
+    if (image.size() != cells()) throw std::runtime_error("Places::query: the image must hold rings x sectors values");
+    std::vector<PlaceMatch> out(k > 0 ? static_cast<size_t>(k) : 1);
+    size_t found = 0;
+    check(sga_places_query_descriptor(ctx, h, image.data(), first, span(first, count), k, out.data(), &found, nullptr, nullptr), "sga_places_query_descriptor");
+    out.resize(found);
+    return out;
+  }
+  /// the rotation about z by shift * 2 pi / sectors: the initial guess T_entry^-1 T_query a shift stands for
+  Isometry3d yaw_guess(int shift) const {
+    const double a = static_cast<double>(shift) * (2.0 * M_PI / static_cast<double>(params.sectors));
+    Isometry3d T;
+    T.m = {std::cos(a), std::sin(a), 0, 0, -std::sin(a), std::cos(a), 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    return T;
+  }
+
+  sga_context* ctx = default_context();
+  PlaceParams params;
+  sga_places* h = nullptr;
+
+private:
+  size_t span(size_t first, size_t count) const {
+    const size_t n = size();
+    return count == SIZE_MAX ? (first < n ? n - first : 0) : count;
+  }
 };
 
 /// The rigid motion most of the index pairs (source point, target point) agree on (sga_ransac_correspondences): hypotheses from three

@@ -125,6 +125,14 @@ int sga_debug_cloud_visibility_launches(unsigned long long* launches);
 int sga_debug_cloud_fpfh_launches(unsigned long long* launches);
 int sga_debug_features_match_launches(unsigned long long* launches);
 int sga_debug_ransac_launches(unsigned long long* launches);
+/* Commands enqueued so far, in this process, by the place-recognition calls (small_gicp_amd.h).  add: what
+ * sga_places_add (three: the fill of the slot, the descriptor, the column norms; one for an empty cloud), sga_places_add_descriptor (one)
+ * and sga_cloud_scan_context (three; two for an empty cloud) enqueue, plus one copy whenever the database grows.  query: what
+ * sga_places_query (four: fill, descriptor, match, selection; three for an empty cloud) and sga_places_query_descriptor (two) enqueue;
+ * none over zero candidates.  waits: the host waits of all these calls (a query: one; an add on a stream-ordered context: none). */
+int sga_debug_places_add_launches(unsigned long long* launches);
+int sga_debug_places_query_launches(unsigned long long* launches);
+int sga_debug_places_waits(unsigned long long* waits);
 /* The host arithmetic of sga_ransac_correspondences, exposed so that it can be tested without a device.  draw: the three distinct pair
  * numbers hypothesis h draws from M >= 3 pairs under `seed` (SGA_ERR_INVALID for M < 3 or M >= 2^31).  rigid_from_sums: the least-squares
  * rigid motion of n point pairs from their plain sums — sum_s = sum p_s, sum_t = sum p_t, cross[3 r + c] = sum p_s[r] p_t[c] — by Horn's

@@ -126,6 +126,18 @@ class RansacResult(C.Structure):
     _fields_ = [("inliers", C.c_uint64), ("inlier_rmse", C.c_double), ("best_hypothesis", C.c_uint64), ("scored", C.c_uint64), ("refit", C.c_int), ("reserved", C.c_int)]
 
 
+class PlaceParams(C.Structure):
+    """sga_place_params: rings, sectors, max_range, height of a Scan Context descriptor."""
+
+    _fields_ = [("rings", C.c_int), ("sectors", C.c_int), ("max_range", C.c_double), ("height", C.c_double)]
+
+
+class PlaceMatch(C.Structure):
+    """sga_place_match: the index of a database entry, its best column shift and its distance."""
+
+    _fields_ = [("index", C.c_int64), ("shift", C.c_int32), ("reserved", C.c_int32), ("distance", C.c_double)]
+
+
 FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
@@ -182,6 +194,20 @@ SYMBOLS = [
     ("sga_features_match", C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_size_t)]),
     ("sga_ransac_default", None, [C.POINTER(Ransac)]),
     ("sga_ransac_correspondences", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(Ransac), _dp, C.POINTER(RansacResult)]),
+    ("sga_place_params_default", None, [C.POINTER(PlaceParams)]),
+    ("sga_places_create", C.c_int, [_vp, C.POINTER(PlaceParams), _pvp]),
+    ("sga_places_destroy", C.c_int, [_vp]),
+    ("sga_places_size", C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    ("sga_places_params", C.c_int, [_vp, C.POINTER(PlaceParams)]),
+    ("sga_places_add", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(C.c_size_t)]),
+    ("sga_places_add_descriptor", C.c_int, [_vp, _vp, _fp, C.POINTER(C.c_size_t)]),
+    ("sga_places_download", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _fp]),
+    ("sga_cloud_scan_context", C.c_int, [_vp, _vp, C.POINTER(PlaceParams), _dp, _fp]),
+    ("sga_places_query", C.c_int, [_vp, _vp, _vp, _dp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(PlaceMatch), C.POINTER(C.c_size_t), _dp, C.POINTER(C.c_int32)]),
+    ("sga_places_query_descriptor", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(PlaceMatch), C.POINTER(C.c_size_t), _dp, C.POINTER(C.c_int32)]),
+    ("sga_debug_places_add_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_places_query_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_places_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),

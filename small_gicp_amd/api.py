@@ -359,6 +359,15 @@ class PointCloud:
         check(load().sga_cloud_fpfh(self.ctx.h, self.h, None if tree is None else tree.h, int(k), _dp(vp), C.byref(h)))
         return Features(ctx=self.ctx, _handle=h)
 
+    def scan_context(self, rings=None, sectors=None, max_range=None, height=None, center=None):
+        """The Scan Context descriptor of this cloud (sga_cloud_scan_context): an (rings, sectors) float32 image
+        of the greatest height + `height` per polar cell about `center` (the sensor's position in the cloud's coordinates; None:
+        zeros), out to max_range.  None: the library's default (20, 60, 80.0, 2.0)."""
+        p = _place_params(rings=rings, sectors=sectors, max_range=max_range, height=height)
+        out = np.empty((p.rings, p.sectors), np.float32) if 0 < p.rings * p.sectors <= 4096 else np.empty((1, 1), np.float32)
+        check(load().sga_cloud_scan_context(self.ctx.h, self.h, C.byref(p), _dp(_center3(center)), _fp(out)))
+        return out
+
     def overlap(self, target, T=None, max_distance=1.0, keep=None, return_dist=False, return_nearest=False, return_kept=False, ctx=None):
         """How much of this cloud, posed by T (4x4, cloud -> target; None: the identity), the target already explains, and which points
         are new (sga_cloud_overlap).  target: a KdTree, a GaussianVoxelMap or a flat map.  A point is matched
@@ -1966,6 +1975,140 @@ def global_align(target_points, source_points, voxel_size, k=20, iterations=2000
     if refine:
         refined = Problem(ttree, src, coarse["T"]).align(setting or make_setting("GICP"), coarse["T"])
     return coarse, refined
+
+
+def _place_params(**fields):
+    p = _lib.PlaceParams()
+    load().sga_place_params_default(C.byref(p))
+    for name, value in fields.items():
+        if value is not None:
+            setattr(p, name, value)
+    return p
+
+
+def _center3(center):
+    return None if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(3))
+
+
+PLACE_MATCH_DTYPE = np.dtype([("index", np.int64), ("shift", np.int32), ("reserved", np.int32), ("distance", np.float64)])
+
+
+class PlaceDatabase:
+    """Scan Context descriptors of keyframes on the device, searched exhaustively at every column shift (sga_places_*; DESIGN.md
+    section 3.25).  add() forms a descriptor on the device, where it stays; query() returns the nearest entries with the column shift
+    that aligns them, which is the yaw between the two visits in units of 2 pi / sectors."""
+
+    def __init__(self, ctx=None, rings=20, sectors=60, max_range=80.0, height=2.0):
+        self.ctx = ctx or default_context()
+        self.h = C.c_void_p()
+        p = _place_params(rings=int(rings), sectors=int(sectors), max_range=float(max_range), height=float(height))
+        check(load().sga_places_create(self.ctx.h, C.byref(p), C.byref(self.h)))
+        self.rings, self.sectors, self.max_range, self.height = p.rings, p.sectors, p.max_range, p.height
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            load().sga_places_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __len__(self):
+        n = C.c_size_t()
+        check(load().sga_places_size(self.h, C.byref(n)))
+        return n.value
+
+    def _image(self, image):
+        a = np.ascontiguousarray(np.asarray(image), dtype=np.float32)
+        if a.shape != (self.rings, self.sectors):
+            raise ValueError(f"image must be ({self.rings}, {self.sectors}), not {a.shape}")
+        return a
+
+    def add(self, cloud, center=None):
+        """The descriptor of a PointCloud becomes the next entry; returns its index.  center: the sensor's position in the cloud's
+        coordinates (None: zeros)."""
+        i = C.c_size_t()
+        check(load().sga_places_add(self.ctx.h, self.h, cloud.h, _dp(_center3(center)), C.byref(i)))
+        return i.value
+
+    def add_descriptor(self, image):
+        """A (rings, sectors) image (finite, >= 0) becomes the next entry: crafted, or reloaded from descriptors(); returns its index."""
+        i = C.c_size_t()
+        check(load().sga_places_add_descriptor(self.ctx.h, self.h, _fp(self._image(image)), C.byref(i)))
+        return i.value
+
+    def descriptors(self, first=0, count=None):
+        """The images of the entries [first, first + count) (count None: to the end), (count, rings, sectors) float32."""
+        count = len(self) - first if count is None else count
+        out = np.empty((max(count, 0), self.rings, self.sectors), np.float32)
+        check(load().sga_places_download(self.ctx.h, self.h, first, count, _fp(out) if count > 0 else None))
+        return out
+
+    def query(self, cloud_or_image, k=1, exclude_recent=0, first=None, count=None, center=None, return_all=False):
+        """The k entries nearest to a PointCloud's descriptor (center as in add) or to a (rings, sectors) image, among the entries
+        [first, first + count): first None: 0; count None: to the end, less the exclude_recent latest entries (the keyframes a mapping
+        loop has just added are no loop closures).  Returns a dict: "index" (m,) int64, "shift" (m,) int32, "distance" (m,) float64 —
+        ascending in (distance, index), m = min(k, candidates) — and "yaw" = shift 2 pi / sectors; with return_all also "all_distance"
+        and "all_shift" for every candidate."""
+        n = len(self)
+        first = 0 if first is None else int(first)
+        count = max(n - first - int(exclude_recent), 0) if count is None else int(count)
+        out = np.zeros(max(int(k), 1), PLACE_MATCH_DTYPE)
+        found = C.c_size_t()
+        all_d = np.empty(count, np.float64) if return_all else None
+        all_s = np.empty(count, np.int32) if return_all else None
+        tail = (first, count, int(k), out.ctypes.data_as(C.POINTER(_lib.PlaceMatch)), C.byref(found), _dp(all_d), None if all_s is None else all_s.ctypes.data_as(C.POINTER(C.c_int32)))
+        if isinstance(cloud_or_image, PointCloud):
+            check(load().sga_places_query(self.ctx.h, self.h, cloud_or_image.h, _dp(_center3(center)), *tail))
+        else:
+            check(load().sga_places_query_descriptor(self.ctx.h, self.h, _fp(self._image(cloud_or_image)), *tail))
+        m = out[: found.value]
+        res = {"index": m["index"].copy(), "shift": m["shift"].copy(), "distance": m["distance"].copy()}
+        res["yaw"] = res["shift"].astype(np.float64) * (2.0 * np.pi / self.sectors)
+        if return_all:
+            res["all_distance"], res["all_shift"] = all_d, all_s
+        return res
+
+    def yaw_guess(self, shift):
+        """The initial guess a shift stands for: the 4x4 rotation about z by shift 2 pi / sectors — T_entry^-1 T_query when the two
+        visits differ by a turn alone."""
+        a = float(shift) * (2.0 * np.pi / self.sectors)
+        T = np.eye(4)
+        T[0, 0], T[0, 1], T[1, 0], T[1, 1] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
+        return T
+
+
+def scan_context_distance(q, c):
+    """The shift-aligned distance of two (rings, sectors) images on the host, in numpy float64 (the rule of small_gicp_amd.h: the mean
+    column cosine distance, least over all circular column shifts, ties to the lowest shift): (distance, shift).  A helper for users
+    who hold descriptors; the device's search is PlaceDatabase.query."""
+    q, c = np.asarray(q, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    if q.ndim != 2 or q.shape != c.shape:
+        raise ValueError("q and c must be (rings, sectors) images of one shape")
+    S = q.shape[1]
+    nq, nc = np.sqrt((q * q).sum(axis=0)), np.sqrt((c * c).sum(axis=0))
+    best, shift = np.inf, 0
+    for s in range(S):
+        cs, ns = np.roll(c, -s, axis=1), np.roll(nc, -s)
+        ok = (nq > 0) & (ns > 0)
+        d = 1.0 - float(((q * cs).sum(axis=0)[ok] / (nq[ok] * ns[ok])).sum()) / ok.sum() if ok.any() else 1.0
+        if d < best:
+            best, shift = d, s
+    return best, shift
+
+
+def places_add_launches():
+    """Diagnostics (sga_debug_places_add_launches): commands enqueued so far by PlaceDatabase.add (three per call), add_descriptor (one)
+    and PointCloud.scan_context (three), plus one copy per growth of a database."""
+    return _launches("sga_debug_places_add_launches")
+
+
+def places_query_launches():
+    """Diagnostics (sga_debug_places_query_launches): commands enqueued so far by PlaceDatabase.query (four by cloud, two by image)."""
+    return _launches("sga_debug_places_query_launches")
+
+
+def places_waits():
+    """Diagnostics (sga_debug_places_waits): host waits so far of the place-recognition calls (a query: one; an add on a
+    stream-ordered context: none)."""
+    return _launches("sga_debug_places_waits")
 
 
 def _launches(name):

@@ -733,6 +733,70 @@ def run_synthetic_pipelined(num_frames=20, pinned=False, **kw):
     return {"frames": num_frames, "ms_per_scan": 1e3 * wall / num_frames, "estimated": poses, "mean_iterations": float(np.mean(iters)) if iters else 0.0}
 
 
+REVISITS = ((10, 150.0, (0.2, -0.15)), (30, -75.0, (-0.1, 0.25)), (50, 33.0, (0.3, 0.0)), (70, 180.0, (-0.15, -0.2)))
+
+
+def _pose_error(T, T_ref):
+    E = np.linalg.inv(T) @ T_ref
+    R = E[:3, :3]
+    s = 0.5 * float(np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]))
+    return float(np.linalg.norm(E[:3, 3])), float(np.arctan2(s, (np.trace(R) - 1.0) / 2.0))
+
+
+def run_synthetic_revisit(keyframes=tuple(range(0, 80, 2)), revisits=REVISITS, n_az=2030, downsampling_resolution=0.25, num_neighbors=10, rings=20, sectors=60, max_range=80.0, height=2.0, seed=1000,
+                          from_identity=False, ctx=None):
+    """Loop closure on the synthetic scene: a first pass stores the Scan Context descriptor of the scan at every
+    keyframe pose of the arc (synthetic._sensor_pose(f), f in keyframes) in a PlaceDatabase; each revisit (frame, yaw in degrees, (dx, dy))
+    then returns to a stored pose moved by (dx, dy) metres in the world frame and turned by yaw about z, looks its scan up, and
+    registers it against the retrieved keyframe by GICP from yaw_guess(shift).  Per revisit: "retrieved" (the keyframe's frame),
+    "rank" (where the revisited keyframe stands in the ranking, 0 = first), "shift", "distance", "place_error_m" (between the retrieved
+    keyframe and the revisit), "yaw_error_rad" (the shift's yaw against the true one), "T" (GICP's T_keyframe_revisit), "converged",
+    "pose_error" ((m, rad) against the generator's relative pose) and — from_identity — "identity_error", what GICP reaches without
+    the guess."""
+    from . import synthetic
+
+    keyframes = tuple(keyframes)
+    ctx = ctx or api.default_context()
+    db = api.PlaceDatabase(ctx, rings, sectors, max_range, height)
+    poses, clouds = [], []
+    for f in keyframes:
+        poses.append(synthetic._sensor_pose(f))
+        clouds.append(api.PointCloud(synthetic.scan_at(poses[-1], n_az=n_az), ctx=ctx))
+        db.add(clouds[-1])
+    setting = api.make_setting("GICP")
+    prepared = {}
+    out = []
+    for frame, yaw_deg, (dx, dy) in revisits:
+        yaw = np.deg2rad(yaw_deg)
+        Tq = synthetic._sensor_pose(frame).copy()
+        Tq[:3, 3] += [dx, dy, 0.0]
+        Tq[:3, :3] = Tq[:3, :3] @ synthetic._rot([0, 0, 1], yaw)
+        scan = api.PointCloud(synthetic.scan_at(Tq, n_az=n_az, seed=seed + frame), ctx=ctx)
+        res = db.query(scan, k=1, return_all=True)
+        i, shift = int(res["index"][0]), int(res["shift"][0])
+        order = np.lexsort((np.arange(len(db)), res["all_distance"]))
+        true = np.linalg.inv(poses[i]) @ Tq
+        true_yaw = np.arctan2(true[1, 0], true[0, 0])
+        if i not in prepared:
+            prepared[i] = api.preprocess_points(clouds[i], downsampling_resolution, num_neighbors)
+        _, tree = prepared[i]
+        src, _ = api.preprocess_points(scan, downsampling_resolution, num_neighbors)
+        guess = db.yaw_guess(shift)
+        r = api.Problem(tree, src, guess).align(setting, guess)
+        row = {
+            "frame": frame, "yaw_deg": yaw_deg, "index": i, "retrieved": keyframes[i], "shift": shift, "distance": float(res["distance"][0]),
+            "rank": int(np.flatnonzero(order == keyframes.index(frame))[0]) if frame in keyframes else None,
+            "place_error_m": float(np.linalg.norm(poses[i][:3, 3] - Tq[:3, 3])),
+            "yaw_error_rad": float((float(res["yaw"][0]) - true_yaw + np.pi) % (2.0 * np.pi) - np.pi),
+            "T": r.T_target_source, "converged": bool(r.converged), "pose_error": _pose_error(r.T_target_source, true), "T_true": true,
+        }
+        if from_identity:
+            r0 = api.Problem(tree, src, np.eye(4)).align(setting, np.eye(4))
+            row["identity_error"] = _pose_error(r0.T_target_source, true)
+        out.append(row)
+    return {"keyframes": len(keyframes), "revisits": out}
+
+
 def _cpp_driver(source, workdir, num_frames):
     """Write the synthetic sequence as KITTI .bin files under workdir/velodyne (once) and compile examples/<source> against the in-tree
     library.  Returns (executable, dataset directory)."""

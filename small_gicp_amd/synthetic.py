@@ -152,6 +152,21 @@ def kitti_like_scan(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02,
     return np.ascontiguousarray(pts, dtype=np.float32), Tws
 
 
+def scan_at(T_world_sensor, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
+    """The scan of the scene of kitti_like_scan from ANY sensor pose (a revisit from another heading, a keyframe off the arc): the same
+    rays, the same casting, the same range gate (3 m .. 80 m); range noise N(0, noise) from default_rng(seed).
+    Returns the points in the sensor frame, float32 (N,3)."""
+    Tws = np.asarray(T_world_sensor, dtype=np.float64)
+    d_s = _ring_directions(n_rings, n_az)
+    d = d_s @ Tws[:3, :3].T
+    t_best, _ = _cast(Tws[:3, 3], d, _walls(layout_seed))
+    keep = np.isfinite(t_best) & (t_best >= 3.0) & (t_best <= 80.0)
+    rng = np.random.default_rng(seed)
+    r = t_best[keep] + rng.normal(0, noise, keep.sum())
+    pts = d_s[keep] * r[:, None]
+    return np.ascontiguousarray(pts, dtype=np.float32)
+
+
 def kitti_like_sweep(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
     """The scan of kitti_like_scan(frame) as a spinning sensor delivers it: RAW, every azimuth column cast from the pose the sensor has at
     its own firing time.  The sweep starts at the pose of frame - 1 and ends at the pose of `frame` (frame >= 1); with
