@@ -444,6 +444,65 @@ int sga_places_query(sga_context* ctx, const sga_places* db, const sga_cloud* cl
                      double* all_dist /* count, or NULL */, int32_t* all_shift /* count, or NULL */);
 int sga_places_query_descriptor(sga_context* ctx, const sga_places* db, const float* image /* R x S */, size_t first, size_t count, int k, sga_place_match* out /* k */, size_t* found, double* all_dist /* count, or NULL */,
                                 int32_t* all_shift /* count, or NULL */);
+/* Fixed-radius neighbourhoods on the device: radius search and clustering, both over one walk of the kd-tree
+ * that visits every record within a radius.  THE PREDICATE, for both: record j is a neighbour of q iff d2(q, j) = dx dx + dy dy + dz dz
+ * <= radius * radius, formed in double from the fp32 records — two records of one cloud as they are, a query of another device frame as
+ * its record plus the origin difference, added in double.  The tree prunes in fp32 against a bound widened so that nothing the predicate
+ * accepts is excluded (csrc/kd_radius.hpp); every candidate is tested in double.
+ *
+ * sga_index_radius_search: for each of the m points of `queries` (any cloud of the context's device; it may be the indexed cloud itself)
+ * the records of the kd-tree within radius.  counts (room for m): the number per query, always written.  Lists, on request (offsets
+ * non-NULL; then indices and sq_dists are required): CSR — offsets[m + 1], indices[total] (positions in the indexed cloud, not kd
+ * positions), sq_dists[total] (double) — in the walk's order within a list, which is reproducible for a given tree and not otherwise
+ * specified.  capacity: the room of indices / sq_dists in entries.  When total exceeds it, counts, offsets and result->total are still
+ * written, the lists are not, result->overflow is 1 and the status is SGA_OK: call again with room for total.  Passes: count, prefix
+ * (one workgroup), fill; one host wait for the counts, a second one behind the copy of the lists.  m == 0, or an index over no points:
+ * SGA_OK without device work (counts zeroed).  Refusals (SGA_ERR_INVALID) — before any handle is read: NULL ctx, kdtree, queries, counts or
+ * result; offsets without indices and sq_dists; a radius that is not finite and > 0 — then: another device, an index that is no kd-tree
+ * (projective: SGA_ERR_UNSUPPORTED), 2^31 queries or more. */
+typedef struct sga_radius_result {
+  uint64_t total;   /* sum of counts */
+  uint64_t written; /* entries of indices / sq_dists written: total, or 0 */
+  int overflow;     /* 1: lists were asked for and total > capacity */
+  int reserved;
+} sga_radius_result; /* 24 bytes */
+int sga_index_radius_search(sga_context* ctx, const sga_index* kdtree, const sga_cloud* queries, double radius, size_t capacity, int64_t* counts /* m */, int64_t* offsets /* m + 1, or NULL */,
+                            int64_t* indices /* capacity, or NULL */, double* sq_dists /* capacity, or NULL */, sga_radius_result* result);
+/* sga_cloud_cluster: DBSCAN with a deterministic border rule, in terms of cloud indices.
+ *   core point    i is core iff at least min_points records lie within radius of it, itself included (min_points <= 1: every point).
+ *   cluster       two core points within radius of each other are in one cluster: the connected components of that graph.
+ *   border point  a non-core point with a core point within radius joins the cluster of its NEAREST core point (d2 in double; ties:
+ *                 the lowest cloud index); with none it is noise.
+ *   size filter   a cluster's size counts core and border members; clusters outside [min_size, max_size] are dropped (max_size 0: no limit).
+ *   numbering     kept clusters are numbered 0 .. C - 1 in ascending order of their SEED, the lowest cloud index among their core points.
+ * labels (room for n, or NULL): the number, or -1 for noise and for members of dropped clusters.  table (room for table_capacity rows,
+ * or NULL with capacity 0): row c = seed, size and box (min / max of the members' fp32 records + the origin, in double) of cluster c;
+ * rows beyond the capacity are not written, result->clusters is the full count.  result (or NULL): clusters kept, noise points, points
+ * of dropped clusters, rows written.  The labels are a function of the records alone: not of scheduling, the tree's layout or the call.
+ * keep 1 / 2: *out is the cloud of the clustered (label >= 0) / the other points, compacted as sga_cloud_crop does (order, normals,
+ * covariances, origin kept; kept, or NULL, room for n: their indices); keep 0: out and kept must be NULL.
+ * kdtree: a kd-tree over THIS cloud, checked as sga_cloud_remove_outliers checks it, or NULL: a temporary one (a cloud with a non-finite
+ * coordinate has no kd-tree and is refused: crop first).  n == 0: SGA_OK, zero clusters, nothing launched.  One host wait.
+ * Refusals (SGA_ERR_INVALID) — before any handle is read: NULL ctx, cloud or params; keep outside [0, 2] or at odds with out / kept; a
+ * table without capacity or a capacity without table; a radius that is not finite and > 0; min_points < 1; min_size < 1; max_size < 0;
+ * min_size > max_size (max_size > 0) — then: as sga_cloud_remove_outliers. */
+typedef struct sga_cluster_params {
+  double radius;    /* eps */
+  int min_points;   /* records within radius, the point included, that make a core point */
+  int keep;         /* 0 no cloud, 1 the clustered points, 2 the rest */
+  int64_t min_size; /* >= 1 */
+  int64_t max_size; /* 0: no limit */
+} sga_cluster_params; /* 32 bytes */
+typedef struct sga_cluster_result {
+  uint64_t clusters, noise, dropped, rows;
+} sga_cluster_result; /* 32 bytes */
+typedef struct sga_cluster_row {
+  int64_t seed, size;
+  double lo[3], hi[3];
+} sga_cluster_row; /* 64 bytes */
+void sga_cluster_params_default(sga_cluster_params* p); /* radius 0.5, min_points 1, keep 0, min_size 1, max_size 0 */
+int sga_cloud_cluster(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_cluster_params* params, int32_t* labels /* n, or NULL */,
+                      sga_cluster_row* table /* table_capacity, or NULL */, size_t table_capacity, int64_t* kept /* n, or NULL */, sga_cluster_result* result /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

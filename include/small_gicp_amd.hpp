@@ -135,6 +135,32 @@ struct OutlierFilter : sga_outlier_filter {
   }
 };
 
+/// What PointCloud::clusters asks for (sga_cluster_params with its defaults: radius 0.5, min_points 1, min_size 1, no max_size, no cloud):
+/// DBSCAN with a deterministic border rule (small_gicp_amd.h).  keep says which points the output cloud holds.
+struct ClusterParams : sga_cluster_params {
+  enum Keep { None = 0, Clustered = 1, Rest = 2 };
+  ClusterParams() { sga_cluster_params_default(this); }
+  explicit ClusterParams(double radius_, int min_points_ = 1, int64_t min_size_ = 1, int64_t max_size_ = 0, Keep keep_ = None) {
+    sga_cluster_params_default(this);
+    radius = radius_, min_points = min_points_, min_size = min_size_, max_size = max_size_, keep = static_cast<int>(keep_);
+  }
+};
+struct PointCloud;
+/// What PointCloud::clusters found: a label per point (-1: noise or a dropped cluster), the counts, a row per kept cluster (seed, size,
+/// box; the first table_capacity of them), and the cloud of the clustered or the other points with their indices (keep other than None).
+struct Clusters {
+  std::vector<int32_t> labels;
+  sga_cluster_result counts{};
+  std::vector<sga_cluster_row> table;
+  std::shared_ptr<PointCloud> cloud;
+  std::vector<int64_t> kept;
+};
+/// What KdTree::radius_search found: the number of neighbours per query and, when asked for, their CSR lists.
+struct RadiusNeighbors {
+  std::vector<int64_t> counts, offsets, indices;
+  std::vector<double> sq_dists;
+};
+
 /// What PointCloud::overlap asks for (sga_overlap with its defaults: max_distance 1, statistics only).  A point is matched when its
 /// nearest target record lies within max_distance; keep says which points the output cloud holds.
 struct Overlap {
@@ -386,6 +412,25 @@ struct PointCloud {
     }
     return r;
   }
+  /// The objects of this cloud (sga_cloud_cluster): labels, counts and a table of up to table_capacity clusters.  kdtree: the handle of
+  /// the KdTree over this cloud, or null: a temporary one is built.  A cloud with a non-finite coordinate is refused: crop first.
+  Clusters clusters(const ClusterParams& params = ClusterParams(), const sga_index* kdtree = nullptr, size_t table_capacity = 1024) const {
+    Clusters r;
+    const size_t n = size();
+    r.labels.resize(n);
+    r.table.resize(table_capacity);
+    if (params.keep != 0) r.kept.resize(n);
+    sga_cloud* made = nullptr;
+    check(sga_cloud_cluster(ctx, h, kdtree, &params, r.labels.empty() ? nullptr : r.labels.data(), r.table.empty() ? nullptr : r.table.data(), table_capacity, r.kept.empty() ? nullptr : r.kept.data(), &r.counts,
+                            params.keep != 0 ? &made : nullptr),
+          "sga_cloud_cluster");
+    r.table.resize(static_cast<size_t>(r.counts.rows));
+    if (params.keep != 0) {
+      r.cloud = std::make_shared<PointCloud>(made, ctx);
+      r.kept.resize(r.cloud->size());
+    }
+    return r;
+  }
   /// One 33-bin Fast Point Feature Histogram per point (sga_cloud_fpfh); the cloud needs normals.  kdtree: the handle of the KdTree over
   /// this cloud, or null: a temporary one is built.  viewpoint (optional, the caller's frame): the normals are turned towards it for
   /// the descriptor; nothing is written back.
@@ -573,6 +618,25 @@ struct KdTree {
     return found;
   }
   size_t nearest_neighbor_search(const double* pt, size_t* k_index, double* k_sq_dist) const { return knn_search(pt, 1, k_index, k_sq_dist); }
+  /// The indexed points within radius of every point of `queries` (sga_index_radius_search; d2 <= radius^2 in double): the counts and,
+  /// with_lists, the CSR lists (indices into the indexed cloud, squared distances), in the walk's order within a list.
+  RadiusNeighbors radius_search(const PointCloud& queries, double radius, bool with_lists = true) const {
+    RadiusNeighbors r;
+    const size_t m = queries.size();
+    r.counts.resize(m + 1);  // (never empty: the library wants a place for the counts)
+    sga_radius_result res{};
+    check(sga_index_radius_search(points->ctx, h, queries.h, radius, 0, r.counts.data(), nullptr, nullptr, nullptr, &res), "sga_index_radius_search");
+    if (with_lists) {
+      r.offsets.resize(m + 1);
+      r.indices.resize(static_cast<size_t>(res.total) + 1);
+      r.sq_dists.resize(static_cast<size_t>(res.total) + 1);
+      check(sga_index_radius_search(points->ctx, h, queries.h, radius, static_cast<size_t>(res.total), r.counts.data(), r.offsets.data(), r.indices.data(), r.sq_dists.data(), &res), "sga_index_radius_search");
+      r.indices.resize(static_cast<size_t>(res.total));
+      r.sq_dists.resize(static_cast<size_t>(res.total));
+    }
+    r.counts.resize(m);
+    return r;
+  }
 
   std::shared_ptr<const PointCloud> points;
   sga_index* h = nullptr;

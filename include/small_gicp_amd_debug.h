@@ -133,6 +133,14 @@ int sga_debug_ransac_launches(unsigned long long* launches);
 int sga_debug_places_add_launches(unsigned long long* launches);
 int sga_debug_places_query_launches(unsigned long long* launches);
 int sga_debug_places_waits(unsigned long long* waits);
+/* Commands enqueued so far, in this process, by the fixed-radius calls (small_gicp_amd.h).
+ * sga_index_radius_search: the count and the prefix — two — and with lists that fit the fill and two copies: five.  sga_cloud_cluster: the
+ * fill of its tables, the hook, the flatten, the sizes, the selection and the labels — six — plus the count and the border pass when
+ * min_points > 1 — eight — plus the compaction's table copy and the compaction when a cloud is made.  The build of a temporary tree is not
+ * counted; an empty cloud / no queries enqueue nothing.  waits: the host waits of both (a clustering: one; a search: one, two with lists). */
+int sga_debug_radius_search_launches(unsigned long long* launches);
+int sga_debug_cloud_cluster_launches(unsigned long long* launches);
+int sga_debug_radius_waits(unsigned long long* waits);
 /* The host arithmetic of sga_ransac_correspondences, exposed so that it can be tested without a device.  draw: the three distinct pair
  * numbers hypothesis h draws from M >= 3 pairs under `seed` (SGA_ERR_INVALID for M < 3 or M >= 2^31).  rigid_from_sums: the least-squares
  * rigid motion of n point pairs from their plain sums — sum_s = sum p_s, sum_t = sum p_t, cross[3 r + c] = sum p_s[r] p_t[c] — by Horn's

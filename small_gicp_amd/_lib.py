@@ -138,6 +138,30 @@ class PlaceMatch(C.Structure):
     _fields_ = [("index", C.c_int64), ("shift", C.c_int32), ("reserved", C.c_int32), ("distance", C.c_double)]
 
 
+class RadiusResult(C.Structure):
+    """sga_radius_result: the sum of the counts, the list entries written, overflow 0 | 1 (lists asked for and total > capacity)."""
+
+    _fields_ = [("total", C.c_uint64), ("written", C.c_uint64), ("overflow", C.c_int), ("reserved", C.c_int)]
+
+
+class ClusterParams(C.Structure):
+    """sga_cluster_params: radius (eps), min_points, keep 0 none | 1 the clustered | 2 the rest, min_size, max_size (0: no limit)."""
+
+    _fields_ = [("radius", C.c_double), ("min_points", C.c_int), ("keep", C.c_int), ("min_size", C.c_int64), ("max_size", C.c_int64)]
+
+
+class ClusterResult(C.Structure):
+    """sga_cluster_result: clusters kept, noise points, points of dropped clusters, table rows written."""
+
+    _fields_ = [("clusters", C.c_uint64), ("noise", C.c_uint64), ("dropped", C.c_uint64), ("rows", C.c_uint64)]
+
+
+class ClusterRow(C.Structure):
+    """sga_cluster_row: a cluster's seed (its lowest core index), size and box."""
+
+    _fields_ = [("seed", C.c_int64), ("size", C.c_int64), ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+
 FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
@@ -208,6 +232,12 @@ SYMBOLS = [
     ("sga_debug_places_add_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_places_query_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_places_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_index_radius_search", C.c_int, [_vp, _vp, _vp, C.c_double, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, C.POINTER(RadiusResult)]),
+    ("sga_cluster_params_default", None, [C.POINTER(ClusterParams)]),
+    ("sga_cloud_cluster", C.c_int, [_vp, _vp, _vp, C.POINTER(ClusterParams), C.POINTER(C.c_int32), C.POINTER(ClusterRow), C.c_size_t, C.POINTER(C.c_int64), C.POINTER(ClusterResult), _pvp]),
+    ("sga_debug_radius_search_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_cloud_cluster_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_radius_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),

@@ -349,6 +349,43 @@ class PointCloud:
             res.append({"stat": stat, "mean": st.mean, "stddev": st.stddev, "threshold": st.threshold, "kept": int(st.kept)})
         return res[0] if len(res) == 1 else tuple(res)
 
+    def clusters(self, radius, min_points=1, min_size=1, max_size=None, tree=None, keep=None, return_table=True, table_capacity=None):
+        """The objects of this cloud (sga_cloud_cluster): DBSCAN with a deterministic border rule.  A point with
+        at least min_points records within radius (itself included; d2 <= radius^2 in double) is a core point; core points within
+        radius of each other share a cluster; a non-core point joins the cluster of its nearest core point within radius (ties: the
+        lowest index) or is noise; clusters of fewer than min_size or more than max_size (None: no limit) members are dropped; the
+        kept ones are numbered in ascending order of their seed, the lowest index among their core points.  tree: the KdTree over this
+        cloud (None: a temporary one).  A cloud with a non-finite coordinate is refused: crop first.  Returns a dict: "labels" (numpy
+        int32, -1 for noise and dropped), "num_clusters", "noise", "dropped" and — with return_table — "seeds", "sizes" (int64) and
+        "boxes" ((C, 2, 3) float64: min and max corner, caller's frame) of the first table_capacity clusters (None: all of them, by a
+        second call when more than 1024 are found), and "cloud" — the clustered points or the others — when keep is "clustered" or
+        "rest" (this cloud's order, normals, covariances and origin), then also "kept" (numpy int64: their indices)."""
+        p = _cluster_params(radius, min_points, min_size, max_size, keep)
+        n = self.size()
+        cap = 0 if not return_table else (1024 if table_capacity is None else int(table_capacity))
+        lib = load()
+        while True:
+            labels = np.empty(n, np.int32)
+            rows = (_lib.ClusterRow * max(1, cap))()
+            kept = np.empty(n, np.int64) if p.keep != 0 else None
+            res = _lib.ClusterResult()
+            h = C.c_void_p()
+            check(lib.sga_cloud_cluster(self.ctx.h, self.h, None if tree is None else tree.h, C.byref(p), labels.ctypes.data_as(C.POINTER(C.c_int32)), rows if cap > 0 else None, cap,
+                                        None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(res), C.byref(h) if p.keep != 0 else None))
+            cloud = PointCloud(ctx=self.ctx, _handle=h) if p.keep != 0 else None
+            if return_table and table_capacity is None and res.clusters > res.rows:
+                cap = int(res.clusters)  # (the labels are a function of the records: the second call gives the same ones)
+                continue
+            break
+        out = {"labels": labels, "num_clusters": int(res.clusters), "noise": int(res.noise), "dropped": int(res.dropped)}
+        if return_table:
+            table = np.frombuffer(rows, dtype=CLUSTER_ROW_DTYPE, count=int(res.rows)) if res.rows else np.zeros(0, CLUSTER_ROW_DTYPE)
+            out["seeds"], out["sizes"] = table["seed"].copy(), table["size"].copy()
+            out["boxes"] = np.stack([table["lo"], table["hi"]], axis=1).astype(np.float64).reshape(-1, 2, 3)
+        if cloud is not None:
+            out["cloud"], out["kept"] = cloud, kept[: cloud.size()].copy()
+        return out
+
     def fpfh(self, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
         """One 33-bin Fast Point Feature Histogram per point, as Features on the device (sga_cloud_fpfh).  The
         cloud needs normals.  tree: the KdTree over this cloud (None: a temporary one is built).  k: neighbours per point, 2 .. 63.
@@ -595,6 +632,33 @@ class KdTree:
     def nearest_neighbor_search(self, pt):
         idx, d2 = self.knn_search(pt, 1)
         return (1 if idx[0] >= 0 else 0), int(idx[0]), float(d2[0])
+
+    def radius_search(self, queries, radius, return_lists=True, capacity=None):
+        """The points of the indexed cloud within radius of every query (sga_index_radius_search): record j is a
+        neighbour of query q iff d2(q, j) <= radius * radius, in double from the fp32 records.  queries: a PointCloud of the tree's
+        context (the indexed cloud itself is one) or an (M,3|4) array (uploaded first).  Returns counts (M,) int64 — and, with
+        return_lists, CSR lists: offsets (M + 1,) int64, indices (total,) int64 (positions in the indexed cloud) and sq_dists (total,)
+        float64, in the walk's order within a list.  capacity: the room of the lists in entries for the first call (None: the counts
+        are taken first); the call is repeated with room for the total when they do not fit."""
+        q = queries if isinstance(queries, PointCloud) else PointCloud(queries, ctx=self.ctx)
+        m = q.size()
+        _i64 = C.POINTER(C.c_int64)
+        counts = np.zeros(m, np.int64)
+        res = _lib.RadiusResult()
+        lib = load()
+        if not return_lists:
+            check(lib.sga_index_radius_search(self.ctx.h, self.h, q.h, float(radius), 0, counts.ctypes.data_as(_i64), None, None, None, C.byref(res)))
+            return counts
+        offsets = np.zeros(m + 1, np.int64)
+        if capacity is None:
+            check(lib.sga_index_radius_search(self.ctx.h, self.h, q.h, float(radius), 0, counts.ctypes.data_as(_i64), None, None, None, C.byref(res)))
+            capacity = int(res.total)
+        while True:
+            indices, sq = np.empty(max(1, int(capacity)), np.int64), np.empty(max(1, int(capacity)), np.float64)
+            check(lib.sga_index_radius_search(self.ctx.h, self.h, q.h, float(radius), int(capacity), counts.ctypes.data_as(_i64), offsets.ctypes.data_as(_i64), indices.ctypes.data_as(_i64), _dp(sq), C.byref(res)))
+            if not res.overflow:
+                return counts, offsets, indices[: int(res.total)].copy(), sq[: int(res.total)].copy()
+            capacity = int(res.total)
 
 
 class ProjectiveSearch:
@@ -2115,6 +2179,46 @@ def _launches(name):
     v = C.c_ulonglong()
     check(getattr(load(), name)(C.byref(v)))
     return v.value
+
+
+CLUSTER_ROW_DTYPE = np.dtype([("seed", np.int64), ("size", np.int64), ("lo", np.float64, (3,)), ("hi", np.float64, (3,))])  # sga_cluster_row
+_CLUSTER_KEEP = {None: 0, "clustered": 1, "rest": 2}
+
+
+def _cluster_params(radius=0.5, min_points=1, min_size=1, max_size=None, keep=None):
+    """The sga_cluster_params of PointCloud.clusters' arguments (one is passed through).  The library judges the values."""
+    if isinstance(radius, _lib.ClusterParams):
+        return radius
+    if keep not in _CLUSTER_KEEP:
+        raise ValueError('keep must be None, "clustered" or "rest"')
+    p = _lib.ClusterParams()
+    load().sga_cluster_params_default(C.byref(p))
+    p.radius, p.min_points, p.min_size, p.max_size, p.keep = float(radius), int(min_points), int(min_size), 0 if max_size is None else int(max_size), _CLUSTER_KEEP[keep]
+    return p
+
+
+def cluster_cloud(points, radius, min_points=1, min_size=1, max_size=None, tree=None, keep=None, return_table=True, table_capacity=None):
+    """PointCloud.clusters of a PointCloud or of an (N,3|4) array (uploaded first)."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    return cloud.clusters(radius, min_points, min_size, max_size, tree, keep, return_table, table_capacity)
+
+
+def cloud_cluster_launches():
+    """Diagnostics (sga_debug_cloud_cluster_launches): commands enqueued so far by PointCloud.clusters — six per call, eight with
+    min_points > 1, two more when a cloud is made; the build of a temporary tree is not counted."""
+    return _launches("sga_debug_cloud_cluster_launches")
+
+
+def radius_search_launches():
+    """Diagnostics (sga_debug_radius_search_launches): commands enqueued so far by KdTree.radius_search — two per call for the counts,
+    five with lists that fit."""
+    return _launches("sga_debug_radius_search_launches")
+
+
+def radius_waits():
+    """Diagnostics (sga_debug_radius_waits): host waits so far of PointCloud.clusters (one per call) and KdTree.radius_search (one; two
+    with lists)."""
+    return _launches("sga_debug_radius_waits")
 
 
 def cloud_fpfh_launches():

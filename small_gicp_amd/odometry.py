@@ -823,6 +823,45 @@ def _cpp_driver(source, workdir, num_frames):
     return exe, data
 
 
+def run_synthetic_movers(num_frames=8, radius=0.5, min_size=10, min_points=1, downsampling_resolution=0.25, ctx=None, **visibility):
+    """Where did the mover go?  At the generator's poses (no registration): keyframe f - 1 is the voxel grid of scan f - 1 with the
+    moving sphere (synthetic.with_moving_sphere at synthetic.mover_centre(f - 1)); raw scan f, with the sphere one step on, sees through
+    the points the sphere left behind (PointCloud.visibility(keep="seen_through")), and PointCloud.clusters groups them into objects
+    (DESIGN.md section 3.26).  Keyword arguments beyond the named ones go to visibility.  Returns one dict per frame f = 1 .. num_frames - 1:
+    "frame", "centre" (the sphere's true centre at f - 1 in the keyframe's frame), "seen_through" (the number of such points),
+    "detections" (a list of {"seed", "size", "box" (2,3)}), "labels" (of the seen-through points) and the objects behind them: "keyframe",
+    "scan", "T" (scan f into keyframe f - 1), "seen" (the seen-through cloud) and "kept" (its points' indices in the keyframe)."""
+    from . import synthetic
+
+    ctx = ctx or api.default_context()
+    out = []
+    prev = None
+    for f in range(num_frames):
+        pts, Tws = synthetic.kitti_like_scan(f)
+        pts, _ = synthetic.with_moving_sphere(pts, Tws, synthetic.mover_centre(f))
+        scan = api.PointCloud(pts, ctx=ctx)
+        if prev is not None:
+            key, Tkey = prev
+            T = np.linalg.inv(Tkey) @ Tws
+            _, seen, kept = key.visibility(scan, T, keep="seen_through", return_kept=True, **visibility)
+            found = seen.clusters(radius, min_points=min_points, min_size=min_size)
+            Ti = np.linalg.inv(Tkey)
+            out.append({
+                "frame": f,
+                "centre": Ti[:3, :3] @ synthetic.mover_centre(f - 1) + Ti[:3, 3],
+                "seen_through": seen.size(),
+                "detections": [{"seed": int(s), "size": int(n), "box": b} for s, n, b in zip(found["seeds"], found["sizes"], found["boxes"])],
+                "labels": found["labels"],
+                "keyframe": key,
+                "scan": scan,
+                "T": T,
+                "seen": seen,
+                "kept": kept,
+            })
+        prev = (api.voxelgrid_sampling(scan, downsampling_resolution), Tws)
+    return out
+
+
 def _read_trajectory(path):
     poses = []
     for ln in open(path):
