@@ -795,8 +795,8 @@ int sga_problem_set_rejector(sga_problem* problem, sga_rejector_fn fn, void* use
 /* Factor::linearize per source point, as the reference's Python binding exposes it (src/python/factors.cpp:52-101; gicp_factor.hpp:35-73,
  * icp_factor.hpp:20-54, plane_icp_factor.hpp:19-57): runs one linearization at T, then returns for every source point (caller's order)
  * values28 n*28 doubles = [0..20] upper triangle of H_i row-wise, [21..26] b_i, [27] e_i, and inlier n bytes (0: no correspondence, all
- * values 0).  kd-tree targets, and flat voxel maps (the correspondences of that linearization); per-pair arithmetic in fp64.  A diagnostic /
- * binding entry point, not the hot path. */
+ * values 0).  kd-tree targets and flat voxel maps; the pairs are the correspondences of that linearization (sga_problem_get_factors
+ * afterwards), a host rejector's verdicts included; per-pair arithmetic in fp64.  A diagnostic / binding entry point, not the hot path. */
 int sga_linearize_per_point(sga_context* ctx, sga_problem* problem, const sga_factor_params* params, const double T[16], double* values28, unsigned char* inlier);
 /* Factor state in the caller's source order: target_index n int64 (-1 = outlier; voxel id for voxel maps), mahalanobis6 n*6 floats (GICP only). */
 int sga_problem_get_factors(sga_context* ctx, const sga_problem* problem, int64_t* target_index, float* mahalanobis6);

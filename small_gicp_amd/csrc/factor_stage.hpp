@@ -25,14 +25,11 @@ __device__ __forceinline__ bool pair_moments(const LinParams<Real>& p, int i, in
 template <typename Real, int PTS>
 __device__ __forceinline__ void accumulate_moments(const Real (&P)[PTS][3], const Sym3<Real> (&Mp)[PTS], const Real (&G)[PTS][3], const Real (&E)[PTS], int inliers, double* __restrict__ acc_row, int lane);
 
-// One correspondence (source point i at q = T p, target candidate j at t): rejector, fused mahalanobis, robust weight, the 28
-// values of the pair's system.  Returns whether the pair is an inlier; caches the mahalanobis (GICP).
+// One correspondence the pass has kept (source point i, its target j or -1, the residual r = t_j - T p_i): fused mahalanobis, robust
+// weight, the 28 values of the pair's system.  Returns whether there is a pair; caches the mahalanobis (GICP).
 template <typename Real, int FACTOR>
-__device__ __forceinline__ bool pair_factor(const LinParams<Real>& p, int i, int j, bool within_bound, Real px, Real py, Real pz, Real qx, Real qy, Real qz, Real tx, Real ty, Real tz, Real* vals, Sym3<Real>* Mp_out = nullptr,
-                                            Real* g_out = nullptr) {
-  const Real rx = tx - qx, ry = ty - qy, rz = tz - qz;
-  const Real d2 = rx * rx + ry * ry + rz * rz;
-  const bool inlier = (j >= 0) && within_bound && !(d2 > p.max_sq);
+__device__ __forceinline__ bool pair_factor(const LinParams<Real>& p, int i, int j, Real px, Real py, Real pz, Real rx, Real ry, Real rz, Real* vals, Sym3<Real>* Mp_out = nullptr, Real* g_out = nullptr) {
+  const bool inlier = j >= 0;
   if (inlier) {
     Sym3<Real> M;
     if constexpr (FACTOR == SGA_GICP) {

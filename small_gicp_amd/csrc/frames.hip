@@ -37,11 +37,11 @@ void system_to_caller(const double o[3], double H[36], double b[6]) {
       HA[i][j] = v;
     }
   for (int i = 0; i < 6; i++)
-    for (int j = 0; j < 6; j++) {
+    for (int j = i; j < 6; j++) {  // the upper triangle, mirrored as frame_accumulator_kernel does: the two roundings of an entry pair would differ
       double v = HA[i][j];
       if (i < 3)
         for (int k = 0; k < 3; k++) v += X[k][i] * HA[3 + k][j];  // (A^T)[i][3 + k] = X[k][i]
-      H[6 * i + j] = v;
+      H[6 * i + j] = H[6 * j + i] = v;
     }
   for (int i = 0; i < 3; i++)
     for (int k = 0; k < 3; k++) b[i] += X[k][i] * b[3 + k];

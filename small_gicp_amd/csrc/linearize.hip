@@ -672,30 +672,54 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ba
 }
 
 // Per-point export of the same factors (the reference's Python binding exposes Factor::linearize per source point,
-// src/python/factors.cpp:52-101): the 28 values of every pair instead of their sum.  Runs after a linearize pass at the same pose
-// (kd-tree: the neighbours come from hint[]; flat map, FLAT: the correspondences that pass kept in corr[], slot or -1); not on the hot path.
-template <typename Real, int FACTOR, bool FLAT = false>
+// src/python/factors.cpp:52-101): the 28 values of every pair instead of their sum.  Runs after a linearize pass at the same pose over
+// the correspondences that pass kept in corr[] (kd position or flat-map slot, -1 = none): the pass has decided every pair — the double
+// re-decision between the walk's two candidates, the rejector's distance test or the host rejector's verdicts — so the export neither
+// searches nor rejects again, and the matrix pair_factor caches is the pass's own.  Not on the hot path.
+//
+// The residual is formed without the rounding of q = R p + t: a point that lies ON its target's plane has |n . r| of 1e-5 m where q, 50 m
+// from the origin, is rounded by 1e-14 m — 1e-9 of the point-to-plane b_i and e_i.  t_j - t - sum R_ak p_k is accumulated as hi + lo with
+// error-free products (fma) and sums, so r carries the rounding of its own size only.
+__device__ __forceinline__ void exact_add(double& hi, double& lo, double x) {  // hi + lo + x, hi + x exactly (Knuth's two-sum)
+  const double s = hi + x, b = s - hi;
+  lo += (hi - (s - b)) + (x - b);
+  hi = s;
+}
+__device__ __forceinline__ double exact_residual(double tj, double t, double r0, double r1, double r2, double x, double y, double z) {
+  double hi = tj, lo = 0.0;
+  exact_add(hi, lo, -t);
+  const double a[3] = {-r0, -r1, -r2}, v[3] = {x, y, z};
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double prod = a[k] * v[k];
+    // the rounded product as a value of its own: built with -ffp-contract=fast, the compiler would otherwise fuse it into the sum that
+    // follows, which then no longer adds the product whose rounding lo holds
+    asm volatile("" : "+v"(prod));
+    lo += fma(a[k], v[k], -prod);  // the product's own rounding
+    exact_add(hi, lo, prod);
+  }
+  return hi + lo;
+}
+template <typename Real, int FACTOR>
 __global__ __launch_bounds__(256) void per_point_kernel(const LinParams<Real> p, double* __restrict__ out28, unsigned char* __restrict__ ok) {
+  static_assert(sizeof(Real) == 8, "the export is double");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
   const float4 ps4 = p.src_pts[i];
   const Real px = ps4.x, py = ps4.y, pz = ps4.z;
-  Real qx, qy, qz;
-  transform_point(p.T, px, py, pz, qx, qy, qz);
   Real vals[28];
 #pragma unroll
   for (int k = 0; k < 28; k++) vals[k] = Real(0);
-  const int j = FLAT ? p.corr[i] : p.hint[i];
-  Real tx = 0, ty = 0, tz = 0;
-  bool within = false;
+  const int j = p.corr[i];
+  Real rx = 0, ry = 0, rz = 0;
   if (j >= 0) {
     const float4 m = p.tgt_pts[j];
-    tx = m.x;
-    ty = m.y;
-    tz = m.z;
-    within = FLAT || kd_dist2(m.x, m.y, m.z, static_cast<float>(qx), static_cast<float>(qy), static_cast<float>(qz)) < p.bound2;
+    const Real* R = p.T.r;
+    rx = exact_residual(m.x, p.T.t[0], R[0], R[1], R[2], px, py, pz);
+    ry = exact_residual(m.y, p.T.t[1], R[3], R[4], R[5], px, py, pz);
+    rz = exact_residual(m.z, p.T.t[2], R[6], R[7], R[8], px, py, pz);
   }
-  const bool inlier = pair_factor<Real, FACTOR>(p, i, j, within, px, py, pz, qx, qy, qz, tx, ty, tz, vals);
+  const bool inlier = pair_factor<Real, FACTOR>(p, i, j, px, py, pz, rx, ry, rz, vals);
   const uint32_t orig = __float_as_uint(ps4.w);  // the caller's source order
   ok[orig] = inlier ? 1 : 0;
 #pragma unroll
@@ -1462,18 +1486,13 @@ int sga_linearize_per_point(sga_context* ctx, sga_problem* pb, const sga_factor_
   const size_t n = pb->n;
   if (n == 0) return SGA_OK;
   double Td[16];
-  const LinParams<double> p = factor_params<double>(pb, fp, problem_pose(pb, T, Td), false);
+  const LinParams<double> p = factor_params<double>(pb, fp, problem_pose(pb, T, Td), false);  // (the export reads corr[]: the verdicts of the pass above, no test of its own)
   DevBuf<double> d_vals;
   DevBuf<unsigned char> d_ok;
   SGA_TRY(d_vals.alloc(n * 28));
   SGA_TRY(d_ok.alloc(n));
   const dim3 grid((n + 255) / 256), block(256);
-  with_factor(fp->factor_kind, [&](auto f) {
-    if (flat)
-      hipLaunchKernelGGL((per_point_kernel<double, decltype(f)::value, true>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p);
-    else
-      hipLaunchKernelGGL((per_point_kernel<double, decltype(f)::value>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p);
-  });
+  with_factor(fp->factor_kind, [&](auto f) { hipLaunchKernelGGL((per_point_kernel<double, decltype(f)::value>), grid, block, 0, ctx->stream, p, d_vals.p, d_ok.p); });
   SGA_HIP(hipGetLastError());
   SGA_HIP(hipMemcpyAsync(values28, d_vals.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   SGA_HIP(hipMemcpyAsync(inlier, d_ok.p, n, hipMemcpyDeviceToHost, ctx->stream));

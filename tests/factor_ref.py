@@ -14,6 +14,9 @@ is accumulated in float64 from the fp32 values the device stores.  Written from 
   error      factors/*_factor.hpp error(): the stale correspondence (and GICP's stale mahalanobis) at a trial pose, robustified as
              robust_kernel.hpp:95-97; summed as registration/reduction_omp.hpp:62-67 does.
 
+per_pair() is linearize() before its sum — H_i, b_i, e_i and M_i of every pair, with the magnitudes that bound their rounding — for the
+outputs a pass leaves per pair (tests/test_pass_outputs_gpu.py); tests/test_factor_ref.py holds its sums to linearize().
+
 Kinds and robust kinds use the C-ABI numbering: ICP 0, PLANE_ICP 1, GICP 2; none 0, Huber 1, Cauchy 2.
 """
 import numpy as np
@@ -113,6 +116,44 @@ def linearize(src, tgt, corr, T, kind, robust=ROBUST_NONE, c=1.0, src_cov=None, 
         e += float((w * ei).sum())
     H = np.triu(H) + np.triu(H, 1).T  # one value per entry pair, as the engine's 21-value upper triangle
     return Sums(H, b, e, len(inl), maha)
+
+
+class Pairs:
+    """What per_pair returns, one row per pair (i, corr[i]) with corr[i] >= 0, in the order of idx (the source indices): H (m, 6, 6),
+    b (m, 6), e (m,) with the robust weight applied, M (m, 3, 3) the factor's own matrix (no weight), and the magnitudes
+    Hmag = w |J|^T |M| |J| and bmag = w |J|^T |M| |r|, which bound what rounding each product once can do to H and b."""
+
+    def __init__(self, idx, H, b, e, M, Hmag, bmag):
+        self.idx, self.H, self.b, self.e, self.M, self.Hmag, self.bmag = idx, H, b, e, M, Hmag, bmag
+
+
+def per_pair(src, tgt, corr, T, kind, robust=ROBUST_NONE, c=1.0, src_cov=None, tgt_cov=None, tgt_nrm=None):
+    """linearize() before its sum: the system of every pair (i, corr[i]) with corr[i] >= 0 at pose T, in float64, by the formulas of the
+    header (H_i = w J^T M J, b_i = w J^T M r, e_i = w 1/2 r^T M r, w the robust weight at sqrt(1/2 r^T M r))."""
+    T = np.asarray(T, dtype=np.float64)
+    R = T[:3, :3]
+    corr = np.asarray(corr)
+    src, tgt = np.asarray(src, dtype=np.float64), np.asarray(tgt, dtype=np.float64)
+    si = np.flatnonzero(corr >= 0)
+    ti = corr[si]
+    p = src[si][:, :3]
+    # the residual alone is formed in extended precision (64-bit mantissa where numpy has it) and then rounded: in float64 the rounding of
+    # q = R p + t, 1e-14 m at 50 m, is 1e-9 of a point-to-plane residual of 1e-5 m, ten times the bound this restatement is used with
+    L = np.longdouble
+    r = (tgt[ti][:, :3].astype(L) - ((p.astype(L)[:, None, :] * R.astype(L)[None]).sum(2) + T[:3, 3].astype(L))).astype(np.float64)
+    M = np.array(mahalanobis(kind, T, src_cov, tgt_cov, tgt_nrm, si, ti))
+    J = np.zeros((len(si), 3, 6))
+    J[:, :, :3] = R[None] @ skew(p)
+    J[:, :, 3:] = -R[None]
+    Mr = np.einsum("nij,nj->ni", M, r)
+    e0 = 0.5 * np.einsum("ni,ni->n", r, Mr)
+    w = robust_weight(robust, c, e0)
+    H = w[:, None, None] * np.einsum("nki,nkl,nlj->nij", J, M, J)
+    b = w[:, None] * np.einsum("nki,nk->ni", J, Mr)
+    aJ, aM = np.abs(J), np.abs(M)
+    Hmag = w[:, None, None] * np.einsum("nki,nkl,nlj->nij", aJ, aM, aJ)
+    bmag = w[:, None] * np.einsum("nki,nkl,nl->ni", aJ, aM, np.abs(r))
+    return Pairs(si, H, b, w * e0, M, Hmag, bmag)
 
 
 def error(src, tgt, corr, T, kind, robust=ROBUST_NONE, c=1.0, maha=None, tgt_nrm=None):

@@ -60,6 +60,32 @@ def test_factor_ref_matches_oracle_c1(orc, c1_f32, kind, robust):
             assert abs(eq - eoq) <= 1e-12 * abs(eoq), (k, eq, eoq)
 
 
+@pytest.mark.parametrize("robust", [fr.ROBUST_NONE, fr.ROBUST_HUBER, fr.ROBUST_CAUCHY])
+@pytest.mark.parametrize("kind", [fr.ICP, fr.PLANE_ICP, fr.GICP])
+def test_per_pair_sums_to_linearize_c1(orc, c1_f32, kind, robust):
+    """per_pair (the restatement the per-pair outputs of a pass are measured against) summed over its pairs is linearize — both float64,
+    in another order — so the pins of linearize to the oracle above hold it too; its M is the matrix linearize caches."""
+    d = c1_f32
+    otc, osc = d["otc"], d["osc"]
+    st = orc.default_setting(factor_kind=kind, robust_kind=robust, robust_c=C, num_threads=4)
+    for k, P in enumerate(POSES):
+        T = pose(P)
+        f = orc.Factors(len(osc))
+        orc.linearize(otc, osc, st, T, f)
+        ti, _ = f.get()
+        s = fr.linearize(d["sp"], d["tp"], ti, T, kind, robust, C, d["sc"], d["tc"], d["tn"])
+        pp = fr.per_pair(d["sp"], d["tp"], ti, T, kind, robust, C, d["sc"], d["tc"], d["tn"])
+        assert np.array_equal(pp.idx, np.flatnonzero(ti >= 0)) and len(pp.idx) == s.inliers > 1000
+        assert pp.H.shape == (s.inliers, 6, 6) and pp.b.shape == (s.inliers, 6) and pp.e.shape == (s.inliers,) and pp.M.shape == (s.inliers, 3, 3)
+        H = pp.H.sum(0)
+        assert rel(H, s.H) <= 1e-13 and rel(pp.b.sum(0), s.b) <= 1e-13 and abs(pp.e.sum() - s.e) <= 1e-13 * abs(s.e), (k, rel(H, s.H), rel(pp.b.sum(0), s.b), pp.e.sum(), s.e)
+        assert np.abs(pp.H - pp.H.transpose(0, 2, 1)).max() <= 1e-13 * np.abs(pp.H).max()
+        if kind == fr.GICP:
+            assert np.array_equal(pp.M, s.maha[pp.idx])
+        # the magnitudes dominate what they bound, entry by entry
+        assert (np.abs(pp.H) <= pp.Hmag * (1 + 1e-12)).all() and (np.abs(pp.b) <= pp.bmag * (1 + 1e-12)).all() and (pp.e >= 0).all()
+
+
 def test_factor_ref_rejector_is_strict():
     """A pair exactly at max_dist_sq is kept (rejector.hpp:24: reject iff sq_dist > max_dist_sq); sq_dist is float64 from fp32 points."""
     tgt = np.zeros((1, 3), np.float32)

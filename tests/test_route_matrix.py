@@ -475,7 +475,7 @@ def test_fp64_rejector_threshold_is_double():
     assert (ok32[clear] == inl_ref[clear]).all() and n32 == ok32.sum()
     # a posed case: T s is no longer exact in fp32, so the walks measure from a query up to 2^-24 |q| per axis away from the double one
     # the factor kernel tests (40 m: ~1e-6 m, 5e-5 of d2 at d = 0.1 m — far beyond the fp32 nudge).  The routes re-decide the pair in
-    # double; the per-point export (sga_linearize_per_point, fp64) tests the search's own reach, widened by the query's rounding.
+    # double; the per-point export (sga_linearize_per_point) reports the pairs of its own fp64 pass.
     Tp, tp2, sp2, d2p = posed_edge_pairs()
     inl_p = d2p <= 0.01
     assert 0 < inl_p.sum() < len(d2p)
