@@ -503,6 +503,61 @@ typedef struct sga_cluster_row {
 void sga_cluster_params_default(sga_cluster_params* p); /* radius 0.5, min_points 1, keep 0, min_size 1, max_size 0 */
 int sga_cloud_cluster(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_cluster_params* params, int32_t* labels /* n, or NULL */,
                       sga_cluster_row* table /* table_capacity, or NULL */, size_t table_capacity, int64_t* kept /* n, or NULL */, sga_cluster_result* result /* or NULL */, sga_cloud** out /* NULL iff keep == 0 */);
+/* Plane segmentation on the device: sga_cloud_segment_plane — the plane with the most points within
+ * distance_threshold among `iterations` hypotheses, each through three records, refitted to its inliers.  THE RULE is a function of the
+ * records, the parameters and the seed alone.  All arithmetic is in double on the cloud's fp32 records in the cloud's own frame, as
+ * differences from a record; r_i is record i as doubles.  The origin enters on the host alone, when the plane is reported.
+ *   hypothesis h  id = the draw of sga_ransac_correspondences (seed, h, n); a, b, c = r_id[0], r_id[1], r_id[2]; u = b - a, v = c - a,
+ *                 m = u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx), |w| = sqrt((wx wx + wy wy) + wz wz).  Dropped when
+ *                 !(|m| > 0) (a triple with a NaN drops out here), when |m| < 1e-9 |u| |v|, or when !(|m| < infinity) (a triple
+ *                 with an infinite coordinate).  nhat = m / |m|.  With an axis: s = (nhat_x axis_x + nhat_y axis_y) + nhat_z axis_z; s < 0
+ *                 flips nhat and s; dropped unless s / |axis| >= cos(max_angle).  Without: nhat is flipped so that the first non-zero
+ *                 of (nhat_z, nhat_y, nhat_x) is positive.
+ *   score         the number of records i with |dist_i| <= distance_threshold, dist_i = (nhat_x dx + nhat_y dy) + nhat_z dz, (dx, dy,
+ *                 dz) = r_i - a.  (The device contracts products into the sums, fused multiply-adds, in ONE function that every kernel
+ *                 calls.)  A record with a non-finite coordinate is never an inlier: the comparison is false.
+ *   best          the greatest score, ties to the lowest h.  scores[h] (room for `iterations`, or NULL): the score, 0xFFFFFFFF for a
+ *                 dropped hypothesis.  Nothing scored, or a best score below min_inliers: SGA_OK, result->inliers 0, a zero plane, *out
+ *                 an empty cloud (keep 1) or the whole cloud (keep 2).
+ *   refit         (refit 1) over the best hypothesis' inliers, x = r_i - a: k, sum x and sum x x^T; c = a + sum x / k, S = sum x x^T -
+ *                 (sum x)(sum x)^T / k; the normal is the unit eigenvector of S's smallest eigenvalue (Jacobi), oriented as above.  The
+ *                 triple's plane stays, result->refit 0, when k < 3, when lambda_1 - lambda_0 <= 1e-12 lambda_2, or when the refitted
+ *                 normal violates the axis constraint.  Sums over points: lane t of workgroup g of G adds the records 256 g + t +
+ *                 256 G j, j = 0, 1, ..., in that order; the 256 lanes of a workgroup meet in a binary tree (t += t + 128, 64, ...,
+ *                 1); the host adds the workgroups' partials g = 0 .. G - 1 in order, G = min(256, ceil(n / 1024)).
+ *   final         the FINAL inliers are the records within distance_threshold of the final plane about its anchor (c, or a).
+ *                 plane = (n, d) with n . p + d = 0 in the caller's frame, d = -((n_x (anchor_x + origin_x) + n_y (..)) + n_z (..)).
+ *                 result: inliers (final), rmse (sqrt of the mean squared distance of the final inliers, summed as above),
+ *                 hypothesis_inliers, best_hypothesis, scored (hypotheses not dropped), refit.
+ * keep 1 / 2: *out is the cloud of the final inliers / of all the other records (those with a non-finite coordinate among them),
+ * compacted as sga_cloud_crop does (order, normals, covariances, origin kept; kept, or NULL, room for n: their indices); keep 0: out and
+ * kept must be NULL.  n < 3: SGA_OK, nothing scored, none of the routine's kernels launched.  Host waits: one behind the sums, one at
+ * the end when a refit or a cloud follows.  Refusals (SGA_ERR_INVALID) — before any handle is read, *out = NULL: NULL ctx, cloud, params,
+ * plane or result; a distance_threshold that is not finite and > 0; iterations outside [1, 2^20]; a non-finite axis; max_angle outside
+ * [0, pi/2], or 0 with a non-zero axis; min_inliers < 3; refit outside {0, 1}; keep outside [0, 2] or at odds with out / kept — then:
+ * another device, 2^31 points or more. */
+typedef struct sga_plane_params {
+  double distance_threshold; /* finite, > 0 */
+  uint64_t iterations;       /* hypotheses, 1 .. 2^20 (the hypothesis table is device memory) */
+  uint64_t seed;
+  double axis[3];            /* 0 0 0: no constraint */
+  double max_angle;          /* radians, (0, pi/2], with an axis */
+  uint64_t min_inliers;      /* >= 3 */
+  int refit;                 /* 0 or 1 */
+  int keep;                  /* 0 no cloud, 1 the plane's points, 2 the rest */
+} sga_plane_params; /* 72 bytes */
+typedef struct sga_plane_result {
+  uint64_t inliers;            /* of the final plane */
+  double rmse;                 /* over them */
+  uint64_t hypothesis_inliers; /* the best hypothesis' score */
+  uint64_t best_hypothesis;
+  uint64_t scored;             /* hypotheses that were not dropped */
+  int refit;                   /* 1: the final plane is the refitted one */
+  int reserved;
+} sga_plane_result; /* 48 bytes */
+void sga_plane_default(sga_plane_params* p); /* distance_threshold 0.1, iterations 1000, seed 0, no axis, min_inliers 3, refit 1, keep 0 */
+int sga_cloud_segment_plane(sga_context* ctx, const sga_cloud* cloud, const sga_plane_params* params, double plane[4], uint32_t* scores /* iterations, or NULL */, int64_t* kept /* n, or NULL */,
+                            sga_cloud** out /* NULL iff keep == 0 */, sga_plane_result* result);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

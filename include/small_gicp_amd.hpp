@@ -155,6 +155,39 @@ struct Clusters {
   std::shared_ptr<PointCloud> cloud;
   std::vector<int64_t> kept;
 };
+/// What PointCloud::segment_plane asks for (sga_plane_params with its defaults: threshold 0.1, 1000 hypotheses, seed 0, no axis, at least
+/// 3 inliers, refit, no cloud): RANSAC over triples of records (small_gicp_amd.h).  keep says which points the output cloud holds.
+struct PlaneParams : sga_plane_params {
+  enum Keep { None = 0, Plane = 1, Rest = 2 };
+  PlaneParams() { sga_plane_default(this); }
+  explicit PlaneParams(double distance_threshold_, uint64_t iterations_ = 1000, uint64_t seed_ = 0, Keep keep_ = None) {
+    sga_plane_default(this);
+    distance_threshold = distance_threshold_, iterations = iterations_, seed = seed_, keep = static_cast<int>(keep_);
+  }
+  /// only planes whose normal lies within max_angle_ (radians) of +-axis, the normal turned towards the axis
+  PlaneParams& along(double x, double y, double z, double max_angle_) {
+    axis[0] = x, axis[1] = y, axis[2] = z, max_angle = max_angle_;
+    return *this;
+  }
+};
+/// What PointCloud::segment_plane found: coefficients = (n, d) with n . p + d = 0 in the caller's frame (zeros and result.inliers 0: no
+/// plane), the counts, the score of every hypothesis when asked for, and the cloud of the plane's or of the other points with their indices.
+struct Plane {
+  std::array<double, 4> coefficients{};
+  sga_plane_result result{};
+  std::vector<uint32_t> scores;
+  std::shared_ptr<PointCloud> cloud;
+  std::vector<int64_t> kept;
+  bool found() const { return result.inliers > 0; }
+};
+/// What segment_planes found: the planes in the order found, a label per point of the original cloud (the plane's number, -1 for none),
+/// the cloud left over and its points' indices in the original cloud.
+struct Planes {
+  std::vector<Plane> planes;
+  std::vector<int32_t> labels;
+  std::shared_ptr<PointCloud> rest;
+  std::vector<int64_t> rest_indices;
+};
 /// What KdTree::radius_search found: the number of neighbours per query and, when asked for, their CSR lists.
 struct RadiusNeighbors {
   std::vector<int64_t> counts, offsets, indices;
@@ -431,6 +464,21 @@ struct PointCloud {
     }
     return r;
   }
+  /// The dominant plane of this cloud (sga_cloud_segment_plane): a function of the records, the parameters and the seed alone.
+  /// with_scores: also the score of every hypothesis (0xFFFFFFFF: dropped); with a keep other than None the cloud and its indices.
+  Plane segment_plane(const PlaneParams& params = PlaneParams(), bool with_scores = false) const {
+    Plane r;
+    if (with_scores) r.scores.resize(params.iterations >= 1 && params.iterations <= (1ull << 20) ? static_cast<size_t>(params.iterations) : 1);
+    if (params.keep != 0) r.kept.resize(size());
+    sga_cloud* made = nullptr;
+    check(sga_cloud_segment_plane(ctx, h, &params, r.coefficients.data(), r.scores.empty() ? nullptr : r.scores.data(), r.kept.empty() ? nullptr : r.kept.data(), params.keep != 0 ? &made : nullptr, &r.result),
+          "sga_cloud_segment_plane");
+    if (params.keep != 0) {
+      r.cloud = std::make_shared<PointCloud>(made, ctx);
+      r.kept.resize(r.cloud->size());
+    }
+    return r;
+  }
   /// One 33-bin Fast Point Feature Histogram per point (sga_cloud_fpfh); the cloud needs normals.  kdtree: the handle of the KdTree over
   /// this cloud, or null: a temporary one is built.  viewpoint (optional, the caller's frame): the normals are turned towards it for
   /// the descriptor; nothing is written back.
@@ -585,6 +633,39 @@ inline RansacResult ransac_correspondences(const PointCloud& source, const Point
   RansacResult r;
   check(sga_ransac_correspondences(source.ctx, source.h, target.h, pairs.empty() ? nullptr : pairs.data()->data(), pairs.size(), &params, r.T_target_source.m.data(), &r), "sga_ransac_correspondences");
   return r;
+}
+
+/// Up to max_planes planes of a cloud, one after the other (a host loop over PointCloud::segment_plane): round r runs with seed + r and
+/// keep Rest on what round r - 1 left, and stops at the first round that finds fewer than min_inliers points.
+inline Planes segment_planes(const std::shared_ptr<const PointCloud>& cloud, size_t max_planes, PlaneParams params = PlaneParams()) {
+  Planes out;
+  const size_t n = cloud->size();
+  out.labels.assign(n, -1);
+  out.rest_indices.resize(n);
+  for (size_t i = 0; i < n; i++) out.rest_indices[i] = static_cast<int64_t>(i);
+  std::shared_ptr<const PointCloud> rest = cloud;
+  params.keep = PlaneParams::Rest;
+  const uint64_t seed = params.seed;
+  for (size_t r = 0; r < max_planes; r++) {
+    params.seed = seed + r;
+    Plane p = rest->segment_plane(params);
+    if (p.result.inliers < params.min_inliers) break;
+    std::vector<int64_t> index(p.kept.size());
+    size_t k = 0;
+    for (size_t i = 0; i < out.rest_indices.size(); i++) {
+      if (k < p.kept.size() && p.kept[k] == static_cast<int64_t>(i))
+        index[k++] = out.rest_indices[i];
+      else
+        out.labels[static_cast<size_t>(out.rest_indices[i])] = static_cast<int32_t>(r);
+    }
+    out.rest_indices.swap(index);
+    rest = p.cloud;
+    p.cloud.reset();
+    p.kept.clear();
+    out.planes.push_back(std::move(p));
+  }
+  out.rest = std::const_pointer_cast<PointCloud>(rest);
+  return out;
 }
 
 /// kNN for m queries in device memory against a kd-tree, a Gaussian or a flat voxel map (sga_index_knn_device): d_idx m*k int64 and

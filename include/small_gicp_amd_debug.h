@@ -141,6 +141,19 @@ int sga_debug_places_waits(unsigned long long* waits);
 int sga_debug_radius_search_launches(unsigned long long* launches);
 int sga_debug_cloud_cluster_launches(unsigned long long* launches);
 int sga_debug_radius_waits(unsigned long long* waits);
+/* Commands enqueued so far, in this process, by sga_cloud_segment_plane (small_gicp_amd.h): the hypotheses, the
+ * scores, the selection and the sums — four — plus the flags when the refit succeeded or a cloud is made — five — plus the compaction's
+ * table copy and the compaction when a cloud is made — seven.  Nothing for n < 3 but the compaction's two with keep 2 and n >= 1.  waits:
+ * its host waits — one behind the sums, a second one (the compaction's, or a synchronisation) whenever the flags kernel ran; when no
+ * plane is found, the one behind the sums and the compaction's with keep 2. */
+int sga_debug_segment_plane_launches(unsigned long long* launches);
+int sga_debug_segment_plane_waits(unsigned long long* waits);
+/* The host arithmetic of sga_cloud_segment_plane's refit, exposed so that it can be tested without a device: from k, sum x and sum x x^T
+ * (sum_xx6 = xx, xy, xz, yy, yz, zz) of the inliers' differences x from an anchor: centroid_offset = sum x / k, eigenvalues (ascending)
+ * of S = sum x x^T - (sum x)(sum x)^T / k, and normal = the unit eigenvector of the smallest, with the first non-zero of (z, y, x)
+ * positive.  Returns 1, or 0 when there is no refit: k < 3, a non-finite sum, or lambda_1 - lambda_0 <= 1e-12 lambda_2 (then normal is
+ * untouched; centroid_offset and eigenvalues are written when k >= 1 and the sums are finite). */
+int sga_debug_plane_from_sums(uint64_t k, const double sum_x[3], const double sum_xx6[6], double normal[3], double centroid_offset[3], double eigenvalues[3]);
 /* The host arithmetic of sga_ransac_correspondences, exposed so that it can be tested without a device.  draw: the three distinct pair
  * numbers hypothesis h draws from M >= 3 pairs under `seed` (SGA_ERR_INVALID for M < 3 or M >= 2^31).  rigid_from_sums: the least-squares
  * rigid motion of n point pairs from their plain sums — sum_s = sum p_s, sum_t = sum p_t, cross[3 r + c] = sum p_s[r] p_t[c] — by Horn's

@@ -162,6 +162,20 @@ class ClusterRow(C.Structure):
     _fields_ = [("seed", C.c_int64), ("size", C.c_int64), ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
 
 
+class PlaneParams(C.Structure):
+    """sga_plane_params: distance_threshold, iterations (1 .. 2^20), seed, axis (zeros: none), max_angle, min_inliers, refit 0 | 1,
+    keep 0 none | 1 the plane's points | 2 the rest."""
+
+    _fields_ = [("distance_threshold", C.c_double), ("iterations", C.c_uint64), ("seed", C.c_uint64), ("axis", C.c_double * 3), ("max_angle", C.c_double), ("min_inliers", C.c_uint64),
+                ("refit", C.c_int), ("keep", C.c_int)]
+
+
+class PlaneResult(C.Structure):
+    """sga_plane_result: the final plane's inliers and their rmse, the best hypothesis' score and number, the hypotheses scored, refit 0 | 1."""
+
+    _fields_ = [("inliers", C.c_uint64), ("rmse", C.c_double), ("hypothesis_inliers", C.c_uint64), ("best_hypothesis", C.c_uint64), ("scored", C.c_uint64), ("refit", C.c_int), ("reserved", C.c_int)]
+
+
 FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
@@ -238,6 +252,11 @@ SYMBOLS = [
     ("sga_debug_radius_search_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_cluster_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_radius_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_plane_default", None, [C.POINTER(PlaneParams)]),
+    ("sga_cloud_segment_plane", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), _pvp, C.POINTER(PlaneResult)]),
+    ("sga_debug_segment_plane_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_segment_plane_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_plane_from_sums", C.c_int, [C.c_uint64, _dp, _dp, _dp, _dp, _dp]),
     ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),

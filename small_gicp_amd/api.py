@@ -386,6 +386,36 @@ class PointCloud:
             out["cloud"], out["kept"] = cloud, kept[: cloud.size()].copy()
         return out
 
+    def segment_plane(self, distance_threshold=0.1, iterations=1000, seed=0, axis=None, max_angle=0.0, min_inliers=3, refit=True, keep=None, return_kept=False, return_scores=False):
+        """The dominant plane of this cloud (sga_cloud_segment_plane): RANSAC over `iterations` triples drawn by
+        the counter-based generator under `seed`, scored by the records within distance_threshold, the best one refitted to its inliers
+        (refit).  axis, max_angle: only planes whose normal lies within max_angle (radians) of +-axis are considered, and the normal
+        is turned towards the axis; without an axis the normal's first non-zero of (z, y, x) is positive.  A plane is reported only
+        with at least min_inliers points on the best hypothesis.  The result is a function of the records, the arguments and the seed
+        alone.  Returns a dict: "plane" ((4,) float64: n and d with n . p + d = 0 in the caller's frame; zeros when none is found),
+        "inliers", "rmse", "hypothesis_inliers", "best_hypothesis", "scored", "refit"; with keep "plane" or "rest" also "cloud" — the
+        plane's points or all the others, records with a non-finite coordinate among the others (this cloud's order, normals,
+        covariances and origin) — and, with return_kept, "kept" (numpy int64: their indices); with return_scores "scores" (numpy
+        uint32 per hypothesis, 0xFFFFFFFF for a dropped one)."""
+        p = _plane_params(distance_threshold, iterations, seed, axis, max_angle, min_inliers, refit, keep)
+        n = self.size()
+        plane = np.zeros(4, np.float64)
+        scores = np.empty(max(int(p.iterations), 1) if 0 < p.iterations <= (1 << 20) else 1, np.uint32) if return_scores else None
+        kept = np.empty(n, np.int64) if (return_kept and p.keep != 0) else None
+        res = _lib.PlaneResult()
+        h = C.c_void_p()
+        check(load().sga_cloud_segment_plane(self.ctx.h, self.h, C.byref(p), _dp(plane), None if scores is None else scores.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h) if p.keep != 0 else None, C.byref(res)))
+        out = {"plane": plane, "inliers": int(res.inliers), "rmse": float(res.rmse), "hypothesis_inliers": int(res.hypothesis_inliers), "best_hypothesis": int(res.best_hypothesis),
+               "scored": int(res.scored), "refit": int(res.refit)}
+        if p.keep != 0:
+            out["cloud"] = PointCloud(ctx=self.ctx, _handle=h)
+            if kept is not None:
+                out["kept"] = kept[: out["cloud"].size()].copy()
+        if return_scores:
+            out["scores"] = scores
+        return out
+
     def fpfh(self, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
         """One 33-bin Fast Point Feature Histogram per point, as Features on the device (sga_cloud_fpfh).  The
         cloud needs normals.  tree: the KdTree over this cloud (None: a temporary one is built).  k: neighbours per point, 2 .. 63.
@@ -2219,6 +2249,65 @@ def radius_waits():
     """Diagnostics (sga_debug_radius_waits): host waits so far of PointCloud.clusters (one per call) and KdTree.radius_search (one; two
     with lists)."""
     return _launches("sga_debug_radius_waits")
+
+
+_PLANE_KEEP = {None: 0, "plane": 1, "rest": 2}
+
+
+def _plane_params(distance_threshold=0.1, iterations=1000, seed=0, axis=None, max_angle=0.0, min_inliers=3, refit=True, keep=None):
+    """The sga_plane_params of PointCloud.segment_plane's arguments (one is passed through).  The library judges the values."""
+    if isinstance(distance_threshold, _lib.PlaneParams):
+        return distance_threshold
+    if keep not in _PLANE_KEEP:
+        raise ValueError('keep must be None, "plane" or "rest"')
+    p = _lib.PlaneParams()
+    load().sga_plane_default(C.byref(p))
+    p.distance_threshold, p.iterations, p.seed = float(distance_threshold), int(iterations), int(seed) & 0xFFFFFFFFFFFFFFFF
+    ax = (0.0, 0.0, 0.0) if axis is None else tuple(float(v) for v in np.asarray(axis, dtype=np.float64).reshape(3))
+    p.axis[0], p.axis[1], p.axis[2] = ax
+    p.max_angle, p.min_inliers, p.refit, p.keep = float(max_angle), int(min_inliers), int(refit), _PLANE_KEEP[keep]
+    return p
+
+
+def segment_plane(points, distance_threshold=0.1, iterations=1000, seed=0, axis=None, max_angle=0.0, min_inliers=3, refit=True, keep=None, return_kept=False, return_scores=False):
+    """PointCloud.segment_plane of a PointCloud or of an (N,3|4) array (uploaded first)."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    return cloud.segment_plane(distance_threshold, iterations, seed, axis, max_angle, min_inliers, refit, keep, return_kept, return_scores)
+
+
+def segment_planes(points, max_planes, distance_threshold=0.1, iterations=1000, seed=0, axis=None, max_angle=0.0, min_inliers=3, refit=True):
+    """Up to max_planes planes of a PointCloud or an (N,3|4) array, one after the other (a host loop): round r
+    calls segment_plane with seed + r and keep "rest" on what round r - 1 left, and stops at the first round that finds fewer than
+    min_inliers points.  Returns a dict: "labels" (numpy int32 over the ORIGINAL cloud: the round that took the point, -1 for none),
+    "planes" (a list of segment_plane's dicts without their clouds, in the order found), "rest" (the PointCloud left over) and
+    "rest_indices" (numpy int64: its points' indices in the original cloud)."""
+    rest = points if isinstance(points, PointCloud) else PointCloud(points)
+    index = np.arange(rest.size(), dtype=np.int64)
+    labels = np.full(rest.size(), -1, np.int32)
+    planes = []
+    for r in range(int(max_planes)):
+        res = rest.segment_plane(distance_threshold, iterations, (int(seed) + r) & 0xFFFFFFFFFFFFFFFF, axis, max_angle, min_inliers, refit, "rest", True)
+        if res["inliers"] < int(min_inliers):
+            break
+        taken = np.ones(len(index), bool)
+        taken[res["kept"]] = False
+        labels[index[taken]] = r
+        index, rest = index[res["kept"]], res.pop("cloud")
+        res.pop("kept")
+        planes.append(res)
+    return {"labels": labels, "planes": planes, "rest": rest, "rest_indices": index}
+
+
+def segment_plane_launches():
+    """Diagnostics (sga_debug_segment_plane_launches): commands enqueued so far by PointCloud.segment_plane — four per call, five when the
+    refit succeeded or a cloud is made, two more (the compaction) with a cloud."""
+    return _launches("sga_debug_segment_plane_launches")
+
+
+def segment_plane_waits():
+    """Diagnostics (sga_debug_segment_plane_waits): host waits so far of PointCloud.segment_plane (one; two when the refit succeeded or a
+    cloud is made)."""
+    return _launches("sga_debug_segment_plane_waits")
 
 
 def cloud_fpfh_launches():

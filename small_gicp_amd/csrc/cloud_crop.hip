@@ -35,7 +35,8 @@ struct CropMember {
   double r2min, r2max;
   double blo[3], bhi[3];
   uint32_t n, tiles;
-  int box_mode, pad;
+  int box_mode;
+  int every_record;          // 1: the crop's own predicate is not applied (CropStat::every_record, cloud_ops.hpp)
 };
 static_assert(sizeof(CropMember) % 8 == 0, "the table is copied in 8-byte words");
 
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_cloud_kernel(const CropMemb
   uint32_t wave_total = 0;
 #pragma unroll
   for (int j = 0; j < kCropItems; j++) {
-    bool keep = first + 64u * j < g.n && crop_keeps(g, p[j]);
+    bool keep = first + 64u * j < g.n && (g.every_record != 0 || crop_keeps(g, p[j]));  // (uniform)
     if (g.stat != nullptr) keep = keep && g.stat[first + 64u * j] <= *g.limit;  // (uniform; read only where the point exists and passes)
     kept[j] = __ballot(keep);
     wave_total += static_cast<uint32_t>(__popcll(kept[j]));
@@ -292,7 +293,7 @@ int cloud_crop(sga_context* ctx, const sga_cloud* const* clouds, const sga_crop*
     if (kept != nullptr && kept[k] != nullptr) g.kept32 = static_cast<uint32_t*>(kslot->dev) + kat, kat += g.n;
     g.kept64 = reinterpret_cast<long long*>(d_kept);
     g.acc = lay.at(boxes.acc, table.p) + 8 * j, g.slot = forest_slot_dev(ctx, j, kBoxSlotWords);
-    if (stat != nullptr) g.stat = stat->d, g.limit = stat->limit != nullptr ? stat->limit : lay.at(s_limit, table.p);
+    if (stat != nullptr) g.stat = stat->d, g.limit = stat->limit != nullptr ? stat->limit : lay.at(s_limit, table.p), g.every_record = stat->every_record ? 1 : 0;
     prefix[j + 1] = prefix[j] + g.tiles;
   }
   IoOrder ord;

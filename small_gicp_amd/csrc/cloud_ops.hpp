@@ -49,12 +49,13 @@ const void* pinned_device_view(const void* p, size_t bytes, bool* on_device = nu
 // ---- cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip) sga_cloud_overlap (cloud_overlap.hip, 3.22) and sga_cloud_visibility (cloud_visibility.hip, 3.23) ----
 // The crop's compaction — its table, its ONE launch, its one wait, its output cloud — over the points i of `cloud` with d[i] <= the limit.
 // d (the cloud's size, the cloud's order) and limit are device memory that launches enqueued earlier on the context's stream write;
-// limit == nullptr: limit_value travels in the call's table.  The table copy and the launch are counted under `chain`.
+// limit == nullptr: limit_value travels in the call's table; d == nullptr (with every_record): every point is kept.  The table copy and the launch are counted under `chain`.
 struct CropStat {
   const double* d;
   const double* limit;
   double limit_value;
   Chain chain = Chain::Outliers;
+  bool every_record = false;  // the statistic alone decides: records with a non-finite coordinate, which the crop's own predicate drops, pass it (cloud_plane.hip)
 };
 int cloud_crop_stat(sga_context* ctx, const sga_cloud* cloud, const CropStat& stat, int64_t* kept /* or null */, sga_cloud** out);
 

@@ -32,5 +32,8 @@ __host__ __device__ inline void ransac_draw(uint64_t seed, uint64_t h, uint64_t 
 // rigid_fit.hip: the least-squares rigid motion of n point pairs from their plain sums (Horn's quaternion form over a Jacobi eigen-solver).
 // T column-major 4x4.  false, T untouched: n < 3, or the centred cross-covariance has rank < 2.
 bool rigid_from_sums(uint64_t n, const double sum_s[3], const double sum_t[3], const double cross[9], double T[16]);
+// rigid_fit.hip: the same Jacobi solver on a symmetric 3x3 matrix S = {xx, xy, xz, yy, yz, zz}: the eigenvalues in ascending order and
+// their unit eigenvectors, vectors[k] belonging to values[k].  The refit of sga_cloud_segment_plane (cloud_plane.hip).
+void sym3_eigen(const double S[6], double values[3], double vectors[3][3]);
 
 }  // namespace sga

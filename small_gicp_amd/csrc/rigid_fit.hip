@@ -46,6 +46,25 @@ void jacobi_eigen(double A[N][N], double V[N][N]) {
 
 }  // namespace
 
+void sym3_eigen(const double S[6], double values[3], double vectors[3][3]) {
+  double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}}, V[3][3];
+  jacobi_eigen<3>(A, V);
+  int order[3] = {0, 1, 2};
+  for (int a = 0; a < 2; a++)
+    for (int b = a + 1; b < 3; b++)
+      if (A[order[b]][order[b]] < A[order[a]][order[a]]) {
+        const int x = order[a];
+        order[a] = order[b];
+        order[b] = x;
+      }
+  for (int k = 0; k < 3; k++) {
+    const int c = order[k];
+    values[k] = A[c][c];
+    const double len = std::sqrt((V[0][c] * V[0][c] + V[1][c] * V[1][c]) + V[2][c] * V[2][c]);
+    for (int r = 0; r < 3; r++) vectors[k][r] = len > 0.0 ? V[r][c] / len : 0.0;
+  }
+}
+
 bool rigid_from_sums(uint64_t n, const double sum_s[3], const double sum_t[3], const double cross[9], double T[16]) {
   if (n < 3) return false;
   const double inv = 1.0 / static_cast<double>(n);

@@ -862,6 +862,49 @@ def run_synthetic_movers(num_frames=8, radius=0.5, min_size=10, min_points=1, do
     return out
 
 
+def run_synthetic_ground(num_frames=4, distance_threshold=0.1, iterations=256, seed=0, max_angle_degrees=15.0, downsampling_resolution=0.25, radius=0.5, min_size=10, ctx=None):
+    """The objects that stand on the ground.  For each raw synthetic.kitti_like_scan(f): the ground is the plane PointCloud.segment_plane
+    finds under the constraint axis = +z within max_angle_degrees (keep="rest"), the rest is downsampled at
+    downsampling_resolution and grouped by PointCloud.clusters(radius, min_size=min_size).  Returns one dict per frame: "frame", "plane"
+    ((4,) n and d, sensor frame), "ground" (the plane's points), "ground_share" (of the scan), "inliers", "rmse", "best_hypothesis",
+    "hypothesis_inliers", "scored", "refit", "rest_points" (after the voxel grid), "objects" (their number), "sizes", "boxes"
+    ((C, 2, 3)), "largest_share" (the largest object's share of the downsampled rest) and the objects behind them: "scan", "rest" (the
+    cloud without the ground), "kept" (its points' indices in the scan) and "labels" (of the downsampled rest)."""
+    from . import synthetic
+
+    ctx = ctx or api.default_context()
+    out = []
+    for f in range(num_frames):
+        pts, _ = synthetic.kitti_like_scan(f)
+        scan = api.PointCloud(pts, ctx=ctx)
+        seg = scan.segment_plane(distance_threshold, iterations, seed, axis=(0.0, 0.0, 1.0), max_angle=np.radians(max_angle_degrees), keep="rest", return_kept=True)
+        down = api.voxelgrid_sampling(seg["cloud"], downsampling_resolution)
+        found = down.clusters(radius, min_size=min_size)
+        sizes = found["sizes"]
+        out.append({
+            "frame": f,
+            "plane": seg["plane"],
+            "ground": seg["inliers"],
+            "ground_share": seg["inliers"] / max(1, scan.size()),
+            "inliers": seg["inliers"],
+            "rmse": seg["rmse"],
+            "best_hypothesis": seg["best_hypothesis"],
+            "hypothesis_inliers": seg["hypothesis_inliers"],
+            "scored": seg["scored"],
+            "refit": seg["refit"],
+            "rest_points": down.size(),
+            "objects": found["num_clusters"],
+            "sizes": sizes,
+            "boxes": found["boxes"],
+            "largest_share": (float(sizes.max()) / max(1, down.size())) if len(sizes) else 0.0,
+            "scan": scan,
+            "rest": seg["cloud"],
+            "kept": seg["kept"],
+            "labels": found["labels"],
+        })
+    return out
+
+
 def _read_trajectory(path):
     poses = []
     for ln in open(path):
