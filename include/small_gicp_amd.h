@@ -367,6 +367,10 @@ int sga_features_create(sga_context* ctx, const float* rows, size_t n, int dim, 
 int sga_features_size(const sga_features* features, size_t* n, int* dim);
 int sga_features_download(sga_context* ctx, const sga_features* features, float* rows);
 int sga_features_destroy(sga_features* features);
+/* Row j of *out is row indices[j] of `features`: one gather launch, no host wait; repeats are allowed; m == 0:
+ * an empty handle of the same dim, nothing launched.  Refusals (SGA_ERR_INVALID, *out = NULL): NULL ctx, features or out, indices NULL with
+ * m > 0, m >= 2^31 — then: another device, an index outside the rows (named by its position), before anything is enqueued. */
+int sga_features_select(sga_context* ctx, const sga_features* features, const int64_t* indices, size_t m, sga_features** out);
 #define SGA_FPFH_DIM 33
 int sga_cloud_fpfh(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, int k, const double viewpoint[3] /* or NULL */, sga_features** out);
 int sga_features_match(sga_context* ctx, const sga_features* source, const sga_features* target, int mutual, int64_t* match /* n */, double* dist /* n, or NULL */, size_t* matched /* or NULL */);
@@ -558,6 +562,37 @@ typedef struct sga_plane_result {
 void sga_plane_default(sga_plane_params* p); /* distance_threshold 0.1, iterations 1000, seed 0, no axis, min_inliers 3, refit 1, keep 0 */
 int sga_cloud_segment_plane(sga_context* ctx, const sga_cloud* cloud, const sga_plane_params* params, double plane[4], uint32_t* scores /* iterations, or NULL */, int64_t* kept /* n, or NULL */,
                             sga_cloud** out /* NULL iff keep == 0 */, sga_plane_result* result);
+/* ISS keypoints on the device: sga_cloud_iss_keypoints — the salient points of a cloud (Intrinsic Shape
+ * Signatures, as Open3D computes them), in terms of cloud indices.  THE RULE is a function of the records, the tree and the parameters
+ * alone.  All arithmetic is in double from the fp32 records of the cloud's own device frame; the origin never enters: everything is a
+ * difference from the query's own record.
+ *   1 neighbourhood  N_i(r) = { j : d2(i, j) <= r * r }, the predicate of sga_index_radius_search; i is a member.  c_i = |N_i(salient_radius)|.
+ *   2 scatter        x_j = r_j - r_i; s = sum x_j and S = sum x_j x_j^T over N_i(salient_radius) in the walk's order;
+ *                    C = S / c_i - (s / c_i)(s / c_i)^T, the unweighted covariance; l1 >= l2 >= l3 its eigenvalues (cyclic Jacobi).
+ *   3 saliency       sal_i = l3 when c_i >= min_neighbors, l1 > 0, l2 < gamma_21 l1, l3 < gamma_32 l2 and l3 > 1e-9 l1 (products, never a
+ *                    division; the floor keeps an exactly planar neighbourhood, whose l3 is rounding noise of either sign, from
+ *                    deciding anything); else sal_i = 0.
+ *   4 suppression    i is a keypoint iff sal_i > 0, |N_i(non_max_radius)| >= min_neighbors, and no j != i in N_i(non_max_radius) has
+ *                    sal_j > sal_i, or sal_j == sal_i with j < i (ties go to the lowest index).
+ *   5 determinism    no floating-point atomics: two calls give the same bytes.
+ * saliency (room for n, or NULL): sal_i.  kept (room for n, or NULL): the keypoints' indices, ascending; *count: their number.  keep 1:
+ * *out is the cloud of the keypoints, compacted as sga_cloud_crop does (order, normals, covariances, origin kept); keep 0: out must be
+ * NULL, and no cloud is made.  kdtree: the kd-tree over this cloud, or NULL: a temporary one is built (a cloud with a non-finite
+ * coordinate has no kd-tree and is refused: crop first).  n == 0: SGA_OK, nothing launched.  One host wait.  Refusals (SGA_ERR_INVALID)
+ * — before any handle is read, *out = NULL and *count = 0: NULL ctx, cloud, params or count; a radius that is not finite and > 0; a gamma
+ * outside (0, 1]; min_neighbors < 1; keep outside {0, 1} or at odds with out — then: another device; a tree of another kind, size or
+ * device frame. */
+typedef struct sga_iss_params {
+  double salient_radius; /* finite, > 0: no default */
+  double non_max_radius; /* finite, > 0: no default */
+  double gamma_21;       /* (0, 1] */
+  double gamma_32;       /* (0, 1] */
+  int32_t min_neighbors; /* >= 1 */
+  int32_t keep;          /* 0 no cloud, 1 the keypoints */
+} sga_iss_params; /* 40 bytes */
+void sga_iss_default(sga_iss_params* p); /* radii 0 (to be set), gamma_21 = gamma_32 = 0.975, min_neighbors 5, keep 0 */
+int sga_cloud_iss_keypoints(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_iss_params* params, double* saliency /* n, or NULL */,
+                            int64_t* kept /* n, or NULL */, size_t* count, sga_cloud** out /* NULL iff keep == 0 */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

@@ -155,6 +155,21 @@ struct Clusters {
   std::shared_ptr<PointCloud> cloud;
   std::vector<int64_t> kept;
 };
+/// What PointCloud::iss_keypoints asks for (sga_iss_params with its defaults: gamma_21 = gamma_32 = 0.975, min_neighbors 5, no cloud; the
+/// two radii have none): Intrinsic Shape Signatures (small_gicp_amd.h).
+struct IssParams : sga_iss_params {
+  IssParams(double salient_radius_, double non_max_radius_, bool keep_ = false) {
+    sga_iss_default(this);
+    salient_radius = salient_radius_, non_max_radius = non_max_radius_, keep = keep_ ? 1 : 0;
+  }
+};
+/// What PointCloud::iss_keypoints found: the keypoints' indices (ascending), the saliency of every point when asked for, and the cloud of
+/// the keypoints (null unless params.keep).
+struct Keypoints {
+  std::vector<int64_t> indices;
+  std::vector<double> saliency;
+  std::shared_ptr<PointCloud> cloud;
+};
 /// What PointCloud::segment_plane asks for (sga_plane_params with its defaults: threshold 0.1, 1000 hypotheses, seed 0, no axis, at least
 /// 3 inliers, refit, no cloud): RANSAC over triples of records (small_gicp_amd.h).  keep says which points the output cloud holds.
 struct PlaneParams : sga_plane_params {
@@ -261,6 +276,12 @@ struct Features {
     std::vector<float> rows(size() * static_cast<size_t>(dim()));
     check(sga_features_download(ctx, h, rows.empty() ? nullptr : rows.data()), "sga_features_download");
     return rows;
+  }
+  /// New features whose row j is this one's row indices[j] (sga_features_select: one launch); repeats are allowed
+  Ptr selected(const std::vector<int64_t>& indices) const {
+    sga_features* made = nullptr;
+    check(sga_features_select(ctx, h, indices.empty() ? nullptr : indices.data(), indices.size(), &made), "sga_features_select");
+    return std::make_shared<Features>(made, ctx);
   }
   sga_context* ctx = default_context();
   sga_features* h = nullptr;
@@ -477,6 +498,21 @@ struct PointCloud {
       r.cloud = std::make_shared<PointCloud>(made, ctx);
       r.kept.resize(r.cloud->size());
     }
+    return r;
+  }
+  /// The salient points of this cloud (sga_cloud_iss_keypoints): a function of the records, the tree and the parameters alone.
+  /// kdtree: the handle of the KdTree over this cloud, or null: a temporary one is built.  with_saliency: also the saliency per point.
+  Keypoints iss_keypoints(const IssParams& params, const sga_index* kdtree = nullptr, bool with_saliency = false) const {
+    Keypoints r;
+    const size_t n = size();
+    r.indices.resize(n);
+    if (with_saliency) r.saliency.resize(n);
+    size_t count = 0;
+    sga_cloud* made = nullptr;
+    check(sga_cloud_iss_keypoints(ctx, h, kdtree, &params, r.saliency.empty() ? nullptr : r.saliency.data(), r.indices.empty() ? nullptr : r.indices.data(), &count, params.keep != 0 ? &made : nullptr),
+          "sga_cloud_iss_keypoints");
+    r.indices.resize(count);
+    if (params.keep != 0) r.cloud = std::make_shared<PointCloud>(made, ctx);
     return r;
   }
   /// One 33-bin Fast Point Feature Histogram per point (sga_cloud_fpfh); the cloud needs normals.  kdtree: the handle of the KdTree over

@@ -148,6 +148,11 @@ int sga_debug_radius_waits(unsigned long long* waits);
  * plane is found, the one behind the sums and the compaction's with keep 2. */
 int sga_debug_segment_plane_launches(unsigned long long* launches);
 int sga_debug_segment_plane_waits(unsigned long long* waits);
+/* Commands enqueued so far, in this process, by sga_cloud_iss_keypoints (small_gicp_amd.h): the saliencies and
+ * the suppression — two — plus the listing kernel without a cloud — three — or the compaction's table copy and the compaction with
+ * one — four.  The build of a temporary tree is not counted; an empty cloud enqueues nothing.  waits: its host waits, one per call. */
+int sga_debug_iss_launches(unsigned long long* launches);
+int sga_debug_iss_waits(unsigned long long* waits);
 /* The host arithmetic of sga_cloud_segment_plane's refit, exposed so that it can be tested without a device: from k, sum x and sum x x^T
  * (sum_xx6 = xx, xy, xz, yy, yz, zz) of the inliers' differences x from an anchor: centroid_offset = sum x / k, eigenvalues (ascending)
  * of S = sum x x^T - (sum x)(sum x)^T / k, and normal = the unit eigenvector of the smallest, with the first non-zero of (z, y, x)

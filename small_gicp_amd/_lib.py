@@ -176,6 +176,12 @@ class PlaneResult(C.Structure):
     _fields_ = [("inliers", C.c_uint64), ("rmse", C.c_double), ("hypothesis_inliers", C.c_uint64), ("best_hypothesis", C.c_uint64), ("scored", C.c_uint64), ("refit", C.c_int), ("reserved", C.c_int)]
 
 
+class IssParams(C.Structure):
+    """sga_iss_params: salient_radius, non_max_radius (no defaults), gamma_21, gamma_32 in (0, 1], min_neighbors >= 1, keep 0 none | 1 the keypoints."""
+
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double), ("min_neighbors", C.c_int32), ("keep", C.c_int32)]
+
+
 FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
@@ -257,6 +263,11 @@ SYMBOLS = [
     ("sga_debug_segment_plane_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_segment_plane_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_plane_from_sums", C.c_int, [C.c_uint64, _dp, _dp, _dp, _dp, _dp]),
+    ("sga_iss_default", None, [C.POINTER(IssParams)]),
+    ("sga_cloud_iss_keypoints", C.c_int, [_vp, _vp, _vp, C.POINTER(IssParams), _dp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t), _pvp]),
+    ("sga_features_select", C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_size_t, _pvp]),
+    ("sga_debug_iss_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_iss_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),

@@ -416,6 +416,30 @@ class PointCloud:
             out["scores"] = scores
         return out
 
+    def iss_keypoints(self, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, tree=None, keep=False, return_saliency=False):
+        """The salient points of this cloud (sga_cloud_iss_keypoints): Intrinsic Shape Signatures.  With the
+        eigenvalues l1 >= l2 >= l3 of the unweighted covariance of the records within salient_radius (the point included; d2 <=
+        radius^2 in double), a point's saliency is l3 when it has at least min_neighbors such records, l2 < gamma_21 l1, l3 <
+        gamma_32 l2 and l3 > 1e-9 l1, and 0 otherwise; a keypoint is a salient point with at least min_neighbors records within
+        non_max_radius none of which has a greater saliency (ties: the lowest index).  tree: the KdTree over this cloud (None: a
+        temporary one).  A cloud with a non-finite coordinate is refused: crop first.  Returns a dict: "indices" (numpy int64,
+        ascending), "count", with keep "cloud" (the keypoints with this cloud's normals, covariances and origin), with
+        return_saliency "saliency" (numpy float64 per point)."""
+        p = _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, keep)
+        n = self.size()
+        kept = np.empty(n, np.int64)
+        sal = np.empty(n, np.float64) if return_saliency else None
+        cnt = C.c_size_t()
+        h = C.c_void_p()
+        check(load().sga_cloud_iss_keypoints(self.ctx.h, self.h, None if tree is None else tree.h, C.byref(p), _dp(sal) if n else None, kept.ctypes.data_as(C.POINTER(C.c_int64)) if n else None, C.byref(cnt),
+                                             C.byref(h) if p.keep != 0 else None))
+        out = {"indices": kept[: cnt.value].copy(), "count": int(cnt.value)}
+        if p.keep != 0:
+            out["cloud"] = PointCloud(ctx=self.ctx, _handle=h)
+        if return_saliency:
+            out["saliency"] = sal
+        return out
+
     def fpfh(self, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
         """One 33-bin Fast Point Feature Histogram per point, as Features on the device (sga_cloud_fpfh).  The
         cloud needs normals.  tree: the KdTree over this cloud (None: a temporary one is built).  k: neighbours per point, 2 .. 63.
@@ -2014,6 +2038,14 @@ class Features:
         check(load().sga_features_download(self.ctx.h, self.h, _fp(out) if n else None))
         return out
 
+    def selected(self, indices):
+        """New Features whose row j is this one's row indices[j] (sga_features_select: one launch, no host wait); repeats are allowed,
+        an index outside the rows is refused and named by its position."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        h = C.c_void_p()
+        check(load().sga_features_select(self.ctx.h, self.h, idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(idx) else None, len(idx), C.byref(h)))
+        return Features(ctx=self.ctx, _handle=h)
+
 
 def compute_fpfh(points, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):
     """PointCloud.fpfh of a PointCloud with normals."""
@@ -2055,16 +2087,60 @@ def ransac_correspondences(source, target, pairs, max_distance=None, iterations=
     return {"T": T.reshape(4, 4).T.copy(), "inliers": int(r.inliers), "inlier_rmse": r.inlier_rmse, "best_hypothesis": int(r.best_hypothesis), "scored": int(r.scored), "refit": int(r.refit)}
 
 
-def global_align(target_points, source_points, voxel_size, k=20, iterations=20000, seed=0, refine=True, setting=None, viewpoint=(0.0, 0.0, 0.0)):
+def _iss_params(salient_radius, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, keep=False):
+    """The sga_iss_params of PointCloud.iss_keypoints' arguments (one is passed through).  The library judges the values."""
+    if isinstance(salient_radius, _lib.IssParams):
+        return salient_radius
+    p = _lib.IssParams()
+    load().sga_iss_default(C.byref(p))
+    p.salient_radius, p.non_max_radius, p.gamma_21, p.gamma_32, p.min_neighbors, p.keep = float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors), 1 if keep else 0
+    return p
+
+
+def iss_keypoints(points, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, tree=None, keep=False, return_saliency=False):
+    """PointCloud.iss_keypoints of a PointCloud or of an (N,3|4) array (uploaded first)."""
+    cloud = points if isinstance(points, PointCloud) else PointCloud(points)
+    return cloud.iss_keypoints(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, tree, keep, return_saliency)
+
+
+def iss_launches():
+    """Diagnostics (sga_debug_iss_launches): commands enqueued so far by PointCloud.iss_keypoints — three per call, four when a cloud is
+    made; the build of a temporary tree is not counted."""
+    return _launches("sga_debug_iss_launches")
+
+
+def iss_waits():
+    """Diagnostics (sga_debug_iss_waits): host waits so far of PointCloud.iss_keypoints, one per call."""
+    return _launches("sga_debug_iss_waits")
+
+
+def global_align(target_points, source_points, voxel_size, k=20, iterations=20000, seed=0, refine=True, setting=None, viewpoint=(0.0, 0.0, 0.0), keypoints=None):
     """A pose from geometry alone, then the local registration from it: voxel grid at voxel_size, trees, normals
     and covariances, FPFH with the viewpoint at each cloud's sensor origin (viewpoint, in each cloud's own frame; default (0, 0, 0)), mutual matching, RANSAC with max_distance = 1.5
     voxel_size and min_edge = 2 voxel_size, and — refine — GICP (setting: a make_setting; default "GICP") from the coarse pose.
-    Returns (coarse, refined): the dict of ransac_correspondences with "pairs" added, and the RegistrationResult (None without refine)."""
+    keypoints: None — every point is described and matched; True, or a dict of PointCloud.iss_keypoints'
+    arguments (True: salient_radius = 3 voxel_size, non_max_radius = 1.5 voxel_size) — only the ISS keypoints of both clouds are
+    matched (FPFH is still computed over the whole clouds), the pairs name points of the clouds, and RANSAC and the refinement
+    run over the full clouds as without.
+    Returns (coarse, refined): the dict of ransac_correspondences with "pairs" added (and, with keypoints, "keypoints": their numbers
+    (source, target)), and the RegistrationResult (None without refine)."""
+    if keypoints is not None and keypoints is not True and not isinstance(keypoints, dict):
+        raise ValueError("keypoints must be None, True or a dict of iss_keypoints' arguments")
     tgt, ttree = preprocess_points(target_points, voxel_size, k)
     src, stree = preprocess_points(source_points, voxel_size, k)
-    pairs = match_features(src.fpfh(stree, k, viewpoint), tgt.fpfh(ttree, k, viewpoint), mutual=True)
+    if keypoints is None:
+        pairs = match_features(src.fpfh(stree, k, viewpoint), tgt.fpfh(ttree, k, viewpoint), mutual=True)
+    else:
+        args = dict(salient_radius=3.0 * voxel_size, non_max_radius=1.5 * voxel_size) if keypoints is True else dict(keypoints)
+        if {"tree", "keep", "return_saliency"} & set(args):
+            raise ValueError("keypoints: tree, keep and return_saliency are global_align's own")
+        ks, kt = src.iss_keypoints(tree=stree, **args)["indices"], tgt.iss_keypoints(tree=ttree, **args)["indices"]
+        rows = match_features(src.fpfh(stree, k, viewpoint).selected(ks), tgt.fpfh(ttree, k, viewpoint).selected(kt), mutual=True)
+        pairs = np.ascontiguousarray(np.stack([ks[rows[:, 0]], kt[rows[:, 1]]], axis=1))  # keypoint rows -> cloud indices
     coarse = ransac_correspondences(src, tgt, pairs, max_distance=1.5 * voxel_size, iterations=iterations, seed=seed, min_edge=2.0 * voxel_size)
     coarse["pairs"] = pairs
+    if keypoints is not None:
+        coarse["keypoints"] = (len(ks), len(kt))
     refined = None
     if refine:
         refined = Problem(ttree, src, coarse["T"]).align(setting or make_setting("GICP"), coarse["T"])

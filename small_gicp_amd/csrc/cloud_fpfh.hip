@@ -189,6 +189,14 @@ __global__ __launch_bounds__(kFpWaves * 64) void fpfh_rows_kernel(const FpfhArgs
   if (lane < kFpDim) a.rows[static_cast<size_t>(i) * kFpDim + lane] = static_cast<float>(v);
 }
 
+// sga_features_select: value t of the output is value t % dim of row idx[t / dim] (a thread per value: the loads of a row are coalesced)
+__global__ __launch_bounds__(256) void features_gather_kernel(const float* __restrict__ rows, const uint32_t* __restrict__ idx, uint32_t dim, unsigned long long total, float* __restrict__ out) {
+  const unsigned long long t = blockIdx.x * 256ull + threadIdx.x;
+  if (t >= total) return;
+  const unsigned long long j = t / dim;
+  out[t] = rows[static_cast<unsigned long long>(idx[j]) * dim + (t - j * dim)];
+}
+
 namespace {
 
 struct IndexDestroy {
@@ -253,6 +261,34 @@ int sga_features_download(sga_context* ctx, const sga_features* features, float*
 
 int sga_features_destroy(sga_features* features) {
   delete features;
+  return SGA_OK;
+}
+
+int sga_features_select(sga_context* ctx, const sga_features* features, const int64_t* indices, size_t m, sga_features** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !features || !out || (m > 0 && !indices)) return fail(SGA_ERR_INVALID, "null argument");
+  if (m >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many indices (%zu; limit 2^31-1)", m);
+  if (features->device != ctx->device) return fail(SGA_ERR_INVALID, "features live on another device");
+  for (size_t j = 0; j < m; j++)
+    if (indices[j] < 0 || static_cast<unsigned long long>(indices[j]) >= features->n) return fail(SGA_ERR_INVALID, "indices[%zu] = %lld is outside the %zu rows", j, static_cast<long long>(indices[j]), features->n);
+  SGA_ENTER(ctx);
+  std::unique_ptr<sga_features> f;
+  SGA_TRY(features_new(ctx, m, features->dim, &f));
+  if (m > 0) {  // the indices go through a slot of the staging ring, which is reused only behind the kernel: no host wait
+    SGA_TRY(wait_ready(ctx, features->ready));
+    sga_context::StageSlot* slot = nullptr;
+    SGA_TRY(stage_acquire(ctx, m * sizeof(uint32_t), &slot));
+    uint32_t* host = static_cast<uint32_t*>(slot->host);
+    for (size_t j = 0; j < m; j++) host[j] = static_cast<uint32_t>(indices[j]);
+    const unsigned long long total = static_cast<unsigned long long>(m) * static_cast<unsigned long long>(features->dim);
+    hipLaunchKernelGGL(features_gather_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream, features->rows.p, static_cast<const uint32_t*>(slot->dev), static_cast<uint32_t>(features->dim), total,
+                       f->rows.p);
+    SGA_HIP(hipGetLastError());
+    SGA_TRY(stage_release(ctx, slot));
+    SGA_TRY(mark_ready(ctx, f->ready));
+    if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));  // a blocking context reports what its kernel met
+  }
+  *out = f.release();
   return SGA_OK;
 }
 

@@ -46,7 +46,7 @@ int ensure_box64(sga_context* ctx);  // the context's 64-bit box accumulator (d_
 // address.  on_device (optional): set when p is device memory, which no host entry point takes
 const void* pinned_device_view(const void* p, size_t bytes, bool* on_device = nullptr);
 
-// ---- cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip) sga_cloud_overlap (cloud_overlap.hip, 3.22) and sga_cloud_visibility (cloud_visibility.hip, 3.23) ----
+// ---- cloud_crop.hip, for sga_cloud_remove_outliers (cloud_outliers.hip) sga_cloud_overlap (cloud_overlap.hip, 3.22) sga_cloud_visibility (cloud_visibility.hip, 3.23) and sga_cloud_iss_keypoints (cloud_keypoints.hip, 3.28) ----
 // The crop's compaction — its table, its ONE launch, its one wait, its output cloud — over the points i of `cloud` with d[i] <= the limit.
 // d (the cloud's size, the cloud's order) and limit are device memory that launches enqueued earlier on the context's stream write;
 // limit == nullptr: limit_value travels in the call's table; d == nullptr (with every_record): every point is kept.  The table copy and the launch are counted under `chain`.

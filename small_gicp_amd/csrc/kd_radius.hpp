@@ -21,6 +21,8 @@
 // by their distance (a radius beyond kKdFar would accept them).
 // A query whose coordinates are not finite floats in the tree's frame has no neighbours.
 #pragma once
+#include <type_traits>
+
 #include "kd_search.hpp"
 
 namespace sga {
@@ -31,7 +33,8 @@ struct KdRadius {
   float dropped;      // kd_walk's note of what it discarded: not read here
   double qx, qy, qz;  // the query, the tree's device frame
   double r2;          // radius * radius
-  F& f;               // f(cloud index of the record, d2): called once per record within the radius, in the walk's order
+  F& f;               // f(cloud index of the record, d2) or f(index, d2, dx, dy, dz) — the record minus the query, the terms of d2 —: called
+                      // once per record within the radius, in the walk's order
 };
 
 __device__ __forceinline__ float kd_radius_open(double radius, double e) {
@@ -54,7 +57,12 @@ __device__ __forceinline__ void kd_scan_leaf(const KdView& t, uint32_t leaf_node
   for (int i = 0; i < kKdLeafMax; i++) {
     const double dx = static_cast<double>(X[i]) - s.qx, dy = static_cast<double>(Y[i]) - s.qy, dz = static_cast<double>(Z[i]) - s.qz;
     const double d2 = dx * dx + dy * dy + dz * dz;
-    if (static_cast<uint32_t>(i) < count && d2 <= s.r2) s.f(__float_as_uint(I[i]), d2);
+    if (static_cast<uint32_t>(i) < count && d2 <= s.r2) {
+      if constexpr (std::is_invocable_v<F&, uint32_t, double, double, double, double>)
+        s.f(__float_as_uint(I[i]), d2, dx, dy, dz);
+      else
+        s.f(__float_as_uint(I[i]), d2);
+    }
   }
 }
 
