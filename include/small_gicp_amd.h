@@ -593,6 +593,95 @@ typedef struct sga_iss_params {
 void sga_iss_default(sga_iss_params* p); /* radii 0 (to be set), gamma_21 = gamma_32 = 0.975, min_neighbors 5, keep 0 */
 int sga_cloud_iss_keypoints(sga_context* ctx, const sga_cloud* cloud, const sga_index* kdtree /* over this cloud, or NULL: a temporary one */, const sga_iss_params* params, double* saliency /* n, or NULL */,
                             int64_t* kept /* n, or NULL */, size_t* count, sga_cloud** out /* NULL iff keep == 0 */);
+/* ---- occupancy grid: posed scans ray-cast into free and occupied space -----------------------------------------
+ * The product a mapping loop hands to a planner or a map cleaner: a volume that says free, occupied or never observed, accumulated over
+ * many scans.  A persistent handle on the device; double arithmetic from the fp32 records, integer atomics only, every log-odds value
+ * written by one lane per scan: the result is a function of the inputs alone, and two runs give the same bytes.  tests/occupancy_ref.py
+ * restates the rule in numpy.
+ *
+ * THE GRID.  Dense and caller-placed: origin g (the box's minimum corner in the world), leaf > 0, dims nx x ny x nz (each >= 1, product
+ * <= 2^27).  inv_leaf = 1.0 / leaf, formed once.  Cell (x, y, z) has the linear index (z * ny + y) * nx + x and holds 8 bytes: a uint32
+ * stamp — 0: never observed; otherwise 2 * epoch + (1 if the cell was an endpoint in that scan, else 0) of the last scan that touched it —
+ * and an fp32 log-odds L (0 at creation).  l_hit, l_miss, l_min, l_max are fp32 (defaults OctoMap's: 0.85, -0.4, -2.0, 3.5).
+ *
+ * THE RULE of sga_occupancy_integrate(scan, T, min_range, max_range, mode).  Every successful call advances the epoch by one (an empty
+ * scan too); the scan's epoch e is the new value.  The scan is in the sensor frame (record r at the cloud's origin o_c); T = [R t]
+ * (column-major 4x4, NULL: the identity) maps the sensor frame into the world, so the sensor sits at t.
+ *  1. Per return s = r + o_c (double): rho = sqrt((sx^2 + sy^2) + sz^2), every operation rounded.  A return with a non-finite component
+ *     or rho, or with rho < min_range, is IGNORED.  With rho > max_range the beam is TRUNCATED: p = s * (max_range / rho), the quotient
+ *     formed once; it marks free space only.  Otherwise the beam is a HIT.
+ *  2. Grid coordinates, with q0 = t - g and q = (R o_c + t) - g formed once on the host in double (R o_c per component as (R[k][0] o0 +
+ *     R[k][1] o1) + R[k][2] o2):  go = q0 * inv_leaf;  a hit's end ge = ((R r) + q) * inv_leaf, a truncated beam's ge = ((R p) + q0) *
+ *     inv_leaf, R v per component as above.  (A return whose ge is not finite — a T that is no rigid motion — is ignored.)  Cells c =
+ *     floor(go), ce = floor(ge).
+ *  3. The walk, with d = ge - go, per axis a: rem_a = |ce_a - c_a|; if ce_a > c_a: tmax_a = ((c_a + 1) - go_a) / d_a, tdel_a = 1 / d_a;
+ *     if ce_a < c_a: tmax_a = (go_a - c_a) / (-d_a), tdel_a = 1 / (-d_a).  While rem_x + rem_y + rem_z > 0: the current cell is a free
+ *     candidate; the axis a of least tmax among those with rem_a > 0, ties to the lowest axis, is stepped: c_a moves one cell towards
+ *     ce_a, tmax_a += tdel_a, rem_a -= 1.  The walk ends in ce after exactly the Manhattan distance of the two cells; the loop counts
+ *     that INTEGER down (at most 3 * (4096 + 2): a beam that would need more is dropped), never a floating-point exit.  A truncated beam
+ *     also offers ce as a free candidate; a hit beam offers ce as the hit cell.  Cells outside dims are walked but not touched (the walk
+ *     stops early once an axis is outside the box for good: an integer test that changes no result).
+ *  4. Per scan a cell is updated ONCE, and an endpoint wins (OctoMap's rule): the hit cells H: L = min(fp32(L + l_hit), l_max), stamp
+ *     2 e + 1; the free candidates not in H: L = max(fp32(L + l_miss), l_min), stamp 2 e.  mode 1 (endpoints only) skips the free phase.
+ * If the box lies farther than max_range from the sensor (the distance of t to [g, g + dims * leaf], in double on the host), or the scan is
+ * empty, the epoch advances and nothing is enqueued (stats: beams alone).
+ * Commands: mode 0 two launches — the endpoints (a lane per return: atomicMax(stamp, 2 e + 1), the lane that raised it writes L), then
+ * the walk (a lane per beam: a plain load of the stamp skips cells this scan has touched, atomicMax(stamp, 2 e), the lane that raised it
+ * writes L) — mode 1 one; NO host wait, on any context: the call returns with its kernels in flight, and every later call on the grid,
+ * from whichever context, orders itself behind them.  stats (or NULL): beams, ignored, hits, truncated, and the cells hit / freed,
+ * counted where the first toucher is decided; asking for them costs ONE wait.
+ *
+ * sga_occupancy_classify: per point of a posed cloud (record r at origin o_c; T maps the cloud's frame into the world, NULL: the
+ * identity): gc = ((R r) + q) * inv_leaf with q as above; state 0 UNKNOWN: a non-finite gc, a component outside [0, dims), or stamp 0;
+ * 1 FREE: L < threshold; 2 OCCUPIED: L >= threshold (L widened to double).  state (room for n, or NULL); counts (or NULL): total = n and
+ * the three counts, with the epoch.  keep_mask: bit 0 unknown, bit 1 free, bit 2 occupied; 0 — no cloud, out must be NULL; otherwise *out
+ * receives the points whose state's bit is set as an ordinary cloud, by the compaction of sga_cloud_crop: the cloud's order, origin,
+ * normals and covariances, record j of *out equal to record kept[j] bit for bit (a non-finite record is unknown, and kept with bit 0);
+ * nothing kept, or an empty cloud, yields an empty cloud without attributes.  kept (room for n, or NULL; only with keep_mask != 0): the
+ * indices kept, ascending.  keep_mask 5 is the cleaner a keyframe runs against accumulated evidence.  One launch and one wait; with an
+ * output cloud the compaction's table copy and launch follow, and the one wait is the compaction's.  An empty cloud enqueues nothing.
+ * sga_occupancy_stats: the unknown / free / occupied cells (total = the cells) and the epoch; one launch, one wait.
+ * sga_occupancy_export: the cells whose state's bit is set in which_mask (1 .. 7), in ascending linear index, the first min(*count,
+ * capacity) of them written: *out (or NULL) a cloud of cell centres at origin g with the records fp32((i + 0.5) * leaf) per axis,
+ * indices (or NULL) their linear indices, log_odds (or NULL) their L; *count: the number selected, whatever the capacity.  The count needs
+ * ONE wait (one launch); the fill — two more launches, only when something is selected and asked for — a SECOND (a stream-ordered context
+ * that asks for the cloud alone returns without it).
+ * sga_occupancy_download: the raw arrays (stamp and / or log_odds, room for the cells each), for tests and persistence.
+ * sga_occupancy_clear: every cell back to {0, 0} and the epoch to 0; one fill.  sga_occupancy_get: the parameters and / or the epoch.
+ *
+ * Refusals (SGA_ERR_INVALID; *out = NULL on every failure, nothing enqueued) — before any handle is read: NULL arguments; create: a
+ * non-finite origin, leaf not finite or <= 0, a dim below 1, more than 2^27 cells, a non-finite log-odds parameter, l_hit <= 0, l_miss >=
+ * 0, l_min >= l_max; integrate: min_range not finite or < 0, max_range not finite or < min_range, a mode other than 0 or 1; a
+ * non-finite entry of T; a NaN threshold; keep_mask outside 0 .. 7, out given with keep_mask 0 or missing otherwise, kept given with
+ * keep_mask 0; which_mask outside 1 .. 7 — then: a grid or cloud of another device, 2^31 points or more, max_range / leaf > 4096, an
+ * epoch of 2^31 - 1. */
+typedef struct sga_occupancy_params {
+  double origin[3];
+  double leaf;
+  int dims[3];
+  int reserved;
+  float l_hit, l_miss, l_min, l_max;
+} sga_occupancy_params; /* 64 bytes */
+typedef struct sga_occupancy_scan_stats {
+  size_t beams, ignored, hits, truncated, cells_hit, cells_freed;
+} sga_occupancy_scan_stats; /* 48 bytes */
+typedef struct sga_occupancy_counts {
+  size_t total, unknown, free, occupied;
+  uint64_t epoch;
+} sga_occupancy_counts; /* 40 bytes */
+typedef struct sga_occupancy sga_occupancy;
+void sga_occupancy_params_default(sga_occupancy_params* p); /* origin 0, leaf 0 and dims 0 (to be set), 0.85, -0.4, -2.0, 3.5 */
+int sga_occupancy_create(sga_context* ctx, const sga_occupancy_params* params, sga_occupancy** out);
+int sga_occupancy_destroy(sga_occupancy* grid);
+int sga_occupancy_get(const sga_occupancy* grid, sga_occupancy_params* params /* or NULL */, uint64_t* epoch /* or NULL */);
+int sga_occupancy_clear(sga_context* ctx, sga_occupancy* grid);
+int sga_occupancy_integrate(sga_context* ctx, sga_occupancy* grid, const sga_cloud* scan, const double T[16] /* or NULL */, double min_range, double max_range, int mode, sga_occupancy_scan_stats* stats /* or NULL */);
+int sga_occupancy_classify(sga_context* ctx, const sga_occupancy* grid, const sga_cloud* cloud, const double T[16] /* or NULL */, double threshold, int keep_mask, uint8_t* state /* n, or NULL */,
+                           int64_t* kept /* n, or NULL; only with keep_mask != 0 */, sga_occupancy_counts* counts /* or NULL */, sga_cloud** out /* NULL iff keep_mask == 0 */);
+int sga_occupancy_stats(sga_context* ctx, const sga_occupancy* grid, double threshold, sga_occupancy_counts* counts);
+int sga_occupancy_export(sga_context* ctx, const sga_occupancy* grid, double threshold, int which_mask, size_t capacity, int64_t* indices /* capacity, or NULL */, float* log_odds /* capacity, or NULL */, size_t* count,
+                         sga_cloud** out /* or NULL */);
+int sga_occupancy_download(sga_context* ctx, const sga_occupancy* grid, uint32_t* stamp /* cells, or NULL */, float* log_odds /* cells, or NULL */);
 int sga_cloud_destroy(sga_cloud* cloud);
 int sga_cloud_size(const sga_cloud* cloud, size_t* n);
 int sga_cloud_has(const sga_cloud* cloud, int* has_normals, int* has_covs);

@@ -662,6 +662,111 @@ private:
   }
 };
 
+/// Where an OccupancyGrid lies and how it weighs evidence (sga_occupancy_params: the box's minimum corner, the leaf, the dims; the
+/// log-odds of a hit and a miss and their clamps, OctoMap's by default).
+struct OccupancyParams : sga_occupancy_params {
+  OccupancyParams() { sga_occupancy_params_default(this); }
+  OccupancyParams(const std::array<double, 3>& origin_, double leaf_, const std::array<int, 3>& dims_) {
+    sga_occupancy_params_default(this);
+    for (int k = 0; k < 3; k++) origin[k] = origin_[k], dims[k] = dims_[k];
+    leaf = leaf_;
+  }
+};
+/// What OccupancyGrid::classify found: the points per state with the epoch, the cloud of the kept points (null when keep_mask is 0)
+/// and — where asked for — the state per point and the indices of the output cloud's points, ascending.
+struct OccupancyClassified {
+  sga_occupancy_counts counts{};
+  std::shared_ptr<PointCloud> cloud;
+  std::vector<uint8_t> state;
+  std::vector<int64_t> kept;
+};
+/// What OccupancyGrid::export_cells found: the number of selected cells (whatever the capacity), the first of them in ascending linear
+/// index (z * ny + y) * nx + x with their log-odds, and the cloud of their centres.
+struct OccupancyCells {
+  size_t count = 0;
+  std::vector<int64_t> indices;
+  std::vector<float> log_odds;
+  std::shared_ptr<PointCloud> cloud;
+};
+/// A dense occupancy grid on the device (sga_occupancy_*): posed scans are ray-cast into it — free space along every beam, an endpoint
+/// at every return within range — and it answers unknown / free / occupied for points and cells.
+class OccupancyGrid {
+public:
+  enum State : uint8_t { Unknown = 0, Free = 1, Occupied = 2 };
+  enum Mask { UnknownBit = 1, FreeBit = 2, OccupiedBit = 4 };
+  explicit OccupancyGrid(const OccupancyParams& params_, sga_context* context = default_context()) : ctx(context), params(params_) { check(sga_occupancy_create(ctx, &params, &h), "sga_occupancy_create"); }
+  OccupancyGrid(const OccupancyGrid&) = delete;
+  OccupancyGrid& operator=(const OccupancyGrid&) = delete;
+  ~OccupancyGrid() { sga_occupancy_destroy(h); }
+  size_t cells() const { return static_cast<size_t>(params.dims[0]) * static_cast<size_t>(params.dims[1]) * static_cast<size_t>(params.dims[2]); }
+  uint64_t epoch() const {
+    uint64_t e = 0;
+    check(sga_occupancy_get(h, nullptr, &e), "sga_occupancy_get");
+    return e;
+  }
+  void clear() { check(sga_occupancy_clear(ctx, h), "sga_occupancy_clear"); }
+  /// Ray-cast `scan` (sensor frame; T: sensor frame -> world, null: the identity).  mode 1: the endpoints only.  No host wait.
+  void integrate(const PointCloud& scan, const Isometry3d* T = nullptr, double min_range = 0.5, double max_range = 60.0, int mode = 0) {
+    check(sga_occupancy_integrate(ctx, h, scan.h, T ? T->data() : nullptr, min_range, max_range, mode, nullptr), "sga_occupancy_integrate");
+  }
+  /// ... and wait once for the scan's statistics
+  sga_occupancy_scan_stats integrate_with_stats(const PointCloud& scan, const Isometry3d* T = nullptr, double min_range = 0.5, double max_range = 60.0, int mode = 0) {
+    sga_occupancy_scan_stats st{};
+    check(sga_occupancy_integrate(ctx, h, scan.h, T ? T->data() : nullptr, min_range, max_range, mode, &st), "sga_occupancy_integrate");
+    return st;
+  }
+  /// The state of every point of `cloud` posed by T; keep_mask (Mask bits) other than 0: also the cloud of the points in those states.
+  OccupancyClassified classify(const PointCloud& cloud, const Isometry3d* T = nullptr, double threshold = 0.0, int keep_mask = 0, bool with_state = false, bool with_kept = false) const {
+    OccupancyClassified r;
+    const size_t n = cloud.size();
+    if (with_state) r.state.resize(n);
+    if (with_kept) r.kept.resize(n);
+    sga_cloud* made = nullptr;
+    check(sga_occupancy_classify(ctx, h, cloud.h, T ? T->data() : nullptr, threshold, keep_mask, r.state.empty() ? nullptr : r.state.data(), r.kept.empty() ? nullptr : r.kept.data(), &r.counts, keep_mask != 0 ? &made : nullptr),
+          "sga_occupancy_classify");
+    if (keep_mask != 0) {
+      r.cloud = std::make_shared<PointCloud>(made, ctx);
+      r.kept.resize(with_kept ? r.cloud->size() : 0);
+    }
+    return r;
+  }
+  sga_occupancy_counts stats(double threshold = 0.0) const {
+    sga_occupancy_counts c{};
+    check(sga_occupancy_stats(ctx, h, threshold, &c), "sga_occupancy_stats");
+    return c;
+  }
+  /// The cells in the states of which_mask, at most `capacity` of them (SIZE_MAX: the cells)
+  OccupancyCells export_cells(double threshold = 0.0, int which_mask = OccupiedBit, size_t capacity = SIZE_MAX, bool with_cloud = true) const {
+    OccupancyCells r;
+    const size_t cap = capacity == SIZE_MAX ? cells() : capacity;
+    r.indices.resize(cap);
+    r.log_odds.resize(cap);
+    sga_cloud* made = nullptr;
+    check(sga_occupancy_export(ctx, h, threshold, which_mask, cap, cap ? r.indices.data() : nullptr, cap ? r.log_odds.data() : nullptr, &r.count, with_cloud ? &made : nullptr), "sga_occupancy_export");
+    r.indices.resize(r.count < cap ? r.count : cap);
+    r.log_odds.resize(r.indices.size());
+    if (with_cloud) r.cloud = std::make_shared<PointCloud>(made, ctx);
+    return r;
+  }
+  /// the centres of the occupied cells
+  std::shared_ptr<PointCloud> occupied_cloud(double threshold = 0.0) const {
+    size_t count = 0;
+    sga_cloud* made = nullptr;
+    check(sga_occupancy_export(ctx, h, threshold, OccupiedBit, cells(), nullptr, nullptr, &count, &made), "sga_occupancy_export");
+    return std::make_shared<PointCloud>(made, ctx);
+  }
+  /// the raw arrays, cell (x, y, z) at (z * ny + y) * nx + x
+  void download(std::vector<uint32_t>& stamp, std::vector<float>& log_odds) const {
+    stamp.resize(cells());
+    log_odds.resize(cells());
+    check(sga_occupancy_download(ctx, h, stamp.data(), log_odds.data()), "sga_occupancy_download");
+  }
+
+  sga_context* ctx = default_context();
+  OccupancyParams params;
+  sga_occupancy* h = nullptr;
+};
+
 /// The rigid motion most of the index pairs (source point, target point) agree on (sga_ransac_correspondences): hypotheses from three
 /// pairs each, scored by the pairs within max_distance, the best refitted over its inliers.  Fewer than three pairs, or no hypothesis
 /// that passed the tests: inliers 0 and the identity.

@@ -153,6 +153,12 @@ int sga_debug_segment_plane_waits(unsigned long long* waits);
  * one — four.  The build of a temporary tree is not counted; an empty cloud enqueues nothing.  waits: its host waits, one per call. */
 int sga_debug_iss_launches(unsigned long long* launches);
 int sga_debug_iss_waits(unsigned long long* waits);
+/* Commands enqueued so far, in this process, by the occupancy grid's calls (small_gicp_amd.h): sga_occupancy_create
+ * two fills, clear one; integrate two launches (one with mode 1; none for an empty scan or a box out of reach); classify one, plus the
+ * compaction's table copy and launch with an output cloud; stats one; export one, plus two when it fills.  waits: their host waits —
+ * integrate none (one with stats), classify one, stats one, export one or two, download one per 2^20 cells. */
+int sga_debug_occupancy_launches(unsigned long long* launches);
+int sga_debug_occupancy_waits(unsigned long long* waits);
 /* The host arithmetic of sga_cloud_segment_plane's refit, exposed so that it can be tested without a device: from k, sum x and sum x x^T
  * (sum_xx6 = xx, xy, xz, yy, yz, zz) of the inliers' differences x from an anchor: centroid_offset = sum x / k, eigenvalues (ascending)
  * of S = sum x x^T - (sum x)(sum x)^T / k, and normal = the unit eigenvector of the smallest, with the first non-zero of (z, y, x)

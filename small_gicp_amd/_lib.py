@@ -182,6 +182,24 @@ class IssParams(C.Structure):
     _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double), ("min_neighbors", C.c_int32), ("keep", C.c_int32)]
 
 
+class OccupancyParams(C.Structure):
+    """sga_occupancy_params: the box's minimum corner, the leaf, the dims (x, y, z), the fp32 log-odds of a hit and a miss and their clamps."""
+
+    _fields_ = [("origin", C.c_double * 3), ("leaf", C.c_double), ("dims", C.c_int * 3), ("reserved", C.c_int), ("l_hit", C.c_float), ("l_miss", C.c_float), ("l_min", C.c_float), ("l_max", C.c_float)]
+
+
+class OccupancyScanStats(C.Structure):
+    """sga_occupancy_scan_stats: the returns of a scan by kind, and the cells it hit and freed."""
+
+    _fields_ = [("beams", C.c_size_t), ("ignored", C.c_size_t), ("hits", C.c_size_t), ("truncated", C.c_size_t), ("cells_hit", C.c_size_t), ("cells_freed", C.c_size_t)]
+
+
+class OccupancyCounts(C.Structure):
+    """sga_occupancy_counts: points or cells per state, and the grid's epoch."""
+
+    _fields_ = [("total", C.c_size_t), ("unknown", C.c_size_t), ("free", C.c_size_t), ("occupied", C.c_size_t), ("epoch", C.c_uint64)]
+
+
 FPFH_DIM = 33
 F32, F64 = 0, 1
 IO_NO_ORDER, IO_RELATIVE = 1, 2
@@ -268,6 +286,18 @@ SYMBOLS = [
     ("sga_features_select", C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_size_t, _pvp]),
     ("sga_debug_iss_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_iss_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_occupancy_params_default", None, [C.POINTER(OccupancyParams)]),
+    ("sga_occupancy_create", C.c_int, [_vp, C.POINTER(OccupancyParams), _pvp]),
+    ("sga_occupancy_destroy", C.c_int, [_vp]),
+    ("sga_occupancy_get", C.c_int, [_vp, C.POINTER(OccupancyParams), C.POINTER(C.c_uint64)]),
+    ("sga_occupancy_clear", C.c_int, [_vp, _vp]),
+    ("sga_occupancy_integrate", C.c_int, [_vp, _vp, _vp, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(OccupancyScanStats)]),
+    ("sga_occupancy_classify", C.c_int, [_vp, _vp, _vp, _dp, C.c_double, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(OccupancyCounts), _pvp]),
+    ("sga_occupancy_stats", C.c_int, [_vp, _vp, C.c_double, C.POINTER(OccupancyCounts)]),
+    ("sga_occupancy_export", C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_size_t), _pvp]),
+    ("sga_occupancy_download", C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), _fp]),
+    ("sga_debug_occupancy_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_occupancy_waits", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_cloud_fpfh_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_features_match_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_debug_ransac_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),

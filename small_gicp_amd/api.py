@@ -2281,6 +2281,151 @@ def places_waits():
     return _launches("sga_debug_places_waits")
 
 
+OCCUPANCY_STATES = {"unknown": 1, "free": 2, "occupied": 4}
+
+
+def _state_mask(what, name):
+    """An int as it is, a state's name, or several of them: the bits of sga_occupancy_classify / export (1 unknown, 2 free, 4 occupied)."""
+    if what is None:
+        return 0
+    if isinstance(what, (int, np.integer)):
+        return int(what)
+    names = [what] if isinstance(what, str) else list(what)
+    for w in names:
+        if w not in OCCUPANCY_STATES:
+            raise ValueError("%s must name unknown, free or occupied, not %r" % (name, w))
+    return sum({OCCUPANCY_STATES[w] for w in names})
+
+
+def _occupancy_counts(c):
+    return {"total": int(c.total), "unknown": int(c.unknown), "free": int(c.free), "occupied": int(c.occupied), "epoch": int(c.epoch)}
+
+
+class OccupancyGrid:
+    """A dense occupancy grid on the device (sga_occupancy_*): the box with the minimum corner `origin` (world),
+    dims = (nx, ny, nz) cells of `leaf` metres; a cell holds a stamp (0: never observed) and an fp32 log-odds.  integrate() ray-casts a
+    posed scan into it — free space along every beam, an endpoint at every return within range; classify() says unknown / free /
+    occupied for the points of a posed cloud and hands back the kept ones; stats(), export() and download() read the cells.  The log-odds
+    parameters are OctoMap's by default."""
+
+    def __init__(self, origin, leaf, dims, l_hit=0.85, l_miss=-0.4, l_min=-2.0, l_max=3.5, ctx=None):
+        self.ctx = ctx or default_context()
+        self.h = C.c_void_p()
+        p = _lib.OccupancyParams()
+        load().sga_occupancy_params_default(C.byref(p))
+        o, d = np.asarray(origin, dtype=np.float64).reshape(3), np.asarray(dims).reshape(3)
+        for k in range(3):
+            p.origin[k], p.dims[k] = float(o[k]), int(d[k])
+        p.leaf, p.l_hit, p.l_miss, p.l_min, p.l_max = float(leaf), float(l_hit), float(l_miss), float(l_min), float(l_max)
+        check(load().sga_occupancy_create(self.ctx.h, C.byref(p), C.byref(self.h)))
+        self.origin, self.leaf, self.dims = o.copy(), p.leaf, (int(d[0]), int(d[1]), int(d[2]))
+        self.cells = self.dims[0] * self.dims[1] * self.dims[2]
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value:
+            load().sga_occupancy_destroy(self.h)
+            self.h = C.c_void_p()
+
+    @property
+    def epoch(self):
+        """The scans integrated since creation or the last clear()."""
+        e = C.c_uint64()
+        check(load().sga_occupancy_get(self.h, None, C.byref(e)))
+        return e.value
+
+    def clear(self, ctx=None):
+        """Every cell back to never observed, the epoch to 0."""
+        check(load().sga_occupancy_clear((ctx or self.ctx).h, self.h))
+
+    def integrate(self, scan, T=None, min_range=0.5, max_range=60.0, mode=0, return_stats=False, ctx=None):
+        """Ray-cast a PointCloud in its sensor frame, posed by T (4x4: sensor frame -> world; None: the identity): returns nearer than
+        min_range are ignored, beams beyond max_range are cut there and mark free space only (max_range / leaf <= 4096).  mode 1: the
+        endpoints only, no free space.  Two launches and no host wait; return_stats=True waits once and returns a dict — "beams",
+        "ignored", "hits", "truncated", "cells_hit", "cells_freed"."""
+        st = _lib.OccupancyScanStats() if return_stats else None
+        t16 = None if T is None else _T16(T)
+        check(load().sga_occupancy_integrate((ctx or self.ctx).h, self.h, scan.h, _dp(t16), float(min_range), float(max_range), int(mode), C.byref(st) if return_stats else None))
+        if return_stats:
+            return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+    def classify(self, cloud, T=None, threshold=0.0, keep=None, return_state=False, return_kept=False, ctx=None):
+        """The state of every point of a PointCloud posed by T (None: the identity): 0 unknown (outside the box, non-finite, never
+        observed), 1 free (log-odds < threshold), 2 occupied.  Returns a dict — "total", "unknown", "free", "occupied", "epoch" —
+        followed, as requested and in this order, by the cloud of the kept points (keep: a state's name, a list of names, or the bit
+        mask 1 unknown | 2 free | 4 occupied; the cloud's order, normals, covariances and origin are kept: keep=("unknown", "occupied")
+        is the cleaner a keyframe runs against accumulated evidence), "state" (numpy uint8) and "kept" (numpy int64, ascending; needs
+        keep)."""
+        ctx = ctx or self.ctx
+        mask = _state_mask(keep, "keep")
+        n = cloud.size()
+        state = np.empty(n, np.uint8) if return_state else None
+        kept = np.empty(n, np.int64) if return_kept else None
+        c = _lib.OccupancyCounts()
+        h = C.c_void_p()
+        t16 = None if T is None else _T16(T)
+        check(load().sga_occupancy_classify(ctx.h, self.h, cloud.h, _dp(t16), float(threshold), mask, None if state is None else state.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(c), C.byref(h) if mask != 0 else None))
+        res = [_occupancy_counts(c)]
+        out = None
+        if mask != 0:
+            out = PointCloud(ctx=ctx, _handle=h)
+            res.append(out)
+        if return_state:
+            res.append(state)
+        if return_kept:
+            res.append(kept[: out.size()].copy())
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def stats(self, threshold=0.0, ctx=None):
+        """The cells per state and the epoch: a dict — "total", "unknown", "free", "occupied", "epoch"."""
+        c = _lib.OccupancyCounts()
+        check(load().sga_occupancy_stats((ctx or self.ctx).h, self.h, float(threshold), C.byref(c)))
+        return _occupancy_counts(c)
+
+    def export(self, threshold=0.0, which="occupied", capacity=None, return_cloud=True, ctx=None):
+        """The selected cells (which: as classify's keep) in ascending linear index (z * ny + y) * nx + x: a dict — "count" (the number
+        selected, whatever the capacity), "indices" (int64), "log_odds" (float32) and, with return_cloud, "cloud": the PointCloud of
+        the cell centres at this grid's origin.  capacity None: the cells."""
+        ctx = ctx or self.ctx
+        cap = self.cells if capacity is None else int(capacity)
+        idx, lo = np.empty(cap, np.int64), np.empty(cap, np.float32)
+        count = C.c_size_t()
+        h = C.c_void_p()
+        check(load().sga_occupancy_export(ctx.h, self.h, float(threshold), _state_mask(which, "which"), cap, idx.ctypes.data_as(C.POINTER(C.c_int64)) if cap else None, _fp(lo) if cap else None, C.byref(count),
+                                          C.byref(h) if return_cloud else None))
+        m = min(count.value, cap)
+        res = {"count": count.value, "indices": idx[:m].copy(), "log_odds": lo[:m].copy()}
+        if return_cloud:
+            res["cloud"] = PointCloud(ctx=ctx, _handle=h)
+        return res
+
+    def occupied_cloud(self, threshold=0.0, ctx=None):
+        """The PointCloud of the centres of the occupied cells."""
+        ctx = ctx or self.ctx
+        count = C.c_size_t()
+        h = C.c_void_p()
+        check(load().sga_occupancy_export(ctx.h, self.h, float(threshold), OCCUPANCY_STATES["occupied"], self.cells, None, None, C.byref(count), C.byref(h)))
+        return PointCloud(ctx=ctx, _handle=h)
+
+    def download(self, ctx=None):
+        """The raw arrays: (stamp (nz, ny, nx) uint32, log-odds (nz, ny, nx) float32)."""
+        shape = (self.dims[2], self.dims[1], self.dims[0])
+        stamp, lo = np.empty(shape, np.uint32), np.empty(shape, np.float32)
+        check(load().sga_occupancy_download((ctx or self.ctx).h, self.h, stamp.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(lo)))
+        return stamp, lo
+
+
+def occupancy_launches():
+    """Diagnostics (sga_debug_occupancy_launches): commands enqueued so far by the OccupancyGrid calls (create two, clear one, integrate
+    two — one with mode 1 —, classify one plus the compaction's two, stats one, export one plus two when it fills)."""
+    return _launches("sga_debug_occupancy_launches")
+
+
+def occupancy_waits():
+    """Diagnostics (sga_debug_occupancy_waits): host waits so far of the OccupancyGrid calls (integrate: none, one with statistics)."""
+    return _launches("sga_debug_occupancy_waits")
+
+
 def _launches(name):
     v = C.c_ulonglong()
     check(getattr(load(), name)(C.byref(v)))

@@ -862,6 +862,46 @@ def run_synthetic_movers(num_frames=8, radius=0.5, min_size=10, min_points=1, do
     return out
 
 
+def run_synthetic_occupancy(num_frames=8, mover=True, mode=0, leaf=0.5, extent=(50.0, 32.0, 6.0), offset=(-10.13, -15.87, -2.31), min_range=1.0, max_range=40.0, threshold=0.0, window=5, poses=None,
+                            ctx=None, **scan):
+    """What is free, what is occupied?  The raw synthetic scans (synthetic.kitti_like_scan, keyword arguments beyond the named ones go
+    to it; mover: through synthetic.with_moving_sphere at synthetic.mover_centre(frame)) are ray-cast into ONE OccupancyGrid (DESIGN.md
+    section 3.29) at the poses SubmapOdometry(window) estimates for them (poses: a list of 4x4 world poses to use in their place, e.g.
+    the generator's).  The grid has cells of `leaf` metres over `extent` metres from the first sensor's position plus `offset`.  mode 1
+    integrates the endpoints only: the baseline without free space.  Returns a dict: "mode", "frames", "cells" (the unknown / free /
+    occupied counts and the epoch), "ghost_cells" — the occupied cells whose centre lies within one radius of the mover's centre at an
+    EARLIER frame and outside 1.1 radii of its centre at the last: the trail it left in the map (0 without a mover) —, "ghost_indices"
+    (their linear indices), "scan_stats" (per scan), "poses" (world) and the objects behind them: "grid"."""
+    from . import synthetic
+
+    ctx = ctx or api.default_context()
+    raw = []
+    for f in range(num_frames):
+        pts, Tws = synthetic.kitti_like_scan(f, **scan)
+        if mover:
+            pts, _ = synthetic.with_moving_sphere(pts, Tws, synthetic.mover_centre(f))
+        raw.append((pts, Tws))
+    T0 = raw[0][1]
+    if poses is None:
+        odom = SubmapOdometry(window=window)
+        poses = [T0 @ odom.estimate(pts) for pts, _ in raw]  # the estimates are in the first scan's frame
+        odom.close()
+    origin = T0[:3, 3] + np.asarray(offset, dtype=np.float64)
+    dims = [max(1, int(np.ceil(e / leaf))) for e in extent]
+    grid = api.OccupancyGrid(origin, leaf, dims, ctx=ctx)
+    stats = [grid.integrate(api.PointCloud(pts, ctx=ctx), T, min_range, max_range, mode, return_stats=True) for (pts, _), T in zip(raw, poses)]
+    found = grid.export(threshold, "occupied")
+    ghosts = np.zeros(0, np.int64)
+    if mover and num_frames > 1:
+        radius = 1.0
+        w = found["cloud"].xyz64()  # the centres, in the world
+        trail = np.zeros(len(w), bool)
+        for f in range(num_frames - 1):
+            trail |= np.linalg.norm(w - synthetic.mover_centre(f), axis=1) <= radius
+        ghosts = found["indices"][trail & (np.linalg.norm(w - synthetic.mover_centre(num_frames - 1), axis=1) > 1.1 * radius)]
+    return {"mode": mode, "frames": num_frames, "cells": grid.stats(threshold), "ghost_cells": int(len(ghosts)), "ghost_indices": ghosts, "scan_stats": stats, "poses": list(poses), "grid": grid}
+
+
 def run_synthetic_ground(num_frames=4, distance_threshold=0.1, iterations=256, seed=0, max_angle_degrees=15.0, downsampling_resolution=0.25, radius=0.5, min_size=10, ctx=None):
     """The objects that stand on the ground.  For each raw synthetic.kitti_like_scan(f): the ground is the plane PointCloud.segment_plane
     finds under the constraint axis = +z within max_angle_degrees (keep="rest"), the rest is downsampled at
