@@ -1045,6 +1045,56 @@ int sga_align(sga_context* ctx, const sga_index* target, const sga_cloud* source
 /* Same, on an existing problem (re-uses the sorted source and the factor buffers). */
 int sga_align_problem(sga_context* ctx, sga_problem* problem, const double init_T[16], const sga_registration_setting* setting, sga_result* out);
 
+/* ---- sweep registration: the pose and the twist of a RAW sweep at once ---------------------------------------
+ * State: T (column-major 4x4, target <- sensor at ref_time) and twist xi (6 values, rotation first, sga_se3_exp's convention: the
+ * sensor's motion per unit of time, as in sga_cloud_deskew).  Source point i with the time s_i = times[i] (a host float array in the
+ * cloud's storage order; it reaches the device through the staging ring) has a pose of its own:  a_i = double(s_i) - ref_time,
+ * E_i = exp(a_i xi) (evaluated without cancellation, as sga_cloud_deskew does), p'_i = E_i p_i, q_i = T p'_i.  Its pair j is the exact
+ * nearest target record of float(q_i) — sga_cloud_overlap's walk, the bound widened by |q_i - float(q_i)|, the winner's distance
+ * measured again in double — rejected when d^2 > max_dist_sq (max_dist_sq < 0: no rejector); a point with a non-finite coordinate or
+ * time has no pair.  Per pair, in double from the fp32 records:  r = t_j - q_i,  J_T = [R_T skew(p'_i) | -R_T],
+ * J_xi = J_T a_i J_l(a_i xi) with J_l(x) = sum_k ad(x)^k / (k + 1)! the left Jacobian of SE(3) (its series, cut where the terms left out
+ * are below 1e-17 of J_T),  J = [J_T | J_xi];  H = sum J^T M J (12 x 12, row-major, order [pose: rx ry rz tx ty tz | twist: the same]),
+ * b = sum J^T M r,  e = sum r^T M r / 2, with M = (C^t_j + (R_T R_Ei) C_i (R_T R_Ei)^T)^-1 (SGA_GICP), diag(n_j^2) (SGA_PLANE_ICP) or I
+ * (SGA_ICP).  params->math_mode is not read.  The sums are formed without floating-point atomics in an order that depends on nothing
+ * but n: two calls give the same bytes.  A call is TWO launches and one host wait; an empty source launches nothing and gives zeros.
+ * Target: a kd-tree (voxel maps and projective searches: SGA_ERR_UNSUPPORTED); GICP needs covariances on both sides (SGA_ERR_INVALID),
+ * PLANE_ICP target normals (SGA_ERR_UNSUPPORTED), as in sga_linearize.  Refusals before any handle is read: NULL arguments (nearest may
+ * be NULL), a non-finite entry of T, twist or ref_time (SGA_ERR_INVALID), a robust kernel (SGA_ERR_UNSUPPORTED).  Then: another device,
+ * 2^31 points or more, times in device memory, and a twist with max_i |a_i| (|omega| + |v|) > 8, where the series is not summed
+ * (SGA_ERR_INVALID).
+ * nearest (or NULL; room for n): the pair's ORIGINAL target index, -1 without a pair. */
+int sga_sweep_linearize(sga_context* ctx, const sga_index* target, const sga_cloud* source, const float* times, const sga_factor_params* params, const double T[16], const double twist[6], double ref_time, double H[144],
+                        double b[12], double* e, uint64_t* num_inliers, int64_t* nearest /* n, or NULL */);
+/* e at another state (T, twist) over the pairs — and, for GICP, the M — of the last sga_sweep_linearize of this (ctx, target, source,
+ * factor kind), which the context keeps: Reduction::error for a sweep.  Two launches, one wait.  SGA_ERR_INVALID without such a
+ * linearization; the other refusals are sga_sweep_linearize's. */
+int sga_sweep_error(sga_context* ctx, const sga_index* target, const sga_cloud* source, const float* times, const sga_factor_params* params, const double T[16], const double twist[6], double ref_time, double* e);
+typedef struct sga_sweep_params {
+  double ref_time;              /* default 1.0 */
+  double twist_prior[6];        /* default 0 */
+  double twist_information[36]; /* symmetric, PSD; all zero (default) = no prior */
+} sga_sweep_params;
+typedef struct sga_sweep_result {
+  double T_target_source[16];
+  double twist[6];
+  int converged;
+  uint64_t iterations, num_inliers;
+  double H[144]; /* the last linearization, the prior included */
+  double b[12];
+  double error;
+} sga_sweep_result;
+void sga_sweep_params_default(sga_sweep_params* p); /* ref_time 1.0, no prior */
+/* The loop of sga_align in 12 dimensions:  (H + lambda I) delta = -b by an LDL^T in double,  T <- T exp(delta[0:6]),
+ * xi <- xi + delta[6:12];  LM (the default) takes a trial's error from sga_sweep_error and handles lambda as sga_align does, GN uses
+ * gn_lambda;  converged when BOTH halves of delta meet rotation_eps / translation_eps.  The prior adds twist_information to the twist
+ * block of H, twist_information (xi - twist_prior) to b and (xi - twist_prior)^T twist_information (xi - twist_prior) / 2 to e, on the
+ * host.  init_T NULL: the identity; init_twist NULL: zero.  An empty source: SGA_OK with the initial state, converged = 0, nothing
+ * launched.  Refusals before any handle is read: those of sga_sweep_linearize, a non-finite entry of the prior or of its information, an
+ * information that is not symmetric (SGA_ERR_INVALID), restrict_dof_lambda > 0 (SGA_ERR_UNSUPPORTED). */
+int sga_align_sweep(sga_context* ctx, const sga_index* target, const sga_cloud* source, const float* times, const double init_T[16] /* or NULL */, const double init_twist[6] /* or NULL */,
+                    const sga_registration_setting* setting, const sga_sweep_params* sweep_params, sga_sweep_result* out);
+
 /* ---- several independent registrations in one chain of launches ---------------------------------------------------------------------
  * A batch pairs `count` existing problems of ONE context (it borrows them: the caller keeps ownership and destroys the batch first).
  * One linearization of the batch is ONE search + factor launch over the tiles of all its active pairs, ONE row reduction and ONE

@@ -1486,4 +1486,60 @@ RegistrationResult align(const std::vector<std::array<T, D>>& target, const std:
   return align(*target_points, *source_points, *target_tree, init_T, setting);
 }
 
+// ---- sweep registration: the pose and the twist of a raw sweep at once (sga_align_sweep) -------------------------
+/// What align_sweep takes beyond a registration's setting (sga_sweep_params with its defaults): the time the pose refers to, the initial
+/// twist ([rx ry rz tx ty tz], the sensor's motion per unit of time) and a Gaussian prior on the twist (information all zero: none).
+struct SweepParams {
+  double ref_time = 1.0;
+  std::array<double, 6> init_twist{};
+  std::array<double, 6> twist_prior{};
+  std::array<double, 36> twist_information{};  // 6x6 row-major, symmetric
+};
+/// sga_sweep_result: T_target_source is target <- sensor at ref_time; H (12x12, row-major) and b in the order [pose | twist]
+struct SweepResult {
+  Isometry3d T_target_source = Isometry3d::Identity();
+  std::array<double, 6> twist{};
+  bool converged = false;
+  size_t iterations = 0;
+  size_t num_inliers = 0;
+  std::array<double, 144> H{};
+  std::array<double, 12> b{};
+  double error = 0.0;
+};
+/// The raw sweep `source` — point i measured at times[i] in the sensor frame of that instant; times.size() == source.size() — registered
+/// against `target` through its KdTree, the pose and the twist estimated together.  ICP, PLANE_ICP (target normals) or GICP (covariances
+/// on both sides); setting.type VGICP is refused by the library's kd-tree check.
+inline SweepResult align_sweep(const PointCloud& target, const PointCloud& source, const std::vector<float>& times, const KdTree& target_tree, const Isometry3d& init_T = Isometry3d::Identity(),
+                               const SweepParams& params = SweepParams(), const RegistrationSetting& setting = RegistrationSetting()) {
+  (void)target;
+  if (times.size() != source.size()) throw std::invalid_argument("align_sweep: one time per point of the sweep");
+  check(sga_index_refresh_attributes(source.ctx, target_tree.h, target_tree.points->h), "sga_index_refresh_attributes");
+  sga_registration_setting s;
+  sga_registration_setting_default(&s);
+  s.factor.factor_kind = setting.type == RegistrationSetting::ICP ? SGA_ICP : setting.type == RegistrationSetting::PLANE_ICP ? SGA_PLANE_ICP : SGA_GICP;
+  s.factor.max_dist_sq = setting.max_correspondence_distance * setting.max_correspondence_distance;
+  s.rotation_eps = setting.rotation_eps;
+  s.translation_eps = setting.translation_eps;
+  s.max_iterations = setting.max_iterations;
+  s.verbose = setting.verbose ? 1 : 0;
+  sga_sweep_params p;
+  sga_sweep_params_default(&p);
+  p.ref_time = params.ref_time;
+  std::memcpy(p.twist_prior, params.twist_prior.data(), sizeof(p.twist_prior));
+  std::memcpy(p.twist_information, params.twist_information.data(), sizeof(p.twist_information));
+  static const float no_time = 0.f;  // (an empty sweep: a pointer that is not NULL; nothing is read)
+  sga_sweep_result r;
+  check(sga_align_sweep(source.ctx, target_tree.h, source.h, times.empty() ? &no_time : times.data(), init_T.data(), params.init_twist.data(), &s, &p, &r), "sga_align_sweep");
+  SweepResult out;
+  std::memcpy(out.T_target_source.m.data(), r.T_target_source, sizeof(double) * 16);
+  std::memcpy(out.twist.data(), r.twist, sizeof(double) * 6);
+  out.converged = r.converged != 0;
+  out.iterations = r.iterations;
+  out.num_inliers = r.num_inliers;
+  std::memcpy(out.H.data(), r.H, sizeof(double) * 144);
+  std::memcpy(out.b.data(), r.b, sizeof(double) * 12);
+  out.error = r.error;
+  return out;
+}
+
 }  // namespace small_gicp_amd

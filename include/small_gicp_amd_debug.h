@@ -113,6 +113,9 @@ int sga_debug_cloud_outliers_launches(unsigned long long* launches);
  * and, when a cloud is made, the compaction's table copy and the compaction: four, whatever the cloud's size and the kind of target.  An
  * empty cloud enqueues nothing.  (The compaction of an overlap call is counted here, not by sga_debug_cloud_outliers_launches.) */
 int sga_debug_cloud_overlap_launches(unsigned long long* launches);
+/* Launches enqueued so far, in this process, by sga_sweep_linearize, sga_sweep_error and sga_align_sweep: two per pass (the pass kernel
+ * and the sum of its rows), whatever the cloud's size; an empty source and a refused call enqueue nothing. */
+int sga_debug_sweep_launches(unsigned long long* launches);
 /* Commands enqueued so far, in this process, by sga_cloud_visibility: per call the fill that clears the range image, the image kernel
  * (none for an empty scan), the states and the counts — four for a statistics-only call, three with an empty scan — and, when a cloud is
  * made, the compaction's table copy and the compaction: six / five.  An empty map enqueues nothing, unless the range image is asked for:

@@ -55,6 +55,27 @@ class ResultC(C.Structure):
     ]
 
 
+class SweepParams(C.Structure):
+    """sga_sweep_params: ref_time, the prior on the twist and its information (row-major 6 x 6; all zero: no prior)."""
+
+    _fields_ = [("ref_time", C.c_double), ("twist_prior", C.c_double * 6), ("twist_information", C.c_double * 36)]
+
+
+class SweepResultC(C.Structure):
+    """sga_sweep_result"""
+
+    _fields_ = [
+        ("T_target_source", C.c_double * 16),
+        ("twist", C.c_double * 6),
+        ("converged", C.c_int),
+        ("iterations", C.c_uint64),
+        ("num_inliers", C.c_uint64),
+        ("H", C.c_double * 144),
+        ("b", C.c_double * 12),
+        ("error", C.c_double),
+    ]
+
+
 REJECTOR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_ubyte))
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)  # sga_allreduce_fn
 LINEARIZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64))
@@ -410,6 +431,13 @@ SYMBOLS = [
     ("sga_registration_setting_default", None, [C.POINTER(RegistrationSettingC)]),
     ("sga_align", C.c_int, [_vp, _vp, _vp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(ResultC)]),
     ("sga_align_problem", C.c_int, [_vp, _vp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(ResultC)]),
+    ("sga_sweep_params_default", None, [C.POINTER(SweepParams)]),
+    # ctx, target, source, times, factor params, T, twist, ref_time, H144, b12, e, num_inliers, nearest
+    ("sga_sweep_linearize", C.c_int, [_vp, _vp, _vp, _fp, C.POINTER(FactorParams), _dp, _dp, C.c_double, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    ("sga_sweep_error", C.c_int, [_vp, _vp, _vp, _fp, C.POINTER(FactorParams), _dp, _dp, C.c_double, _dp]),
+    # ctx, target, source, times, init_T, init_twist, setting, sweep params, result
+    ("sga_align_sweep", C.c_int, [_vp, _vp, _vp, _fp, _dp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(SweepParams), C.POINTER(SweepResultC)]),
+    ("sga_debug_sweep_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, _pvp]),
     ("sga_multi_destroy", C.c_int, [_vp]),
     ("sga_multi_num_devices", C.c_int, [_vp]),

@@ -2799,3 +2799,113 @@ def align(
     target_tree.refresh_attributes()
     setting = make_setting(registration_type, max_correspondence_distance, max_iterations, verbose=verbose, **kw)
     return Problem(target_tree, source, init_T_target_source).align(setting, init_T_target_source)
+
+
+# ---- sweep registration: the pose and the twist of a raw sweep at once ------------------------------------------
+class SweepResult:
+    """sga_sweep_result: T_target_source (4x4, target <- sensor at ref_time), twist (6,), converged, iterations, num_inliers, H (12x12)
+    and b (12) of the last linearization (order [pose | twist], the prior included) and error."""
+
+    def __init__(self, rc=None):
+        if rc is None:
+            self.T_target_source, self.twist = np.eye(4), np.zeros(6)
+            self.converged, self.iterations, self.num_inliers = False, 0, 0
+            self.H, self.b, self.error = np.zeros((12, 12)), np.zeros(12), 0.0
+        else:
+            self.T_target_source = np.array(rc.T_target_source).reshape(4, 4).T.copy()
+            self.twist = np.array(rc.twist)
+            self.converged = bool(rc.converged)
+            self.iterations = int(rc.iterations)
+            self.num_inliers = int(rc.num_inliers)
+            self.H = np.array(rc.H).reshape(12, 12)
+            self.b = np.array(rc.b)
+            self.error = float(rc.error)
+
+    def __repr__(self):
+        return f"SweepResult(converged={self.converged}, iterations={self.iterations}, num_inliers={self.num_inliers}, error={self.error:.6g})"
+
+
+def _sweep_inputs(target, source, times, target_tree, registration_type):
+    """The clouds, the tree and the times of a sweep call.  Arrays are uploaded as they are (no voxel grid: it cannot carry times) and
+    given what the factor needs (10 neighbours, as align's preprocessing); PointClouds are taken as they are."""
+    kind = _FACTOR_BY_NAME[registration_type] if isinstance(registration_type, str) else int(registration_type)
+    made_target = not isinstance(target, PointCloud)
+    if made_target:
+        target = PointCloud(np.asarray(target))
+    if not isinstance(source, PointCloud):
+        source = PointCloud(np.asarray(source), ctx=target.ctx)
+        if kind == GICP and source.size() > 0:
+            estimate_covariances(source, None, 10)
+    if target_tree is None:
+        target_tree = KdTree(target)
+        if made_target and target.size() > 0 and kind != ICP:
+            _estimate(target, target_tree, 10, 3)
+    target_tree.refresh_attributes()
+    t = np.ascontiguousarray(np.asarray(times, dtype=np.float32).reshape(-1))
+    if len(t) != source.size():
+        raise ValueError(f"{len(t)} times for a cloud of {source.size()} points")
+    if len(t) == 0:
+        t = np.zeros(1, np.float32)  # (a pointer that is not NULL; nothing is read)
+    return target_tree, source, t
+
+
+def _twist6(twist):
+    return np.zeros(6) if twist is None else np.ascontiguousarray(np.asarray(twist, dtype=np.float64).reshape(6))
+
+
+def linearize_sweep(target, source, times, target_tree=None, T=None, twist=None, ref_time=1.0, registration_type="GICP", max_correspondence_distance=1.0, setting=None, return_nearest=True):
+    """sga_sweep_linearize at the state (T, twist): (H (12,12), b (12,), e, num_inliers, nearest) — nearest (N,) int64, the pair's index
+    in the target's own order, -1 without a pair (None with return_nearest=False)."""
+    tree, source, t = _sweep_inputs(target, source, times, target_tree, registration_type)
+    fp = setting.factor if setting is not None else make_setting(registration_type, max_correspondence_distance).factor
+    H, b = np.empty(144), np.empty(12)
+    e, ninl = C.c_double(), C.c_uint64()
+    nearest = np.empty(source.size(), np.int64) if return_nearest else None
+    t16, xi = _T16(np.eye(4) if T is None else T), _twist6(twist)
+    check(load().sga_sweep_linearize(source.ctx.h, tree.h, source.h, _fp(t), C.byref(fp), _dp(t16), _dp(xi), float(ref_time), _dp(H), _dp(b), C.byref(e), C.byref(ninl),
+                                     nearest.ctypes.data_as(C.POINTER(C.c_int64)) if return_nearest and source.size() > 0 else None))
+    return H.reshape(12, 12), b, e.value, ninl.value, nearest
+
+
+def sweep_error(target, source, times, target_tree=None, T=None, twist=None, ref_time=1.0, registration_type="GICP", max_correspondence_distance=1.0, setting=None):
+    """sga_sweep_error: e at (T, twist) over the pairs of the last linearize_sweep of the same target_tree and source (pass the same
+    PointCloud and KdTree objects: arrays would be uploaded again, and be another source)."""
+    tree, source, t = _sweep_inputs(target, source, times, target_tree, registration_type)
+    fp = setting.factor if setting is not None else make_setting(registration_type, max_correspondence_distance).factor
+    e = C.c_double()
+    t16, xi = _T16(np.eye(4) if T is None else T), _twist6(twist)
+    check(load().sga_sweep_error(source.ctx.h, tree.h, source.h, _fp(t), C.byref(fp), _dp(t16), _dp(xi), float(ref_time), C.byref(e)))
+    return e.value
+
+
+def _sweep_params(ref_time=1.0, twist_prior=None, twist_information=None):
+    p = _lib.SweepParams()
+    load().sga_sweep_params_default(C.byref(p))
+    p.ref_time = float(ref_time)
+    if twist_prior is not None:
+        for k, v in enumerate(np.asarray(twist_prior, dtype=np.float64).reshape(6)):
+            p.twist_prior[k] = float(v)
+    if twist_information is not None:
+        for k, v in enumerate(np.asarray(twist_information, dtype=np.float64).reshape(36)):
+            p.twist_information[k] = float(v)
+    return p
+
+
+def align_sweep(target, source, times, target_tree=None, init_T=None, init_twist=None, ref_time=1.0, registration_type="GICP", max_correspondence_distance=1.0, twist_prior=None, twist_information=None, setting=None):
+    """The pose (target <- sensor at ref_time) and the twist (the sensor's motion per unit of time, [rx ry rz tx ty tz]) of the raw sweep
+    `source` — point i measured at times[i] in the sensor frame of that instant — against `target`, estimated together
+    (sga_align_sweep): a SweepResult.  twist_prior / twist_information (6,) / (6,6): a Gaussian prior on the twist; None: none.
+    target / source: PointClouds (with target_tree, or a tree is built) or arrays, which are uploaded as they are."""
+    tree, source, t = _sweep_inputs(target, source, times, target_tree, registration_type)
+    st = setting if setting is not None else make_setting(registration_type, max_correspondence_distance)
+    p = _sweep_params(ref_time, twist_prior, twist_information)
+    rc = _lib.SweepResultC()
+    t16 = None if init_T is None else _T16(init_T)
+    xi = None if init_twist is None else _twist6(init_twist)
+    check(load().sga_align_sweep(source.ctx.h, tree.h, source.h, _fp(t), _dp(t16), _dp(xi), C.byref(st), C.byref(p), C.byref(rc)))
+    return SweepResult(rc)
+
+
+def sweep_launches():
+    """Diagnostics (sga_debug_sweep_launches): launches enqueued so far by the sweep calls, two per pass."""
+    return _launches("sga_debug_sweep_launches")

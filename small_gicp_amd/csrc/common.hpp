@@ -179,6 +179,16 @@ struct sga_context {
   sga_allreduce_fn comm_fn = nullptr;  // caller-supplied sum over ranks (sga_comm_init_callback) instead of RCCL
   void* comm_user = nullptr;
   bool sharded() const { return comm != nullptr || comm_fn != nullptr; }
+  // sweep registration (sweep.hip): the pairs of the last sga_sweep_linearize — the winner's kd position per
+  // source point (-1: no pair) and, for GICP, the six entries of its M (entry-major: [k * n + i]) — with what they belong to, and the
+  // workgroups' rows of partial sums (grow-only)
+  sga::DevBuf<int> sweep_j;
+  sga::DevBuf<double> sweep_m, sweep_partials;
+  const sga_cloud* sweep_source = nullptr;
+  const sga_index* sweep_target = nullptr;
+  unsigned long long sweep_source_serial = 0, sweep_target_serial = 0;  // (a handle's address may be handed out again)
+  size_t sweep_n = 0;
+  int sweep_factor = -1;
 };
 
 // cloud_io.hip: the context's pinned staging ring.  A slot with room for `bytes` (grow-only); a slot handed out before is reused only after
@@ -229,8 +239,18 @@ void pose_to_device(const double T[16], const double o_s[3], const double o_t[3]
 void system_to_caller(const double o_s[3], double H[36], double b[6]);
 }  // namespace sga
 
+namespace sga {
+// a number no other cloud or index of this process carries: what remembers a handle (the sweep pairs of a context) can tell it from a
+// later one at the same address
+inline unsigned long long next_serial() {
+  static std::atomic<unsigned long long> serial{0};
+  return ++serial;
+}
+}  // namespace sga
+
 struct sga_cloud {
   int device = 0;
+  unsigned long long serial = sga::next_serial();
   mutable sga::Ready ready;
   size_t n = 0;
   double origin[3] = {0, 0, 0};  // the device holds p - origin (see "device frames" above)
@@ -257,6 +277,7 @@ constexpr int kFlatCap = 16;  // point slots per voxel of a flat map (max_num_po
 struct sga_index {
   int kind = SGA_INDEX_KDTREE;
   int device = 0;
+  unsigned long long serial = sga::next_serial();
   mutable sga::Ready ready;
   size_t n = 0;  // points (kd-tree) or voxels (voxel map)
   double origin[3] = {0, 0, 0};  // device frame of the fp32 records (kd-tree: the cloud's; voxel maps: of the exported means / points — voxel

@@ -22,8 +22,24 @@ class OnlineOdometry:
     and the context's RCCL communicator (Context.comm_init) sums the shards' systems once per linearization / error pass, so every rank
     computes the same pose."""
 
-    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None, outlier_k=None, outlier_std_mul=1.0):
+    def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None, outlier_k=None, outlier_std_mul=1.0,
+                 estimate_twist=False, twist_prior_information=None, sweep_points=12000):
         self.shard = shard
+        # estimate_twist (False: off, the default — a sweep is deskewed with the previous motion): a RAW sweep is registered against the
+        # previous deskewed scan by api.align_sweep (DESIGN.md section 3.30), which estimates its pose and its twist together — from the
+        # previous motion as the initial twist AND the initial pose, or from zero and the identity when there is none — and the sweep is then
+        # deskewed with the ESTIMATED twist, downsampled, and registered rigidly once more from the sweep's pose (the sample's pose refined).
+        # What is registered is an even sample of at most sweep_points of the (cropped) raw points, taken with PointCloud.selected so that
+        # the times follow; the voxel grid cannot carry times.  twist_prior_information (None: no prior; a number w: w I; or (6,6)): the
+        # information of a Gaussian prior on the twist centred on the previous motion, once there is one.
+        self.estimate_twist = bool(estimate_twist)
+        self.sweep_points = int(sweep_points)
+        if twist_prior_information is None:
+            self.twist_information = None
+        else:
+            w = np.asarray(twist_prior_information, dtype=np.float64)
+            self.twist_information = w * np.eye(6) if w.ndim == 0 else w.reshape(6, 6)
+        self.twists = []  # estimate_twist: the twist of every registered sweep
         # outlier_k (None: off, the default): every downsampled scan loses its isolated returns on the device (PointCloud.without_outliers:
         # the mean distance to outlier_k neighbours above mean + outlier_std_mul * stddev) after the voxel grid and before the kd-tree and
         # the covariances.  None: no such call is made.
@@ -72,7 +88,9 @@ class OnlineOdometry:
         raw = api.PointCloud(points, ctx=self.ctx)
         if self.crop is not None:
             raw, times = self._cropped(raw, times)
-        bootstrap = times is not None and self.motion is None and self.target is not None  # the first registration of a sequence of sweeps
+        if self.estimate_twist and times is not None and self.target is not None:
+            return self._estimate_sweep(raw, times, t0)
+        bootstrap =times is not None and self.motion is None and self.target is not None  # the first registration of a sequence of sweeps
         if times is not None and self.motion is not None:
             raw = raw.deskewed(times, api.se3_log(self.motion), 1.0)
         cloud = self._downsampled(raw)
@@ -103,6 +121,41 @@ class OnlineOdometry:
         self.total_ms.append(1e3 * (t2 - t0))
         return self.T_world.copy()
 
+    def _estimate_sweep(self, raw, times, t0):
+        """estimate_twist: the raw sweep's pose and twist from api.align_sweep over an even sample of it, then the sweep deskewed with that
+        twist as the next target.  (The times are a host array here: a sample's times are gathered on the host.)"""
+        if self.shard is not None:
+            raise ValueError("estimate_twist is not available on a sharded estimator")
+        times = np.ascontiguousarray(np.asarray(times, dtype=np.float32).reshape(-1))
+        n = raw.size()
+        idx = np.arange(0, n, max(1, -(-n // max(1, self.sweep_points))), dtype=np.int64)
+        sample = raw if len(idx) == n else raw.selected(idx)
+        self.ctx.synchronize()
+        t1 = time.perf_counter()
+        api.estimate_covariances(sample, None, self.k)
+        tgt_cloud, tgt_tree = self.target
+        centre = None if self.motion is None else api.se3_log(self.motion)
+        prior = self.twist_information if centre is not None else None
+        # under a constant twist the pose at the sweep's end, seen from its start, is exp(twist): the previous motion is the guess for both
+        # (from the identity a step of more than the correspondence distance is outside the loop's reach: 1.4 m errors on the slalom)
+        init_T = self.motion if self.motion is not None else np.eye(4)
+        res = api.align_sweep(tgt_cloud, sample, times[idx], tgt_tree, init_T=init_T, init_twist=centre, ref_time=1.0, twist_prior=centre if prior is not None else None, twist_information=prior, setting=self.setting)
+        pose = res.T_target_source
+        self.twists.append(res.twist)
+        self.iterations.append(res.iterations + 1)
+        cloud = self._downsampled(raw.deskewed(times, res.twist, 1.0))
+        tree = api.KdTree(cloud)
+        api.estimate_covariances(cloud, tree, self.k)
+        # the deskewed scan, at the voxel grid's full density, registered rigidly from the sweep's pose: the sample's pose refined
+        pose = api.Problem(tgt_tree, tree, pose).align(self.setting, pose).T_target_source
+        self.T_world = self.T_world @ pose
+        self.motion = pose
+        self.ctx.synchronize()
+        t2 = time.perf_counter()
+        self.target = (cloud, tree)
+        self.reg_ms.append(1e3 * (t2 - t1))
+        self.total_ms.append(1e3 * (t2 - t0))
+        return self.T_world.copy()
 
     def _downsampled(self, raw):
         """The voxel grid of the raw cloud and, when outlier_k is given, that cloud without its isolated returns (a temporary tree: the
@@ -488,7 +541,7 @@ class PipelinedOdometry:
         return poses, wall, iters
 
 
-def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_range=None, max_range=None, outliers=False, outlier_share=0.01, **kw):
+def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_range=None, max_range=None, outliers=False, outlier_share=0.01, trajectory="arc", n_rings=64, n_az=2030, **kw):
     """Drive OnlineOdometry over the frozen KITTI-shaped synthetic sequence (small_gicp_amd.synthetic.kitti_like_scan).
     pinned: the scans are held in pinned host memory (api.pinned_copy) before the timed loop, like a driver that reads its scans into
     memory from sga_host_alloc — the reference's benchmark holds them in host memory too (benchmark/benchmark_odom.hpp:36-47); the upload
@@ -498,9 +551,15 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
     withholds the times, so the skewed sweeps are registered as if they were snapshots (what the deskew is compared against).
     min_range / max_range: the estimator crops every scan to these ranges on the device first (OnlineOdometry); both None: no crop.
     outliers: outlier_share of every scan's returns (1 % by default) are replaced by isolated returns along their own rays
-    (synthetic.with_isolated_returns, seeded by the frame); outlier_k= / outlier_std_mul= (OnlineOdometry) remove them on the device."""
+    (synthetic.with_isolated_returns, seeded by the frame); outlier_k= / outlier_std_mul= (OnlineOdometry) remove them on the device.
+    trajectory: "arc" (the default: synthetic._sensor_pose, constant speed and yaw rate) or "slalom" (synthetic.slalom_pose: both change
+    from frame to frame; sweep f is synthetic.sweep_between(slalom_pose(f), slalom_pose(f + 1)), a snapshot synthetic.scan_at(slalom_pose(f))).
+    n_rings / n_az: the sensor's rays.  estimate_twist= / twist_prior_information= (OnlineOdometry): sweeps are registered with their
+    twist free (api.align_sweep) instead of being deskewed with the previous motion; "twists" then holds the estimates."""
     from . import synthetic
 
+    if trajectory not in ("arc", "slalom"):
+        raise ValueError("trajectory must be 'arc' or 'slalom'")
     odom = OnlineOdometry(min_range=min_range, max_range=max_range, **kw)
     est, gt, sizes = [], [], []
     # every scan is in host memory before the loop starts, as in the reference's driver (benchmark/benchmark_odom.hpp:36-47; the generator
@@ -508,10 +567,16 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
     scans, stamps, T0 = [], [], None
     for f in range(num_frames):
         if sweeps:
-            pts, ts, Tws = synthetic.kitti_like_sweep(f + 1)[:3]
+            if trajectory == "slalom":
+                pts, ts, Tws = synthetic.sweep_between(synthetic.slalom_pose(f), synthetic.slalom_pose(f + 1), n_rings=n_rings, n_az=n_az, seed=777 + f + 1)[:3]
+            else:
+                pts, ts, Tws = synthetic.kitti_like_sweep(f + 1, n_rings=n_rings, n_az=n_az)[:3]
             stamps.append(ts if times else None)
+        elif trajectory == "slalom":
+            Tws = synthetic.slalom_pose(f)
+            pts = synthetic.scan_at(Tws, n_rings=n_rings, n_az=n_az, seed=777 + f)
         else:
-            pts, Tws = synthetic.kitti_like_scan(f)
+            pts, Tws = synthetic.kitti_like_scan(f, n_rings=n_rings, n_az=n_az)
         if outliers:
             pts = synthetic.with_isolated_returns(pts, outlier_share, seed=4242 + f)[0]
         scans.append(api.pinned_copy(pts[:, :3], np.float32) if pinned else np.ascontiguousarray(pts[:, :3], dtype=np.float32))
@@ -542,6 +607,7 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
         "rpe_trans_m": rpe_t,
         "ate_trans_m_max": max(float(np.linalg.norm(e[:3, 3] - g[:3, 3])) for e, g in zip(est, gt)),
         "sweeps": bool(sweeps),
+        "twists": list(odom.twists),
         "estimated": est,
         "ground_truth": gt,
     }

@@ -174,11 +174,19 @@ def kitti_like_sweep(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02
     Returns (points in the sensor frame AT FIRING TIME float32 (N,3), times float32 (N,), T_world_sensor at the sweep's end, xi (6,),
     surface (N,): the surface each return hit, -1 = ground, else the wall number).  Deskewed with xi to ref_time = 1 — p' =
     exp((s - 1) xi) p — the points are what a rigid snapshot at T_world_sensor would have measured."""
-    from .api import se3_exp, se3_log
-
     if int(frame) < 1:
         raise ValueError("kitti_like_sweep: a sweep ends at its frame and starts at the one before, so frame >= 1")
-    T0, T1 = _sensor_pose(frame - 1), _sensor_pose(frame)
+    return sweep_between(_sensor_pose(frame - 1), _sensor_pose(frame), n_rings, n_az, layout_seed, noise, seed + frame)
+
+
+def sweep_between(T0, T1, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02, seed=777):
+    """kitti_like_sweep's casting between ANY two sensor poses: the sweep starts at T0 (T_world_sensor) and ends at T1, the sensor moving
+    with the constant twist xi = se3_log(T0^-1 T1); column c fires at s = float32((c + 0.5) / n_az) from T0 exp(s xi).  Range noise
+    N(0, noise) from default_rng(seed).  Returns what kitti_like_sweep returns: (points float32 (N,3), times float32 (N,), T1, xi (6,),
+    surface (N,))."""
+    from .api import se3_exp, se3_log
+
+    T0, T1 = np.asarray(T0, dtype=np.float64), np.asarray(T1, dtype=np.float64)
     xi = se3_log(np.linalg.inv(T0) @ T1)
     s_col = ((np.arange(n_az) + 0.5) / n_az).astype(np.float32)
     T_col = np.stack([T0 @ se3_exp(float(s) * xi) for s in s_col])  # (n_az, 4, 4)
@@ -187,10 +195,26 @@ def kitti_like_sweep(frame, n_rings=64, n_az=2030, layout_seed=12345, noise=0.02
     d = np.einsum("nij,nj->ni", T_col[col, :3, :3], d_s)
     t_best, surface = _cast(T_col[col, :3, 3], d, _walls(layout_seed))
     keep = np.isfinite(t_best) & (t_best >= 3.0) & (t_best <= 80.0)
-    rng = np.random.default_rng(seed + frame)
+    rng = np.random.default_rng(seed)
     r = t_best[keep] + rng.normal(0, noise, keep.sum())
     pts = d_s[keep] * r[:, None]
     return np.ascontiguousarray(pts, dtype=np.float32), np.ascontiguousarray(s_col[col][keep]), T1, xi, surface[keep]
+
+
+def slalom_pose(frame):
+    """T_world_sensor of a frame of the slalom: 1.8 m above ground from (-30, -20), the speed and the yaw rate changing from frame to
+    frame.  Step f (from frame f to f + 1) advances by v_f = 1.0 + 0.5 sin(0.9 f) metres along the heading psi_f and then turns by
+    w_f = 3 sin(1.3 f) degrees:  pos_{f+1} = pos_f + v_f (cos psi_f, sin psi_f, 0),  psi_{f+1} = psi_f + w_f,  psi_0 = 0.  The relative
+    motion of consecutive sweeps differs by up to 0.5 m and 3.8 degrees, so the previous motion is a poor twist for the next sweep."""
+    pos = np.array([-30.0, -20.0, 1.8])
+    psi = 0.0
+    for f in range(int(frame)):
+        pos = pos + (1.0 + 0.5 * np.sin(0.9 * f)) * np.array([np.cos(psi), np.sin(psi), 0.0])
+        psi = psi + np.deg2rad(3.0 * np.sin(1.3 * f))
+    Tws = np.eye(4)
+    Tws[:3, :3] = _rot([0, 0, 1], psi)
+    Tws[:3, 3] = pos
+    return Tws
 
 
 def with_isolated_returns(points, share=0.01, seed=4242, min_range=5.0, max_range=60.0):
