@@ -367,6 +367,12 @@ int sga_features_create(sga_context* ctx, const float* rows, size_t n, int dim, 
 int sga_features_size(const sga_features* features, size_t* n, int* dim);
 int sga_features_download(sga_context* ctx, const sga_features* features, float* rows);
 int sga_features_destroy(sga_features* features);
+/* sga_features_create / sga_features_download with the rows in device memory of the caller's ("device-resident data" below: the struct,
+ * the ordering of user_stream, the pointer checks): float or double rows of cols = dim (1..128) values, any stride >= cols; a double
+ * is rounded to fp32 once on the way in and a float widened on the way out.  One launch, none for n == 0. */
+struct sga_device_array;
+int sga_features_create_device(sga_context* ctx, const struct sga_device_array* rows, size_t n, void* user_stream, int flags, sga_features** out);
+int sga_features_export_device(sga_context* ctx, const sga_features* features, const struct sga_device_array* rows, void* user_stream, int flags);
 /* Row j of *out is row indices[j] of `features`: one gather launch, no host wait; repeats are allowed; m == 0:
  * an empty handle of the same dim, nothing launched.  Refusals (SGA_ERR_INVALID, *out = NULL): NULL ctx, features or out, indices NULL with
  * m > 0, m >= 2^31 — then: another device, an index outside the rows (named by its position), before anything is enqueued. */
@@ -747,6 +753,35 @@ int sga_problem_get_factors_device(sga_context* ctx, const sga_problem* problem,
 /* ---- preprocessing (registration_helper.cpp:22-34 preprocess_points) ----------------------------------------------- */
 /* util/downsampling.hpp:23-78 voxelgrid_sampling: centroid per occupied voxel, output in ascending packed-key order. */
 int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf_size, sga_cloud** out);
+/* The voxel grid that carries per-point columns — times, intensities, rings, labels — through the merge.
+ * *out is the cloud sga_voxelgrid_sampling makes of `in`, byte for byte; voxel v is its row v.  The members of a voxel are the input
+ * points whose voxel it is, taken in ascending original index i_0 < ... < i_{N-1}.  Row v of *out_fields holds, per column c under
+ * ops[c] (ops NULL: MEAN each):
+ *   MEAN     fl32(S / N), S the sum of the N values formed in double in an order that depends on N alone (no atomics);
+ *   MIN/MAX  the least / greatest value (equal under ==; the sign of a zero is not specified); NaN values are skipped, all NaN: NaN;
+ *   FIRST    the value of i_0, bit for bit;
+ *   NEAREST  the value, bit for bit, of the member whose fp32 record r minimises sum_a (double(r_a) - double(c_a))^2, c the fp32
+ *            record this call writes for the voxel; ties go to the lowest original index.  (What a column that must come from ONE
+ *            real return follows the grid by: a time across the seam of a sweep, a label.)
+ * counts[v] = N (or NULL; room for in's size, the first size-of-*out entries are written); voxel_of[i] = the row of input point i, -1
+ * for a point the grid drops (a non-finite coordinate, outside the grid), or NULL.  fields == NULL with out_fields == NULL: membership
+ * only.  Two calls give the same bytes in every output.  The chain is sga_voxelgrid_sampling's — keys, one sort, the runs — with ONE
+ * other last launch that writes the centroids, every reduced column, counts and voxel_of; one host wait, the voxel count.  An empty
+ * input, or one of which every point is dropped: an empty cloud and an empty features handle of the same dim.
+ * Refusals (SGA_ERR_INVALID, every out pointer NULL, nothing enqueued) — before any handle is read: NULL ctx, in or out; out_fields
+ * NULL with fields given, or the reverse; a leaf that is not positive; in the device form, whose struct tells the number of columns,
+ * a dtype, cols outside [1, 32] or stride the struct cannot have and an op outside 0..4, named by its column — then (the host form
+ * reads the number of ops from the handle: its dim and its ops are checked first): fields or a cloud of another device, 2^31 points or
+ * more, a row count other than the cloud's size; for the device form the pointer checks of sga_cloud_create_device, for fields (the
+ * last row need only reach its last column: scan[:, 3:4] of an N x 4 tensor goes down as a view), d_counts and d_voxel_of. */
+enum { SGA_REDUCE_MEAN = 0, SGA_REDUCE_MIN = 1, SGA_REDUCE_MAX = 2, SGA_REDUCE_FIRST = 3, SGA_REDUCE_NEAREST = 4 };
+int sga_voxelgrid_sampling_fields(sga_context* ctx, const sga_cloud* in, const sga_features* fields /* in's size rows, dim 1..32; or NULL */, const int* ops /* dim entries, or NULL: MEAN each */, double leaf_size, sga_cloud** out,
+                                  sga_features** out_fields /* NULL iff fields is NULL */, int32_t* counts /* or NULL */, int64_t* voxel_of /* or NULL; in's size entries */);
+/* the same with the fields in device memory of the caller's (float | double — a double is rounded to fp32 once, on entry —, cols = dim,
+ * any stride >= cols) and counts / voxel_of written to device memory; user_stream and flags order the streams as
+ * sga_cloud_create_device does */
+int sga_voxelgrid_sampling_fields_device(sga_context* ctx, const sga_cloud* in, const sga_device_array* fields, const int* ops, double leaf_size, sga_cloud** out, sga_features** out_fields, int32_t* d_counts, int64_t* d_voxel_of,
+                                         void* user_stream, int flags);
 /* sga_voxelgrid_sampling(ctx, clouds[k], leaf_size, &out[k]) for `count` clouds on the context's device in one chain of launches on the
  * context's stream — keys, ONE sort over the concatenation under the key (member << W) | the member's own short key, runs, centroids —
  * whose length does not grow with count.  out[k] is an ordinary cloud, owning its buffers, in the input's device frame, its records

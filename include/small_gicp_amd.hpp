@@ -283,6 +283,15 @@ struct Features {
     check(sga_features_select(ctx, h, indices.empty() ? nullptr : indices.data(), indices.size(), &made), "sga_features_select");
     return std::make_shared<Features>(made, ctx);
   }
+  /// Features from rows that live in device memory of the context's device (sga_features_create_device): float or double, cols = dim,
+  /// any stride >= cols; a double is rounded to float once.  stream: as PointCloud::from_device.
+  static Ptr from_device(sga_context* context, const sga_device_array& rows, size_t n, void* stream = nullptr, int flags = 0) {
+    sga_features* made = nullptr;
+    check(sga_features_create_device(context, &rows, n, stream, flags, &made), "sga_features_create_device");
+    return std::make_shared<Features>(made, context);
+  }
+  /// The rows into a device array of the caller's, cols = dim (sga_features_export_device)
+  void export_device(const sga_device_array& rows, void* stream = nullptr, int flags = 0) const { check(sga_features_export_device(ctx, h, &rows, stream, flags), "sga_features_export_device"); }
   sga_context* ctx = default_context();
   sga_features* h = nullptr;
 };
@@ -1008,6 +1017,36 @@ inline PointCloud::Ptr voxelgrid_sampling(const PointCloud& points, double leaf_
   sga_cloud* out = nullptr;
   check(sga_voxelgrid_sampling(points.ctx, points.h, leaf_size, &out), "sga_voxelgrid_sampling");
   return std::make_shared<PointCloud>(out, points.ctx);
+}
+/// How voxelgrid_sampling reduces a column of per-point fields over the members of a voxel (SGA_REDUCE_*): Nearest is the value of the
+/// member nearest the voxel's centroid — one real return's, for a time or a label.
+enum class Reduce : int { Mean = SGA_REDUCE_MEAN, Min = SGA_REDUCE_MIN, Max = SGA_REDUCE_MAX, First = SGA_REDUCE_FIRST, Nearest = SGA_REDUCE_NEAREST };
+/// What the voxel grid that carries fields returns: the cloud voxelgrid_sampling(cloud, leaf) makes, row v of `fields` the reduced
+/// columns of voxel v (null without input fields), counts[v] its members, voxel_of[i] the row of input point i (-1: dropped).
+struct GridFields {
+  PointCloud::Ptr cloud;
+  Features::Ptr fields;
+  std::vector<int32_t> counts;
+  std::vector<int64_t> voxel_of;
+};
+/// sga_voxelgrid_sampling_fields: fields one row per point (or null: membership only), ops one per column (empty: Mean each)
+inline GridFields voxelgrid_sampling(const PointCloud& cloud, const Features* fields, const std::vector<Reduce>& ops, double leaf_size, bool want_counts = false, bool want_voxel_of = false) {
+  GridFields r;
+  const size_t n = cloud.size();
+  std::vector<int> op(ops.size());
+  for (size_t c = 0; c < ops.size(); c++) op[c] = static_cast<int>(ops[c]);
+  if (fields != nullptr && !op.empty() && op.size() != static_cast<size_t>(fields->dim())) throw std::invalid_argument("voxelgrid_sampling: one reduction per column of the fields");
+  std::vector<int32_t> counts(want_counts ? n : 0);
+  r.voxel_of.resize(want_voxel_of ? n : 0);
+  sga_cloud* out = nullptr;
+  sga_features* reduced = nullptr;
+  check(sga_voxelgrid_sampling_fields(cloud.ctx, cloud.h, fields ? fields->h : nullptr, op.empty() ? nullptr : op.data(), leaf_size, &out, fields ? &reduced : nullptr, counts.empty() ? nullptr : counts.data(),
+                                      r.voxel_of.empty() ? nullptr : r.voxel_of.data()),
+        "sga_voxelgrid_sampling_fields");
+  r.cloud = std::make_shared<PointCloud>(out, cloud.ctx);
+  if (fields) r.fields = std::make_shared<Features>(reduced, cloud.ctx);
+  if (want_counts) r.counts.assign(counts.begin(), counts.begin() + static_cast<std::ptrdiff_t>(r.cloud->size()));
+  return r;
 }
 inline void estimate_normals(PointCloud& cloud, int num_neighbors = 20) {
   check(sga_estimate_normals_covariances(cloud.ctx, cloud.h, nullptr, num_neighbors, 1), "estimate_normals");

@@ -116,6 +116,10 @@ int sga_debug_cloud_overlap_launches(unsigned long long* launches);
 /* Launches enqueued so far, in this process, by sga_sweep_linearize, sga_sweep_error and sga_align_sweep: two per pass (the pass kernel
  * and the sum of its rows), whatever the cloud's size; an empty source and a refused call enqueue nothing. */
 int sga_debug_sweep_launches(unsigned long long* launches);
+/* Launches enqueued so far, in this process, by sga_voxelgrid_sampling_fields and its device form: per call the keys, the sort (counted
+ * as one), the runs and the one launch that writes centroids, columns, counts and voxel_of — four; three when a cloud above the
+ * speculative limit has no voxel and no voxel_of is asked for; none for an empty cloud and for a refused call. */
+int sga_debug_voxelgrid_fields_launches(unsigned long long* launches);
 /* Commands enqueued so far, in this process, by sga_cloud_visibility: per call the fill that clears the range image, the image kernel
  * (none for an empty scan), the states and the counts — four for a statistics-only call, three with an empty scan — and, when a cloud is
  * made, the compaction's table copy and the compaction: six / five.  An empty map enqueues nothing, unless the range image is asked for:

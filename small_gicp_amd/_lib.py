@@ -223,6 +223,7 @@ class OccupancyCounts(C.Structure):
 
 FPFH_DIM = 33
 F32, F64 = 0, 1
+REDUCE_MEAN, REDUCE_MIN, REDUCE_MAX, REDUCE_FIRST, REDUCE_NEAREST = 0, 1, 2, 3, 4  # SGA_REDUCE_*
 IO_NO_ORDER, IO_RELATIVE = 1, 2
 _da = C.POINTER(DeviceArray)
 
@@ -273,6 +274,8 @@ SYMBOLS = [
     ("sga_features_size", C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     ("sga_features_download", C.c_int, [_vp, _vp, _fp]),
     ("sga_features_destroy", C.c_int, [_vp]),
+    ("sga_features_create_device", C.c_int, [_vp, C.POINTER(DeviceArray), C.c_size_t, _vp, C.c_int, _pvp]),
+    ("sga_features_export_device", C.c_int, [_vp, _vp, C.POINTER(DeviceArray), _vp, C.c_int]),
     ("sga_cloud_fpfh", C.c_int, [_vp, _vp, _vp, C.c_int, _dp, _pvp]),
     ("sga_features_match", C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_size_t)]),
     ("sga_ransac_default", None, [C.POINTER(Ransac)]),
@@ -335,6 +338,8 @@ SYMBOLS = [
     ("sga_index_knn_device", C.c_int, [C.c_void_p, C.c_void_p, _da, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("sga_problem_get_factors_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("sga_voxelgrid_sampling", C.c_int, [_vp, _vp, C.c_double, _pvp]),
+    ("sga_voxelgrid_sampling_fields", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int), C.c_double, _pvp, _pvp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    ("sga_voxelgrid_sampling_fields_device", C.c_int, [_vp, _vp, C.POINTER(DeviceArray), C.POINTER(C.c_int), C.c_double, _pvp, _pvp, _vp, _vp, _vp, C.c_int]),
     ("sga_estimate_normals_covariances", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     ("sga_index_build_kdtree", C.c_int, [_vp, _vp, _pvp]),
     ("sga_index_build_kdtree_batch", C.c_int, [_vp, _pvp, C.c_size_t, _pvp]),
@@ -438,6 +443,7 @@ SYMBOLS = [
     # ctx, target, source, times, init_T, init_twist, setting, sweep params, result
     ("sga_align_sweep", C.c_int, [_vp, _vp, _vp, _fp, _dp, _dp, C.POINTER(RegistrationSettingC), C.POINTER(SweepParams), C.POINTER(SweepResultC)]),
     ("sga_debug_sweep_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
+    ("sga_debug_voxelgrid_fields_launches", C.c_int, [C.POINTER(C.c_ulonglong)]),
     ("sga_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, _pvp]),
     ("sga_multi_destroy", C.c_int, [_vp]),
     ("sga_multi_num_devices", C.c_int, [_vp]),

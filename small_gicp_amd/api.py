@@ -2018,6 +2018,34 @@ class Features:
         check(load().sga_features_create(f.ctx.h, _fp(a) if len(a) else None, a.shape[0], a.shape[1], C.byref(f.h)))
         return f
 
+    @staticmethod
+    def from_torch(rows, ctx=None, stream=None):
+        """Features from an (n,) / (n, dim) float32 / float64 tensor on the context's device, any row stride (sga_features_create_device:
+        one launch, nothing touches the host; a double is rounded to float32 once)."""
+        t = rows[:, None] if getattr(rows, "dim", lambda: 0)() == 1 else rows
+        a, n = _torch_rows(t, "rows", ctx, range(1, 129))
+        f = Features(ctx)
+        _torch_rows(t, "rows", f.ctx, range(1, 129))
+        check(load().sga_features_create_device(f.ctx.h, C.byref(a), int(n), C.c_void_p(_torch_stream(f.ctx, stream)), 0, C.byref(f.h)))
+        return f
+
+    def to_torch(self, dtype=None, stream=None):
+        """The rows as an (n, dim) tensor on the context's device (sga_features_export_device), allocated on `stream`."""
+        import torch
+
+        dtype = torch.float32 if dtype is None else dtype
+        if str(dtype).replace("torch.", "") not in _IO_DTYPES:
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        n, d = self._shape()
+        dev = torch.device("cuda", int(self.ctx.device))
+        s = _torch_stream(self.ctx, stream)
+        with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)) if stream is not None else torch.cuda.device(dev):
+            t = torch.empty((n, d), dtype=dtype, device=dev)
+        if n > 0:
+            a = _torch_rows(t, "rows", self.ctx, (d,))[0]
+            check(load().sga_features_export_device(self.ctx.h, self.h, C.byref(a), C.c_void_p(s), 0))
+        return t
+
     def _shape(self):
         n, d = C.c_size_t(), C.c_int()
         check(load().sga_features_size(self.h, C.byref(n), C.byref(d)))
@@ -2045,6 +2073,77 @@ class Features:
         h = C.c_void_p()
         check(load().sga_features_select(self.ctx.h, self.h, idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(idx) else None, len(idx), C.byref(h)))
         return Features(ctx=self.ctx, _handle=h)
+
+
+REDUCE = {"mean": _lib.REDUCE_MEAN, "min": _lib.REDUCE_MIN, "max": _lib.REDUCE_MAX, "first": _lib.REDUCE_FIRST, "nearest": _lib.REDUCE_NEAREST}
+
+
+def _reduce_ops(reduce, dim):
+    names = [reduce] * dim if isinstance(reduce, (str, int, np.integer)) else list(reduce)
+    if len(names) != dim:
+        raise ValueError(f"reduce names {len(names)} columns, the fields have {dim}")
+    ops = []
+    for c, r in enumerate(names):
+        if isinstance(r, str):
+            if r.lower() not in REDUCE:
+                raise ValueError(f"reduce of column {c}: {r!r} is none of {sorted(REDUCE)}")
+            r = REDUCE[r.lower()]
+        ops.append(int(r))
+    return (C.c_int * dim)(*ops)
+
+
+def voxelgrid_sampling_fields(cloud, fields, resolution, reduce="mean", return_counts=False, return_voxel_of=False, stream=None):
+    """voxelgrid_sampling(cloud, resolution) with per-point columns carried through the merge (sga_voxelgrid_sampling_fields): row v of
+    the returned Features reduces, column by column, the rows of `fields` of the points that fell into voxel v — "mean", "min", "max",
+    "first" (the member of lowest index) or "nearest" (the member nearest the centroid: a time or a label that must come from one real
+    return); one name for all columns or one per column.  fields: a numpy (n,) / (n, dim) array, a Features, a torch tensor on the
+    context's device (a view such as scan[:, 3:4] goes down as it is; counts / voxel_of are then tensors too), or None: membership only.
+    Returns (PointCloud, Features | None[, counts (M,) int32][, voxel_of (n,) int64: the row of every input point, -1 for a dropped one])."""
+    if not isinstance(cloud, PointCloud):
+        cloud = PointCloud(cloud)
+    ctx, n = cloud.ctx, cloud.size()
+    out, out_f = C.c_void_p(), C.c_void_p()
+    is_torch = fields is not None and not isinstance(fields, (Features, np.ndarray, list, tuple)) and hasattr(fields, "data_ptr")
+    if is_torch:
+        import torch
+
+        t = fields[:, None] if fields.dim() == 1 else fields
+        fa, rows = _torch_rows(t, "fields", ctx, range(1, 33))
+        if rows != n:
+            raise ValueError(f"fields have {rows} rows, the cloud has {n} points")
+        ops = _reduce_ops(reduce, fa.cols)
+        dev = torch.device("cuda", int(ctx.device))
+        s = _torch_stream(ctx, stream)
+        with torch.cuda.stream(torch.cuda.ExternalStream(s, device=dev)) if stream is not None else torch.cuda.device(dev):
+            counts = torch.empty(n, dtype=torch.int32, device=dev) if return_counts else None
+            voxel_of = torch.empty(n, dtype=torch.int64, device=dev) if return_voxel_of else None
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and n > 0 else None)  # noqa: E731
+        check(load().sga_voxelgrid_sampling_fields_device(ctx.h, cloud.h, C.byref(fa), ops, float(resolution), C.byref(out), C.byref(out_f), ptr(counts), ptr(voxel_of), C.c_void_p(s), 0))
+        res = [PointCloud(ctx=ctx, _handle=out), Features(ctx=ctx, _handle=out_f)]
+        if return_counts:
+            res.append(counts[: res[0].size()])
+    else:
+        keep = None
+        if fields is not None and not isinstance(fields, Features):
+            a = np.asarray(fields)
+            keep = fields = Features.from_array(a.reshape(len(a), -1) if a.ndim != 2 else a, ctx)
+        ops = None if fields is None else _reduce_ops(reduce, fields.dim)
+        counts = np.empty(n, np.int32) if return_counts else None
+        voxel_of = np.empty(n, np.int64) if return_voxel_of else None
+        check(load().sga_voxelgrid_sampling_fields(ctx.h, cloud.h, None if fields is None else fields.h, ops, float(resolution), C.byref(out), None if fields is None else C.byref(out_f),
+                                                   None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_int32)), None if voxel_of is None else voxel_of.ctypes.data_as(C.POINTER(C.c_int64))))
+        del keep
+        res = [PointCloud(ctx=ctx, _handle=out), None if fields is None else Features(ctx=ctx, _handle=out_f)]
+        if return_counts:
+            res.append(counts[: res[0].size()].copy())
+    if return_voxel_of:
+        res.append(voxel_of)
+    return tuple(res)
+
+
+def voxelgrid_fields_launches():
+    """Diagnostics (sga_debug_voxelgrid_fields_launches): launches enqueued so far by voxelgrid_sampling_fields, four per call."""
+    return _launches("sga_debug_voxelgrid_fields_launches")
 
 
 def compute_fpfh(points, tree=None, k=20, viewpoint=(0.0, 0.0, 0.0)):

@@ -3,6 +3,7 @@
 // the FPFH rows (a lane per bin, the weighted sum in the list's order).  Everything in double from the fp32 records; no floating-point
 // atomics: two calls give the same bytes.
 #include "cloud_ops.hpp"
+#include "device_io.hpp"
 #include "forest.hpp"
 #include "knn_wave.hpp"
 
@@ -197,6 +198,18 @@ __global__ __launch_bounds__(256) void features_gather_kernel(const float* __res
   out[t] = rows[static_cast<unsigned long long>(idx[j]) * dim + (t - j * dim)];
 }
 
+// sga_features_create_device / sga_features_export_device: value t of the handle's rows (row t / dim, column t % dim) from or to a caller's
+// strided array of floats or doubles (a double is rounded to fp32 once; a float becomes the double it is)
+template <typename T, bool kExport>
+__global__ __launch_bounds__(256) void features_rows_kernel(float* __restrict__ rows, T* __restrict__ user, uint32_t dim, uint32_t stride, unsigned long long total) {
+  const unsigned long long t = blockIdx.x * 256ull + threadIdx.x;
+  if (t >= total) return;
+  const unsigned long long j = t / dim;
+  const unsigned long long u = j * stride + (t - j * dim);
+  if constexpr (kExport) user[u] = static_cast<T>(rows[t]);
+  else rows[t] = static_cast<float>(user[u]);
+}
+
 namespace {
 
 struct IndexDestroy {
@@ -239,6 +252,69 @@ int sga_features_create(sga_context* ctx, const float* rows, size_t n, int dim, 
   }
   *out = f.release();
   return SGA_OK;
+}
+
+// the caller's array `a` of n rows against its allocation: the last row ends with its last column (a view of a wider array)
+static int features_array_check(sga_context* ctx, const sga_device_array* a, size_t n, const char* host_entry) {
+  const size_t elem = a->dtype == SGA_F64 ? 8 : 4;
+  size_t span = 0;
+  if (__builtin_mul_overflow(n - 1, static_cast<size_t>(a->stride) * elem, &span) || __builtin_add_overflow(span, static_cast<size_t>(a->cols) * elem, &span))
+    return fail(SGA_ERR_INVALID, "rows: %zu rows of stride %d overflow the address space", n, a->stride);
+  return check_device_range(ctx, a->data, span, elem, "rows", host_entry);
+}
+static int features_array_layout(const sga_device_array* a) {
+  if (a->dtype != SGA_F32 && a->dtype != SGA_F64) return fail(SGA_ERR_INVALID, "rows: dtype %d is neither SGA_F32 nor SGA_F64", a->dtype);
+  if (a->cols < 1 || a->cols > 128) return fail(SGA_ERR_INVALID, "features: dim must be in [1,128], got %d", a->cols);
+  if (a->stride < a->cols) return fail(SGA_ERR_INVALID, "rows: stride %d < cols %d", a->stride, a->cols);
+  return SGA_OK;
+}
+
+int sga_features_create_device(sga_context* ctx, const sga_device_array* rows, size_t n, void* user_stream, int flags, sga_features** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !out || !rows) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(features_array_layout(rows));
+  if (n >= (1ull << 31)) return fail(SGA_ERR_INVALID, "too many rows (%zu; limit 2^31-1)", n);
+  SGA_ENTER(ctx);
+  if (n > 0) SGA_TRY(features_array_check(ctx, rows, n, "sga_features_create"));
+  std::unique_ptr<sga_features> f;
+  SGA_TRY(features_new(ctx, n, rows->cols, &f));
+  if (n > 0) {
+    IoOrder ord;
+    SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+    const unsigned long long total = static_cast<unsigned long long>(n) * static_cast<unsigned long long>(rows->cols);
+    const dim3 grid(static_cast<unsigned>((total + 255) / 256)), block(256);
+    if (rows->dtype == SGA_F64)
+      hipLaunchKernelGGL((features_rows_kernel<const double, false>), grid, block, 0, ctx->stream, f->rows.p, static_cast<const double*>(rows->data), static_cast<uint32_t>(rows->cols), static_cast<uint32_t>(rows->stride), total);
+    else
+      hipLaunchKernelGGL((features_rows_kernel<const float, false>), grid, block, 0, ctx->stream, f->rows.p, static_cast<const float*>(rows->data), static_cast<uint32_t>(rows->cols), static_cast<uint32_t>(rows->stride), total);
+    SGA_HIP(hipGetLastError());
+    SGA_TRY(io_end(ctx, ord));
+    SGA_TRY(mark_ready(ctx, f->ready));
+  }
+  *out = f.release();
+  return SGA_OK;
+}
+
+int sga_features_export_device(sga_context* ctx, const sga_features* features, const sga_device_array* rows, void* user_stream, int flags) {
+  if (!ctx || !features || !rows) return fail(SGA_ERR_INVALID, "null argument");
+  SGA_TRY(features_array_layout(rows));
+  if (features->device != ctx->device) return fail(SGA_ERR_INVALID, "features live on another device");
+  if (rows->cols != features->dim) return fail(SGA_ERR_INVALID, "rows: cols = %d, the features have dim %d", rows->cols, features->dim);
+  if (features->n == 0) return SGA_OK;
+  SGA_ENTER(ctx);
+  SGA_TRY(features_array_check(ctx, rows, features->n, "sga_features_download"));
+  SGA_TRY(wait_ready(ctx, features->ready));
+  IoOrder ord;
+  SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+  const unsigned long long total = static_cast<unsigned long long>(features->n) * static_cast<unsigned long long>(features->dim);
+  const dim3 grid(static_cast<unsigned>((total + 255) / 256)), block(256);
+  void* data = const_cast<void*>(rows->data);  // (sga_device_array: written through by the export calls)
+  if (rows->dtype == SGA_F64)
+    hipLaunchKernelGGL((features_rows_kernel<double, true>), grid, block, 0, ctx->stream, features->rows.p, static_cast<double*>(data), static_cast<uint32_t>(rows->cols), static_cast<uint32_t>(rows->stride), total);
+  else
+    hipLaunchKernelGGL((features_rows_kernel<float, true>), grid, block, 0, ctx->stream, features->rows.p, static_cast<float*>(data), static_cast<uint32_t>(rows->cols), static_cast<uint32_t>(rows->stride), total);
+  SGA_HIP(hipGetLastError());
+  return io_end(ctx, ord);
 }
 
 int sga_features_size(const sga_features* features, size_t* n, int* dim) {

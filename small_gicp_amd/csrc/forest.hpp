@@ -137,7 +137,7 @@ int build_into(T** out, Build&& build) {
 
 // ---- the launch counters (diagnostics: the sga_debug_*_launches entry points) --------------------------------------------------------------
 // What a chain counts is its own rule: Forest (kd, features) and Grid count kernels and sorts, the others their table copies as well
-enum class Chain { Forest, Grid, VoxBuild, IvmInsert, Problem, Merge, Deskew, Crop, Outliers, Overlap, Visibility, Fpfh, FeatureMatch, Ransac, PlacesAdd, PlacesQuery, PlacesWait, RadiusSearch, Cluster, RadiusWait, Plane, PlaneWait, Keypoints, KeypointsWait, Occupancy, OccupancyWait, Sweep, kCount };
+enum class Chain { Forest, Grid, VoxBuild, IvmInsert, Problem, Merge, Deskew, Crop, Outliers, Overlap, Visibility, Fpfh, FeatureMatch, Ransac, PlacesAdd, PlacesQuery, PlacesWait, RadiusSearch, Cluster, RadiusWait, Plane, PlaneWait, Keypoints, KeypointsWait, Occupancy, OccupancyWait, Sweep, GridFields, kCount };
 void count_launch(Chain chain);                                  // batch_preprocess.hip
 int report_launches(Chain chain, unsigned long long* launches);  // the body of an sga_debug_*_launches entry point
 

@@ -8,6 +8,7 @@
 #include <memory>
 #include <rocprim/rocprim.hpp>
 
+#include "device_io.hpp"
 #include "forest.hpp"
 #include "kd_search.hpp"
 #include "knn_wave.hpp"
@@ -203,6 +204,137 @@ __device__ __forceinline__ void ds_mean_body(const uint32_t* __restrict__ seg_st
 }
 __global__ void ds_mean_kernel(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ scratch, const uint32_t* __restrict__ order, const float4* __restrict__ pts, float4* __restrict__ out) {
   ds_mean_body(seg_start, scratch, order, pts, out, blockIdx.x * blockDim.x);
+}
+
+// ---- the voxel grid that carries per-point columns -----------------------------------------------------------
+// What one launch needs to know about the columns: where row i of the caller's array lives (fp32 or fp64 elements, `stride` elements
+// from one row to the next: a column of a wider tensor is a view), how many columns there are and how each is reduced: four bits per
+// column, sixteen columns per word (kernel arguments, read with scalar shifts: no array that a runtime index would send to scratch).
+struct FieldArgs {
+  const void* rows;
+  unsigned long long ops[2];
+  int stride, dim, f64;
+};
+constexpr int kFieldChunk = 4;  // columns held in registers at a time
+constexpr uint32_t kFieldNone = 0xffffffffu;
+
+__device__ __forceinline__ int field_op(const FieldArgs& F, int c) { return static_cast<int>((F.ops[c >> 4] >> (4 * (c & 15))) & 15ull); }
+__device__ __forceinline__ float field_at(const FieldArgs& F, uint32_t row, int c) {
+  const size_t e = static_cast<size_t>(row) * static_cast<size_t>(F.stride) + static_cast<size_t>(c);
+  return F.f64 ? static_cast<float>(static_cast<const double*>(F.rows)[e]) : static_cast<const float*>(F.rows)[e];  // fp64: rounded to fp32 once, here
+}
+
+// ds_mean_kernel with the columns of the voxel's members reduced next to its centroid.  Eight lanes per voxel as there.
+//   walk 0: ds_mean_body's sums, statement for statement (the record written is the plain call's, bit for bit); every member's row of
+//           voxel_of[] is written on the way, counts[] with the centroid;
+//   walk 1 .. ceil(dim / 4): four columns at a time in registers.  A column's state is (a: double, idx, val): MEAN sums into a (lane g
+//           sums members g, g + 8, ..., then the butterfly: an order that depends on the member count alone); the other four select ONE
+//           member by the key a — MIN v, MAX -v (NaN values are no candidates), FIRST 0, NEAREST the squared distance of the member's
+//           record to the rounded centroid of walk 0, formed in double with every product and sum rounded (no contraction) — with ties
+//           going to the lower original index, in the lane's loop and in the butterfly alike, so the winner does not depend on which
+//           lane held it.
+// Threads t in [valid points, n) of a launch that was asked for voxel_of also write the -1 of the dropped point at sorted position t: the
+// launch has max(8 * capacity, n) threads then.  No atomics, no LDS, no waiting.
+__global__ __launch_bounds__(256) void ds_fields_kernel(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ scratch, const uint32_t* __restrict__ order, const float4* __restrict__ pts, uint32_t n, const FieldArgs F,
+                                                        float4* __restrict__ out, float* __restrict__ out_fields, int* __restrict__ counts, long long* __restrict__ voxel_of) {
+  const uint32_t block_first = blockIdx.x * blockDim.x;
+  const uint32_t t = block_first + threadIdx.x;
+  const uint32_t v = t >> 3, g = t & 7u;
+  const uint32_t nseg = scratch[1];
+  if (voxel_of != nullptr && t < n && t >= scratch[2]) voxel_of[order[t]] = -1ll;
+  if (block_first >> 3 >= nseg) return;  // workgroup-uniform
+  const bool valid = v < nseg;
+  double sx = 0, sy = 0, sz = 0;
+  uint32_t cnt = 0;
+  uint32_t s = 0, e = 0;
+  if (valid) {
+    s = seg_start[v], e = v + 1 < nseg ? seg_start[v + 1] : scratch[2];
+    uint32_t i = s + g;
+    for (; i + 24 < e; i += 32) {  // four points of this lane in flight
+      const uint32_t i0 = order[i], i1 = order[i + 8], i2 = order[i + 16], i3 = order[i + 24];
+      const float4 p0 = pts[i0], p1 = pts[i1], p2 = pts[i2], p3 = pts[i3];
+      sx += p0.x, sy += p0.y, sz += p0.z;
+      sx += p1.x, sy += p1.y, sz += p1.z;
+      sx += p2.x, sy += p2.y, sz += p2.z;
+      sx += p3.x, sy += p3.y, sz += p3.z;
+      cnt += 4;
+      if (voxel_of != nullptr) voxel_of[i0] = v, voxel_of[i1] = v, voxel_of[i2] = v, voxel_of[i3] = v;
+    }
+    for (; i < e; i += 8) {
+      const uint32_t i0 = order[i];
+      const float4 p = pts[i0];
+      sx += p.x;
+      sy += p.y;
+      sz += p.z;
+      cnt++;
+      if (voxel_of != nullptr) voxel_of[i0] = v;
+    }
+  }
+  for (int off = 1; off < 8; off <<= 1) {  // lanes of one voxel are adjacent: butterfly inside the group of 8
+    sx += __shfl_xor(sx, off);
+    sy += __shfl_xor(sy, off);
+    sz += __shfl_xor(sz, off);
+    cnt += __shfl_xor(cnt, off);
+  }
+  // (the eight lanes hold the same sums: a + b and b + a are the same double)
+  const double inv = 1.0 / cnt;
+  const float cx = static_cast<float>(sx * inv), cy = static_cast<float>(sy * inv), cz = static_cast<float>(sz * inv);
+  if (valid && g == 0) {
+    out[v] = make_float4(cx, cy, cz, __uint_as_float(v));
+    if (counts != nullptr) counts[v] = static_cast<int>(cnt);
+  }
+  for (int c0 = 0; c0 < F.dim; c0 += kFieldChunk) {  // (F.dim == 0: membership only)
+    int op[kFieldChunk];
+    bool nearest = false;
+#pragma unroll
+    for (int j = 0; j < kFieldChunk; j++) {
+      op[j] = c0 + j < F.dim ? field_op(F, c0 + j) : -1;
+      nearest = nearest || op[j] == SGA_REDUCE_NEAREST;
+    }
+    double a[kFieldChunk];
+    uint32_t idx[kFieldChunk];
+    float val[kFieldChunk];
+#pragma unroll
+    for (int j = 0; j < kFieldChunk; j++) a[j] = op[j] == SGA_REDUCE_MEAN ? 0.0 : INFINITY, idx[j] = kFieldNone, val[j] = __uint_as_float(0x7fc00000u);
+    if (valid) {
+      for (uint32_t i = s + g; i < e; i += 8) {
+        const uint32_t row = order[i];
+        double d2 = 0.0;
+        if (nearest) {  // chunk-uniform
+          const float4 p = pts[row];
+          const double dx = static_cast<double>(p.x) - static_cast<double>(cx), dy = static_cast<double>(p.y) - static_cast<double>(cy), dz = static_cast<double>(p.z) - static_cast<double>(cz);
+          d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+        }
+#pragma unroll
+        for (int j = 0; j < kFieldChunk; j++) {
+          if (op[j] < 0) continue;  // (uniform: a kernel argument)
+          const float f = field_at(F, row, c0 + j);
+          if (op[j] == SGA_REDUCE_MEAN) {
+            a[j] += static_cast<double>(f);
+          } else {
+            const double key = op[j] == SGA_REDUCE_MIN ? static_cast<double>(f) : op[j] == SGA_REDUCE_MAX ? -static_cast<double>(f) : op[j] == SGA_REDUCE_NEAREST ? d2 : 0.0;
+            // a NaN key (MIN / MAX of a NaN value) compares false: no candidate.  Rows come in ascending order, idx starts at the top.
+            if (key < a[j] || (key == a[j] && row < idx[j])) a[j] = key, idx[j] = row, val[j] = f;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kFieldChunk; j++) {
+      if (op[j] < 0) continue;
+      for (int off = 1; off < 8; off <<= 1) {
+        const double oa = __shfl_xor(a[j], off);
+        const uint32_t oi = __shfl_xor(idx[j], off);
+        const float ov = __shfl_xor(val[j], off);
+        if (op[j] == SGA_REDUCE_MEAN) {
+          a[j] += oa;
+        } else if (oa < a[j] || (oa == a[j] && oi < idx[j])) {
+          a[j] = oa, idx[j] = oi, val[j] = ov;
+        }
+      }
+      if (valid && g == 0) out_fields[static_cast<size_t>(v) * static_cast<size_t>(F.dim) + static_cast<size_t>(c0 + j)] = op[j] == SGA_REDUCE_MEAN ? static_cast<float>(a[j] / static_cast<double>(cnt)) : val[j];
+    }
+  }
 }
 
 // ---- the grid forest: the voxel grids of B clouds in one chain of launches (forest.hpp) ----------------------
@@ -672,8 +804,12 @@ VoxelPlan voxelgrid_plan(const sga_cloud* in, double leaf) {
   return P;
 }
 
-template <typename Key>
-int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const VoxelPlan& P, sga_cloud* res) {
+// The chain of a voxel-grid call: keys, one sort, the runs, then the launch that turns runs into rows — centroids(capacity, seg_start,
+// order), which the caller supplies (the plain call: ds_mean_kernel; the call that carries columns: ds_fields_kernel) and which is handed
+// the number of voxels to launch for: n ahead of the count (speculative), the count behind it (then possibly 0).  res->pts is allocated
+// before it is called.
+template <typename Key, typename Centroids>
+int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const VoxelPlan& P, sga_cloud* res, Centroids centroids) {
   const VoxelKeyLayout& L = P.L;
   const size_t n = in->n;
   const uint32_t n32 = static_cast<uint32_t>(n);
@@ -709,22 +845,31 @@ int voxelgrid_run(sga_context* ctx, const sga_cloud* in, double leaf, const Voxe
   uint32_t nseg = 0;
   if (P.speculative) {
     SGA_TRY(res->pts.alloc(n));
-    hipLaunchKernelGGL(ds_mean_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, ctx->stream, seg_start.p, ctx->vg_scratch.p, order.p, in->pts.p, res->pts.p);
-    SGA_HIP(hipGetLastError());
+    SGA_TRY(centroids(n, seg_start.p, order.p));
     SGA_TRY(note_wait(ctx, seq, payload));
     nseg = static_cast<uint32_t>(payload[0]);
   } else {
     SGA_TRY(note_wait(ctx, seq, payload));
     nseg = static_cast<uint32_t>(payload[0]);
-    if (nseg > 0) {
-      SGA_TRY(res->pts.alloc(nseg));
-      hipLaunchKernelGGL(ds_mean_kernel, dim3((static_cast<size_t>(nseg) * 8 + 255) / 256), dim3(256), 0, ctx->stream, seg_start.p, ctx->vg_scratch.p, order.p, in->pts.p, res->pts.p);
-      SGA_HIP(hipGetLastError());
-    }
+    if (nseg > 0) SGA_TRY(res->pts.alloc(nseg));
+    SGA_TRY(centroids(nseg, seg_start.p, order.p));
   }
   res->n = nseg;
   return SGA_OK;
 }
+
+// the plain call's last launch: none for no voxel
+struct PlainCentroids {
+  sga_context* ctx;
+  const sga_cloud* in;
+  sga_cloud* res;
+  int operator()(size_t capacity, const uint32_t* seg_start, const uint32_t* order) const {
+    if (capacity == 0) return SGA_OK;
+    hipLaunchKernelGGL(ds_mean_kernel, dim3((capacity * 8 + 255) / 256), dim3(256), 0, ctx->stream, seg_start, ctx->vg_scratch.p, order, in->pts.p, res->pts.p);
+    SGA_HIP(hipGetLastError());
+    return SGA_OK;
+  }
+};
 
 }  // namespace
 
@@ -865,12 +1010,167 @@ int sga_voxelgrid_sampling(sga_context* ctx, const sga_cloud* in, double leaf, s
     return SGA_OK;
   }
   const VoxelPlan P = voxelgrid_plan(in, leaf);
-  SGA_TRY(P.key_bytes == 4 ? voxelgrid_run<uint32_t>(ctx, in, leaf, P, res.get()) : voxelgrid_run<unsigned long long>(ctx, in, leaf, P, res.get()));
+  const PlainCentroids centroids{ctx, in, res.get()};
+  SGA_TRY(P.key_bytes == 4 ? voxelgrid_run<uint32_t>(ctx, in, leaf, P, res.get(), centroids) : voxelgrid_run<unsigned long long>(ctx, in, leaf, P, res.get(), centroids));
   if (!ctx->stream_ordered) SGA_HIP(hipStreamSynchronize(ctx->stream));
   SGA_TRY(mark_ready(ctx, res->ready));
   *out = res.release();
   return SGA_OK;
 }
+
+}  // extern "C"
+
+// ---- sga_voxelgrid_sampling_fields --------------------------------------------------------------------------------
+namespace {
+
+// the last launch of the call that carries columns: ds_fields_kernel for `capacity` voxels — and for the n sorted positions when
+// voxel_of is wanted, whose dropped points it marks; the reduced rows are allocated here, for as many voxels as the launch is for
+struct FieldCentroids {
+  sga_context* ctx;
+  const sga_cloud* in;
+  sga_cloud* res;
+  sga_features* reduced;  // or null: membership only
+  FieldArgs F;
+  int* d_counts;
+  long long* d_voxel_of;
+  int operator()(size_t capacity, const uint32_t* seg_start, const uint32_t* order) const {
+    if (reduced != nullptr && capacity > 0) SGA_TRY(reduced->rows.alloc(capacity * static_cast<size_t>(F.dim)));
+    const size_t threads = std::max(capacity * 8, d_voxel_of != nullptr ? in->n : static_cast<size_t>(0));
+    if (threads == 0) return SGA_OK;
+    count_launch(Chain::GridFields);
+    hipLaunchKernelGGL(ds_fields_kernel, dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, seg_start, ctx->vg_scratch.p, order, in->pts.p, static_cast<uint32_t>(in->n), F, res->pts.p,
+                       reduced != nullptr ? reduced->rows.p : nullptr, d_counts, d_voxel_of);
+    SGA_HIP(hipGetLastError());
+    return SGA_OK;
+  }
+};
+
+// "before any handle is read", shared by the two forms: `dim` < 0 where the number of columns is the handle's to tell (the ops are then
+// checked by fields_ops_pack once it is known)
+int fields_args_check(const sga_context* ctx, const sga_cloud* in, const void* fields, sga_cloud** out, sga_features** out_fields, double leaf) {
+  if (!ctx || !in || !out) return fail(SGA_ERR_INVALID, "null argument");
+  if ((fields != nullptr) != (out_fields != nullptr)) return fail(SGA_ERR_INVALID, fields != nullptr ? "fields are given but out_fields is NULL" : "out_fields is given but fields is NULL");
+  if (!(leaf > 0)) return fail(SGA_ERR_INVALID, "leaf size must be positive");
+  return SGA_OK;
+}
+int fields_ops_pack(const int* ops, int dim, FieldArgs* F) {
+  F->ops[0] = F->ops[1] = 0ull;  // SGA_REDUCE_MEAN each
+  for (int c = 0; ops != nullptr && c < dim; c++) {
+    if (ops[c] < SGA_REDUCE_MEAN || ops[c] > SGA_REDUCE_NEAREST) return fail(SGA_ERR_INVALID, "reduction %d of column %d is none of SGA_REDUCE_MEAN .. SGA_REDUCE_NEAREST (0..4)", ops[c], c);
+    F->ops[c >> 4] |= static_cast<unsigned long long>(ops[c]) << (4 * (c & 15));
+  }
+  return SGA_OK;
+}
+
+// The call behind both forms.  The arguments are checked, the context entered; F.rows is device memory that holds in->n rows (F.dim == 0:
+// no columns), d_counts / d_voxel_of device memory with room for in->n entries, or null.  Enqueues, waits for the voxel count, and leaves
+// the synchronisation of the end to its caller.
+int voxelgrid_fields(sga_context* ctx, const sga_cloud* in, const FieldArgs& F, double leaf, int* d_counts, long long* d_voxel_of, std::unique_ptr<sga_cloud>* out, std::unique_ptr<sga_features>* out_fields) {
+  std::unique_ptr<sga_cloud> res(new sga_cloud);
+  res->device = ctx->device;
+  for (int k = 0; k < 3; k++) res->origin[k] = in->origin[k];
+  std::unique_ptr<sga_features> reduced;
+  if (F.dim > 0) {
+    reduced.reset(new sga_features());
+    reduced->device = ctx->device;
+    reduced->dim = F.dim;
+  }
+  SGA_TRY(wait_ready(ctx, in->ready));
+  if (in->n > 0) {
+    const VoxelPlan P = voxelgrid_plan(in, leaf);
+    const FieldCentroids centroids{ctx, in, res.get(), reduced.get(), F, d_counts, d_voxel_of};
+    for (int k = 0; k < 3; k++) count_launch(Chain::GridFields);  // keys, the sort, the runs: voxelgrid_run's own
+    SGA_TRY(P.key_bytes == 4 ? voxelgrid_run<uint32_t>(ctx, in, leaf, P, res.get(), centroids) : voxelgrid_run<unsigned long long>(ctx, in, leaf, P, res.get(), centroids));
+    if (reduced) reduced->n = res->n;
+  }
+  *out = std::move(res);
+  *out_fields = std::move(reduced);
+  return SGA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sga_voxelgrid_sampling_fields(sga_context* ctx, const sga_cloud* in, const sga_features* fields, const int* ops, double leaf, sga_cloud** out, sga_features** out_fields, int32_t* counts, int64_t* voxel_of) {
+  if (out) *out = nullptr;
+  if (out_fields) *out_fields = nullptr;
+  SGA_TRY(fields_args_check(ctx, in, fields, out, out_fields, leaf));
+  // ---- (from here on the handles are read; the number of ops is the fields' dim)
+  FieldArgs F{nullptr, {0ull, 0ull}, 0, 0, 0};
+  if (fields != nullptr) {
+    if (fields->dim < 1 || fields->dim > 32) return fail(SGA_ERR_INVALID, "fields: dim must be in [1,32], got %d", fields->dim);
+    SGA_TRY(fields_ops_pack(ops, fields->dim, &F));
+    if (fields->device != ctx->device) return fail(SGA_ERR_INVALID, "fields live on another device");
+    if (fields->n != in->n) return fail(SGA_ERR_INVALID, "fields have %zu rows, the cloud has %zu points", fields->n, in->n);
+    F.rows = fields->rows.p, F.stride = fields->dim, F.dim = fields->dim, F.f64 = 0;
+  }
+  if (in->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
+  if (in->n >= (1ull << 31)) return fail(SGA_ERR_INVALID, "cloud too large (%zu points; limit 2^31-1)", in->n);
+  SGA_ENTER(ctx);
+  const size_t n = in->n;
+  if (fields != nullptr) SGA_TRY(wait_ready(ctx, fields->ready));
+  DevBuf<int> d_counts;
+  DevBuf<long long> d_voxel_of;
+  if (counts != nullptr && n > 0) SGA_TRY(d_counts.alloc(n));
+  if (voxel_of != nullptr && n > 0) SGA_TRY(d_voxel_of.alloc(n));
+  std::unique_ptr<sga_cloud> res;
+  std::unique_ptr<sga_features> reduced;
+  SGA_TRY(voxelgrid_fields(ctx, in, F, leaf, d_counts.p, d_voxel_of.p, &res, &reduced));
+  static_assert(sizeof(int) == sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "the device arrays are copied out as they are");
+  if (counts != nullptr && res->n > 0) SGA_HIP(hipMemcpyAsync(counts, d_counts.p, res->n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (voxel_of != nullptr && n > 0) SGA_HIP(hipMemcpyAsync(voxel_of, d_voxel_of.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (!ctx->stream_ordered || ((counts != nullptr || voxel_of != nullptr) && n > 0)) SGA_HIP(hipStreamSynchronize(ctx->stream));  // (host arrays are filled when the call returns)
+  SGA_TRY(mark_ready(ctx, res->ready));
+  if (reduced) SGA_TRY(mark_ready(ctx, reduced->ready));
+  *out = res.release();
+  if (out_fields) *out_fields = reduced.release();
+  return SGA_OK;
+}
+
+int sga_voxelgrid_sampling_fields_device(sga_context* ctx, const sga_cloud* in, const sga_device_array* fields, const int* ops, double leaf, sga_cloud** out, sga_features** out_fields, int32_t* d_counts, int64_t* d_voxel_of,
+                                         void* user_stream, int flags) {
+  if (out) *out = nullptr;
+  if (out_fields) *out_fields = nullptr;
+  SGA_TRY(fields_args_check(ctx, in, fields, out, out_fields, leaf));
+  FieldArgs F{nullptr, {0ull, 0ull}, 0, 0, 0};
+  if (fields != nullptr) {  // (the caller's struct is no handle)
+    if (fields->dtype != SGA_F32 && fields->dtype != SGA_F64) return fail(SGA_ERR_INVALID, "fields: dtype %d is neither SGA_F32 nor SGA_F64", fields->dtype);
+    if (fields->cols < 1 || fields->cols > 32) return fail(SGA_ERR_INVALID, "fields: dim must be in [1,32], got %d", fields->cols);
+    if (fields->stride < fields->cols) return fail(SGA_ERR_INVALID, "fields: stride %d < cols %d", fields->stride, fields->cols);
+    SGA_TRY(fields_ops_pack(ops, fields->cols, &F));
+    F.rows = fields->data, F.stride = fields->stride, F.dim = fields->cols, F.f64 = fields->dtype == SGA_F64 ? 1 : 0;
+  }
+  // ---- (from here on the handles are read)
+  if (in->device != ctx->device) return fail(SGA_ERR_INVALID, "cloud lives on another device");
+  if (in->n >= (1ull << 31)) return fail(SGA_ERR_INVALID, "cloud too large (%zu points; limit 2^31-1)", in->n);
+  SGA_ENTER(ctx);
+  const size_t n = in->n;
+  if (n > 0) {  // every caller pointer against its allocation before a kernel is given it
+    if (fields != nullptr) {
+      const size_t elem = F.f64 ? 8 : 4;
+      size_t span = 0;  // the last element read ends here: columns of a wider array need not own the rest of its last row
+      if (__builtin_mul_overflow(n - 1, static_cast<size_t>(F.stride) * elem, &span) || __builtin_add_overflow(span, static_cast<size_t>(F.dim) * elem, &span))
+        return fail(SGA_ERR_INVALID, "fields: %zu rows of stride %d overflow the address space", n, F.stride);
+      SGA_TRY(check_device_range(ctx, F.rows, span, elem, "fields", "sga_voxelgrid_sampling_fields"));
+    }
+    if (d_counts != nullptr) SGA_TRY(check_device_range(ctx, d_counts, n * sizeof(int32_t), sizeof(int32_t), "d_counts", "sga_voxelgrid_sampling_fields"));
+    if (d_voxel_of != nullptr) SGA_TRY(check_device_range(ctx, d_voxel_of, n * sizeof(int64_t), sizeof(int64_t), "d_voxel_of", "sga_voxelgrid_sampling_fields"));
+  }
+  IoOrder ord;
+  SGA_TRY(io_begin(ctx, user_stream, flags, &ord));
+  std::unique_ptr<sga_cloud> res;
+  std::unique_ptr<sga_features> reduced;
+  SGA_TRY(voxelgrid_fields(ctx, in, F, leaf, reinterpret_cast<int*>(d_counts), reinterpret_cast<long long*>(d_voxel_of), &res, &reduced));
+  SGA_TRY(io_end(ctx, ord));  // (a blocking context synchronises its stream here)
+  SGA_TRY(mark_ready(ctx, res->ready));
+  if (reduced) SGA_TRY(mark_ready(ctx, reduced->ready));
+  *out = res.release();
+  if (out_fields) *out_fields = reduced.release();
+  return SGA_OK;
+}
+
+int sga_debug_voxelgrid_fields_launches(unsigned long long* launches) { return report_launches(Chain::GridFields, launches); }
 
 int sga_debug_voxelgrid_plan(const sga_cloud* cloud, double leaf, int out[9]) {
   if (!cloud || !out) return fail(SGA_ERR_INVALID, "null argument");

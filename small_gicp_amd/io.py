@@ -1,7 +1,8 @@
 """On-disk formats either side of the registration path.
 
 * read_points / write_points : the KITTI `.bin` layout, a flat little-endian float32 x,y,z,intensity array
-  (include/small_gicp/benchmark/read_points.hpp:15-46 of the reference; the 4th component is replaced by 1).
+  (include/small_gicp/benchmark/read_points.hpp:15-46 of the reference; the 4th component is replaced by 1, and handed back
+  separately on request: return_intensity).
 * read_ply                   : "simple PLY" = binary_little_endian, one `element vertex N`, float properties only, first three
   x, y, z (read_points.hpp:52-109; the reference rejects any other property type and warns when the first three are not x/y/z).
 * list_kitti_scans           : sorted `*.bin` files of a directory (benchmark.hpp:96-115).
@@ -14,16 +15,19 @@ import sys
 import numpy as np
 
 
-def read_points(filename):
-    """(N,4) float32, w = 1; empty array (and a message on stderr) if the file cannot be opened — the reference's behaviour."""
+def read_points(filename, return_intensity=False):
+    """(N,4) float32, w = 1; empty array (and a message on stderr) if the file cannot be opened — the reference's behaviour.
+    return_intensity: also the file's fourth column, (N,) float32 — ((N,4), (N,)) — which api.voxelgrid_sampling_fields carries through
+    the voxel grid; the points are what they are without it."""
     try:
         raw = np.fromfile(filename, dtype="<f4")
     except OSError:
         print("error: failed to open %s" % filename, file=sys.stderr)
-        return np.zeros((0, 4), np.float32)
+        return (np.zeros((0, 4), np.float32), np.zeros(0, np.float32)) if return_intensity else np.zeros((0, 4), np.float32)
     pts = raw[: (len(raw) // 4) * 4].reshape(-1, 4).astype(np.float32, copy=True)
+    intensity = pts[:, 3].copy() if return_intensity else None
     pts[:, 3] = 1.0
-    return pts
+    return (pts, intensity) if return_intensity else pts
 
 
 def write_points(filename, points):

@@ -23,15 +23,21 @@ class OnlineOdometry:
     computes the same pose."""
 
     def __init__(self, downsampling_resolution=0.25, num_neighbors=20, max_correspondence_distance=1.0, ctx=None, shard=None, min_range=None, max_range=None, outlier_k=None, outlier_std_mul=1.0,
-                 estimate_twist=False, twist_prior_information=None, sweep_points=12000):
+                 estimate_twist=False, twist_prior_information=None, sweep_points=12000, sweep_source="sample"):
         self.shard = shard
         # estimate_twist (False: off, the default — a sweep is deskewed with the previous motion): a RAW sweep is registered against the
         # previous deskewed scan by api.align_sweep (DESIGN.md section 3.30), which estimates its pose and its twist together — from the
         # previous motion as the initial twist AND the initial pose, or from zero and the identity when there is none — and the sweep is then
         # deskewed with the ESTIMATED twist, downsampled, and registered rigidly once more from the sweep's pose (the sample's pose refined).
-        # What is registered is an even sample of at most sweep_points of the (cropped) raw points, taken with PointCloud.selected so that
-        # the times follow; the voxel grid cannot carry times.  twist_prior_information (None: no prior; a number w: w I; or (6,6)): the
-        # information of a Gaussian prior on the twist centred on the previous motion, once there is one.
+        # What is registered is, with sweep_source="sample" (the default), an even sample of at most sweep_points of the (cropped) raw
+        # points, taken with PointCloud.selected so that the times follow; with sweep_source="voxelgrid", the voxel grid of the raw sweep
+        # at downsampling_resolution — the cloud every other registration here uses — whose times api.voxelgrid_sampling_fields carries
+        # along, reduced by "nearest": the time of the return nearest the centroid, one real return's, which stays meaningful across the
+        # sweep's seam where a mean of 0.02 and 0.98 would not (DESIGN.md section 3.31).  twist_prior_information (None: no prior; a
+        # number w: w I; or (6,6)): the information of a Gaussian prior on the twist centred on the previous motion, once there is one.
+        if sweep_source not in ("sample", "voxelgrid"):
+            raise ValueError("sweep_source must be 'sample' or 'voxelgrid'")
+        self.sweep_source = sweep_source
         self.estimate_twist = bool(estimate_twist)
         self.sweep_points = int(sweep_points)
         if twist_prior_information is None:
@@ -122,14 +128,21 @@ class OnlineOdometry:
         return self.T_world.copy()
 
     def _estimate_sweep(self, raw, times, t0):
-        """estimate_twist: the raw sweep's pose and twist from api.align_sweep over an even sample of it, then the sweep deskewed with that
-        twist as the next target.  (The times are a host array here: a sample's times are gathered on the host.)"""
+        """estimate_twist: the raw sweep's pose and twist from api.align_sweep over an even sample of it (sweep_source="sample") or over its
+        voxel grid with the times carried along ("voxelgrid"), then the sweep deskewed with that twist as the next target.  (The times
+        are a host array here: a sample's times are gathered on the host, the grid's M reduced times come to the host once, for
+        align_sweep's host `times`.)"""
         if self.shard is not None:
             raise ValueError("estimate_twist is not available on a sharded estimator")
         times = np.ascontiguousarray(np.asarray(times, dtype=np.float32).reshape(-1))
         n = raw.size()
-        idx = np.arange(0, n, max(1, -(-n // max(1, self.sweep_points))), dtype=np.int64)
-        sample = raw if len(idx) == n else raw.selected(idx)
+        if self.sweep_source == "voxelgrid":
+            sample, reduced = api.voxelgrid_sampling_fields(raw, times, self.res, reduce="nearest")
+            sample_times = np.ascontiguousarray(reduced.numpy().reshape(-1))
+        else:
+            idx = np.arange(0, n, max(1, -(-n // max(1, self.sweep_points))), dtype=np.int64)
+            sample = raw if len(idx) == n else raw.selected(idx)
+            sample_times = times[idx]
         self.ctx.synchronize()
         t1 = time.perf_counter()
         api.estimate_covariances(sample, None, self.k)
@@ -139,7 +152,7 @@ class OnlineOdometry:
         # under a constant twist the pose at the sweep's end, seen from its start, is exp(twist): the previous motion is the guess for both
         # (from the identity a step of more than the correspondence distance is outside the loop's reach: 1.4 m errors on the slalom)
         init_T = self.motion if self.motion is not None else np.eye(4)
-        res = api.align_sweep(tgt_cloud, sample, times[idx], tgt_tree, init_T=init_T, init_twist=centre, ref_time=1.0, twist_prior=centre if prior is not None else None, twist_information=prior, setting=self.setting)
+        res = api.align_sweep(tgt_cloud, sample, sample_times, tgt_tree, init_T=init_T, init_twist=centre, ref_time=1.0, twist_prior=centre if prior is not None else None, twist_information=prior, setting=self.setting)
         pose = res.T_target_source
         self.twists.append(res.twist)
         self.iterations.append(res.iterations + 1)
@@ -555,7 +568,8 @@ def run_synthetic(num_frames=20, pinned=False, sweeps=False, times=True, min_ran
     trajectory: "arc" (the default: synthetic._sensor_pose, constant speed and yaw rate) or "slalom" (synthetic.slalom_pose: both change
     from frame to frame; sweep f is synthetic.sweep_between(slalom_pose(f), slalom_pose(f + 1)), a snapshot synthetic.scan_at(slalom_pose(f))).
     n_rings / n_az: the sensor's rays.  estimate_twist= / twist_prior_information= (OnlineOdometry): sweeps are registered with their
-    twist free (api.align_sweep) instead of being deskewed with the previous motion; "twists" then holds the estimates."""
+    twist free (api.align_sweep) instead of being deskewed with the previous motion; "twists" then holds the estimates.  sweep_source=
+    (OnlineOdometry: "sample", the default, or "voxelgrid") chooses what of the raw sweep is registered."""
     from . import synthetic
 
     if trajectory not in ("arc", "slalom"):
